@@ -10,6 +10,12 @@ in HBM before the timed region.  value = N_gpus * B * A * steps / wall.
 Launching: `python bench.py --gpus N` starts N ranks itself (one process per GPU, RCCL process group);
 under torchrun (RANK / WORLD_SIZE in the environment) it is one of the ranks.
 
+A plain run sets up, warms up (a throw-away colony of the same shape for --precondition-seconds, then --warmup steps), times
+--steps steps and prints the line; its roofline object comes from the timed steps' own kernel events and the stored counter
+figures.  What is marked (--full) below is measured only with --full.  --dump-outputs DIR writes what the last timed step
+computed (dump_outputs); that step runs on a twin of the colony advanced a fixed number of iterations before the timed region,
+so what it computes depends on the arguments that set the workload, not on --steps or --warmup.
+
 Objects on the JSON line besides the contract's keys:
   roofline      dominant kernel (tsp_scan32_kernel for the default workload) timed live with HIP events on the
                 launch stream.  The fused transition rows live in L2/MALL, so the bound is the L2 -> CU row
@@ -18,18 +24,18 @@ Objects on the JSON line besides the contract's keys:
                 ((n-1)*8n + 8n + 8n^2/A + 8n bytes per ant-tour) over the same time and its ratio to the HBM peak;
                 `hbm` the counter-measured HBM-side bytes per launch (from profiles/, source named) next to the
                 compulsory floor.
-  sustained     the same step loop run for >= --min-seconds after the timed region (so that samplers outside
+  sustained     (--full) the same step loop run for >= --min-seconds after the timed region (so that samplers outside
                 this process can see the GPU busy); not the metric.
-  cpu_baseline  torch-CPU port of the reference's op sequence (oracle/torch_port.py) on this host's cores:
+  cpu_baseline  (--full) torch-CPU port of the reference's op sequence (oracle/torch_port.py) on this host's cores:
                 min(instances, host CPUs / 4) colonies of the same workload side by side (one process each, two
                 intra-op threads: 128 of the 256 hardware threads on the GPU box = its physical cores; the host's
                 aggregate rate is flat from ~16 colonies on, the op sequence is memory-bound), --cpu-iters iterations
                 each (rank 0, N = 1 only), and the best-cost gap against the GPU path on the same instances at the same
                 number of iterations.
-  extras        BASELINE.json's other single-GPU configurations (2, 3, 4, the per-GPU share of 5), the parity modes of
+  extras        (--full) BASELINE.json's other single-GPU configurations (2, 3, 4, the per-GPU share of 5), the parity modes of
                 the sampler, the learned heuristic and the GNN forward, each with its own roofline object and its own
                 cpu_baseline on a bounded sample (N = 1 only; --no-extras skips).
-  rccl          N > 1: ranks, backend and the measured all-reduce bus bandwidth of a [B, n, n] f32 buffer.
+  rccl          N > 1: ranks, backend and (--full) the measured all-reduce bus bandwidth of a [B, n, n] f32 buffer.
 """
 import argparse
 import json
@@ -49,8 +55,16 @@ PEAK_L2_GBS = 34500.0          # aggregate L2 bandwidth (MI355X_MICROARCH.md, L2
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 10; 5 with --config c5)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the sustained loop, the cpu_baseline leg and the best-cost "
+                         "gap, the other configurations (extras), the live counter passes and the all-reduce probe; and write "
+                         "bench_extras.json.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): tours, costs, "
+                         "pheromone, best cost and tour; larger arrays as a fixed, seeded sample (at most 64 MB in all).  The same "
+                         "for any --steps / --warmup: the last step runs on a twin colony in a fixed state")
     ap.add_argument("--nodes", type=int, default=500)
     ap.add_argument("--ants", type=int, default=512)
     ap.add_argument("--batch", type=int, default=64, help="instances per GPU")
@@ -88,13 +102,17 @@ def parse_args():
                          "what an N-GPU run executes, on one GPU)")
     ap.add_argument("--force-device", type=int, default=None,
                     help="testing only: put every rank on this GPU (needs --dist-backend gloo)")
-    return apply_config(ap.parse_args())
+    args = apply_config(ap.parse_args())
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def apply_config(args):
     if args.config == "c5":
         args.nodes, args.ants, args.batch = 1000, 2048, 64
-        args.steps = min(args.steps, 5)
+    if args.steps is None:
+        args.steps = 5 if args.config == "c5" else 10
     return args
 
 
@@ -214,13 +232,13 @@ def quiet_stdout():
         os.dup2(2, 1)
 
 
-def emit(full):
+def emit(full, extras_file=True):
     """Full record -> bench_extras.json (repo root, and gpurun_out/ when it exists so that it travels back from a GPU box);
-    compact record -> the last stdout line."""
+    compact record -> the last stdout line.  extras_file=False (a run without --full): the line only."""
     full = _finite(full)
     for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
         try:
-            if os.path.isdir(d):
+            if extras_file and os.path.isdir(d):
                 with open(os.path.join(d, "bench_extras.json"), "w") as f:
                     json.dump(full, f, indent=1)
         except OSError as e:
@@ -258,9 +276,13 @@ def make_instances(B, n, seed):
     import torch
     g = torch.Generator().manual_seed(seed)
     coords = torch.rand(B, n, 2, generator=g)
-    # the reference's expression (torch.norm of the coordinate differences); torch.cdist's matmul form returns exact zeros
-    # for close pairs, i.e. an infinite 1/d
-    dist = torch.cat([torch.norm(c[:, None] - c, dim=2, p=2).unsqueeze(0) for c in coords])
+    # the reference's expression, the norm of the coordinate differences (torch.cdist's matmul form returns exact zeros for
+    # close pairs, i.e. an infinite 1/d), written as element-wise operations: each is rounded once, the same way on every host.
+    # (torch.norm's CPU reduction is not: its result depends on the instruction set ATen dispatches to, so the same seed gave
+    # other instances, and other tours, on another host.)
+    dx = coords[:, :, None, 0] - coords[:, None, :, 0]
+    dy = coords[:, :, None, 1] - coords[:, None, :, 1]
+    dist = torch.sqrt(dx * dx + dy * dy)
     idx = torch.arange(n)
     dist[:, idx, idx] = 1e9
     return dist
@@ -344,6 +366,48 @@ def time_launches(fn, steps, warm=2):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps
+
+
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+TWIN_ITERATIONS = 2               # untimed iterations of the colony whose step is the last timed one (worker)
+DUMP_BIG, DUMP_SMALL = 4 << 20, 1 << 20      # elements per array: tours and pheromone, the other three (44 MB of float32 in all)
+
+
+def _dump_sample(name, t, dims, limit):
+    """t cut to at most `limit` elements: along each of `dims` in turn, while still too large, a sorted sample of its indices
+    drawn from a generator seeded by the array's name and shape (the same cut in every run with the same arguments)."""
+    import zlib
+    import numpy as np
+    import torch
+    rng = np.random.default_rng([zlib.crc32(name.encode()), *t.shape])
+    for d in dims:
+        if t.numel() <= limit:
+            break
+        keep = max(1, min(t.shape[d], limit // (t.numel() // t.shape[d])))
+        idx = np.sort(rng.choice(t.shape[d], keep, replace=False))
+        t = t.index_select(d, torch.as_tensor(idx, device=t.device))
+    return t
+
+
+def dump_outputs(out_dir, paths, costs, colony):
+    """What the last timed step computed, as float32 .npy files under out_dir: its tours (paths [B, n, A], ants sampled first)
+    and costs [B, A] as step() returned them (a StreamedTSP step returns nothing: only the colony's state then), and the state
+    the step left -- pheromone [B, n, n] (instances sampled first), lowest_cost [B], shortest_path [B, n].  Node ids and costs
+    are exact in float32 (n <= 4096)."""
+    import numpy as np
+    tau = colony.tau if hasattr(colony, "tau") else colony.pheromone
+    arrays = [("paths", paths, (2, 0, 1), DUMP_BIG), ("costs", costs, (0, 1), DUMP_SMALL), ("pheromone", tau, (0, 1, 2), DUMP_BIG),
+              ("lowest_cost", colony.lowest_cost, (0,), DUMP_SMALL), ("shortest_path", colony.shortest_path, (0, 1), DUMP_SMALL)]
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t, dims, limit in arrays:
+        if t is None:
+            continue
+        a = _dump_sample(name, t.detach(), dims, limit).cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+        log(f"dump: {name} {tuple(t.shape)} -> {a.shape}")
+    log(f"dump: {total / 2**20:.1f} MB under {out_dir}")
 
 
 # ---------------------------------------------------------------------------------------------- CPU leg
@@ -1491,17 +1555,18 @@ def worker(args):
         _, idx = torch.topk(d_dev, k=k_sparse, dim=2, largest=False)
         sparse = torch.full_like(d_dev, 1e10)
         sparse.scatter_(2, idx, torch.gather(d_dev, 2, idx))
-        # the SAME sampler as the N = 1 line: "auto" resolves to the head / tail rows with the k of the
-        # sparsified heuristic, exactly as BatchedTSP.sparsify(k) leaves it
-        colony = engine.ant_sharded_tsp(d_dev, A, rank, world, heuristic=(1 / sparse).contiguous(),
-                                        sampler=args.sampler, head_k=min(k_sparse, 127), seed=1234,
-                                        exchange=args.exchange)
-        _step = colony.step
-        colony.step = lambda events=None: _step()
     streams = 1 if ant_sharded else max(1, min(args.streams, B))
 
     def make_colony(seed, gid0):
-        if streams > 1:      # (StreamedTSP.sparsify keeps the parts' heuristics contiguous)
+        if ant_sharded:
+            # the SAME sampler as the N = 1 line: "auto" resolves to the head / tail rows with the k of the
+            # sparsified heuristic, exactly as BatchedTSP.sparsify(k) leaves it
+            col = engine.ant_sharded_tsp(d_dev, A, rank, world, heuristic=(1 / sparse).contiguous(),
+                                         sampler=args.sampler, head_k=min(k_sparse, 127), seed=seed,
+                                         exchange=args.exchange)
+            _step = col.step
+            col.step = lambda events=None: _step()
+        elif streams > 1:      # (StreamedTSP.sparsify keeps the parts' heuristics contiguous)
             col = engine.StreamedTSP(dist_cpu.to(dev), parts=streams, n_ants=A, sampler=args.sampler, seed=seed, ant_gid0=gid0)
             col.sparsify(k_sparse)
         else:
@@ -1510,8 +1575,14 @@ def worker(args):
             col.heuristic = col.heuristic.contiguous()
         return col
 
-    if not ant_sharded:
-        colony = make_colony(1234, rank * B * A)
+    colony = make_colony(1234, rank * B * A)
+    # The last timed step runs on a twin of the colony: the same instances and seed, advanced TWIN_ITERATIONS untimed iterations
+    # here.  What that step computes -- the result of the timed path that --dump-outputs writes -- then depends on the arguments
+    # alone, not on how many warm-up and timed steps ran before it (--steps is chosen from a run's ms_per_step); its work is
+    # that of every other timed step (a colony iteration of the same shape, its head rows formed by its own last update).
+    twin = make_colony(1234, rank * B * A)
+    for _ in range(TWIN_ITERATIONS):
+        twin.step()
 
     if ant_sharded:
         resolved = engine.resolve_sampler(args.sampler, n, min(k_sparse, 127), None, {})[0]
@@ -1544,9 +1615,13 @@ def worker(args):
     for _ in range(args.warmup):
         colony.step()
 
+    last = [None]
+
     def timed():
-        for s in range(args.steps):
+        for s in range(args.steps - 1):
             colony.step(events=ev[s] if streams > 1 else ev[s][0])
+        # (the twin: what the last step returns is kept for --dump-outputs; a StreamedTSP step returns nothing)
+        last[0] = twin.step(events=ev[-1] if streams > 1 else ev[-1][0])
 
     elapsed = barrier_max_time(timed, dev, distributed)
     log(f"timed region: {elapsed*1e3:.1f} ms for {args.steps} steps")
@@ -1555,10 +1630,14 @@ def worker(args):
     tours_per_step = B * A if ant_sharded else world * B * A
     value = tours_per_step * args.steps / elapsed
     gpu_best = colony.lowest_cost.detach().cpu()
+    if args.dump_outputs and rank == 0:
+        paths, costs = last[0] if last[0] is not None else (None, None)
+        dump_outputs(args.dump_outputs, paths, costs, twin)
+    last[0] = twin = None
 
     # sustained loop (not the metric): the same steps for >= min-seconds
     sustained = None
-    if args.min_seconds > 0:
+    if args.full and args.min_seconds > 0:
         chunk = max(1, int(0.25 / max(elapsed / args.steps, 1e-5)))
         state = {"steps": 0}
 
@@ -1593,6 +1672,7 @@ def worker(args):
                 rccl["version"] = ".".join(str(x) for x in torch.cuda.nccl.version())
             except Exception:
                 rccl["version"] = None
+        if args.dist_backend == "nccl" and args.full:
             buf = torch.ones((B, n, n), device=dev)
             for _ in range(2):
                 dist_pkg.all_reduce(buf)
@@ -1605,7 +1685,7 @@ def worker(args):
 
     if rank == 0:
         traffic, tsrc = load_traffic().get(f"tsp{n}_a{A}_b{B}_{resolved}", (None, None))
-        if world == 1 and not args.no_extras and not ant_sharded and streams == 1 and resolved in ("scan_sparse", "scan"):
+        if args.full and world == 1 and not args.no_extras and not ant_sharded and streams == 1 and resolved in ("scan_sparse", "scan"):
             # the HBM-side bytes of the dominant kernel, collected in THIS run (a stored figure cannot show a
             # regression): two counter passes of the kernel alone at this workload, in subprocesses
             needle = "scan_sparse_kernel" if resolved == "scan_sparse" else "tsp_scan32_kernel"
@@ -1645,13 +1725,13 @@ def worker(args):
         }
         if rccl:
             line["rccl"] = rccl
-        if world == 1 and not args.no_extras and not ant_sharded:
+        if args.full and world == 1 and not args.no_extras and not ant_sharded:
             try:
                 line["extras"] = extra_configs(dev, colony, cpu=not args.no_cpu)
             except Exception as e:          # the headline must still be reported
                 log(f"extras failed: {e!r}")
                 line["extras"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu and not ant_sharded:
+        if args.full and world == 1 and not args.no_cpu and not ant_sharded:
             # 16 colonies x 2 threads: the best aggregate found on this host class (round 2: 2 103 ant-tours/s; 64 x 2 on the
             # same 128 cores gave 1 594 -- the op sequence is memory-bound and slows down as colonies are added)
             # (round 6: 32 colonies x 20 iterations -- the gap's interval needs the instances; the aggregate rate is the same)
@@ -1673,7 +1753,7 @@ def worker(args):
             except Exception:
                 pass
             line["speedup_vs_cpu"] = value / cb["value"]
-        emit(line)
+        emit(line, extras_file=args.full)
     if distributed:
         dist_pkg.barrier()
         dist_pkg.destroy_process_group()

@@ -79,3 +79,16 @@ def test_headline_record_carries_the_three_gaps():
     assert set(rec["best_cost_gap"]["samplers"]) == {"scan_sparse", "scan", "race"}
     assert rec["best_cost_gap"]["samplers"]["race"] == [0.001, -0.001, 0.003, False, 14]
     assert bench.gap_samplers("scan_sparse") == ["scan_sparse", "scan", "race"] and bench.gap_samplers("scan") == ["scan", "race"]
+
+
+def test_instances_do_not_depend_on_the_host():
+    """The same seed gives the same instances bit for bit whatever instruction set ATen's CPU kernels dispatch to (a host without
+    AVX-512 or AVX2 runs the lower ones), so that two runs of bench.py with the same arguments compute the same tours.  (A
+    torch.norm reduction here gave other distances under each dispatch level.)"""
+    import subprocess
+    code = ("import hashlib, sys; sys.path.insert(0, %r); import bench; "
+            "print(hashlib.sha256(bench.make_instances(4, 300, 1234).numpy().tobytes()).hexdigest())" % ROOT)
+    got = {cap: subprocess.run([sys.executable, "-c", code], env=dict(os.environ, ATEN_CPU_CAPABILITY=cap), capture_output=True,
+                               text=True, check=True).stdout.strip()
+           for cap in ("default", "avx2", "avx512")}
+    assert len(set(got.values())) == 1, got

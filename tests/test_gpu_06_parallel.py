@@ -299,11 +299,30 @@ def test_bench_eight_ranks_the_drivers_launch_path():
     assert json.loads(lines[0])["n_gpus"] == 4
 
 
+def test_bench_dumps_the_same_outputs_whatever_the_step_counts(tmp_path):
+    """bench.py --dump-outputs: the arrays of the last timed step are the same in every run with the same workload arguments --
+    run twice, and with other --steps / --warmup (the step count of a later run is chosen from an earlier run's ms_per_step)."""
+    import numpy as np
+    common = ("--nodes", "200", "--ants", "64", "--batch", "4")
+    runs = {"a": ("--steps", "3", "--warmup", "1"), "b": ("--steps", "3", "--warmup", "1"), "c": ("--steps", "7", "--warmup", "4")}
+    for tag, steps in runs.items():
+        line = _bench_line(*common, *steps, "--dump-outputs", str(tmp_path / tag))
+        assert line["steps"] == int(steps[1]) and line["warmup"] == int(steps[3])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["costs.npy", "lowest_cost.npy", "paths.npy", "pheromone.npy", "shortest_path.npy"]
+    for tag in ("b", "c"):
+        for f in names:
+            x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / tag / f)
+            assert x.dtype == np.float32 and np.array_equal(x, y), (tag, f)
+    paths = np.load(tmp_path / "a" / "paths.npy")
+    assert paths.shape == (4, 200, 64) and (np.sort(paths, axis=1) == np.arange(200)[None, :, None]).all()    # tours
+
+
 def test_bench_world_size_one_on_rccl():
     """bench.py --force-dist: the distributed code path (init_process_group("nccl", device_id), barrier / max reduce on device
     tensors, the all-reduce bus-bandwidth probe, the `rccl` object on the line) with ONE rank on one GPU."""
     common = ("--no-cpu", "--no-extras", "--min-seconds", "0", "--steps", "3", "--warmup", "1", "--nodes", "120",
-              "--ants", "64", "--batch", "4", "--force-dist")
+              "--ants", "64", "--batch", "4", "--force-dist", "--full")          # (--full: the all-reduce probe)
     inst = _bench_line(*common)
     assert inst["n_gpus"] == 1 and inst["rccl"]["ranks"] == 1 and inst["rccl"]["backend"] == "nccl"
     assert inst["rccl"]["allreduce_ms"] > 0 and inst["value"] > 0

@@ -98,19 +98,47 @@ REF_LIBS = {"built_here": os.path.join(os.path.dirname(HERE), "oracle", "_ref", 
             "shipped": "/root/reference/cvrp_nls/HGS-CVRP-main/build/libhgscvrp.so"}
 
 
-@pytest.mark.parametrize("which", ["built_here", "shipped"])
-def test_oracle_against_the_reference_library_live(which):
-    """Fresh random solutions (not the committed ones) through the reference's library -- oracle/_ref/libhgscvrp.so (g++ over the
-    reference's sources, oracle/Makefile) and the reference's own shipped build -- and the restatement: the same routes."""
+LIVE = os.path.join(HERE, "golden", "g12_hgs_ls_live.npz")
+
+
+def live_cases():
+    """The random solutions of test_oracle_against_the_reference_library_live (tests/golden/gen_g12_hgs_ls_live.py records them
+    with the library's routes): per (n, SWAP*) one instance, four random feasible solutions -- clients in random order, cut where
+    the load would pass 1.  Yields (n, use_swap_star, positions, distances, demands, sequence, call id)."""
+    rng = np.random.default_rng(5)
+    for n, sw in ((15, 0), (40, 1), (90, 0), (90, 1)):
+        pos = rng.random((n + 1, 2))
+        d = np.linalg.norm(pos[:, None] - pos[None], axis=-1)
+        d[np.arange(n + 1), np.arange(n + 1)] = 1e-10
+        cap = 30 if n < 50 else 50
+        dem = np.concatenate(([0.0], rng.integers(1, 10, n) / cap))
+        for _ in range(4):
+            routes, cur, load = [], [], 0.0
+            for c in rng.permutation(np.arange(1, n + 1)):
+                if load + dem[c] > 1.0:
+                    routes.append(cur); cur, load = [], 0.0
+                cur.append(int(c)); load += dem[c]
+            routes.append(cur)
+            seq = np.array([v for r in routes for v in [0] + r] + [0])
+            yield n, sw, pos, d, dem, seq, int(rng.integers(1, 2 ** 30))
+
+
+def ref_library(which):
+    """The reference's library `which` of REF_LIBS, or None where it is not on this machine."""
+    import ctypes as C
+    if not os.path.isfile(REF_LIBS[which]):
+        return None
+    try:
+        return C.CDLL(REF_LIBS[which])
+    except OSError:
+        return None
+
+
+def ref_local_search(lib, pos, d, dem, seq, sw, callid):
+    """The routes the reference's library returns for the solution `seq` (called as cvrp_nls/swapstar.py does, through /tmp
+    route files): [0] + route for every route, concatenated."""
     import ctypes as C
     import sys
-    import tempfile
-    if not (os.path.isdir("/root/reference/cvrp_nls") and os.path.isfile(REF_LIBS[which])):
-        pytest.skip("needs the reference checkout (this container only)")
-    try:
-        lib = C.CDLL(REF_LIBS[which])
-    except OSError as e:
-        pytest.skip(f"{REF_LIBS[which]} does not load here: {e}")
 
     class FullAP(C.Structure):
         _fields_ = [("nbGranular", C.c_int), ("mu", C.c_int), ("lambda_", C.c_int), ("nbElite", C.c_int), ("nbClose", C.c_int),
@@ -120,38 +148,41 @@ def test_oracle_against_the_reference_library_live(which):
     dp = C.POINTER(C.c_double)
     lib.local_search.argtypes = [C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_char, C.c_int, C.POINTER(FullAP),
                                  C.c_char, C.c_int, C.c_int]
-    rng = np.random.default_rng(5)
-    for n, sw in ((15, 0), (40, 1), (90, 0), (90, 1)):
-        pos = rng.random((n + 1, 2))
-        d = np.linalg.norm(pos[:, None] - pos[None], axis=-1)
-        d[np.arange(n + 1), np.arange(n + 1)] = 1e-10
-        cap = 30 if n < 50 else 50
-        dem = np.concatenate(([0.0], rng.integers(1, 10, n) / cap))
-        for _ in range(4):
-            # a random feasible solution: clients in random order, cut where the load would pass 1
-            routes, cur, load = [], [], 0.0
-            for c in rng.permutation(np.arange(1, n + 1)):
-                if load + dem[c] > 1.0:
-                    routes.append(cur); cur, load = [], 0.0
-                cur.append(int(c)); load += dem[c]
-            routes.append(cur)
-            seq = np.array([v for r in routes for v in [0] + r] + [0])
-            callid = int(rng.integers(1, 2 ** 30))
-            with open(f"/tmp/route-{callid}", "w") as f:
-                for i, r in enumerate(routes):
-                    f.write(f"Route #{i + 1}: " + " ".join(map(str, r)) + "\n")
-            ap = FullAP(20, 25, 40, 4, 5, 100, 0.2, 0.85, 1.2, 1, 20000, 500, 0.0, sw)
-            x, y = np.ascontiguousarray(pos[:, 0]), np.ascontiguousarray(pos[:, 1])
-            m, s, dm = np.ascontiguousarray(d).reshape(-1), np.zeros(n + 1), np.ascontiguousarray(dem * 1000)
-            lib.local_search(n + 1, x.ctypes.data_as(dp), y.ctypes.data_as(dp), m.ctypes.data_as(dp), s.ctypes.data_as(dp),
-                             dm.ctypes.data_as(dp), 1000.001, sys.float_info.max, b'\0', len(routes), C.byref(ap), b'\0',
-                             callid, 100)
-            got = []
-            with open(f"/tmp/swapstar-result-{callid}") as f:
-                for line in f:
-                    if line.startswith("Route"):
-                        got += [0] + list(map(int, line.split(":")[1].split()))
-            os.remove(f"/tmp/swapstar-result-{callid}")
-            os.remove(f"/tmp/route-{callid}")
-            out, rc = oracle.hgs_local_search(pos, d, dem, seq, 100, out_len=len(seq) + 2, use_swap_star=sw)
-            assert rc == 0 and out[: len(got)].tolist() == got and not out[len(got):].any()
+    n = len(pos) - 1
+    routes = [r.tolist() for r in np.split(seq, np.flatnonzero(seq == 0))[1:-1]]
+    routes = [r[1:] for r in routes]
+    with open(f"/tmp/route-{callid}", "w") as f:
+        for i, r in enumerate(routes):
+            f.write(f"Route #{i + 1}: " + " ".join(map(str, r)) + "\n")
+    ap = FullAP(20, 25, 40, 4, 5, 100, 0.2, 0.85, 1.2, 1, 20000, 500, 0.0, sw)
+    x, y = np.ascontiguousarray(pos[:, 0]), np.ascontiguousarray(pos[:, 1])
+    m, s, dm = np.ascontiguousarray(d).reshape(-1), np.zeros(n + 1), np.ascontiguousarray(dem * 1000)
+    lib.local_search(n + 1, x.ctypes.data_as(dp), y.ctypes.data_as(dp), m.ctypes.data_as(dp), s.ctypes.data_as(dp),
+                     dm.ctypes.data_as(dp), 1000.001, sys.float_info.max, b'\0', len(routes), C.byref(ap), b'\0',
+                     callid, 100)
+    got = []
+    with open(f"/tmp/swapstar-result-{callid}") as f:
+        for line in f:
+            if line.startswith("Route"):
+                got += [0] + list(map(int, line.split(":")[1].split()))
+    os.remove(f"/tmp/swapstar-result-{callid}")
+    os.remove(f"/tmp/route-{callid}")
+    return got
+
+
+@pytest.mark.parametrize("which", ["built_here", "shipped"])
+def test_oracle_against_the_reference_library_live(which):
+    """Random solutions (not those of g11) through the reference's library -- oracle/_ref/libhgscvrp.so (g++ over the reference's
+    sources, oracle/Makefile) and the reference's own shipped build -- and the restatement: the same routes.  The library's routes
+    are recorded in tests/golden/g12_hgs_ls_live.npz, so the restatement is held to them on every machine; where the library is
+    present it is called again on the same solutions and must still return them."""
+    z = np.load(LIVE)
+    lib = ref_library(which)
+    for j in range(int(z["cases"])):
+        k = int(z[f"inst{j}"])
+        pos, d, dem, sw = z[f"pos{k}"], z[f"d{k}"], z[f"dem{k}"], int(z[f"sw{k}"])
+        seq, want = z[f"seq{j}"], z[f"{which}{j}"].tolist()
+        if lib is not None:
+            assert ref_local_search(lib, pos, d, dem, seq, sw, int(z[f"callid{j}"])) == want, (which, j)
+        out, rc = oracle.hgs_local_search(pos, d, dem, seq, 100, out_len=len(seq) + 2, use_swap_star=sw)
+        assert rc == 0 and out[: len(want)].tolist() == want and not out[len(want):].any(), (which, j)

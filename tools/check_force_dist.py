@@ -14,7 +14,7 @@ steps = sys.argv[1] if len(sys.argv) > 1 else "20"
 
 
 def run(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "3", "--no-extras", "--no-cpu", "--min-seconds", "0"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "3", "--no-extras", "--no-cpu", "--min-seconds", "0", "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not lines:

@@ -21,7 +21,7 @@ timeout 900 python tools/check_force_dist.py 20 > $OUT/force_dist.log 2>&1
 echo "force-dist rc=$?" >> $OUT/force_dist.log
 wait $GAP
 cat $OUT/best_cost_gap.log | tail -3
-( time python bench.py ) > $OUT/bench_default.log 2> $OUT/bench_default.err
+( time python bench.py --full ) > $OUT/bench_default.log 2> $OUT/bench_default.err
 tail -1 $OUT/bench_default.log | head -c 3000
 tail -5 $OUT/bench_default.err
 cp bench_extras.json $OUT/ 2>/dev/null

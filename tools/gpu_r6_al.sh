@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/r06al
 mkdir -p $OUT
 cd $R
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench rc=$?"
 tail -1 $OUT/bench_default.log > $OUT/bench_default_line.json
 cp gpurun_out/bench_extras.json $OUT/bench_extras.json 2>/dev/null
 python - <<'PY'

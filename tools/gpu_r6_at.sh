@@ -10,11 +10,11 @@ timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; echo "smoke r
 timeout 1500 python -m pytest tests -m gpu -q --timeout 300 > $OUT/pytest_gpu.log 2>&1
 echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 tail -5 $OUT/pytest_gpu.log | cut -c1-300
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench rc=$?"
 tail -1 $OUT/bench_default.log > $OUT/bench_default_line.json
 cp gpurun_out/bench_extras.json $OUT/bench_extras.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
-(cd $R && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats_headline -o p -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras > $OUT/stats_headline.log 2>&1)
+(cd $R && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats_headline -o p -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras > $OUT/stats_headline.log 2>&1)
 cp /tmp/stats_headline/p_kernel_stats.csv $OUT/kernel_stats_headline.csv 2>/dev/null || cp $(find /tmp/stats_headline -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_headline.csv
 TRAIN_MODES=graph timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats_train -o p -- python $R/tools/time_train_step.py 20 --shape 100 > $OUT/stats_train.log 2>&1
 cp $(find /tmp/stats_train -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_train_graph_tsp100.csv

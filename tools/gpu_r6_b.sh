@@ -10,8 +10,8 @@ timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1
 echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 tail -5 $OUT/pytest_gpu.log
 for i in 1 2; do
-  python bench.py --no-cpu --no-extras --min-seconds 3 --steps 20 2>/dev/null | tail -1 > $OUT/headline_fused_$i.json
-  DACO_FUSE_HEAD_ROWS=0 python bench.py --no-cpu --no-extras --min-seconds 3 --steps 20 2>/dev/null | tail -1 > $OUT/headline_prepass_$i.json
+  python bench.py --full --no-cpu --no-extras --min-seconds 3 --steps 20 2>/dev/null | tail -1 > $OUT/headline_fused_$i.json
+  DACO_FUSE_HEAD_ROWS=0 python bench.py --full --no-cpu --no-extras --min-seconds 3 --steps 20 2>/dev/null | tail -1 > $OUT/headline_prepass_$i.json
 done
 python - <<'PY'
 import json,glob,os

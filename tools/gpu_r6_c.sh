@@ -14,8 +14,8 @@ timeout 900 python -m pytest tests -m gpu -q --timeout 240 > $OUT/pytest_gpu.log
 echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 tail -15 $OUT/pytest_gpu.log
 for i in 1 2; do
-  timeout 120 python bench.py --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/headline_fused_$i.json
-  DACO_FUSE_HEAD_ROWS=0 timeout 120 python bench.py --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/headline_prepass_$i.json
+  timeout 120 python bench.py --full --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/headline_fused_$i.json
+  DACO_FUSE_HEAD_ROWS=0 timeout 120 python bench.py --full --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/headline_prepass_$i.json
 done
 python - <<'PY'
 import json,glob,os

@@ -9,8 +9,8 @@ cd $R
 timeout 300 python -m pytest tests/test_gpu_11_scan_sparse.py tests/test_gpu_15_full_batch.py -q -x --timeout 200 -k "scan_sparse or head or lds or grouped or categorical" > $OUT/pytest_first.log 2>&1
 echo "first rc=$?" | tee -a $OUT/pytest_first.log; tail -4 $OUT/pytest_first.log
 for i in 1 2; do
-  timeout 120 python bench.py --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/headline_fused_$i.json
-  DACO_FUSE_HEAD_ROWS=0 timeout 120 python bench.py --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/headline_prepass_$i.json
+  timeout 120 python bench.py --full --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/headline_fused_$i.json
+  DACO_FUSE_HEAD_ROWS=0 timeout 120 python bench.py --full --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/headline_prepass_$i.json
 done
 python - <<'PY'
 import json,glob,os

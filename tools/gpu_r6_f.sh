@@ -14,9 +14,9 @@ for i in 1 2 3; do
 done
 for f in ab_kernel_r5 ab_kernel_new ab_plain_r5 ab_plain_new; do echo $f; cut -c1-120 $OUT/$f.txt; done
 for i in 1 2; do
-  (cd $R/.ab_r5 && timeout 120 python bench.py --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1) > $OUT/bench_r5_$i.json
-  timeout 120 python bench.py --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/bench_fused_$i.json
-  DACO_FUSE_HEAD_ROWS=0 timeout 120 python bench.py --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/bench_prepass_$i.json
+  (cd $R/.ab_r5 && timeout 120 python bench.py --full --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1) > $OUT/bench_r5_$i.json
+  timeout 120 python bench.py --full --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/bench_fused_$i.json
+  DACO_FUSE_HEAD_ROWS=0 timeout 120 python bench.py --full --no-cpu --no-extras --min-seconds 2 --steps 20 2>/dev/null | tail -1 > $OUT/bench_prepass_$i.json
 done
 python - <<'PY'
 import json,glob,os

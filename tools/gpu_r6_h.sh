@@ -8,7 +8,7 @@ cd $R
 timeout 900 python -m pytest tests -m gpu -q --timeout 240 > $OUT/pytest_gpu.log 2>&1
 echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 tail -6 $OUT/pytest_gpu.log
-( time python bench.py ) > $OUT/bench_default.log 2> $OUT/bench_default.err
+( time python bench.py --full ) > $OUT/bench_default.log 2> $OUT/bench_default.err
 tail -1 $OUT/bench_default.log | head -c 3800; echo
 grep -E "^\[bench\]|real" $OUT/bench_default.err | tail -12
 cp bench_extras.json $OUT/ 2>/dev/null

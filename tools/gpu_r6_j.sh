@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 for i in 1 2 3; do
   for st in 1 2 3; do
-    timeout 120 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras --min-seconds 3 --streams $st 2>/dev/null | tail -1 > $OUT/streams${st}_$i.json
+    timeout 120 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras --min-seconds 3 --streams $st 2>/dev/null | tail -1 > $OUT/streams${st}_$i.json
   done
 done
 python - <<'PY'

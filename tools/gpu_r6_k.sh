@@ -9,7 +9,7 @@ cd $R
 timeout 900 python -m pytest tests -m gpu -q --timeout 240 > $OUT/pytest_gpu.log 2>&1
 echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 tail -4 $OUT/pytest_gpu.log
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_default.log 2> $OUT/bench_default.err
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_default.log 2> $OUT/bench_default.err
 tail -1 $OUT/bench_default.log > $OUT/bench_default_line.json
 head -c 600 $OUT/bench_default_line.json; echo
 grep -E "^\[bench\]|real" $OUT/bench_default.err | tail -8

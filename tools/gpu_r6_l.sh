@@ -10,7 +10,7 @@ timeout 900 python -m pytest tests -m gpu -q --timeout 240 > $OUT/pytest_gpu.log
 echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 tail -4 $OUT/pytest_gpu.log
 timeout 200 python tools/b1_modes.py 300 > $OUT/b1_modes.txt 2>&1; grep '"n": 500' $OUT/b1_modes.txt
-for i in 1 2; do timeout 120 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras --min-seconds 2 2>/dev/null | tail -1 > $OUT/headline_$i.json; done
+for i in 1 2; do timeout 120 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras --min-seconds 2 2>/dev/null | tail -1 > $OUT/headline_$i.json; done
 python - <<'PY'
 import json,glob,os
 for f in sorted(glob.glob(os.path.join(os.environ.get("GRAFT_REPO_ROOT","."),"gpurun_out/r06l/headline_*.json"))):

@@ -9,7 +9,7 @@ timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; echo "smoke r
 timeout 1200 python -m pytest tests -m gpu -q --timeout 240 > $OUT/pytest_gpu.log 2>&1
 echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 tail -6 $OUT/pytest_gpu.log | cut -c1-300
-timeout 900 python bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench rc=$?"
 tail -1 $OUT/bench_default.log > $OUT/bench_default_line.json
 cp gpurun_out/bench_extras.json $OUT/bench_extras.json 2>/dev/null
 python - <<'PY'

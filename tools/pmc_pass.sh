@@ -14,6 +14,6 @@ for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_
            "WRITE_SIZE TCC_MISS_sum TCC_REQ_sum" \
            "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum"; do
   i=$((i+1))
-  timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $ROOT/$OUT/pmc_${TAG}_$i -o p -- python $ROOT/bench.py --no-cpu --steps 3 --warmup 1 "$@" > $ROOT/$OUT/pmc_${TAG}_$i.log 2>&1
+  timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $ROOT/$OUT/pmc_${TAG}_$i -o p -- python $ROOT/bench.py --full --no-cpu --steps 3 --warmup 1 "$@" > $ROOT/$OUT/pmc_${TAG}_$i.log 2>&1
   echo "pass $i rc=$?"
 done

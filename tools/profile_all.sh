@@ -30,7 +30,7 @@ if total:
     shutil.copy("$R/profiles/two_opt_l2.json", "$OUT/two_opt_l2.json")      # (profiles/ on the GPU box does not travel back)
 EOF
 # 2. the bench line, its kernel trace, its counters
-python $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.log
+python $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o p -- python $R/bench.py --no-cpu --no-extras --min-seconds 0 > $OUT/bench_profiled.log 2>&1
 cp $OUT/stats/p_kernel_stats.csv $OUT/kernel_stats_bench_default.csv
 (cd $R && bash tools/pmc_pass.sh gpurun_out/$TAG/pmc final -- --no-extras --min-seconds 0 > /dev/null && python tools/pmc_summary.py gpurun_out/$TAG/pmc daco > $OUT/pmc_summary.txt)

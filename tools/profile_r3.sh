@@ -24,8 +24,8 @@ pmc() {   # pmc <tag> <command...>: one rocprofv3 pass per counter group (kernel
 }
 if [ "${2:-all}" != "pmc" ]; then
 # 1. the bench line (with extras and CPU legs), then the same command without the CPU legs under the kernel trace
-(cd $R && python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.log)
-(cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o p -- python bench.py --no-cpu --min-seconds 0 > $OUT/bench_profiled.log 2>&1)
+(cd $R && python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.log)
+(cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o p -- python bench.py --full --no-cpu --min-seconds 0 > $OUT/bench_profiled.log 2>&1)
 cp $OUT/stats/p_kernel_stats.csv $OUT/kernel_stats_bench_default.csv 2>/dev/null
 find $OUT/stats -name "*.db" -delete 2>/dev/null
 fi

@@ -34,7 +34,7 @@ stats() {  # stats <tag> <command...>: rocprofv3 --kernel-trace --stats of one c
 if [ "$WHAT" != "pmc" ] && [ "$WHAT" != "sparse" ]; then
   # the headline launches ONLY (no extras, no learned / gap colonies in the same kernel row), then the whole default bench
   stats headline python bench.py --no-cpu --no-extras --min-seconds 0
-  stats bench_default python bench.py --no-cpu --min-seconds 0
+  stats bench_default python bench.py --full --no-cpu --min-seconds 0
   (cd $R && python bench.py --no-cpu --no-extras --min-seconds 0 --batch 1 --steps 50 --warmup 5 2>/dev/null | grep "^{" > $OUT/bench_b1.json)
   (cd $R && python bench.py --gpus 2 --dist-backend gloo --force-device 0 --no-cpu --no-extras --min-seconds 0 --batch 32 2>/dev/null | grep "^{" > $OUT/bench_2ranks_one_gpu.json)
   (cd $R && python tools/run_train_step.py > $OUT/train_step.json 2>&1)

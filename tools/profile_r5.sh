@@ -50,7 +50,7 @@ fi
 if [ "$WHAT" != "pmc" ]; then
   stats headline python bench.py --no-cpu --no-extras --min-seconds 0
   stats headline_dense python bench.py --no-cpu --no-extras --min-seconds 0 --sampler scan
-  stats bench_default python bench.py --no-cpu --min-seconds 0
+  stats bench_default python bench.py --full --no-cpu --min-seconds 0
   stats train python tools/run_train_step.py 5
   stats siblings python tools/measure_siblings.py
   stats hgs_ls python tools/bench_hgs_ls.py --batch 64 --no-short
