@@ -495,8 +495,9 @@ def sibling_sample(kind, tau, eta, n_ants, alpha=1.0, beta=1.0, aux_vec=None, au
 
 
 def sibling_backward(kind, tau, eta, alpha, beta, paths, rowsum, grad_logp, lens=None, aux_vec=None, aux_mat=None,
-                     scalar0=0.0, item_weights=None):
-    """Gradient of sum(grad_logp * log_probs) w.r.t. eta for a fused sibling construction -> [B,n,n]."""
+                     scalar0=0.0, item_weights=None, out=None):
+    """Gradient of sum(grad_logp * log_probs) w.r.t. eta for a fused sibling construction -> [B,n,n].
+    `out`: a contiguous float32 [B,n,n] tensor the gradient is accumulated into (and returned) instead of fresh zeros."""
     _require_gpu(tau, eta, paths, rowsum, grad_logp, aux_vec, aux_mat, item_weights)
     n = tau.shape[-1]
     B, rows, A = paths.shape
@@ -519,7 +520,13 @@ def sibling_backward(kind, tau, eta, alpha, beta, paths, rowsum, grad_logp, lens
             item_weights = item_weights.unsqueeze(0).expand(B, n, mdim).contiguous()
     dev = paths.device
     with _on(dev):
-        grad = torch.zeros((B, n, n), dtype=torch.float32, device=dev)
+        if out is None:
+            grad = torch.zeros((B, n, n), dtype=torch.float32, device=dev)
+        else:
+            _require_gpu(out)
+            if out.dtype != torch.float32 or tuple(out.shape) != (B, n, n) or not out.is_contiguous():
+                raise _lib.DacoError(f"sibling_backward: out must be a contiguous float32 [{B}, {n}, {n}] tensor")
+            grad = out
         rc = _lib.lib().daco_sibling_backward(
             _stream(dev), SIB_KINDS[kind], B, n, A, rows, tau.data_ptr(), tbs, eta.data_ptr(), ebs, float(alpha),
             float(beta), aux_vec.data_ptr() if aux_vec is not None else None,

@@ -329,6 +329,11 @@ if __name__ == "__main__":
     print(f"{n_cases // 20} sibling cases (fused vs draw-by-draw), {s_bad} mismatches, {time.time() - t0:.1f} s")
     n_bad += s_bad
     t0 = time.time()
+    sg_bad = run_siblings(n_cases // 20, int(sys.argv[2]) if len(sys.argv) > 2 else 1, grad=True)
+    print(f"{n_cases // 20} sibling gradient cases (fused replay vs draw-by-draw autograd; the closed form holds both in "
+          f"tests/test_gpu_17_sibling_grad.py), {sg_bad} mismatches, {time.time() - t0:.1f} s")
+    n_bad += sg_bad
+    t0 = time.time()
     g_bad = run_grads(n_cases // 20, int(sys.argv[2]) if len(sys.argv) > 2 else 1)
     print(f"{n_cases // 20} gradient cases, {g_bad} mismatches, {time.time() - t0:.1f} s")
     n_bad += g_bad

@@ -186,6 +186,8 @@ def test_mkp(fix):
 
 
 def test_sibling_gradients_flow():
+    """Only that a gradient arrives.  What it is worth is held in tests/test_gpu_17_sibling_grad.py: all six problems against
+    the reference's own heuristic.grad (fixtures s7_grad_*) and against the float64 closed form of oracle/grad.py."""
     from deepaco_amd.smtwtp.aco import ACO
     g = load_golden("s4_smtwtp_n20")
     heu = T(g["heuristic"]).requires_grad_(True)

@@ -215,6 +215,56 @@ def test_grad_closed_form_cvrp():
     np.testing.assert_allclose(out, g["grad"], rtol=2e-4, atol=2e-6 * scale)
 
 
+S7 = ["s7_grad_sop_n20", "s7_grad_sop_n50", "s7_grad_pctsp_n20", "s7_grad_pctsp_n100", "s7_grad_op_n30", "s7_grad_op_n100",
+      "s7_grad_mkp_n20", "s7_grad_mkp_n50", "s7_grad_smtwtp_n20", "s7_grad_smtwtp_n50", "s7_grad_bpp_n24", "s7_grad_bpp_n120"]
+
+
+def s7_closed_form(name, g):
+    """(grad, log_probs or None, aux or None) of the float64 closed form on a s7_grad_* fixture's own solutions, with the
+    REINFORCE weights of its loss."""
+    from oracle import grad as ograd
+    kind = name.split("_")[2]
+    sols = g["sols"] if "sols" in g else g["paths"]
+    obj = (g["objs"] if "objs" in g else g["costs"]).astype(np.float64)
+    A = sols.shape[1]
+    a, b = float(g["alpha"]), float(g["beta"])
+    G = np.tile(((obj - obj.mean()) / A)[None, :], (g["log_probs"].shape[0], 1))
+    tau, eta = g["pheromone"], g["heuristic"]
+    if kind == "smtwtp":                       # a permutation after the dummy start node 0: the TSP form
+        full = np.concatenate((np.zeros((1, A), sols.dtype), sols))
+        return ograd.tsp_grad(tau, eta, a, b, full, G), None, None
+    if kind == "bpp":                          # the CVRP form with the items' sizes as demands
+        return ograd.cvrp_grad(tau, eta, a, b, g["demand"], float(g["capacity"]), sols, G), None, None
+    problem = {"sop": lambda: dict(prec_cons=g["prec_cons"]),
+               "pctsp": lambda: dict(prizes=g["prizes"], min_prizes=len(g["prizes"]) / 4),
+               "op": lambda: dict(distances=g["distances"], max_len=float(g["max_len"])),
+               "mkp": lambda: dict(weight=g["weight"], cap=(g["weight"].shape[0] - 1) // 2)}[kind]()
+    out, aux = ograd.sibling_grad(kind, tau, eta, a, b, sols, None, G, **problem)
+    return out, aux["logp"], aux
+
+
+@pytest.mark.parametrize("name", S7)
+def test_grad_closed_form_siblings(name):
+    """s7_grad_* (tests/golden/gen_s7_sibling_grads.py): the float64 closed form on the reference's solutions gives the
+    reference's log_probs and heuristic.grad, at the tolerance the g3 gradient fixtures carry on the GPU
+    (rtol 3e-4, atol 3e-6 max|grad|: the reference's float32 autograd against float64).  The worst ratio
+    |closed - ref| / (atol + rtol |ref|) of every fixture is in DESIGN.md section 5; the largest is 0.16 (sop 50)."""
+    g = load_golden(name)
+    out, logp, aux = s7_closed_form(name, g)
+    ref = g["grad"].astype(np.float64)
+    scale = np.abs(ref).max()
+    ratio = np.abs(out - ref) / (3e-6 * scale + 3e-4 * np.abs(ref))
+    assert ratio.max() <= 1.0, f"{name}: worst |closed - ref| / tol = {ratio.max():.3g} at scale {scale:.3g}"
+    # (support: where the closed form is non-zero so is the reference; the converse fails only in row 0, which all ants leave
+    # by the same draw: the weights obj - mean sum to zero there and float32 leaves a 1e-8 residue where float64 leaves none)
+    assert (ref[out != 0] != 0).all() and (out[1:][ref[1:] != 0] != 0).all(), name
+    if logp is not None:
+        np.testing.assert_allclose(logp, g["log_probs"], atol=2e-6, rtol=1e-5)
+        # the fixture is worth having: most draws carry gradient
+        assert aux["unclamped"].mean() >= 0.5
+    assert (ref != 0).sum() >= ref.shape[0]
+
+
 @pytest.mark.parametrize("name", names("g5_net"))
 def test_gnn_restatement(name):
     """oracle/gnn.py against Net.forward of the reference with its shipped checkpoints (eval + train BN)."""
