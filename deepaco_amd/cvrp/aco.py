@@ -98,54 +98,37 @@ class ACO():
     # ------------------------------------------------------------------ cvrp/aco.py:72-104
     @torch.no_grad()
     def run(self, n_iterations):
-        """The reference's loop (cvrp/aco.py:72-104) without its per-iteration host round trips: route costs and
-        the deposit's successor table come fused out of the construction kernel and the `if best_cost <
-        self.lowest_cost` bookkeeping is daco_track_best.  One sync at the end trims `shortest_path` to its route.
+        """The reference's loop (cvrp/aco.py:72-104) without its per-iteration host round trips, as a one-instance
+        engine.BatchedCVRP kept with this object: route costs and the deposit's successor table come fused out of the
+        construction kernel and the `if best_cost < self.lowest_cost` bookkeeping is daco_track_best.  One sync at the end
+        reads the flag words and trims `shortest_path` to its route.
         (If `gen_path` / `gen_path_costs` were replaced on the instance, the plain call sequence runs instead.)"""
         if "gen_path" in self.__dict__ or "gen_path_costs" in self.__dict__ or type(self).gen_path is not ACO.gen_path \
                 or type(self).gen_path_costs is not ACO.gen_path_costs:
             return self._run_plain(n_iterations)
-        dev = self.distances.device
-        dist = self.distances.detach().float().contiguous()
-        n = self.problem_size
-        lowest = torch.as_tensor(self.lowest_cost, dtype=torch.float32, device=dev).reshape(1).clone()
-        shortest = torch.zeros((1, 2 * n + 1), dtype=torch.int64, device=dev)
+        key = (self.distances, self.demand, self.heuristic, self.capacity, self.sampler, self.n_ants, self.decay, self.alpha,
+               self.beta, bool(self.elitist), bool(self.min_max), self.seed)
+        hit = self.__dict__.get("_colony")
+        if hit is None or not engine.same_state(hit[0], key):
+            col = engine.BatchedCVRP(self.distances.detach().float().contiguous().unsqueeze(0), self.demand.detach(),
+                                     n_ants=self.n_ants, decay=self.decay, alpha=self.alpha, beta=self.beta, elitist=self.elitist,
+                                     min_max=self.min_max, heuristic=self.heuristic.detach().to(torch.float32).contiguous().unsqueeze(0),
+                                     min=self.min if self.min_max else None, capacity=self.capacity, sampler=self.sampler,
+                                     seed=self.seed)
+            hit = self._colony = (key, col)
+        col = hit[1]
+        shortest = torch.zeros((1, 2 * self.problem_size + 1), dtype=torch.int64, device=self.distances.device)
         if self.shortest_path is not None:
             shortest[0, :self.shortest_path.numel()] = self.shortest_path
-        flags_seen = torch.zeros(1, dtype=torch.int32, device=dev)
-        # one private copy for the whole loop (see tsp/aco.py run): updated in place, rebound at the end
-        tau = self.pheromone.detach().to(torch.float32).clone().contiguous().unsqueeze(0)
-        eta = self.heuristic.detach()
-        cmin_t = torch.full((1,), float(self.min), device=dev) if self.min_max else None
-        # (loop invariants formed once: at CVRP-20 / 100 with 20 ants an iteration is three library calls whose HOST time is the
-        # iteration time -- tools/host_overhead_small.py -- so the demands are laid out [1, n] here, not copied per call, and the
-        # flag words are the loop's own, OR-ed into by every construction)
-        dem = self.demand.detach()
-        dem = (dem if dem.dtype == torch.float64 else dem.to(torch.float32)).reshape(1, -1).contiguous()
-        for _ in range(n_iterations):
-            paths, _, _, lens, _, costs, table = engine.cvrp_sample(
-                tau, eta, dem, self.capacity, self.n_ants, self.alpha,
-                self.beta, mode=self.sampler, seed=self.seed, it=self._calls, batch=1, dist=dist, want_table=True, flags=flags_seen)
-            self._calls += 1
-            new_max = engine.track_best_(costs, paths, lowest, shortest,
-                                         mmas_scale=self.problem_size if self.min_max else None)
-            cmin = cmax = None
-            if self.min_max:
-                if self.max is None:
-                    tau *= new_max[0] / tau.max()
-                self.max = new_max[0]
-                cmin, cmax = cmin_t, new_max
-            engine.pheromone_update_(tau, paths, costs, self.decay, self.elitist, False, cmin, cmax, floor=1e-10,
-                                     nbr=table)
-        self.pheromone = tau[0]
-        fl = int(flags_seen[0])                      # the only host sync of the loop
+        engine.run_kept_colony(self, col, n_iterations, shortest)
+        fl = int(col._flags[0])                      # the only host sync of the loop
         if fl & 1:
             raise ValueError("ACO.run: a transition row had no feasible candidate")
         if fl & 2:
             raise RuntimeError("ACO.run: route buffer too short")
-        route = shortest[0]
+        route = col.shortest_path[0]
         last = int(torch.nonzero(route).max()) if bool((route != 0).any()) else 0
-        self.lowest_cost, self.shortest_path = lowest[0], route[:last + 2].clone()
+        self.shortest_path = route[:last + 2].clone()
         return self.lowest_cost
 
     @torch.no_grad()

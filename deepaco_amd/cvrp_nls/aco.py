@@ -99,7 +99,7 @@ class ACO(_CvrpACO):
     def heuristic_dist(self):
         if self._heuristic_dist is None:
             heu = self.heuristic.detach().float()
-            self._heuristic_dist = (1 / (heu / heu.max(-1, keepdim=True).values + 1e-5)).contiguous()
+            self._heuristic_dist = engine.heuristic_dist(heu)
         return self._heuristic_dist
 
     # ------------------------------------------------------------------ cvrp_nls/aco.py:273-287
@@ -133,7 +133,7 @@ class ACO(_CvrpACO):
                 heu = self.heuristic.detach()
             else:
                 heu = self._heu_src if self._heu_src is not None else 1 / self._dist_src
-            hd = 1 / (heu / heu.max(-1, keepdim=True).values + 1e-5)
+            hd = engine.heuristic_dist(heu)
             self._hgs = (engine.HgsTables(self._dist_src), engine.HgsTables(hd))
         return self._hgs
 

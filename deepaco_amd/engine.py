@@ -85,6 +85,42 @@ def _bstride(t, n):
     return (t, 0) if t.dim() == 2 else (t, n * n)
 
 
+def _rows(t, B, dtype=torch.float32):
+    """Per-node values [n] (shared by the B instances) or [B, n] -> contiguous [B, n] of `dtype`."""
+    t = t if (t.dtype == dtype and t.is_contiguous()) else t.contiguous().to(dtype)
+    return t if t.dim() == 2 else t.unsqueeze(0).expand(B, -1).contiguous()
+
+
+def _demand_rows(demand, B):
+    """(float32 demands [B, n], the float64 ones | None): float64 demands select the float64 load bookkeeping (cvrp_sample)."""
+    return _rows(demand, B), (_rows(demand, B, torch.float64) if demand.dtype == torch.float64 else None)
+
+
+def _sibling_aux(B, n, aux_vec, aux_mat, item_weights):
+    """daco_sibling_sample's instance data as the kernels take it: (aux_vec [B,n] | None, aux_mat | None, its instance stride,
+    item_weights [B,n,m] | None, m)."""
+    if aux_vec is not None:
+        aux_vec = _f32c(aux_vec).reshape(-1, n)
+        if aux_vec.shape[0] != B:
+            aux_vec = aux_vec.expand(B, n).contiguous()
+    abs_ = 0
+    if aux_mat is not None:
+        aux_mat, abs_ = _bstride(aux_mat, n)
+    mdim = 0
+    if item_weights is not None:
+        item_weights = _f32c(item_weights)
+        mdim = item_weights.shape[-1]
+        if item_weights.dim() == 2:
+            item_weights = item_weights.unsqueeze(0).expand(B, n, mdim).contiguous()
+    return aux_vec, aux_mat, abs_, item_weights, mdim
+
+
+def heuristic_dist(h):
+    """The perturbation matrix of the neural-guided local searches (tsp_nls/aco.py:230-232, cvrp_nls/aco.py:128-132), in h's
+    dtype: small where the heuristic is large relative to its row's maximum."""
+    return (1 / (h / h.amax(dim=-1, keepdim=True) + 1e-5)).contiguous()
+
+
 def tsp_sample(tau, eta, n_ants, alpha=1.0, beta=1.0, mode="scan", norm_passes=1, start=None,
                fixed_start=-1, noise=None, seed=0, it=0, ant_gid0=0, require_prob=False, batch=None,
                events=None, dist=None, want_nbr=False, iter_dev=None, ant_gid_bstride=0, flags=None):
@@ -248,6 +284,14 @@ def take_auto_top(cache, heuristic):
     return hit[1] if hit is not None and hit[0] is heuristic else None
 
 
+def head_table(heuristic, k, B, cache=None):
+    """sparse_head(.., k) of a colony's heuristic object ([n,n] shared, or [B,n,n]) for its B instances; cache: the colony's
+    resolve_sampler cache, whose sorted top values for this object are taken (take_auto_top)."""
+    h = heuristic.detach()
+    h = h if h.dim() == 3 else h.unsqueeze(0).expand(B, *h.shape)
+    return sparse_head(_f32c(h), k, top=take_auto_top(cache, heuristic))
+
+
 def sparse_workspace(device, B, n, n_ants, unit_exponents=True):
     """A scratch tensor of the head-row samplers that a colony KEEPS (daco_tsp_sparse_workspace_bytes: the iteration's head rows
     and, for n > 512, the tours as they are built): pheromone_update_(heads=...) writes the next iteration's head rows into it and
@@ -347,14 +391,7 @@ def cvrp_sample(tau, eta, demand, capacity, n_ants, alpha=1.0, beta=1.0, mode="s
     dev = tau.device
     tau, tbs = _bstride(tau, n)
     eta, ebs = _bstride(eta, n)
-    demand64 = None
-    if demand.dtype == torch.float64:
-        demand64 = demand.detach().contiguous()
-        if demand64.dim() == 1:
-            demand64 = demand64.unsqueeze(0).expand(B, n).contiguous()
-    demand = _f32c(demand)
-    if demand.dim() == 1:
-        demand = demand.unsqueeze(0).expand(B, n).contiguous()
+    demand, demand64 = _demand_rows(demand, B)
     m = MODES[mode] if isinstance(mode, str) else int(mode)
     Lmax = Lmax or 2 * n + 1
     L = _lib.lib()
@@ -411,13 +448,7 @@ def sample_backward(tau, eta, alpha, beta, paths, rowsum, grad_logp, lens=None, 
     dev = paths.device
     demand64 = None
     if demand is not None:
-        if demand.dtype == torch.float64:                  # replay the capacity rule in double, as the sampler applied it
-            demand64 = demand.detach().contiguous()
-            if demand64.dim() == 1:
-                demand64 = demand64.unsqueeze(0).expand(B, n).contiguous()
-        demand = _f32c(demand)
-        if demand.dim() == 1:
-            demand = demand.unsqueeze(0).expand(B, n).contiguous()
+        demand, demand64 = _demand_rows(demand, B)         # (float64: the capacity rule is replayed in double, as the sampler applied it)
         lens = lens.contiguous()
     with _on(dev):
         grad = torch.zeros((B, n, n), dtype=torch.float32, device=dev)
@@ -450,19 +481,7 @@ def sibling_sample(kind, tau, eta, n_ants, alpha=1.0, beta=1.0, aux_vec=None, au
     varlen = kind != "sop"
     rows = (Lmax or 2 * n + 1) if varlen else n
     m = MODES[mode] if isinstance(mode, str) else int(mode)
-    if aux_vec is not None:
-        aux_vec = _f32c(aux_vec).reshape(-1, n)
-        if aux_vec.shape[0] != B:
-            aux_vec = aux_vec.expand(B, n).contiguous()
-    abs_ = 0
-    if aux_mat is not None:
-        aux_mat, abs_ = _bstride(aux_mat, n)
-    mdim = 0
-    if item_weights is not None:
-        item_weights = _f32c(item_weights)
-        mdim = item_weights.shape[-1]
-        if item_weights.dim() == 2:
-            item_weights = item_weights.unsqueeze(0).expand(B, n, mdim).contiguous()
+    aux_vec, aux_mat, abs_, item_weights, mdim = _sibling_aux(B, n, aux_vec, aux_mat, item_weights)
     L = _lib.lib()
     with _on(dev):
         paths = torch.empty((B, rows, n_ants), dtype=torch.int64, device=dev)
@@ -505,19 +524,7 @@ def sibling_backward(kind, tau, eta, alpha, beta, paths, rowsum, grad_logp, lens
     eta, ebs = _bstride(eta, n)
     paths = paths.contiguous()
     rowsum, grad_logp = _f32c(rowsum), _f32c(grad_logp)
-    if aux_vec is not None:
-        aux_vec = _f32c(aux_vec).reshape(-1, n)
-        if aux_vec.shape[0] != B:
-            aux_vec = aux_vec.expand(B, n).contiguous()
-    abs_ = 0
-    if aux_mat is not None:
-        aux_mat, abs_ = _bstride(aux_mat, n)
-    mdim = 0
-    if item_weights is not None:
-        item_weights = _f32c(item_weights)
-        mdim = item_weights.shape[-1]
-        if item_weights.dim() == 2:
-            item_weights = item_weights.unsqueeze(0).expand(B, n, mdim).contiguous()
+    aux_vec, aux_mat, abs_, item_weights, mdim = _sibling_aux(B, n, aux_vec, aux_mat, item_weights)
     dev = paths.device
     with _on(dev):
         if out is None:
@@ -849,9 +856,7 @@ def cvrp_local_search_(dist, demand, capacity, paths, max_moves, want_stats=Fals
     assert p3.is_contiguous()
     B, Lmax, A = p3.shape
     dist, dbs = _bstride(dist, n)
-    demand = _f32c(demand)
-    if demand.dim() == 1:
-        demand = demand.unsqueeze(0).expand(B, n).contiguous()
+    demand = _rows(demand, B)
     dev = paths.device
     with _on(dev):
         lens = torch.empty((B, A), dtype=torch.int32, device=dev) if want_stats else None
@@ -1002,6 +1007,92 @@ def nls_(dist, heuristic_dist, tours, maxt, T_nls=10, T_p=20, dist_t=None, heuri
     return (best, best_costs) if want_costs else best
 
 
+class TspLocalSearch:
+    """The local search of tsp_nls/aco.py:234-258 on a batch of colonies' tours, with what it derives from their matrices once:
+    the transposed distances and their TwoOptTables, and -- for "nls" -- the perturbation matrix with its transpose and tables,
+    formed from the heuristic at first use and kept (the reference's cached_property)."""
+
+    def __init__(self, distances):
+        self.distances = distances                # [B,n,n] f32 contiguous
+        self.dist_t = self.tables = None
+        self.hdist = self.hdist_t = self.htables = None
+
+    def heuristic_dist(self, heuristic):
+        if self.hdist is None:
+            self.hdist = heuristic_dist(heuristic.detach().float())
+        return self.hdist
+
+    def improve(self, paths, kind, inference=False, heuristic=None, T_nls=10, T_p=20, want_costs=True, counters=None, events=None):
+        """paths [B,n,A] int64 as the samplers return them -> (the improved paths, their costs [B,A] | None: with want_costs the
+        fused NLS sums the tour lengths in daco_tour_costs' order, bit for bit; 2-opt leaves costing to the caller).
+        kind: "2opt" | "nls" (perturbation matrix from `heuristic`); inference: 2-opt sweeps to convergence (10000) instead of
+        n // 4 (tsp_nls/aco.py:235,242); events: a torch.cuda.Event pair recorded right before / after the search's launches."""
+        maxt = 10000 if inference else self.distances.shape[-1] // 4
+        tours = paths.permute(0, 2, 1).to(torch.int16).contiguous()
+        if events:
+            events[0].record()
+        if self.dist_t is None:
+            self.dist_t = transposed_for_two_opt(self.distances)
+            self.tables = two_opt_tables(self.distances, self.dist_t)
+        costs = None
+        if kind == "2opt":
+            two_opt_(self.distances, tours, maxt, dist_t=self.dist_t, tables=self.tables)
+        else:
+            hd = self.heuristic_dist(heuristic)
+            if self.hdist_t is None:
+                self.hdist_t = transposed_for_two_opt(hd)
+                self.htables = two_opt_tables(hd, self.hdist_t)
+            tours = nls_(self.distances, hd, tours, maxt, T_nls=T_nls, T_p=T_p, dist_t=self.dist_t,
+                         heuristic_dist_t=self.hdist_t, tables=self.tables, heuristic_tables=self.htables,
+                         want_costs=want_costs, counters=counters)
+            if want_costs:
+                tours, costs = tours
+        if events:
+            events[1].record()
+        return tours.permute(0, 2, 1).to(torch.int64).contiguous(), costs
+
+
+def same_state(kept, now):
+    """Is `kept` (a tuple a colony remembered, or None) the state `now`?  Tensors by identity, everything else by value."""
+    return kept is not None and len(kept) == len(now) and all(
+        (a is b) if torch.is_tensor(a) else (a == b) for a, b in zip(kept, now))
+
+
+def _mmas_bounds(col, new_max):
+    """The MMAS part of an iteration (tsp/aco.py:84-88, 113-115) for a batched colony: the first record rescales the pheromone
+    to its upper bound; returns the deposit's clamps (cmin, cmax) -- (None, None) for a colony without min_max."""
+    if not col.min_max:
+        return None, None
+    if col.max is None:
+        col.pheromone *= (new_max / col.pheromone.amax(dim=(1, 2))).view(col.B, 1, 1)
+    col.max = new_max
+    if col._cmin is None:
+        col._cmin = torch.full_like(new_max, col.min)
+    return col._cmin, new_max
+
+
+def run_kept_colony(aco, col, n_iterations, shortest):
+    """ACO.run of the drop-in classes (tsp.ACO, cvrp.ACO) on the one-instance batched colony `col` they keep: the object's
+    state is carried in -- a private copy of its pheromone for the whole loop, rebound at the end (the reference rebinds
+    self.pheromone every iteration, tsp/aco.py:101: a tensor the caller still holds is never modified), the record (`shortest`:
+    its best solution as the colony's [1, len] row), the MMAS bound and the iteration counter `_calls` -- and out again."""
+    dev = col.distances.device
+    col.pheromone = aco.pheromone.detach().to(torch.float32).clone().contiguous().unsqueeze(0)
+    col.lowest_cost = torch.as_tensor(aco.lowest_cost, dtype=torch.float32, device=dev).reshape(1).clone()
+    col.shortest_path = shortest
+    col.iteration = aco._calls
+    if aco.min_max:
+        col.min, col._cmin = aco.min, None
+        col.max = None if aco.max is None else torch.as_tensor(aco.max, dtype=torch.float32, device=dev).reshape(1).clone()
+    col._flags.zero_()
+    col.run(n_iterations)
+    aco._calls = col.iteration
+    if aco.min_max and col.max is not None:
+        aco.max = col.max[0]
+    aco.pheromone = col.pheromone[0]
+    aco.lowest_cost = col.lowest_cost[0]
+
+
 class BatchedTSP:
     """B independent TSP colonies advanced in lock-step on one GPU (the throughput path).
 
@@ -1010,9 +1101,10 @@ class BatchedTSP:
 
     def __init__(self, distances, n_ants=20, decay=0.9, alpha=1, beta=1, elitist=False, min_max=False,
                  pheromone=None, heuristic=None, min=None, sampler="auto", seed=None, ant_gid0=0,
-                 fixed_start=-1, local_search=None, inference=False):
+                 fixed_start=-1, local_search=None, inference=False, norm_passes=1):
         """sampler: 'auto' (default: head / tail rows where they apply -- after sparsify(k) or on a concentrated heuristic,
-        129 <= n <= 1024 -- else the dense scan; resolve_sampler), 'scan', 'scan_wave', 'race', 'scan_sparse'."""
+        129 <= n <= 1024 -- else the dense scan; resolve_sampler), 'scan', 'scan_wave', 'race', 'scan_sparse'.
+        norm_passes: tsp_sample's (2: the row renormalised before Categorical normalises it again, tsp_nls/aco.py:206-207)."""
         _require_gpu(distances)
         assert distances.dim() == 3
         self.distances = _f32c(distances)
@@ -1035,13 +1127,11 @@ class BatchedTSP:
         self.iteration = 0
         self.ant_gid0 = ant_gid0
         self.fixed_start = fixed_start
+        self.norm_passes = norm_passes
         assert local_search in (None, "2opt", "nls")
         self.local_search = local_search          # tsp_nls/aco.py: applied to the tours before costing
         self.inference = inference                # tsp_nls/aco.py:235,242: 2-opt sweeps n//4 (training) or 10000 (inference)
-        self._hdist = None
-        self._hdist_t = None
-        self._dist_t = None
-        self._tables = self._htables = None
+        self._ls = TspLocalSearch(self.distances)
         self._cmin = None
         self.nls_counters = None                  # optional int64[2] on the device: sweeps, list entries walked (bench)
         # sampler="scan_sparse": head / tail rows (tsp_sample_sparse).  The head of a row = the k largest heuristic entries:
@@ -1069,10 +1159,7 @@ class BatchedTSP:
         return (self.pheromone, self.pheromone._version, self.heuristic, head, bool(race), float(self.alpha), float(self.beta))
 
     def _heuristic_dist(self):
-        if self._hdist is None:
-            h = self.heuristic.detach().float()
-            self._hdist = (1 / (h / h.amax(dim=-1, keepdim=True) + 1e-5)).contiguous()
-        return self._hdist
+        return self._ls.heuristic_dist(self.heuristic)
 
     @torch.no_grad()
     def sparsify(self, k_sparse):
@@ -1094,9 +1181,7 @@ class BatchedTSP:
         """(heuristic object it was built from, [B,n,64] head ids) for sampler='scan_sparse'."""
         if self._head is None or self._head[0] is not self.heuristic or (k is not None and self._head[2] != k):
             k = k if k is not None else (self.head_k if self.head_k is not None else max(1, min(127, self.n // 10)))
-            h = self.heuristic.detach()
-            h = h if h.dim() == 3 else h.unsqueeze(0).expand(self.B, self.n, self.n)
-            self._head = (self.heuristic, sparse_head(_f32c(h), k, top=take_auto_top(getattr(self, "_auto", None), self.heuristic)), k)
+            self._head = (self.heuristic, head_table(self.heuristic, k, self.B, getattr(self, "_auto", None)), k)
         return self._head[1]
 
     @torch.no_grad()
@@ -1109,7 +1194,12 @@ class BatchedTSP:
         # events: torch.cuda.Event pair re-recorded around the construction kernel; ls_events: a pair recorded (on the
         # current stream, which is the stream the library launches on) right before / after the local-search launches
         # sampler="race" after sparsify(k): the same tours from the head rows (daco_tsp_sample_race_head), an eighth of the noise
-        sampler, hk = self.resolved_sampler()
+        return self._step(events, _iter_dev, ls_events, want_paths)
+
+    def _step(self, events=None, _iter_dev=None, ls_events=None, want_paths=True, resolved=None):
+        """step() without what run() does once for its whole loop: the no_grad context and resolved_sampler() (`resolved`) -- 2-3 us
+        per iteration, a twentieth of a TSP-20 iteration whose three library calls' HOST time is the iteration time."""
+        sampler, hk = resolved or self.resolved_sampler()
         race_head = sampler == "race" and self.head_k is not None and 128 < self.n <= 1024
         heads = None
         if sampler == "scan_sparse" or race_head:
@@ -1119,9 +1209,7 @@ class BatchedTSP:
                 self._sparse_ws = sparse_workspace(self.distances.device, self.B, self.n, self.n_ants, unit_exponents=unit)
             fused = self.fuse_head_rows and unit                 # (the update forms the rows of tau itself: unit exponents only)
             grouped = fused and self.n_ants % 8 == 0 and self.local_search is None
-            st = self._heads_state(head, race_head)
-            ready = self._heads_for is not None and len(st) == len(self._heads_for) and all(
-                (a is b) if torch.is_tensor(a) else (a == b) for a, b in zip(st, self._heads_for))
+            ready = same_state(self._heads_for, self._heads_state(head, race_head))
             compact = not want_paths and self.local_search is None
             paths, _, costs, nbr = tsp_sample_sparse(self.pheromone, self.heuristic, self.n_ants, head, self.alpha,
                                                      self.beta, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0,
@@ -1139,44 +1227,17 @@ class BatchedTSP:
                                                     self.beta, mode=sampler, seed=self.seed, it=self.iteration,
                                                     ant_gid0=self.ant_gid0, fixed_start=self.fixed_start,
                                                     batch=self.B, events=events, dist=self.distances, want_nbr=True,
-                                                    iter_dev=_iter_dev)
+                                                    iter_dev=_iter_dev, norm_passes=self.norm_passes, flags=self._flags)
         if _iter_dev is None:
             self.iteration += 1
         if self.local_search is not None:
-            ls_costs = None
-            tours = paths.permute(0, 2, 1).to(torch.int16).contiguous()
-            if ls_events:
-                ls_events[0].record()
-            maxt = 10000 if self.inference else self.n // 4
-            if self._dist_t is None:
-                self._dist_t = transposed_for_two_opt(self.distances)
-                self._tables = two_opt_tables(self.distances, self._dist_t)
-            if self.local_search == "2opt":
-                two_opt_(self.distances, tours, maxt, dist_t=self._dist_t, tables=self._tables)
-            else:
-                hd = self._heuristic_dist()
-                if self._hdist_t is None:
-                    self._hdist_t = transposed_for_two_opt(hd)
-                    self._htables = two_opt_tables(hd, self._hdist_t)
-                # (costs: the fused search sums the tour lengths in daco_tour_costs' order, bit for bit)
-                tours, ls_costs = nls_(self.distances, hd, tours, maxt, dist_t=self._dist_t,
-                                       heuristic_dist_t=self._hdist_t, tables=self._tables,
-                                       heuristic_tables=self._htables, want_costs=True, counters=self.nls_counters)
-            if ls_events:
-                ls_events[1].record()
-            paths = tours.permute(0, 2, 1).to(torch.int64).contiguous()
+            paths, ls_costs = self._ls.improve(paths, self.local_search, self.inference, self.heuristic,
+                                               counters=self.nls_counters, events=ls_events)
             costs, nbr = (tour_costs(self.distances, paths) if ls_costs is None else ls_costs), None
         # in place: the best-so-far state lives at fixed addresses (a captured graph replays these very writes)
         new_max = track_best_(costs, paths, self.lowest_cost, self.shortest_path,
                               mmas_scale=self.n if self.min_max else None, tours16=tours16)
-        cmin = cmax = None
-        if self.min_max:
-            if self.max is None:
-                self.pheromone *= (new_max / self.pheromone.amax(dim=(1, 2))).view(self.B, 1, 1)
-            self.max = new_max
-            if self._cmin is None:
-                self._cmin = torch.full_like(new_max, self.min)
-            cmin, cmax = self._cmin, new_max
+        cmin, cmax = _mmas_bounds(self, new_max)
         pheromone_update_(self.pheromone, paths, costs, self.decay, self.elitist, True, cmin, cmax, nbr=nbr, heads=heads)
         self._heads_for = self._heads_state(heads["head"], heads["race"]) if heads is not None else None
         return paths, costs
@@ -1188,22 +1249,23 @@ class BatchedTSP:
         loop: the Philox iteration counter of the captured sampler lives in device memory and is advanced inside
         the graph."""
         if not graph or n_iterations < 3:
+            resolved = self.resolved_sampler()
             for _ in range(n_iterations):
-                self.step(want_paths=False)
+                self._step(want_paths=False, resolved=resolved)
             return self.lowest_cost
-        self.step(want_paths=False)                        # eager: workspaces, first-iteration MMAS rescale
+        self._step(want_paths=False)                       # eager: workspaces, first-iteration MMAS rescale
         dev = self.distances.device
         it_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         torch.cuda.synchronize(dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):                      # one un-captured pass on the capture stream (allocator warm-up)
-            self.step(_iter_dev=it_dev, want_paths=False)
+            self._step(_iter_dev=it_dev, want_paths=False)
             it_dev += 1
         torch.cuda.current_stream(dev).wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=side):
-            self.step(_iter_dev=it_dev, want_paths=False)
+            self._step(_iter_dev=it_dev, want_paths=False)
             it_dev += 1
         for _ in range(n_iterations - 2):
             g.replay()
@@ -1331,14 +1393,17 @@ class BatchedCVRP:
         self._ls_src = (distances.detach(), demand.detach())
         self._hgs = None
         self.distances = _f32c(distances)
-        # float64 demands (cvrp_nls/utils.py:12-26) keep the load bookkeeping of the construction in double, as cvrp_sample does
-        self.demand = demand.contiguous() if demand.dtype == torch.float64 else _f32c(demand)
         self.B, self.n = distances.shape[0], distances.shape[1]
+        # laid out [B, n] once (at CVRP-20 / 100 with 20 ants an iteration is three library calls whose HOST time is the iteration
+        # time -- tools/host_overhead_small.py); float64 demands (cvrp_nls/utils.py:12-26) stay float64: cvrp_sample then keeps the
+        # load bookkeeping of the construction in double
+        self.demand = _rows(demand, self.B, torch.float64 if demand.dtype == torch.float64 else torch.float32)
         self.n_ants, self.decay, self.alpha, self.beta, self.capacity = n_ants, decay, alpha, beta, capacity
         self.elitist, self.min_max = elitist, min_max
         if min_max:
             self.min = 0.1 if min is None else min
             self.max = None
+        self._cmin = None
         self.pheromone = torch.ones_like(self.distances) if pheromone is None else _f32c(pheromone).clone()
         if min_max and pheromone is None:
             self.pheromone = self.pheromone * self.min
@@ -1348,6 +1413,8 @@ class BatchedCVRP:
         self.shortest_path = None               # [B, Lmax] int64 once a step has run (zero-padded routes)
         self.sampler, self.iteration, self.ant_gid0 = sampler, 0, ant_gid0
         self.seed = torch.initial_seed() if seed is None else seed
+        # sticky, OR-ed into by every construction (no fill launch per step): bit 0 a draw without a candidate, bit 1 route buffer too short
+        self._flags = torch.zeros((self.B,), dtype=torch.int32, device=distances.device)
 
     @torch.no_grad()
     def step(self, Lmax=None, trim=False, events=None):
@@ -1355,10 +1422,14 @@ class BatchedCVRP:
         successor table the directed deposit consumes.  Returns (paths [B, Lmax, A], costs [B, A]); rows past
         an ant's route are 0 (self.last_lens holds the used rows; trim=True cuts to their maximum, which syncs).
         events: see cvrp_sample."""
+        return self._step(Lmax, trim, events)
+
+    def _step(self, Lmax=None, trim=False, events=None):
+        """step() without its no_grad context, for run()'s loop under its own (see BatchedTSP._step)."""
         paths, _, _, lens, flags, costs, table = cvrp_sample(
             self.pheromone, self.heuristic, self.demand, self.capacity, self.n_ants, self.alpha, self.beta,
             mode=self.sampler, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0, Lmax=Lmax, batch=self.B,
-            dist=self.distances, want_table=True, events=events)
+            dist=self.distances, want_table=True, events=events, flags=self._flags)
         self.iteration += 1
         self.last_lens, self.last_flags = lens, flags
         if self.local_search == "hgs":
@@ -1368,7 +1439,7 @@ class BatchedCVRP:
                 # 1 / distances is taken from the distances in the dtype they were passed in (float64 instance data).
                 d_src, dem_src = self._ls_src
                 heu = (1 / d_src) if self.heuristic is self._own_heuristic else self.heuristic.detach()
-                hd = 1 / (heu / heu.max(-1, keepdim=True).values + 1e-5)
+                hd = heuristic_dist(heu)
                 td = self._hgs[0] if self._hgs is not None else HgsTables(d_src)
                 self._hgs = (td, HgsTables(hd), dem_src.double() / float(self.capacity), self.heuristic)
             td, th, dem_n, _ = self._hgs
@@ -1388,12 +1459,7 @@ class BatchedCVRP:
             self.shortest_path = torch.zeros((self.B, paths.shape[1]), dtype=torch.int64, device=paths.device)
         new_max = track_best_(costs, paths, self.lowest_cost, self.shortest_path,
                               mmas_scale=self.n if self.min_max else None)
-        cmin = cmax = None
-        if self.min_max:
-            if self.max is None:
-                self.pheromone *= (new_max / self.pheromone.amax(dim=(1, 2))).view(self.B, 1, 1)
-            self.max = new_max
-            cmin, cmax = torch.full_like(new_max, self.min), new_max.contiguous()
+        cmin, cmax = _mmas_bounds(self, new_max)
         pheromone_update_(self.pheromone, paths, costs, self.decay, self.elitist, False, cmin, cmax, floor=1e-10,
                           nbr=table)
         if trim:
@@ -1401,7 +1467,7 @@ class BatchedCVRP:
         return paths, costs
 
     def check_feasible(self):
-        """Raise like the reference's Categorical if any draw of the last step had no feasible candidate (syncs)."""
+        """Raise like the reference's Categorical if any draw so far had no feasible candidate (syncs; the flag words are sticky)."""
         fl = int(self.last_flags.max())
         if fl & 1:
             raise ValueError("BatchedCVRP: a transition row had no feasible candidate")
@@ -1411,7 +1477,7 @@ class BatchedCVRP:
     @torch.no_grad()
     def run(self, n_iterations):
         for _ in range(n_iterations):
-            self.step()
+            self._step()
         return self.lowest_cost
 
 
@@ -1432,7 +1498,8 @@ def ant_sharded_tsp(distances, n_ants, rank, world, decay=0.9, alpha=1.0, beta=1
     dist_ = _f32c(distances)
     B, n, _ = dist_.shape
     eta = (1 / dist_) if heuristic is None else heuristic
-    state, cache = {}, {}
+    state, auto = {}, {}                           # (auto: what resolve_sampler keeps per heuristic object, as a colony's _auto)
+    ls = TspLocalSearch(dist_)
     exact = exchange == "tours"
     assert local_search in (None, "2opt", "nls")
 
@@ -1440,13 +1507,11 @@ def ant_sharded_tsp(distances, n_ants, rank, world, decay=0.9, alpha=1.0, beta=1
         # colony-wide ant ids in both modes (ant lo + a of instance b is ant b*A + lo + a of the single-GPU colony):
         # rank-local ids would overlap when n_ants % world != 0 (shard_range gives the first ranks one ant more)
         want_nbr = not exact and not elitist and local_search is None
-        mode, hk = resolve_sampler(sampler, n, head_k, eta, cache)
+        mode, hk = resolve_sampler(sampler, n, head_k, eta, auto)
         if mode == "scan_sparse":
-            if cache.get("head") is None or cache["head"][0] != hk:
-                h = eta.detach()
-                h = h if h.dim() == 3 else h.unsqueeze(0).expand(B, n, n)
-                cache["head"] = (hk, sparse_head(_f32c(h), hk, top=take_auto_top(cache, eta)))     # (the top values are handed over once)
-            paths, _, costs, nbr = tsp_sample_sparse(tau, eta, n_local, cache["head"][1], alpha, beta, seed=seed, it=it, ant_gid0=lo,
+            if state.get("head") is None or state["head"][0] != hk:
+                state["head"] = (hk, head_table(eta, hk, B, auto))
+            paths, _, costs, nbr = tsp_sample_sparse(tau, eta, n_local, state["head"][1], alpha, beta, seed=seed, it=it, ant_gid0=lo,
                                                      ant_gid_bstride=n_ants, fixed_start=fixed_start, batch=B, dist=dist_,
                                                      want_nbr=want_nbr)
         else:
@@ -1454,23 +1519,7 @@ def ant_sharded_tsp(distances, n_ants, rank, world, decay=0.9, alpha=1.0, beta=1
                                                     ant_gid0=lo, ant_gid_bstride=n_ants, fixed_start=fixed_start, batch=B,
                                                     dist=dist_, want_nbr=want_nbr)
         if local_search is not None:
-            tours = paths.permute(0, 2, 1).to(torch.int16).contiguous()
-            maxt = 10000 if inference else n // 4
-            if "dist_t" not in cache:
-                cache["dist_t"] = transposed_for_two_opt(dist_)
-                cache["tables"] = two_opt_tables(dist_, cache["dist_t"])
-            if local_search == "2opt":
-                two_opt_(dist_, tours, maxt, dist_t=cache["dist_t"], tables=cache["tables"])
-                costs = None
-            else:
-                if "hd" not in cache:
-                    h = eta.detach().float()
-                    cache["hd"] = (1 / (h / h.amax(dim=-1, keepdim=True) + 1e-5)).contiguous()
-                    cache["hd_t"] = transposed_for_two_opt(cache["hd"])
-                    cache["htables"] = two_opt_tables(cache["hd"], cache["hd_t"])
-                tours, costs = nls_(dist_, cache["hd"], tours, maxt, dist_t=cache["dist_t"], heuristic_dist_t=cache["hd_t"],
-                                    tables=cache["tables"], heuristic_tables=cache["htables"], want_costs=True)
-            paths = tours.permute(0, 2, 1).to(torch.int64).contiguous()
+            paths, costs = ls.improve(paths, local_search, inference, eta)
             if costs is None:
                 costs = tour_costs(dist_, paths)
             nbr = None

@@ -68,8 +68,7 @@ def _tsp_nls_loss(net, coords, n_ants, k_sparse, seed, it, iter_dev, local_searc
         tours = paths.permute(0, 2, 1).to(torch.int16).contiguous()
         maxt = n // 4                                                 # tsp_nls/aco.py:235,242 (training)
         if local_search == "nls":
-            h = heu_mat.detach()
-            hdist = (1 / (h / h.amax(dim=-1, keepdim=True) + 1e-5)).contiguous()
+            hdist = engine.heuristic_dist(heu_mat.detach())
             # (the perturbation matrix of a learned heuristic is not symmetric in general; handing its transpose over spares
             # nls_ the device comparison -- a host round trip -- that would find that out, and changes no result)
             tours = engine.nls_(dist, hdist, tours, maxt, dist_t="symmetric", heuristic_dist_t=hdist.transpose(1, 2).contiguous())

@@ -21,7 +21,6 @@ except ImportError:
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
     from deepaco_amd import engine
 from deepaco_amd.tsp.aco import ACO as _TspACO
-from deepaco_amd.tsp_nls.two_opt import two_opt_device
 
 
 class ACO(_TspACO):
@@ -53,7 +52,6 @@ class ACO(_TspACO):
                          device, sampler=sampler, seed=seed)
         assert local_search in [None, "2opt", "nls"]
         self.local_search_type = '2opt' if two_opt else local_search
-        self._heuristic_dist = None
 
     # ------------------------------------------------------------------ tsp_nls/aco.py:80-95
     def sample(self, inference=False):
@@ -115,62 +113,30 @@ class ACO(_TspACO):
     # ------------------------------------------------------------------ tsp_nls/aco.py:222-258
     @property
     def heuristic_dist(self):
-        """1 / (eta / rowmax(eta) + 1e-5): the perturbation matrix of the NLS (tsp_nls/aco.py:230-232)."""
-        if self._heuristic_dist is None:
-            h = self.heuristic.detach().to(torch.float32)
-            self._heuristic_dist = (1 / (h / h.max(-1, keepdim=True).values + 1e-5)).contiguous()
-        return self._heuristic_dist
+        """The perturbation matrix of the NLS (tsp_nls/aco.py:230-232: engine.heuristic_dist of the heuristic), formed once."""
+        return self._local_search().heuristic_dist(self.heuristic.unsqueeze(0))[0]
 
-    def _transposed(self, name):
-        """engine.two_opt_'s dist_t for self.<name>, computed once per matrix object ("symmetric" or a transposed copy)."""
-        m = getattr(self, name).detach().to(torch.float32)
-        cache = self.__dict__.setdefault("_t_cache", {})
-        hit = cache.get(name)
-        if hit is None or hit[0] is not getattr(self, name):
-            hit = (getattr(self, name), engine.transposed_for_two_opt(m))
-            cache[name] = hit
+    def _local_search(self):
+        """engine.TspLocalSearch of this colony: the transposed matrices and neighbour lists of the 2-opt kernels, once per
+        matrix object (the distances; the perturbation matrix is formed once per colony)."""
+        hit = self.__dict__.get("_ls")
+        if hit is None or hit[0] is not self.distances:
+            ls = engine.TspLocalSearch(self.distances.detach().to(torch.float32).contiguous().unsqueeze(0))
+            if hit is not None:
+                ls.hdist, ls.hdist_t, ls.htables = hit[1].hdist, hit[1].hdist_t, hit[1].htables
+            hit = self._ls = (self.distances, ls)
         return hit[1]
-
-    def _tables(self, name):
-        """engine.TwoOptTables of self.<name> (neighbour lists for the candidate-list 2-opt kernel), once per matrix object."""
-        cache = self.__dict__.setdefault("_tab_cache", {})
-        hit = cache.get(name)
-        if hit is None or hit[0] is not getattr(self, name):
-            m = getattr(self, name).detach().to(torch.float32)
-            hit = (getattr(self, name), engine.two_opt_tables(m, self._transposed(name)))
-            cache[name] = hit
-        return hit[1]
-
-    def _tours(self, paths):
-        return paths.T.contiguous().to(torch.int16)
-
-    def _paths(self, tours):
-        return tours.T.contiguous().to(torch.int64)
-
-    def _tour_costs(self, tours):
-        return engine.tour_costs(self.distances, self._paths(tours).unsqueeze(0))[0]
 
     @torch.no_grad()
     def two_opt(self, paths, inference=False):
-        maxt = 10000 if inference else self.problem_size // 4
-        best = two_opt_device(self.distances, self._tours(paths), maxt, self._transposed("distances"),
-                              self._tables("distances"))
-        return self._paths(best)
+        return self._local_search().improve(paths.unsqueeze(0), "2opt", inference)[0][0]
 
     @torch.no_grad()
     def nls(self, paths, inference=False, T_nls=10, T_p=20):
         """tsp_nls/aco.py:241-258.  One launch for the whole search of every tour (engine.nls_: daco_tsp_nls) where the
         candidate tables exist (n <= 1024), the pass-by-pass driver otherwise; the same tours either way."""
-        maxt = 10000 if inference else self.problem_size // 4
-        dist = self.distances.to(torch.float32)
-        tabs, hd_tabs = self._tables("distances"), self._tables("heuristic_dist")
-        # (the cached transposes too: without tables -- n > 1024 -- nls_ would otherwise rebuild them, a host sync and an n^2
-        # copy per call)
-        dt, hdt = self._transposed("distances"), self._transposed("heuristic_dist")
-        best = engine.nls_(dist.unsqueeze(0), self.heuristic_dist.unsqueeze(0), self._tours(paths).unsqueeze(0), maxt,
-                           T_nls=T_nls, T_p=T_p, dist_t=dt.unsqueeze(0) if torch.is_tensor(dt) else dt,
-                           heuristic_dist_t=hdt.unsqueeze(0) if torch.is_tensor(hdt) else hdt, tables=tabs, heuristic_tables=hd_tabs)
-        return self._paths(best[0])
+        return self._local_search().improve(paths.unsqueeze(0), "nls", inference, self.heuristic.unsqueeze(0),
+                                            T_nls=T_nls, T_p=T_p, want_costs=False)[0][0]
 
     # ------------------------------------------------------------------ tsp_nls/aco.py:171-182, 222-228
     def gen_numpy_path_costs(self, paths, numpy_distances):

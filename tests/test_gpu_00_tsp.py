@@ -531,18 +531,28 @@ def test_graph_replay_equals_eager_loop(kw, n, A, B):
 @pytest.mark.parametrize("kw", [{}, {"elitist": True}, {"min_max": True}])
 def test_sync_free_run_equals_plain_sequence(kw):
     """ACO.run's device-side bookkeeping (no host sync, fused costs / neighbour table) gives the same colony as the
-    reference's call sequence gen_path -> gen_path_costs -> update_pheronome."""
+    reference's call sequence gen_path -> gen_path_costs -> update_pheronome -- for every dense sampler (n = 80 keeps 'auto' and
+    'race' on the dense kernels), after each of two consecutive calls (the second continues the first: iteration counter, MMAS
+    bound, record)."""
     from deepaco_amd.tsp.aco import ACO
     n, A = 80, 24
     dist, _, _ = make_instance(n, 31)
-    a1 = ACO(dist[0].to(dev()), n_ants=A, device="cuda:0", seed=12, **kw)
-    a2 = ACO(dist[0].to(dev()), n_ants=A, device="cuda:0", seed=12, **kw)
-    r1 = a1.run(6)
-    r2 = a2._run_plain(6)
-    assert torch.equal(a1.pheromone, a2.pheromone)
-    assert float(r1) == float(r2) and torch.equal(a1.shortest_path, a2.shortest_path)
-    r1b = a1.run(3)                                     # continues from tensor state
-    assert float(r1b) <= float(r1)
+    for sampler in ("auto", "scan", "scan_wave", "race"):
+        a1 = ACO(dist[0].to(dev()), n_ants=A, device="cuda:0", seed=12, sampler=sampler, **kw)
+        a2 = ACO(dist[0].to(dev()), n_ants=A, device="cuda:0", seed=12, sampler=sampler, **kw)
+        held = a1.pheromone
+        before = held.clone()
+        lows = []
+        for iters in (6, 3):
+            r1 = a1.run(iters)
+            r2 = a2._run_plain(iters)
+            assert torch.equal(a1.pheromone, a2.pheromone), sampler
+            assert float(r1) == float(r2) and torch.equal(a1.shortest_path, a2.shortest_path), sampler
+            lows.append(float(r1))
+        assert lows[1] <= lows[0]                           # continues from tensor state
+        assert torch.equal(held, before)                    # a tensor the caller still holds is never modified
+        assert a1._calls == a2._calls == 9
+        a1.check_feasible()
 
 
 @pytest.mark.parametrize("kw", [{}, {"elitist": True}, {"min_max": True}, {"min_max": True, "min": 0.05}])

@@ -174,18 +174,24 @@ def test_cvrp_class_run():
 @pytest.mark.parametrize("n", [30, 100])
 def test_cvrp_sync_free_run_equals_plain_sequence(kw, n):
     """ACO.run (fused costs / successor table, device-side bookkeeping) == the reference's call sequence
-    gen_path -> gen_path_costs -> update_pheronome, pheromone bit for bit."""
+    gen_path -> gen_path_costs -> update_pheronome, pheromone bit for bit -- after each of two consecutive calls (the second
+    continues the first: iteration counter, MMAS bound, record)."""
     from deepaco_amd.cvrp.aco import ACO
     d, demand, _, _ = cvrp_instance(n, 5 * n)
     a1 = ACO(d[0].to(dev()), demand[0].to(dev()), n_ants=24, device="cuda:0", seed=8, **kw)
     a2 = ACO(d[0].to(dev()), demand[0].to(dev()), n_ants=24, device="cuda:0", seed=8, **kw)
-    r1, r2 = a1.run(6), a2._run_plain(6)
-    assert float(r1) == float(r2)
-    assert torch.equal(a1.pheromone, a2.pheromone)
-    s1, s2 = a1.shortest_path.tolist(), a2.shortest_path.tolist()
-    while len(s2) > 1 and s2[-1] == 0 and s2[-2] == 0:      # the reference keeps the iteration's padding
-        s2.pop()
-    assert s1 == s2
+    held = a1.pheromone
+    before = held.clone()
+    for iters in (6, 3):
+        r1, r2 = a1.run(iters), a2._run_plain(iters)
+        assert float(r1) == float(r2)
+        assert torch.equal(a1.pheromone, a2.pheromone)
+        s1, s2 = a1.shortest_path.tolist(), a2.shortest_path.tolist()
+        while len(s2) > 1 and s2[-1] == 0 and s2[-2] == 0:      # the reference keeps the iteration's padding
+            s2.pop()
+        assert s1 == s2
+    assert torch.equal(held, before)                        # a tensor the caller still holds is never modified
+    assert a1._calls == a2._calls == 9
 
 
 def test_cvrp_nls_surface_float64_data():

@@ -25,7 +25,7 @@ col.sparsify(50)
 col.step()
 paths, _, _, _ = engine.tsp_sample(col.pheromone, col.heuristic, A, seed=3, batch=B, fixed_start=0)
 tours = paths.permute(0, 2, 1).to(torch.int16).contiguous()
-hd = col._heuristic_dist()
+hd, ls = col._heuristic_dist(), col._ls
 rows = []
 
 
@@ -43,10 +43,10 @@ def call(name, m, t, maxit, tabs, mt):
 
 
 cur = tours.clone()
-call("first", col.distances, cur, n // 4, col._tables, col._dist_t)
+call("first", col.distances, cur, n // 4, ls.tables, ls.dist_t)
 for r in range(10):
-    call(f"perturb{r}", hd, cur, 20, col._htables, col._hdist_t)
-    call(f"repair{r}", col.distances, cur, n // 4, col._tables, col._dist_t)
+    call(f"perturb{r}", hd, cur, 20, ls.htables, ls.hdist_t)
+    call(f"repair{r}", col.distances, cur, n // 4, ls.tables, ls.dist_t)
 for r in rows:
     print(json.dumps(r))
 print(json.dumps({"total_ms": sum(r["ms"] for r in rows)}))
