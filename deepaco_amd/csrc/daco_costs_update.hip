@@ -536,11 +536,10 @@ extern "C" size_t daco_pheromone_update_workspace_bytes(int B, int n, int len, i
 }
 
 // rows per workgroup from an LDS budget: smaller slabs mean more workgroups per CU moving tau while others run
-// their add chains.  Measured (DACO_DEPOSIT_LDS_KB sweep, TSP-500 x 512 x 64 / CVRP-100 x 512 x 256): symmetric
+// their add chains.  Measured (budget sweep, TSP-500 x 512 x 64 / CVRP-100 x 512 x 256): symmetric
 // 80 / 53 / 40 / 32 KiB -> 119 / 91 / 84 / 105 us; directed 80 / 40 / 26 / 20 KiB -> 92 / 70 / 54 / 53 us.
 static int rows_per_block(int n, bool symmetric, int B = 1 << 20) {
-  static const int override_kb = getenv("DACO_DEPOSIT_LDS_KB") ? atoi(getenv("DACO_DEPOSIT_LDS_KB")) : 0;
-  const int budget_kb = override_kb ? override_kb : (symmetric ? 40 : 24);
+  const int budget_kb = symmetric ? 40 : 24;
   int R = (budget_kb * 1024 - 2 * DEP_CHUNK * 4 - 16) / (4 * n + 2 * DEP_CHUNK * 4);
   const int cap = symmetric ? 32 : 64;
   if (R > cap) R = cap;

@@ -416,11 +416,9 @@ extern "C" int daco_cvrp_local_search(void *stream, int B, int n, int A, int Lma
   const size_t lds = ls_fixed_bytes(Lmax, n) + (stage ? (size_t)n * n * 4 : 0);
   hipStream_t s = (hipStream_t)stream;
   // threads per solution: the pair loop is a chain of LDS look-ups -- with the matrix staged only three workgroups fit a CU, and
-  // eight wavefronts each keep it busier than four (DACO_CVRP_LS_THREADS: 256 | 512)
-  static const int nt_env = getenv("DACO_CVRP_LS_THREADS") ? atoi(getenv("DACO_CVRP_LS_THREADS")) : 0;
+  // eight wavefronts each keep it busier than four
   // (measured at CVRP-100, 64 x 512 solutions: 256 / 512 / 1024 threads -> 67.8 / 93.2 / 57.5 k solutions/s; without the staged
   // matrix a workgroup's LDS is small and eight of 256 threads fill the CU: unchanged)
-  const int nt = nt_env == 256 || nt_env == 512 || nt_env == 1024 ? nt_env : (stage ? 512 : 256);
 #define DACO_LS_LAUNCH(STAGE_, NT_)                                                                                              \
   do {                                                                                                                             \
     if (lds > 64 * 1024) {                                                                                                         \
@@ -430,8 +428,7 @@ extern "C" int daco_cvrp_local_search(void *stream, int B, int n, int A, int Lma
     hipLaunchKernelGGL((cvrp_ls_kernel<STAGE_, NT_>), dim3(B * A), dim3(NT_), lds, s, n, A, Lmax, dist, dist_bstride, demand, capacity, \
                        paths, max_moves, lens, moves);                                                                             \
   } while (0)
-  if (stage) { if (nt == 1024) DACO_LS_LAUNCH(true, 1024); else if (nt == 512) DACO_LS_LAUNCH(true, 512); else DACO_LS_LAUNCH(true, 256); }
-  else { if (nt == 1024) DACO_LS_LAUNCH(false, 1024); else if (nt == 512) DACO_LS_LAUNCH(false, 512); else DACO_LS_LAUNCH(false, 256); }
+  if (stage) DACO_LS_LAUNCH(true, 512); else DACO_LS_LAUNCH(false, 256);
 #undef DACO_LS_LAUNCH
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("cvrp_ls_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }

@@ -599,8 +599,8 @@ gnn_fused2_layer_kernel(int n, int E, int feats, int layer, int npw, const int *
       return make_float4(av, av, av, av);
     }
     else {
-      // the edge rows are a stream (each read once per layer, by one lane): with the non-temporal policy (DACO_GNN_NT=0 turns
-      // it off) they do not push the node rows -- which every edge of a node gathers again -- out of the L2
+      // the edge rows are a stream (each read once per layer, by one lane): with the non-temporal policy
+      // (nt != 0) they do not push the node rows -- which every edge of a node gathers again -- out of the L2
       const float4 *ptr = reinterpret_cast<const float4 *>(w0b + (uint32_t)e * 128u + (uint32_t)c0 * 4u);
       if (nt) {
         typedef float f4v __attribute__((ext_vector_type(4)));
@@ -974,18 +974,15 @@ extern "C" int daco_gnn_forward(void *stream, int n, int E, int feats, const flo
     if (npw < 4) npw = 4;
   }
   if (npw > FUSED_MAX_NPW) npw = FUSED_MAX_NPW;
-  // EXPERIMENT (DACO_GNN_INPLACE=1, fused kernels only): the edge state is updated in place -- every row is read once, by the
-  // lane that writes it, before it is written -- so the layers cycle through E * 128 B instead of twice that
-  const int nt_rows = getenv("DACO_GNN_NT") ? atoi(getenv("DACO_GNN_NT")) : 1;      // non-temporal edge rows (measured 1.81 -> 1.72 ms per forward)
+  const int nt_rows = 1;                                                // non-temporal edge rows (measured 1.81 -> 1.72 ms per forward)
   const bool fused2 = E >= split_min && !perm && fused_npw != 0 && fused_v == 2;
   // (the second fused kernel makes layer 0's edge state itself; every other path reads it from the init launch)
   if (!fused2) hipLaunchKernelGGL(gnn_edge_init_kernel, dim3((unsigned)(((long)E * 8 + 255) / 256)), dim3(256), 0, s, E, feats, edge_attr, params, wb[0]);
   // the output head inside the last layer's launch (no embedding asked for; DACO_GNN_HEAD_FUSED=0: the separate head launch)
   const bool head_fused = fused2 && !emb && !(getenv("DACO_GNN_HEAD_FUSED") && atoi(getenv("DACO_GNN_HEAD_FUSED")) == 0);
-  const bool inplace = getenv("DACO_GNN_INPLACE") && atoi(getenv("DACO_GNN_INPLACE")) == 1 && E >= split_min && !perm && fused_npw != 0;
   int wcur = 0;
   for (int l = 0; l < 12; ++l) {
-    float *wout = (l == 11 && emb) ? emb : wb[inplace ? wcur : (wcur ^ 1)];
+    float *wout = (l == 11 && emb) ? emb : wb[wcur ^ 1];
     if (fused2) {
       const dim3 grid((unsigned)(((n + 4 * npw - 1) / (4 * npw) + 7) / 8 * 8));
       if (l == 0) hipLaunchKernelGGL((gnn_fused2_layer_kernel<true, false>), grid, dim3(256), 0, s, n, E, feats, l, npw, src, dst, rowptr, params, xb[cur],
@@ -1007,7 +1004,7 @@ extern "C" int daco_gnn_forward(void *stream, int n, int E, int feats, const flo
                          wout);
     }
     if (l == 11 && emb) { wb[wcur ^ 1] = emb; wcur ^= 1; }
-    else if (!inplace) wcur ^= 1;
+    else wcur ^= 1;
     cur ^= 1;
   }
   // (a head that walks several tiles per wave with the next rows in flight, W1 / W2 in LDS, was measured: 139 us against

@@ -956,8 +956,7 @@ extern "C" int daco_hgs_local_search(void *stream, int B, int n, int A, int Lmax
   int Rmax = Lmax - (n - 1); if (Rmax > n - 1) Rmax = n - 1; if (Rmax < 1) Rmax = 1;
   p.Rmax = Rmax;
   // watchdog of one stage of one solution (links chased + evaluation rounds): far above any search, finite on a broken table
-  static const int budget_env = getenv("DACO_HGS_BUDGET") ? atoi(getenv("DACO_HGS_BUDGET")) : 0;
-  p.budget = budget_env > 0 ? budget_env : 0x7fffffff;
+  p.budget = 0x7fffffff;
   if (n + 2 * Rmax > 65535) { set_error("daco_hgs_local_search: n + 2 routes = %d does not fit 16-bit node ids", n + 2 * Rmax); return DACO_E_TOOLARGE; }
   for (int s = 0; s < nstages; ++s) {
     if (!matrices[s] || !tables[s] || counts[s] < 0) { set_error("daco_hgs_local_search: stage %d: null matrix / table or negative count", s); return DACO_E_BADARG; }

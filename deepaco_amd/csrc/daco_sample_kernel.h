@@ -621,12 +621,7 @@ inline int inst_chunks(int n) {
   for (int c : avail) if (c >= need) return c;
   return -1;
 }
-// DACO_LD_PAD (floats, multiple of 4; measurement knob): extra zero padding per row, to move the row stride off the
-// 2 KB period (tools/l2_bw_shapes.hip measures +7 % L2 row rate at 2304 B) at the price of a larger L2 footprint
-inline int ld_alloc(int n) {
-  static const int pad = getenv("DACO_LD_PAD") ? atoi(getenv("DACO_LD_PAD")) & ~3 : 0;
-  return inst_chunks(n) * 64 * vec_for_n(n) + pad;
-}
+inline int ld_alloc(int n) { return inst_chunks(n) * 64 * vec_for_n(n); }
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- shared by the several-ants-per-wavefront kernels (daco_tsp_scan32.hip, daco_scan16.hip)

@@ -796,10 +796,9 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   if (e != hipSuccess) { set_error("%s pre-pass: %s", what, hipGetErrorString(e)); return DACO_E_HIP; }
   if (ev_begin && hipEventRecord((hipEvent_t)ev_begin, s) != hipSuccess) { set_error("hipEventRecord(ev_begin) failed"); return DACO_E_HIP; }
   // few ants (no more workgroups of four than the chip has CUs) and a head table that fits a CU's LDS: the LDS-heads variant
-  static const int lh_knob = getenv("DACO_SPARSE_LDS_HEADS") ? atoi(getenv("DACO_SPARSE_LDS_HEADS")) : 1;   // (0: never; measurement knob)
   bool lh = false;
   size_t lh_lds = 0;
-  if (lh_knob && !race && spl == 4 && ld == 512 && head_live_max > 0 && head_live_max <= 62 && (long)B * ((A + 3) / 4) <= 256) {
+  if (!race && spl == 4 && ld == 512 && head_live_max > 0 && head_live_max <= 62 && (long)B * ((A + 3) / 4) <= 256) {
     const int kl = (head_live_max + 1 + 3) / 4;
     const size_t table = (size_t)n * kl * sp_lane_bytes(4) + 32;
     lh_lds = (size_t)4 * (512 + 16) + (size_t)4 * (512 + 2) * 2 + (table > 12288 + 1024 ? table : 12288 + 1024);
@@ -809,9 +808,8 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   const int bpi = lh ? (A + 3) / 4 : (A + 15) / 16;
   const dim3 grid((unsigned)(B * bpi));
   // dynamic LDS: flags + tours (n <= 512); the larger of flags + window and eight tours + their inverse table (n > 512)
-  const int pad_lds = getenv("DACO_SPARSE_PAD_LDS") ? atoi(getenv("DACO_SPARSE_PAD_LDS")) : 0;   // (measurement knob: fewer workgroups per CU)
 #define DACO_SPARSE_LDS(C) ((C) == 2 ? 16 * ((C) * 256 + 16) + 16 * ((C) * 256 + 2) * 2 : 2 * 8 * (C) * 256 * 2)
-#define DACO_SPARSE_LAUNCH(C, R, S) hipLaunchKernelGGL((scan_sparse_kernel<C, R, S>), grid, dim3(256), DACO_SPARSE_LDS(C) + pad_lds, s, sp)
+#define DACO_SPARSE_LAUNCH(C, R, S) hipLaunchKernelGGL((scan_sparse_kernel<C, R, S>), grid, dim3(256), DACO_SPARSE_LDS(C), s, sp)
 #define DACO_SPARSE_PICK(C, R) do { if (spl == 4) DACO_SPARSE_LAUNCH(C, R, 4); else DACO_SPARSE_LAUNCH(C, R, 8); } while (0)
   if (lh) {
     // (more than 64 KB of dynamic LDS has to be asked for; per call: the attribute belongs to the current device's copy of the

@@ -594,8 +594,8 @@ extern "C" int daco_two_opt(void *stream, int B, int T, int n, const float *dist
     return (2 * np4 + 2 * W + (8 - 2 * W % 8) % 8 + (stage ? (size_t)W * 2 * np4 : 0)) * 4;
   };
   hipStream_t s = (hipStream_t)stream;
-  // default: the incremental kernel (16 + log2(waves per tour)); the full-sweep kernels (variant = waves per
-  // tour * 2 + staged) stay selectable with DACO_TWO_OPT_VARIANT for tuning / cross-checks.  Measured on the
+  // default: the incremental kernel (17 / 18: two / four waves per tour); the full-sweep kernels (2: one wave, 8: four waves,
+  // anything else: four waves with staged rows) stay selectable with DACO_TWO_OPT_VARIANT as the tests' cross-check.  Measured on the
   // NLS workload (tools/measure_configs.py c3:n): n=100 25 vs 45 ms, n=200 62 vs 189 ms, n=500 507 vs 1985 ms.
   // 32: two_opt_incr2_kernel (explicit row traffic; dist_T lets its patch phase read matrix rows of the changed segment)
   int variant = n <= 128 ? 17 : 32;
@@ -605,14 +605,9 @@ extern "C" int daco_two_opt(void *stream, int B, int T, int n, const float *dist
   auto lds_incr2 = [&](int W) { return lds_incr(W) + 8 * sizeof(int) + (size_t)W * 2 * np4 * sizeof(float); };
   switch (variant) {
     case 32: hipLaunchKernelGGL((two_opt_incr2_kernel<4>), dim3(B * T), dim3(256), lds_incr2(4), s, n, T, dist, dist_T, dist_bstride, tours, max_iterations, sweeps, (int32_t *)nullptr, 0, (const unsigned char *)nullptr, (const unsigned char *)nullptr, (size_t)0, 0); break;
-    case 33: hipLaunchKernelGGL((two_opt_incr2_kernel<2>), dim3(B * T), dim3(128), lds_incr2(2), s, n, T, dist, dist_T, dist_bstride, tours, max_iterations, sweeps, (int32_t *)nullptr, 0, (const unsigned char *)nullptr, (const unsigned char *)nullptr, (size_t)0, 0); break;
-    case 16: hipLaunchKernelGGL((two_opt_incr_kernel<1>), dim3(B * T), dim3(64), lds_incr(1), s, n, T, dist, dist_bstride, tours, max_iterations, sweeps); break;
     case 17: hipLaunchKernelGGL((two_opt_incr_kernel<2>), dim3(B * T), dim3(128), lds_incr(2), s, n, T, dist, dist_bstride, tours, max_iterations, sweeps); break;
     case 18: hipLaunchKernelGGL((two_opt_incr_kernel<4>), dim3(B * T), dim3(256), lds_incr(4), s, n, T, dist, dist_bstride, tours, max_iterations, sweeps); break;
     case 2: DACO_2OPT(1, false); break;
-    case 3: DACO_2OPT(1, true); break;
-    case 4: DACO_2OPT(2, false); break;
-    case 5: DACO_2OPT(2, true); break;
     case 8: DACO_2OPT(4, false); break;
     default: DACO_2OPT(4, true); break;
   }

@@ -169,7 +169,7 @@ two_opt_nbr_kernel(int n, int T, const float *dist, long dist_bs, const unsigned
   uint32_t *wsum = reinterpret_cast<uint32_t *>(red + NW);
   uint32_t *incumbent = wsum + NW;                             // ordered image of the best change any thread has seen this sweep
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // prof (DACO_TWO_OPT_PROFILE=1, a debugging aid): shader-clock cycles per phase as thread 0 sees them, summed over tours
+  // prof (a debugging aid; the host passes nullptr): shader-clock cycles per phase as thread 0 sees them, summed over tours
   unsigned long long tmark = prof ? clock64() : 0;
   auto lap = [&](int slot) {
     if (prof && tid == 0) { const unsigned long long now = clock64(); atomicAdd(prof + slot, now - tmark); tmark = now; }
@@ -397,31 +397,17 @@ int launch_two_opt_nbr(hipStream_t s, int B, int T, int n, const float *dist, lo
                        uint32_t w_switch, int final_pass) {
   const int np2 = (n + 2) & ~1;
   const size_t lds = (size_t)np2 * 8 + (size_t)np2 * 2 * 4 + (size_t)(2 * np2 + 2) * 4 + (size_t)NBR_QUEUE * 4 + 16 * 8 + 16 * 4 + 32;
-  unsigned long long *prof = nullptr;
-  if (getenv("DACO_TWO_OPT_PROFILE")) {                       // debugging aid: synchronises and prints
-    if (hipMalloc((void **)&prof, 8 * sizeof(unsigned long long)) != hipSuccess) prof = nullptr;
-    else (void)hipMemsetAsync(prof, 0, 8 * sizeof(unsigned long long), s);
-  }
   // fewer tours than two per CU: 1024 threads each
   int wide = (long)B * T <= 512;
   if (const char *ev = getenv("DACO_TWO_OPT_WIDE")) wide = atoi(ev);
 #define DACO_NBR_LAUNCH(SYM_, NT_)                                                                                              \
   hipLaunchKernelGGL((two_opt_nbr_kernel<SYM_, NT_>), dim3((unsigned)B * T), dim3(NT_), lds, s, n, T, dist, dist_bstride,      \
                      (const unsigned char *)tables, (const unsigned char *)tables_T, nbr_instance_bytes(n), tours,              \
-                     max_iterations, sweeps, state, w_switch, final_pass, prof)
+                     max_iterations, sweeps, state, w_switch, final_pass, nullptr)
   if (tables == tables_T) { if (wide) DACO_NBR_LAUNCH(true, 1024); else DACO_NBR_LAUNCH(true, 256); }
   else { if (wide) DACO_NBR_LAUNCH(false, 1024); else DACO_NBR_LAUNCH(false, 256); }
 #undef DACO_NBR_LAUNCH
   hipError_t e = hipGetLastError();
-  if (prof) {
-    unsigned long long h[8] = {0};
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(prof);
-    fprintf(stderr, "[two_opt_nbr profile] tours %d sweeps %llu candidates/sweep %.0f | cycles per sweep: prefix %.0f eval %.0f reduce %.0f "
-            "apply %.0f | set-up per tour %.0f\n", B * T, h[6], h[6] ? (double)h[7] / h[6] : 0.0, h[6] ? (double)h[1] / h[6] : 0.0,
-            h[6] ? (double)h[2] / h[6] : 0.0, h[6] ? (double)h[3] / h[6] : 0.0, h[6] ? (double)h[4] / h[6] : 0.0, (double)h[0] / (B * T));
-  }
   if (e != hipSuccess) { set_error("two_opt_nbr_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
   return DACO_OK;
 }

@@ -1144,7 +1144,7 @@ class BatchedTSP:
         self._sparse_ws = None
         self._heads_for = None
         self._flags = torch.zeros((self.B,), dtype=torch.int32, device=dev)      # sticky: bit 0 a draw without a candidate, bit 2 see daco_tsp_sample_heads
-        self.fuse_head_rows = os.environ.get("DACO_FUSE_HEAD_ROWS", "1") != "0"      # (knob: 0 = a pre-pass every iteration, as until round 5)
+        self.fuse_head_rows = True      # (False: a pre-pass every iteration, what smoke() compares against)
 
     def check_feasible(self):
         """Raise like the reference's Categorical if any head-row draw so far had no candidate (bit 0), or the head table holds more

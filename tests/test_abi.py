@@ -97,3 +97,37 @@ def test_two_opt_candidate_entry_points_validate_arguments():
     assert L.daco_two_opt_auto(None, 1, 1, n, 1, None, 0, 1, 1, 1, 10, None) == -1    # sweeps is required (hand-over state)
     # above the table kernels' size the host falls back to the dense kernel (no tables)
     assert engine.two_opt_tables(torch.zeros(1, 1025, 1025)) is None
+
+
+# knobs that no test or tool sets, each with the reason it is read all the same
+KNOBS_WITHOUT_A_USER = {
+    "DACO_LIB_PATH": "selects the build: how two builds of the library are compared in one checkout",
+    "DACO_GNN_FUSED_V": "the first fused GNN layer is still chosen from the size of the edge arrays; no test reaches it at any size",
+}
+
+
+def _files(top, suffixes):
+    for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+        for f in files:
+            if f.endswith(suffixes):
+                yield os.path.join(dirpath, f)
+
+
+def test_every_knob_is_documented_and_used():
+    """Every DACO_* environment variable the library (getenv) or the package (os.environ) reads is a row of the knob table of
+    DESIGN.md section 9 and every row is read somewhere; and each is named by a test or a tool, so that no kernel is left that only
+    a variable in somebody's shell can select."""
+    read = set()
+    for f in _files(os.path.join("deepaco_amd", "csrc"), (".hip", ".h", ".cpp")):
+        read |= set(re.findall(r'getenv\(\s*"(DACO_[A-Z0-9_]+)"', open(f).read()))
+    for f in _files("deepaco_amd", (".py",)):
+        read |= set(re.findall(r'os\.environ[^\n]*?["\'](DACO_[A-Z0-9_]+)["\']', open(f).read()))
+    assert "DACO_SCAN_LAYOUT" in read and "DACO_LIB_PATH" in read          # (the collection itself works)
+    rows = [line.split("|")[1] for line in open(os.path.join(ROOT, "DESIGN.md")) if line.startswith("| `DACO_")]
+    table = set(re.findall(r"DACO_[A-Z0-9_]+", " ".join(rows)))
+    assert read - table == set(), "read by the code, missing from DESIGN.md's knob table"
+    assert table - read == set(), "in DESIGN.md's knob table, read by nothing"
+    me = os.path.abspath(__file__)
+    users = "".join(open(f).read() for top in ("tests", "tools") for f in _files(top, (".py", ".sh", ".hip", ".cpp")) if os.path.abspath(f) != me)
+    orphans = {k for k in read if not re.search(r"\b%s\b" % k, users)}
+    assert orphans == set(KNOBS_WITHOUT_A_USER), "knobs that no test and no tool sets"

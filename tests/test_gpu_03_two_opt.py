@@ -120,7 +120,7 @@ def test_nls_class_surface_and_recorded_noise():
     assert low_inf <= low
 
 
-def test_incremental_equals_full_sweep_kernels():
+def test_incremental_equals_full_sweep_kernels(monkeypatch):
     """The default incremental kernel and the full-sweep kernels (staged / unstaged) choose the same moves:
     identical tours and sweep counts on ACO-sampled tours, symmetric and perturbation (asymmetric) matrices."""
     from deepaco_amd import engine
@@ -131,15 +131,13 @@ def test_incremental_equals_full_sweep_kernels():
     tours = paths.permute(0, 2, 1).to(torch.int16).contiguous()
     hd = (1 / (eta / eta.amax(dim=-1, keepdim=True) + 1e-5)).contiguous()
     results = {}
-    try:
-        for variant in ("17", "18", "9", "8", "2"):
-            os.environ["DACO_TWO_OPT_VARIANT"] = variant
-            t1, s1 = engine.two_opt_(d, tours.clone(), n // 4, want_sweeps=True)
-            t2, s2 = engine.two_opt_(hd, t1.clone(), 20, want_sweeps=True)
-            t3, s3 = engine.two_opt_(d, t2.clone(), 10000, want_sweeps=True)
-            results[variant] = (t1, s1, t2, s2, t3, s3)
-    finally:
-        os.environ.pop("DACO_TWO_OPT_VARIANT", None)
+    for variant in ("17", "18", "9", "8", "2"):
+        monkeypatch.setenv("DACO_TWO_OPT_VARIANT", variant)
+        t1, s1 = engine.two_opt_(d, tours.clone(), n // 4, want_sweeps=True)
+        t2, s2 = engine.two_opt_(hd, t1.clone(), 20, want_sweeps=True)
+        t3, s3 = engine.two_opt_(d, t2.clone(), 10000, want_sweeps=True)
+        results[variant] = (t1, s1, t2, s2, t3, s3)
+    monkeypatch.delenv("DACO_TWO_OPT_VARIANT")
     ref = results["9"]
     for variant, res in results.items():
         for x, y in zip(res, ref):
@@ -206,7 +204,7 @@ def test_reference_test_script_call_pattern_with_host_tensors():
 
 @pytest.mark.parametrize("n,Tn,B,maxit", [(4, 3, 1, 50), (5, 4, 2, 50), (33, 6, 1, 1000), (129, 5, 2, 1000), (257, 4, 1, 30),
                                            (500, 6, 1, 125), (1000, 2, 1, 40)])
-def test_candidate_list_kernel_vs_oracle(n, Tn, B, maxit):
+def test_candidate_list_kernel_vs_oracle(n, Tn, B, maxit, monkeypatch):
     """daco_two_opt_nbr (neighbour-list pruning) makes the reference's moves: tours and sweep counts equal the oracle's
     full evaluation bit for bit, from random permutations (every pair is a candidate at first) to convergence."""
     from deepaco_amd import engine
@@ -217,11 +215,8 @@ def test_candidate_list_kernel_vs_oracle(n, Tn, B, maxit):
     tabs = engine.TwoOptTables(dd)
     refs = [oracle.two_opt_batch(d[b].numpy(), tours[b].astype(np.uint16), maxit) for b in range(B)]
     for kernel, wide in (("nbr", "0"), ("nbr", "1"), ("auto", "0"), ("auto", "1")):     # 256 / 1024 threads per tour
-        os.environ["DACO_TWO_OPT_WIDE"] = wide
-        try:
-            out, sweeps = engine.two_opt_(dd, T(tours), maxit, want_sweeps=True, tables=tabs, kernel=kernel)
-        finally:
-            os.environ.pop("DACO_TWO_OPT_WIDE")
+        monkeypatch.setenv("DACO_TWO_OPT_WIDE", wide)
+        out, sweeps = engine.two_opt_(dd, T(tours), maxit, want_sweeps=True, tables=tabs, kernel=kernel)
         for b in range(B):
             ref, rs = refs[b]
             assert np.array_equal(out[b].cpu().numpy().astype(np.uint16), ref), (n, b, kernel, wide)
@@ -260,14 +255,14 @@ def test_candidate_list_kernel_on_perturbation_and_asymmetric_matrices(wide, mon
     w3, p3 = engine.two_opt_(d, tours.clone(), 10000, want_sweeps=True)
     assert torch.equal(v3, w3) and torch.equal(q3, p3)
     for sw, back in (("3000", "2500"), ("60000", "59000"), ("1", "0")):        # hand-overs at other places / none / never back
-        os.environ["DACO_TWO_OPT_SWITCH"], os.environ["DACO_TWO_OPT_BACK"] = sw, back
-        try:
-            v4, q4 = engine.two_opt_(d, tours.clone(), 10000, want_sweeps=True, tables=td)
-            v5, q5 = engine.two_opt_(hd, t1.clone(), 20, want_sweeps=True, tables=th)
-        finally:
-            os.environ.pop("DACO_TWO_OPT_SWITCH"); os.environ.pop("DACO_TWO_OPT_BACK")
+        monkeypatch.setenv("DACO_TWO_OPT_SWITCH", sw)
+        monkeypatch.setenv("DACO_TWO_OPT_BACK", back)
+        v4, q4 = engine.two_opt_(d, tours.clone(), 10000, want_sweeps=True, tables=td)
+        v5, q5 = engine.two_opt_(hd, t1.clone(), 20, want_sweeps=True, tables=th)
         assert torch.equal(v4, w3) and torch.equal(q4, p3), sw
         assert torch.equal(v5, t2) and torch.equal(q5, s2), sw
+    monkeypatch.delenv("DACO_TWO_OPT_SWITCH")
+    monkeypatch.delenv("DACO_TWO_OPT_BACK")
     # sparse learned-heuristic style matrix: a plateau of 1e5 off the k-NN graph
     k = 20
     _, idx = torch.topk(d, k=k, dim=2, largest=False)
@@ -287,7 +282,7 @@ def test_candidate_list_kernel_on_perturbation_and_asymmetric_matrices(wide, mon
     assert torch.equal(t5, u5) and torch.equal(s5, r5)
 
 
-def test_candidate_list_kernel_many_small_cases_with_ties():
+def test_candidate_list_kernel_many_small_cases_with_ties(monkeypatch):
     """Sixty small searches, candidate-list kernel vs dense kernel vs (a third of them) the oracle: integer grid
     coordinates (many equal distances: tie-breaking on (i, j), tolerance ranks with ties), duplicate points (zero
     distances), row-scaled and random asymmetric matrices, signed entries with a zero diagonal, sweep caps that stop
@@ -320,7 +315,7 @@ def test_candidate_list_kernel_many_small_cases_with_ties():
         tours = np.stack([rng.permutation(n) for _ in range(Tn)]).astype(np.int16)
         dd = T(d)
         tabs = engine.TwoOptTables(dd)
-        os.environ["DACO_TWO_OPT_WIDE"] = str((case // 4) % 2)   # 256 / 1024 threads per tour
+        monkeypatch.setenv("DACO_TWO_OPT_WIDE", str((case // 4) % 2))   # 256 / 1024 threads per tour
         a, sa = engine.two_opt_(dd, T(tours), maxit, want_sweeps=True)
         b, sb = engine.two_opt_(dd, T(tours), maxit, want_sweeps=True, tables=tabs, kernel="nbr")
         c2, sc = engine.two_opt_(dd, T(tours), maxit, want_sweeps=True, tables=tabs)
@@ -329,7 +324,6 @@ def test_candidate_list_kernel_many_small_cases_with_ties():
         if case % 3 == 0:
             ref, rs = oracle.two_opt_batch(d, tours.astype(np.uint16), maxit)
             assert np.array_equal(a.cpu().numpy().astype(np.uint16), ref) and np.array_equal(sa[0].cpu().numpy(), rs), (case, n, kind)
-    os.environ.pop("DACO_TWO_OPT_WIDE", None)
 
 
 # ------------------------------------------------------------------ daco_tsp_nls: dirty-list sweeps, the whole NLS in one launch

@@ -280,7 +280,7 @@ def test_batched_training_step_on_device():
     assert float(c) < first               # the policy improved on the instances it trains on
 
 
-def test_flat_block_training_equals_the_parameter_list():
+def test_flat_block_training_equals_the_parameter_list(monkeypatch):
     """Net.flatten_parameters on the device: the training forward takes the block as it is, the backward's flat gradient is the
     block's .grad and every parameter's .grad a view of it -- the same heuristic and the same gradients as the network whose
     parameters are packed with torch.cat every step (bit for bit: the same kernels on the same values)."""
@@ -297,18 +297,11 @@ def test_flat_block_training_equals_the_parameter_list():
     x = torch.zeros(B, n, 1, device=dev())
     x[:, 0] = 1.0
     coef = torch.randn(B, n * k, device=dev())
-    monkey_env = os.environ.get("DACO_GNN_TRAIN_GATHER")
-    os.environ["DACO_GNN_TRAIN_GATHER"] = "1"                  # (CSR row sums: no f32 atomics, the backward is deterministic)
-    try:
-        heu = net.forward_batch_train(x, ei, ea, k_sparse=k)
-        torch.sum(heu * coef).backward()
-        heu_r = ref.forward_batch_train(x, ei, ea, k_sparse=k)
-        torch.sum(heu_r * coef).backward()
-    finally:
-        if monkey_env is None:
-            del os.environ["DACO_GNN_TRAIN_GATHER"]
-        else:
-            os.environ["DACO_GNN_TRAIN_GATHER"] = monkey_env
+    monkeypatch.setenv("DACO_GNN_TRAIN_GATHER", "1")           # (CSR row sums: no f32 atomics, the backward is deterministic)
+    heu = net.forward_batch_train(x, ei, ea, k_sparse=k)
+    torch.sum(heu * coef).backward()
+    heu_r = ref.forward_batch_train(x, ei, ea, k_sparse=k)
+    torch.sum(heu_r * coef).backward()
     assert torch.equal(heu.detach(), heu_r.detach())
     assert block.grad is not None and block.grad.shape == block.shape
     gmax = max(float(q.grad.abs().max()) for q in ref.parameters() if q.grad is not None)

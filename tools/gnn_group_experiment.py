@@ -37,5 +37,4 @@ for B in (64, 32, 16, 8, 4, 2):
             b.record()
             torch.cuda.synchronize()
         ms = a.elapsed_time(b) / reps
-        print(json.dumps({"B": B, "npw": npw, "ms": round(ms, 4), "us_per_graph": round(ms * 1e3 / B, 2),
-                          "inplace": os.environ.get("DACO_GNN_INPLACE", "")}), flush=True)
+        print(json.dumps({"B": B, "npw": npw, "ms": round(ms, 4), "us_per_graph": round(ms * 1e3 / B, 2)}), flush=True)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/counters.json and profiles/hbm_traffic.json from the counter passes of tools/profile_r6.sh.
+"""profiles/counters.json and profiles/hbm_traffic.json from the counter passes of tools/profile.sh <tag> <workload> pmc.
 
 usage: tools/make_counters.py gpurun_out/<tag> [--merge]   (reads <tag>/pmc_<workload>/pmc_*/p_counter_collection.csv;
        --merge: keep the entries of the existing files (same library version) for workloads <tag> has no passes of)
@@ -55,10 +55,10 @@ def main():
     from deepaco_amd import _lib
     version = _lib.ABI_VERSION
     counters = {"daco_version": version,
-                "source": "profiles/r06_pmc_*.txt (tools/profile_r6.sh + tools/make_counters.py: rocprofv3 --pmc, one pass per counter "
+                "source": "profiles/r06_pmc_*.txt (tools/profile.sh + tools/make_counters.py: rocprofv3 --pmc, one pass per counter "
                           "group, mean per launch of the workload's dominant kernel, all of this library version)"}
     traffic = {"daco_version": version,
-               "source": "profiles/r06_pmc_*.txt (tools/profile_r6.sh: FETCH_SIZE KiB x 1024 x 2 [gfx950 correction] + WRITE_SIZE KiB x "
+               "source": "profiles/r06_pmc_*.txt (tools/profile.sh: FETCH_SIZE KiB x 1024 x 2 [gfx950 correction] + WRITE_SIZE KiB x "
                          "1024, mean per launch of the dominant kernel)"}
     if "--merge" in sys.argv[2:]:
         for name, cur in (("counters.json", counters), ("hbm_traffic.json", traffic)):
