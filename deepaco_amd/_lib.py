@@ -75,11 +75,18 @@ SIGNATURES = {
     "daco_two_opt_prepare": (_i, [_vp, _i, _i, _vp, _l, _vp, _sz]),
     "daco_two_opt_nbr": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp]),
     "daco_two_opt_auto": (_i, [_vp, _i, _i, _i, _vp, _vp, _l, _vp, _vp, _vp, _l, _vp]),
+    "daco_mkpv_sample": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _vp, _i, _vp, _i, _u64, _u64, _u32, _i,
+                              _vp, _vp, _vp, _vp, _vp, _vp]),
+    "daco_mkpv_backward": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "daco_mkpv_update": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _f, _f, _vp, _vp, _vp]),
+    "daco_transformer_param_floats": (_sz, [_i]),
+    "daco_transformer_workspace_bytes": (_sz, [_i, _i]),
+    "daco_transformer_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _sz]),
     "daco_tsp_nls": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _l, _vp, _vp, _vp]),
 }
 
 
-ABI_VERSION = 126          # include/deepaco_hip.h DACO_VERSION this table was written against
+ABI_VERSION = 127          # include/deepaco_hip.h DACO_VERSION this table was written against
 
 
 class DacoError(RuntimeError):

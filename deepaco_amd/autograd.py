@@ -103,3 +103,25 @@ class SiblingSampleFn(torch.autograd.Function):
                                        lens=lens if lens.numel() else None, **kw)
         grad = grad[0] if ctx.needs_input_grad[0] and grad.shape[0] == 1 and eta.dim() == 2 else grad
         return (grad,) + (None,) * 10
+
+
+class MkpvSampleFn(torch.autograd.Function):
+    """Vector-pheromone knapsack construction (mkp_transformer/aco.py) whose log-probabilities carry gradient to the
+    heuristic VECTOR [n+1]: daco_mkpv_sample forward, daco_mkpv_backward (a replay of each ant's solution) backward.
+    -> (sols [1,Lmax,A], log_probs [1,Lmax,A], lens [1,A], objs [1,A], flags [1])."""
+
+    @staticmethod
+    def forward(ctx, heuristic, colony, noise):
+        colony.heuristic = heuristic.detach().float().reshape(1, -1).contiguous()
+        sols, logp, rowsum, lens, objs, flags = colony.sample(require_prob=True, noise=noise)
+        ctx.save_for_backward(colony.pheromone.clone(), colony.heuristic, sols, rowsum, lens)
+        ctx.meta = (colony.alpha, colony.beta, colony.weight)
+        ctx.mark_non_differentiable(sols, lens, objs, flags)
+        return sols, logp, lens, objs, flags
+
+    @staticmethod
+    def backward(ctx, _gs, glogp, _gl, _go, _gf):
+        tau, eta, sols, rowsum, lens = ctx.saved_tensors
+        alpha, beta, weight = ctx.meta
+        grad = engine.mkpv_backward(tau, eta, alpha, beta, weight, sols, rowsum, glogp.contiguous(), lens)
+        return grad[0], None, None

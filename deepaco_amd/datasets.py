@@ -1,6 +1,6 @@
 """`python utils.py` in a problem directory writes that problem's evaluation sets under ../data/<problem>/, as the
 reference's utils.py files do when run as scripts (cvrp/utils.py:55-67, cvrp_nls/utils.py:113-124, op/utils.py:60-70,
-pctsp/utils.py:75-85, sop/utils.py:85-98, smtwtp/utils.py:52-65, bpp/utils.py:45-56, mkp/utils.py:60-82; tsp/ and
+pctsp/utils.py:75-85, sop/utils.py:85-98, smtwtp/utils.py:52-65, bpp/utils.py:45-56, mkp/utils.py:60-82, mkp_transformer/utils.py:46-67; tsp/ and
 tsp_nls/ ship their sets and generate nothing).  One table instead of eight script tails: per problem the seed policy,
 the sizes, how one instance becomes one record, and the container format -- so that the files hold what the reference's
 load_*_dataset functions (and the drop-in's) expect.  Instances come from the problem's own utils module (the drop-in's
@@ -32,6 +32,11 @@ _SPECS = {
              lambda u, n: (lambda prize, w: torch.cat((prize.unsqueeze(1), w), dim=1))(*u.gen_instance(n, 5, "cpu")), _stack),
             ("testDataset-{n}.pt", 123456, False, (50,), 100,
              lambda u, n: (lambda prize, w: torch.cat((prize.unsqueeze(1), w), dim=1))(*u.gen_instance(n, 5, "cpu")), _stack)],
+    # mkp_transformer/utils.py:46-67: row 0 = price, rows 1..m = weights; 30 validation and 100 test instances per size
+    "mkp_transformer": [("valDataset-{n}.pt", 12345, False, (300, 500), 30,
+                         lambda u, n: (lambda price, w: torch.cat((price.unsqueeze(0), w), dim=0))(*u.gen_instance(n, 5)), _stack),
+                        ("testDataset-{n}.pt", 123456, False, (300, 500), 100,
+                         lambda u, n: (lambda price, w: torch.cat((price.unsqueeze(0), w), dim=0))(*u.gen_instance(n, 5)), _stack)],
 }
 
 

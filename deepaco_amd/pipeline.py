@@ -206,3 +206,23 @@ def infer_cvrp_nls_batch(locations, demands, n_ants, t_aco, k_sparse, net=None, 
         done = t
         out.append(colony.lowest_cost.clone())
     return torch.stack(out), colony
+
+
+@torch.no_grad()
+def infer_mkp_transformer_batch(price, weight, n_ants, t_aco, net=None):
+    """The batched form of mkp_transformer/test.py:14-38 (`infer_instance` for B instances at once): reformat -> network
+    `+ 1e-10` (the HIP encoder, one forward for the batch) -> B colonies with item-vector pheromone -> the best objective at each
+    mark of t_aco.  price [B, n], weight [B, m, n]; net: a transformer.TransformerModel or None (the colony's own heuristic,
+    price over summed weight).  Returns ([len(t_aco), B] objectives, the colony)."""
+    heu = None
+    if net is not None:
+        src = torch.cat((price.unsqueeze(2), weight.transpose(1, 2)), dim=2)          # reformat: [B, n, m+1]
+        heu = net.eval().forward_batch(src) + 1e-10
+    col = engine.BatchedMKPVec(price, weight, n_ants, heuristic=heu)
+    marks = [0] + list(t_aco)
+    out = torch.zeros((len(t_aco), price.shape[0]), device=price.device)
+    for i in range(len(t_aco)):
+        col.run(marks[i + 1] - marks[i])
+        out[i] = col.alltime_best_obj
+    col.check_feasible()
+    return out, col

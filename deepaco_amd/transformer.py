@@ -1,0 +1,102 @@
+"""The heuristic network of the reference's mkp_transformer/net.py on MI355X: `TransformerModel`, whose `state_dict()` has the
+reference's keys and shapes (45 entries, 21 761 parameters at six input features), so the pretrained checkpoints load
+unchanged:
+
+    transformer_encoder.layers.{0,1,2}.{self_attn.in_proj_weight [96,32], self_attn.in_proj_bias, self_attn.out_proj.*,
+    linear1.*, linear2.*, norm1.*, norm2.*}, encoder.*, decoder_heu._dummy (empty, frozen), decoder_heu.lins.{0,1,2}.*
+
+With gradients disabled the forward is the HIP encoder (csrc/daco_transformer.hip through engine.transformer_forward; a
+missing library is an error, there is no fall-back).  With gradients enabled it runs on torch ops built from the same
+parameters, so that mkp_transformer/train.py's loss.backward() works through torch autograd; a HIP backward for the encoder
+is the follow-up.  `forward(src)` takes the reference's [n, 1, m+1] and returns [n]; `forward_batch` takes
+[B, n, m+1] and returns [B, n], every sequence divided by its own maximum.
+"""
+import math
+
+import torch
+from torch import nn
+import torch.nn.functional as F
+
+from . import engine
+
+_LAYER_ORDER = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+                "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias",
+                "norm2.weight", "norm2.bias")
+
+
+class MLP(nn.Module):
+    @property
+    def device(self):
+        return self._dummy.device
+
+    def __init__(self, units_list, act_fn):
+        super().__init__()
+        assert act_fn == 'relu'
+        self._dummy = nn.Parameter(torch.empty(0), requires_grad=False)
+        self.units_list = units_list
+        self.depth = len(units_list) - 1
+        self.lins = nn.ModuleList([nn.Linear(units_list[i], units_list[i + 1]) for i in range(self.depth)])
+
+    def forward(self, x):
+        for i, lin in enumerate(self.lins):
+            x = lin(x)
+            x = F.relu(x) if i < self.depth - 1 else torch.sigmoid(x)
+        return x
+
+
+class ParNet(MLP):
+    def __init__(self, depth=3, units=32, preds=1, act_fn='relu'):
+        self.units, self.preds = units, preds
+        super().__init__([units] * depth + [preds], act_fn)
+
+    def forward(self, x):
+        return super().forward(x).squeeze(dim=-1)
+
+
+class TransformerModel(nn.Module):
+
+    def __init__(self, ntoken_input=6, d_model=32, nhead=2, d_hid=32, nlayers=3, dropout=0):
+        super().__init__()
+        assert (d_model, nhead, d_hid, nlayers, dropout) == (32, 2, 32, 3, 0), "the HIP encoder is built for the reference's sizes"
+        self.model_type = 'Transformer'
+        self.transformer_encoder = nn.TransformerEncoder(nn.TransformerEncoderLayer(d_model, nhead, d_hid, dropout), nlayers,
+                                                         enable_nested_tensor=False)
+        self.encoder = nn.Linear(ntoken_input, d_model)
+        self.d_model = d_model
+        self.decoder_heu = ParNet()
+        self.encoder.weight.data.uniform_(-0.1, 0.1)          # mkp_transformer/net.py:29-31
+        self._packed = None
+
+    # ---- the flat parameter block of csrc/daco_transformer.hip
+    def _ordered_parameters(self):
+        ps = [self.encoder.weight, self.encoder.bias]
+        for layer in self.transformer_encoder.layers:
+            sd = dict(layer.named_parameters())
+            ps += [sd[k] for k in _LAYER_ORDER]
+        for lin in self.decoder_heu.lins:
+            ps += [lin.weight, lin.bias]
+        return ps
+
+    def packed_parameters(self):
+        ps = self._ordered_parameters()
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if self._packed is None or self._packed[0] != key:
+            self._packed = (key, torch.cat([p.detach().float().reshape(-1) for p in ps]).contiguous())
+        return self._packed[1]
+
+    def _torch_forward(self, src_n_B_f):
+        x = self.encoder(src_n_B_f) * math.sqrt(self.d_model)
+        heu = self.decoder_heu(self.transformer_encoder(x))            # [n, B]
+        return heu / heu.max(dim=0, keepdim=True).values
+
+    def forward_batch(self, src):
+        """src [B, n, m+1] -> [B, n]"""
+        if not src.is_cuda or not self.encoder.weight.is_cuda:
+            raise engine._lib.DacoError("TransformerModel needs its input and parameters on a HIP device; there is no CPU path")
+        if torch.is_grad_enabled():
+            return self._torch_forward(src.transpose(0, 1)).transpose(0, 1)
+        return engine.transformer_forward(src, self.packed_parameters())
+
+    def forward(self, src):
+        """src [n, 1, m+1] (mkp_transformer/utils.py reformat) -> [n]"""
+        return self.forward_batch(src.transpose(0, 1))[0]

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 126 /* 0.1.21: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n) */
+#define DACO_VERSION 127 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*) */
 
 /* error codes */
 #define DACO_OK 0
@@ -630,6 +630,70 @@ int daco_tsp_knn_graph_csr(void *stream, int B, int n, int k, const float *coord
  */
 int daco_heu_matrix(void *stream, int B, int n, int E, const int64_t *edge_index, const float *heu, float fill, float add,
                     float *out, int32_t *bad);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_mkpv_sample -- fused solution construction of the vector-pheromone knapsack colony (one launch)
+ *   mkp_transformer/aco.py:111-178 gen_sol / pick_item / update_dummy_state / update_knapsack, with :101-109 gen_sol_obj
+ * n counts the dummy item n-1 (n <= 1024, DACO_E_TOOLARGE above).  tau / eta [B][n] f32 are VECTORS over the items
+ * (*_bstride between instances, 0 = shared; eta[n-1] is the dummy's 1e-8 of :64): every draw of every ant uses
+ * p_k = tau_k^alpha * eta_k^beta * [k open], the first item included (:123-129).  item_weights [B][n][m], 1 <= m <= 8,
+ * every capacity is 1 (:7,175): an open item k with any_d(knapsack_d + weight[k][d] > 1) closes for good, strict, float32,
+ * knapsack summed in pick order.  An ant whose real items are all closed is done; the reference then draws the dummy with
+ * probability 1 until the slowest ant is done, which is the padding written here.
+ *   price  [B][n] f32 (price[n-1] = 0) or NULL; with it objs [B][A] = the prices of the picks summed in pick order
+ *   mode, noise [B][noise_steps][A][n], seed / iter / ant_gid0: as daco_sibling_sample; draw t = 0, 1, ... is step t + 1
+ *   sols   [B][Lmax][A] int64 padded with n-1; lens [B][A] = items of each ant; logp / rowsum [B][Lmax][A] or NULL
+ *          (one per draw, log(1 - eps) / 1 in the padding); flags [B] or NULL as daco_cvrp_sample (1: every open candidate had
+ *          weight 0, 2: Lmax or the noise tensor too short)
+ */
+int daco_mkpv_sample(void *stream, int B, int n, int A, int m, const float *tau, long tau_bstride,
+                     const float *eta, long eta_bstride, float alpha, float beta,
+                     const float *item_weights, const float *price, int mode, const float *noise,
+                     int noise_steps, uint64_t seed, uint64_t iter, uint32_t ant_gid0, int Lmax,
+                     int64_t *sols, int32_t *lens, float *logp, float *rowsum, float *objs, int32_t *flags);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_mkpv_backward -- replaces autograd through Categorical(dist).log_prob of mkp_transformer/aco.py:141-148
+ *   (consumed by the REINFORCE loss of mkp_transformer/train.py:26-30)
+ * grad_eta[b][k] += sum over draws (t,a) of grad_logp[t][a] * beta * ( [k = pick] / eta_k - p_k / (eta_k * S_ta) ), 0 where
+ * the probability was clamped; sols / rowsum / lens as daco_mkpv_sample returned them, rows = its Lmax.  grad_eta [B][n]
+ * is accumulated into (caller zeroes); entries of items no draw had open are not touched; entry n-1 (the dummy) never is.
+ * One f32 atomic per (workgroup of four ants, item): reproducible to rounding.
+ */
+int daco_mkpv_backward(void *stream, int B, int n, int A, int m, int rows, const float *tau, long tau_bstride,
+                       const float *eta, long eta_bstride, float alpha, float beta, const float *item_weights,
+                       const int64_t *sols, const float *rowsum, const float *grad_logp, const int32_t *lens,
+                       float *grad_eta);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_mkpv_update -- mkp_transformer/aco.py:85-99 update_pheronome with the best tracking of run() (:71-83)
+ * tau [B][n] in place: tau *= decay; then per ant in index order (elitist != 0: only the first maximum of objs)
+ * tau[k] += Q[b] * objs[a] for every item k that occurs in the ant's column of sols [B][rows][A] -- once, however often
+ * it occurs (the reference's index-put) -- reading the rows below the longest ant's length (lens [B][A]; NULL: all rows).
+ * min_max != 0: every entry below tmin becomes tmin (:98 compares the product (tau > 1e-9) * tau), then every entry above
+ * tmax becomes tmax.  Sequential adds in ant order, no atomics on tau: bit-identical to the reference's loop.
+ * best_obj [B] (in/out) / best_sol [B][rows] (out) or NULL: where max(objs) > best_obj it replaces it and the ant's column
+ * is copied (strict: the first best stays).
+ */
+int daco_mkpv_update(void *stream, int B, int n, int A, int rows, const int64_t *sols, const int32_t *lens,
+                     const float *objs, const float *Q, float decay, int elitist, int min_max, float tmin,
+                     float tmax, float *tau, float *best_obj, int64_t *best_sol);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_transformer_forward -- replaces TransformerModel.forward of mkp_transformer/net.py:9-45 without gradients
+ *   (mkp_transformer/test.py:14-18): Linear(feats, 32) * sqrt(32), three post-norm encoder layers (d_model 32, 2 heads of
+ *   16, softmax over all n keys, d_hid 32, relu, LayerNorm eps 1e-5), ParNet 32-32-32-1 with a sigmoid, heu / heu.max()
+ * src [G][n][feats] f32 (G sequences side by side; the reference's batch dimension is 1 per instance) -> out [G][n] f32.
+ * params: one flat f32 block of daco_transformer_param_floats(feats) floats (0 for feats outside 1..16) in the layout
+ * documented at the top of csrc/daco_transformer.hip (torch's [out][in] matrices in state_dict order of the encoder,
+ * the three layers, the decoder); param_floats must equal that count (DACO_E_BADARG).  n <= 4096 (DACO_E_TOOLARGE).
+ * workspace: daco_transformer_workspace_bytes(G, n) bytes (DACO_E_WORKSPACE below that).  Nine launches, float32 k-ordered
+ * fma chains, no library GEMM, the n x n scores are never written.
+ */
+size_t daco_transformer_param_floats(int feats);
+size_t daco_transformer_workspace_bytes(int G, int n);
+int daco_transformer_forward(void *stream, int G, int n, int feats, const float *src, const float *params,
+                             size_t param_floats, float *out, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
