@@ -86,11 +86,16 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 127          # include/deepaco_hip.h DACO_VERSION this table was written against
+ABI_VERSION = 128          # include/deepaco_hip.h DACO_VERSION this table was written against
 
 
 class DacoError(RuntimeError):
     pass
+
+
+class DacoTooLarge(DacoError, ValueError):
+    """DACO_E_TOOLARGE: a size beyond a kernel's plan.  A ValueError, as it always was, and a DacoError like every other
+    failure of the library, so that `except DacoError` misses nothing the library refuses."""
 
 
 def lib():
@@ -116,5 +121,5 @@ def check(rc, what):
     if rc != 0:
         msg = lib().daco_last_error().decode("utf-8", "replace")
         if rc == -2:
-            raise ValueError(f"{what}: {msg}")
+            raise DacoTooLarge(f"{what}: {msg}")
         raise DacoError(f"{what} failed (code {rc}): {msg}")

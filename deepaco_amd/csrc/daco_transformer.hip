@@ -17,7 +17,8 @@
 // finishes, so a layer is two launches: (a) one thread per token forms q, k, v (layer 0: the input projection first);
 // (b) one thread per token does both heads' attention with an online softmax -- the workgroup streams K and V of the
 // (sequence, head) through LDS in tiles of 128 keys (16 KB static LDS; every lane reads the same key at a time, a
-// broadcast), the n x n scores are never written -- and then, still in registers, out_proj, residual + LayerNorm, the FFN,
+// broadcast), the n x n scores are never written; every tile is summed on its own and merged into the totals, so no
+// float32 chain is longer than a tile -- and then, still in registers, out_proj, residual + LayerNorm, the FFN,
 // residual + LayerNorm.  After the third layer one launch per token for ParNet, one workgroup per sequence for / max:
 // 1 + 3 * 2 + 2 = 9 launches, no host synchronisation.  Every linear is y_o = b_o, then y_o = fma(W[o][i], x_i, y_o) for
 // i ascending (k-ordered chains; the weights are wave-uniform loads); a score is the k-ordered chain of q_d * k_d,
@@ -106,10 +107,15 @@ tf_attn_ffn_kernel(int n, const float *__restrict__ lp, const float *__restrict_
   const float *base = QKV + (size_t)g * n * 96;
   float attn[32];
   for (int h = 0; h < TH; ++h) {
-    float q[THD], acc[THD];
+    float q[THD], tot[THD];
 #pragma unroll
-    for (int d = 0; d < THD; ++d) { q[d] = QKV[row * 96 + h * THD + d]; acc[d] = 0.0f; }
-    float mx = -__builtin_inff(), den = 0.0f;
+    for (int d = 0; d < THD; ++d) { q[d] = QKV[row * 96 + h * THD + d]; tot[d] = 0.0f; }
+    // Two levels of sums: a tile's keys are summed under the tile's own running maximum, starting from zero, and the tile's
+    // (maximum, denominator, accumulators) are then merged into the totals.  One float32 chain over all n keys loses
+    // n * eps: at n = 4095 with the pretrained block that was 2.9 x the tolerance against float64 (1024: 0.83 x); chains of
+    // 128 keys plus n / 128 merges keep 0.06 x.  One tile (n <= 128): the merge is * 1 and + 0, the result
+    // is bit for bit that of the single chain.
+    float tmx = -__builtin_inff(), tden = 0.0f;
     for (int t0 = 0; t0 < n; t0 += TTILE) {
       __syncthreads();
       const int key = t0 + threadIdx.x;
@@ -123,6 +129,10 @@ tf_attn_ffn_kernel(int n, const float *__restrict__ lp, const float *__restrict_
       }
       __syncthreads();
       const int cnt = n - t0 < TTILE ? n - t0 : TTILE;
+      float acc[THD];
+#pragma unroll
+      for (int d = 0; d < THD; ++d) acc[d] = 0.0f;
+      float mx = -__builtin_inff(), den = 0.0f;
       for (int j = 0; j < cnt; ++j) {
         float s = 0.0f;
 #pragma unroll
@@ -140,9 +150,16 @@ tf_attn_ffn_kernel(int n, const float *__restrict__ lp, const float *__restrict_
 #pragma unroll
         for (int d = 0; d < THD; ++d) acc[d] = __builtin_fmaf(p, Vs[j * THD + d], acc[d]);
       }
+      // merge the tile (cnt >= 1: mx is a score) into the totals; first tile: exp(-inf) = 0 times zeros
+      const float m = tmx > mx ? tmx : mx;
+      const float ct = expf(tmx - m), ca = expf(mx - m);
+      tden = __builtin_fmaf(tden, ct, den * ca);
+#pragma unroll
+      for (int d = 0; d < THD; ++d) tot[d] = __builtin_fmaf(tot[d], ct, acc[d] * ca);
+      tmx = m;
     }
 #pragma unroll
-    for (int d = 0; d < THD; ++d) attn[h * THD + d] = acc[d] / den;
+    for (int d = 0; d < THD; ++d) attn[h * THD + d] = tot[d] / tden;
   }
   if (!live) return;                                     // (no barrier below)
   float x[32], y[32];

@@ -65,7 +65,6 @@ class TransformerModel(nn.Module):
         self.d_model = d_model
         self.decoder_heu = ParNet()
         self.encoder.weight.data.uniform_(-0.1, 0.1)          # mkp_transformer/net.py:29-31
-        self._packed = None
 
     # ---- the flat parameter block of csrc/daco_transformer.hip
     def _ordered_parameters(self):
@@ -78,11 +77,10 @@ class TransformerModel(nn.Module):
         return ps
 
     def packed_parameters(self):
-        ps = self._ordered_parameters()
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if self._packed is None or self._packed[0] != key:
-            self._packed = (key, torch.cat([p.detach().float().reshape(-1) for p in ps]).contiguous())
-        return self._packed[1]
+        """The flat block, packed from the parameters as they are NOW on every call.  No cache: a write through `.data`
+        (net.py:31's own `encoder.weight.data.uniform_`, an EMA's `p.data.copy_`) changes neither `data_ptr()` nor `_version`,
+        so nothing cheap tells a stale block from a fresh one; one cat of 44 small tensors is the price."""
+        return torch.cat([p.detach().float().reshape(-1) for p in self._ordered_parameters()]).contiguous()
 
     def _torch_forward(self, src_n_B_f):
         x = self.encoder(src_n_B_f) * math.sqrt(self.d_model)

@@ -257,12 +257,49 @@ def race_two_draws(w, W, noise):
     return np.stack((first, second))
 
 
-def encoder_forward(flat, src):
+ENCODER_TILE = 128          # keys per LDS tile of tf_attn_ffn_kernel: where the mutants below cut
+
+
+def encoder_mutants(n, batch_member=False):
+    """The mutants of encoder_forward that change anything at n tokens: ("drop", j) for j in {0, 127, 128, n-1} (n >= 2: an
+    attention row needs a key), "first_tile" / "last_tile" (more than one tile), "swap_heads", and for a sequence g > 0 of a
+    batch "kv_of_seq0"."""
+    ms = [("drop", j) for j in sorted({0, 127, 128, n - 1}) if j < n and n >= 2]
+    if n > ENCODER_TILE:
+        ms += ["first_tile", "last_tile"]
+    ms.append("swap_heads")
+    if batch_member:
+        ms.append("kv_of_seq0")
+    return ms
+
+
+def encoder_forward(flat, src, mutant=None, seq0=None, stats=None):
     """float64 restatement of the heuristic network (mkp_transformer/net.py:9-45) reading the FLAT parameter block in the
-    layout documented at the top of csrc/daco_transformer.hip: src [n, feats] -> heu [n] (divided by its maximum)."""
+    layout documented at the top of csrc/daco_transformer.hip: src [n, feats] -> heu [n] (divided by its maximum).
+
+    mutant (None: the network itself, the arithmetic untouched): a deliberately wrong attention, in every layer and head, that a
+    test case must be able to tell from the right one -- ("drop", j): key j is missing; "first_tile": only keys 0..127 are
+    seen; "last_tile": only the keys of the last tile of 128; "swap_heads": the two heads' outputs change places;
+    "kv_of_seq0": keys and values are those of another sequence `seq0` [n, feats] of the batch (a lost g * n * 96 offset).
+    stats: a dict that receives, per layer and head, the widest score span of a row ("span") and every row's
+    highest-scoring key ("top")."""
     flat, x = np.asarray(flat, np.float64), np.asarray(src, np.float64)
     n, feats = x.shape
     pos = [0]
+    keys = None
+    if isinstance(mutant, tuple) and mutant[0] == "drop":
+        keys = np.delete(np.arange(n), mutant[1])
+    elif mutant == "first_tile":
+        keys = np.arange(min(n, ENCODER_TILE))
+    elif mutant == "last_tile":
+        keys = np.arange((n - 1) // ENCODER_TILE * ENCODER_TILE, n)
+    elif mutant not in (None, "swap_heads", "kv_of_seq0"):
+        raise ValueError(mutant)
+    assert keys is None or keys.size > 0
+    x0 = None
+    if mutant == "kv_of_seq0":
+        x0 = np.asarray(seq0, np.float64)
+        assert x0.shape == x.shape
 
     def take(*shape):
         k = int(np.prod(shape))
@@ -276,19 +313,36 @@ def encoder_forward(flat, src):
         return (v - mu) / np.sqrt(var + 1e-5) * w + b
     W, b = take(32, feats), take(32)
     x = (x @ W.T + b) * np.sqrt(32.0)
+    if x0 is not None:
+        x0 = (x0 @ W.T + b) * np.sqrt(32.0)
     for _ in range(3):
         in_w, in_b, out_w, out_b = take(96, 32), take(96), take(32, 32), take(32)
         l1_w, l1_b, l2_w, l2_b = take(32, 32), take(32), take(32, 32), take(32)
         n1_w, n1_b, n2_w, n2_b = take(32), take(32), take(32), take(32)
-        qkv = x @ in_w.T + in_b
-        heads = []
-        for h in range(2):
-            q, k, v = (qkv[:, o + 16 * h:o + 16 * h + 16] for o in (0, 32, 64))
-            s = q @ k.T * 0.25
-            p = np.exp(s - s.max(axis=1, keepdims=True))
-            heads.append((p / p.sum(axis=1, keepdims=True)) @ v)
-        x = norm(x + np.concatenate(heads, axis=1) @ out_w.T + out_b, n1_w, n1_b)
-        x = norm(x + np.maximum(x @ l1_w.T + l1_b, 0) @ l2_w.T + l2_b, n2_w, n2_b)
+
+        def block(x, kv, mutate):
+            qkv = x @ in_w.T + in_b
+            kv = qkv if kv is None else kv
+            heads = []
+            for h in range(2):
+                q = qkv[:, 16 * h:16 * h + 16]
+                k, v = (kv[:, o + 16 * h:o + 16 * h + 16] for o in (32, 64))
+                if mutate and keys is not None:
+                    k, v = k[keys], v[keys]
+                s = q @ k.T * 0.25
+                if stats is not None and mutate:
+                    stats.setdefault("span", []).append(float((s.max(axis=1) - s.min(axis=1)).max()))
+                    stats.setdefault("top", []).append(s.argmax(axis=1))
+                p = np.exp(s - s.max(axis=1, keepdims=True))
+                heads.append((p / p.sum(axis=1, keepdims=True)) @ v)
+            if mutate and mutant == "swap_heads":
+                heads = heads[::-1]
+            x = norm(x + np.concatenate(heads, axis=1) @ out_w.T + out_b, n1_w, n1_b)
+            return norm(x + np.maximum(x @ l1_w.T + l1_b, 0) @ l2_w.T + l2_b, n2_w, n2_b)
+        if x0 is None:
+            x = block(x, None, True)
+        else:
+            x, x0 = block(x, x0 @ in_w.T + in_b, True), block(x0, None, False)
     for i in range(3):
         W, b = take(32 if i < 2 else 1, 32), take(32 if i < 2 else 1)
         x = x @ W.T + b

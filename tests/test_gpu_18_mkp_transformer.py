@@ -228,11 +228,15 @@ def test_in_kernel_draws_follow_the_masked_categorical(mode, n1, m, alpha, beta)
 
 
 # ------------------------------------------------------------------ 5. the batched colony loop
-@pytest.mark.parametrize("elitist,min_max", [(False, False), (True, False), (False, True)])
-def test_batched_run_equals_the_class_step_by_step(elitist, min_max):
+@pytest.mark.parametrize("elitist,min_max,size", [
+    pytest.param(False, False, (80, 10, 6), id="False-False"), pytest.param(True, False, (80, 10, 6), id="True-False"),
+    pytest.param(False, True, (80, 10, 6), id="False-True"),
+    # a second tile of ants (A > 64) and items in the third lane of a thread (more than 512)
+    pytest.param(False, False, (600, 70, 3), id="False-False-n600-A70")])
+def test_batched_run_equals_the_class_step_by_step(elitist, min_max, size):
     from deepaco_amd import engine
     from deepaco_amd.mkp_transformer.aco import ACO
-    B, n, m, A, Tn = 3, 80, 5, 10, 6
+    (n, A, Tn), B, m = size, 3, 5
     rng = np.random.default_rng(99)
     price = T(np.stack([spec.gen_instance(rng, n, m)[0] for _ in range(B)]))
     weight = T(np.stack([spec.gen_instance(rng, n, m)[1] for _ in range(B)]))

@@ -99,7 +99,7 @@ def test_spec_race_draws_follow_the_masked_categorical(n1, m):
 # ------------------------------------------------------------------ the new surface, as far as it goes without a GPU
 def test_abi_argument_checks():
     L = _lib.lib()
-    assert L.daco_version() >= 127
+    assert L.daco_version() >= 128
 
     def sample(B=1, n=21, A=4, m=5, tau=1, eta=1, w=1, mode=2, noise=None, steps=0, Lmax=20, sols=1, lens=1):
         return L.daco_mkpv_sample(None, B, n, A, m, tau, 0, eta, 0, 1.0, 1.0, w, None, mode, noise, steps, 0, 0, 0, Lmax, sols, lens,
