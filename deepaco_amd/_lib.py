@@ -82,11 +82,15 @@ SIGNATURES = {
     "daco_transformer_param_floats": (_sz, [_i]),
     "daco_transformer_workspace_bytes": (_sz, [_i, _i]),
     "daco_transformer_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _sz]),
+    "daco_transformer_saved_floats": (_sz, [_i, _i]),
+    "daco_transformer_train_workspace_bytes": (_sz, [_i, _i]),
+    "daco_transformer_forward_train": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz]),
+    "daco_transformer_backward": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz]),
     "daco_tsp_nls": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _l, _vp, _vp, _vp]),
 }
 
 
-ABI_VERSION = 128          # include/deepaco_hip.h DACO_VERSION this table was written against
+ABI_VERSION = 129          # include/deepaco_hip.h DACO_VERSION this table was written against
 
 
 class DacoError(RuntimeError):

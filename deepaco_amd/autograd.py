@@ -125,3 +125,44 @@ class MkpvSampleFn(torch.autograd.Function):
         alpha, beta, weight = ctx.meta
         grad = engine.mkpv_backward(tau, eta, alpha, beta, weight, sols, rowsum, glogp.contiguous(), lens)
         return grad[0], None, None
+
+
+class MkpvBatchSampleFn(torch.autograd.Function):
+    """MkpvSampleFn for B colonies at once: heuristic [B, n+1] (the dummy's 1e-8 last) -> (sols [B,Lmax,A], log_probs
+    [B,Lmax,A], lens [B,A], objs [B,A], flags [B]); the backward is one daco_mkpv_backward launch for all instances."""
+
+    @staticmethod
+    def forward(ctx, heuristic, colony, noise):
+        colony.heuristic = heuristic.detach().float().reshape(colony.B, -1).contiguous()
+        sols, logp, rowsum, lens, objs, flags = colony.sample(require_prob=True, noise=noise)
+        ctx.save_for_backward(colony.pheromone.clone(), colony.heuristic, sols, rowsum, lens)
+        ctx.meta = (colony.alpha, colony.beta, colony.weight)
+        ctx.mark_non_differentiable(sols, lens, objs, flags)
+        return sols, logp, lens, objs, flags
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _gs, glogp, _gl, _go, _gf):
+        tau, eta, sols, rowsum, lens = ctx.saved_tensors
+        alpha, beta, weight = ctx.meta
+        return engine.mkpv_backward(tau, eta, alpha, beta, weight, sols, rowsum, glogp.contiguous(), lens), None, None
+
+
+class TransformerFn(torch.autograd.Function):
+    """The mkp_transformer heuristic network on HIP with gradients: src [G, n, feats], flat (the parameter block of
+    transformer.TransformerModel, a differentiable torch.cat of the 44 tensors, whose own backward hands every tensor its
+    slice) -> [G, n].  daco_transformer_forward_train forward, daco_transformer_backward backward; the context holds the
+    forward's `saved` tensor.  No gradient for src (the network's input is instance data)."""
+
+    @staticmethod
+    def forward(ctx, src, flat):
+        src, flat = src.detach(), flat.detach()
+        out, saved = engine.transformer_forward_train(src, flat)
+        ctx.save_for_backward(src, flat, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        src, flat, saved = ctx.saved_tensors
+        return None, engine.transformer_backward(src, flat, saved, grad_out)

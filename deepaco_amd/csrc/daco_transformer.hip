@@ -24,45 +24,16 @@
 // i ascending (k-ordered chains; the weights are wave-uniform loads); a score is the k-ordered chain of q_d * k_d,
 // times 1/4.  The 32-wide linears are plain v_fma here, not MFMA: at 21 761 parameters and n <= 1023 tokens the forward
 // is bound by the dependent chain of a token's layers, not by FLOPs.
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+//
+// Training forward (daco_transformer_forward_train): the same kernels instantiated with SAVE.  Same arithmetic -- the output is
+// bit for bit the no-grad forward's -- and every intermediate the backward (daco_transformer_train.hip) needs goes to a
+// caller-owned `saved` buffer, 871 floats per token + 2 per sequence (layout: daco_transformer.h): layer inputs, q/k/v, the
+// attention output, both LayerNorm inputs, the ReLU input, the log-sum-exp of every (token, head), ParNet's hidden rows, the
+// raw sigmoid, every sequence's maximum and the first index attaining it.  X and QKV live in `saved` there: the training
+// forward needs no scratch, its workspace argument may be NULL / 0 bytes.
+#include "daco_transformer.h"
 
 namespace daco {
-
-constexpr int TH = 2, THD = 16, TLAYERS = 3, TTILE = 128;
-// per layer: in_w 3072, in_b 96, out_w 1024, out_b 32, l1_w 1024, l1_b 32, l2_w 1024, l2_b 32, 4 x 32 norm = 6464
-constexpr int OFF_IN_W = 0, OFF_IN_B = 3072, OFF_OUT_W = 3168, OFF_OUT_B = 4192, OFF_L1_W = 4224, OFF_L1_B = 5248,
-              OFF_L2_W = 5280, OFF_L2_B = 6304, OFF_N1_W = 6336, OFF_N1_B = 6368, OFF_N2_W = 6400, OFF_N2_B = 6432,
-              LAYER_FLOATS = 6464;
-constexpr int HEAD_FLOATS = 1024 + 32 + 1024 + 32 + 32 + 1;
-
-__host__ __device__ inline size_t t_layer_off(int feats, int l) { return (size_t)32 * feats + 32 + (size_t)l * LAYER_FLOATS; }
-
-// y[0..NO) = W x + b, W [NO][32] row-major
-template <int NO>
-__device__ inline void linear32(const float *__restrict__ W, const float *__restrict__ b, const float (&x)[32], float *y) {
-#pragma unroll 4
-  for (int o = 0; o < NO; ++o) {
-    float acc = b[o];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) acc = __builtin_fmaf(W[o * 32 + i], x[i], acc);
-    y[o] = acc;
-  }
-}
-
-// LayerNorm over 32 values in place: mean, biased variance, (x - mean) / sqrt(var + 1e-5) * w + b
-__device__ inline void layer_norm32(float (&x)[32], const float *__restrict__ w, const float *__restrict__ b) {
-  float mean = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 32; ++i) mean = mean + x[i];
-  mean = mean * (1.0f / 32.0f);
-  float var = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 32; ++i) { const float d = x[i] - mean; var = __builtin_fmaf(d, d, var); }
-  const float rstd = 1.0f / sqrtf(var * (1.0f / 32.0f) + 1e-5f);
-#pragma unroll
-  for (int i = 0; i < 32; ++i) x[i] = __builtin_fmaf((x[i] - mean) * rstd, w[i], b[i]);
-}
 
 // (a) q, k, v of one token; layer 0 forms x from the input features first
 __global__ void __launch_bounds__(128)
@@ -97,8 +68,13 @@ tf_qkv_kernel(int n, int feats, int first, const float *__restrict__ src, const 
 }
 
 // (b) attention of both heads, out_proj, residual + LN1, FFN, residual + LN2 for one token
+// SAVE (the training forward): the same arithmetic, and O, r1, the ReLU input, r2 and the log-sum-exp of every (token, head)
+// go to the `saved` buffer (daco_transformer.h); X is the layer's input, Xout its output (no-grad forward: Xout == X).
+template <bool SAVE>
 __global__ void __launch_bounds__(128)
-tf_attn_ffn_kernel(int n, const float *__restrict__ lp, const float *__restrict__ QKV, float *__restrict__ X) {
+tf_attn_ffn_kernel(int n, const float *__restrict__ lp, const float *__restrict__ QKV, float *X, float *Xout,
+                   float *__restrict__ svO, float *__restrict__ svR1, float *__restrict__ svH, float *__restrict__ svR2,
+                   float *__restrict__ svLse) {
   __shared__ __attribute__((aligned(16))) float Ks[TTILE * THD];
   __shared__ __attribute__((aligned(16))) float Vs[TTILE * THD];
   const int g = blockIdx.y, tok = blockIdx.x * 128 + threadIdx.x;
@@ -160,30 +136,49 @@ tf_attn_ffn_kernel(int n, const float *__restrict__ lp, const float *__restrict_
     }
 #pragma unroll
     for (int d = 0; d < THD; ++d) attn[h * THD + d] = tot[d] / tden;
+    if (SAVE && live) svLse[row * 2 + h] = tmx + logf(tden);
   }
   if (!live) return;                                     // (no barrier below)
+  if (SAVE) {
+#pragma unroll
+    for (int o = 0; o < 32; ++o) svO[row * 32 + o] = attn[o];
+  }
   float x[32], y[32];
 #pragma unroll
   for (int o = 0; o < 32; ++o) x[o] = X[row * 32 + o];
   linear32<32>(lp + OFF_OUT_W, lp + OFF_OUT_B, attn, y);
 #pragma unroll
   for (int o = 0; o < 32; ++o) x[o] = x[o] + y[o];
+  if (SAVE) {
+#pragma unroll
+    for (int o = 0; o < 32; ++o) svR1[row * 32 + o] = x[o];
+  }
   layer_norm32(x, lp + OFF_N1_W, lp + OFF_N1_B);
   float hdn[32];
   linear32<32>(lp + OFF_L1_W, lp + OFF_L1_B, x, hdn);
+  if (SAVE) {
+#pragma unroll
+    for (int o = 0; o < 32; ++o) svH[row * 32 + o] = hdn[o];
+  }
 #pragma unroll
   for (int o = 0; o < 32; ++o) hdn[o] = hdn[o] > 0.0f ? hdn[o] : 0.0f;
   linear32<32>(lp + OFF_L2_W, lp + OFF_L2_B, hdn, y);
 #pragma unroll
   for (int o = 0; o < 32; ++o) x[o] = x[o] + y[o];
+  if (SAVE) {
+#pragma unroll
+    for (int o = 0; o < 32; ++o) svR2[row * 32 + o] = x[o];
+  }
   layer_norm32(x, lp + OFF_N2_W, lp + OFF_N2_B);
 #pragma unroll
-  for (int o = 0; o < 32; ++o) X[row * 32 + o] = x[o];
+  for (int o = 0; o < 32; ++o) Xout[row * 32 + o] = x[o];
 }
 
 // ParNet 32-32-32-1 with a sigmoid (mkp_transformer/net.py:48-75)
+template <bool SAVE>
 __global__ void __launch_bounds__(128)
-tf_head_kernel(int n, const float *__restrict__ hp, const float *__restrict__ X, float *__restrict__ raw) {
+tf_head_kernel(int n, const float *__restrict__ hp, const float *__restrict__ X, float *__restrict__ raw,
+               float *__restrict__ svH1, float *__restrict__ svH2) {
   const int g = blockIdx.y, tok = blockIdx.x * 128 + threadIdx.x;
   if (tok >= n) return;
   const size_t row = (size_t)g * n + tok;
@@ -191,9 +186,17 @@ tf_head_kernel(int n, const float *__restrict__ hp, const float *__restrict__ X,
 #pragma unroll
   for (int o = 0; o < 32; ++o) x[o] = X[row * 32 + o];
   linear32<32>(hp, hp + 1024, x, y);
+  if (SAVE) {
+#pragma unroll
+    for (int o = 0; o < 32; ++o) svH1[row * 32 + o] = y[o];
+  }
 #pragma unroll
   for (int o = 0; o < 32; ++o) x[o] = y[o] > 0.0f ? y[o] : 0.0f;
   linear32<32>(hp + 1056, hp + 2080, x, y);
+  if (SAVE) {
+#pragma unroll
+    for (int o = 0; o < 32; ++o) svH2[row * 32 + o] = y[o];
+  }
 #pragma unroll
   for (int o = 0; o < 32; ++o) x[o] = y[o] > 0.0f ? y[o] : 0.0f;
   float z;
@@ -202,9 +205,13 @@ tf_head_kernel(int n, const float *__restrict__ hp, const float *__restrict__ X,
 }
 
 // heu / heu.max() per sequence (mkp_transformer/net.py:44)
+// SAVE: the maximum and the FIRST index attaining it go to svMx / svArg (the backward's `/ max` needs both)
+template <bool SAVE>
 __global__ void __launch_bounds__(256)
-tf_max_div_kernel(int n, const float *__restrict__ raw, float *__restrict__ out) {
+tf_max_div_kernel(int n, const float *__restrict__ raw, float *__restrict__ out, float *__restrict__ svMx,
+                  int *__restrict__ svArg) {
   __shared__ float red[256];
+  __shared__ int arg[256];
   const int g = blockIdx.x;
   float mx = -__builtin_inff();
   for (int i = threadIdx.x; i < n; i += 256) mx = fmaxf(mx, raw[(size_t)g * n + i]);
@@ -216,13 +223,23 @@ tf_max_div_kernel(int n, const float *__restrict__ raw, float *__restrict__ out)
   }
   mx = red[0];
   for (int i = threadIdx.x; i < n; i += 256) out[(size_t)g * n + i] = raw[(size_t)g * n + i] / mx;
+  if (SAVE) {
+    int first = n;
+    for (int i = threadIdx.x; i < n; i += 256)
+      if (raw[(size_t)g * n + i] == mx && i < first) first = i;
+    arg[threadIdx.x] = first;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s && arg[threadIdx.x + s] < arg[threadIdx.x]) arg[threadIdx.x] = arg[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) { svMx[g] = mx; svArg[g] = arg[0]; }
+  }
 }
 
 }  // namespace daco
 
 using namespace daco;
-
-constexpr int TF_MAX_FEATS = 16, TF_MAX_TOKENS = 4096;
 
 extern "C" size_t daco_transformer_param_floats(int feats) {
   if (feats < 1 || feats > TF_MAX_FEATS) return 0;
@@ -248,11 +265,53 @@ extern "C" int daco_transformer_forward(void *stream, int G, int n, int feats, c
   for (int l = 0; l < TLAYERS; ++l) {
     const float *lp = params + t_layer_off(feats, l);
     hipLaunchKernelGGL(tf_qkv_kernel, grid, block, 0, s, n, feats, l == 0 ? 1 : 0, src, params, lp, X, QKV);
-    hipLaunchKernelGGL(tf_attn_ffn_kernel, grid, block, 0, s, n, lp, QKV, X);
+    hipLaunchKernelGGL(tf_attn_ffn_kernel<false>, grid, block, 0, s, n, lp, QKV, X, X, nullptr, nullptr, nullptr, nullptr, nullptr);
   }
-  hipLaunchKernelGGL(tf_head_kernel, grid, block, 0, s, n, params + t_layer_off(feats, TLAYERS), X, raw);
-  hipLaunchKernelGGL(tf_max_div_kernel, dim3((unsigned)G), dim3(256), 0, s, n, raw, out);
+  hipLaunchKernelGGL(tf_head_kernel<false>, grid, block, 0, s, n, params + t_layer_off(feats, TLAYERS), X, raw, nullptr, nullptr);
+  hipLaunchKernelGGL(tf_max_div_kernel<false>, dim3((unsigned)G), dim3(256), 0, s, n, raw, out, nullptr, nullptr);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("transformer kernels launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
+  return DACO_OK;
+}
+
+// ---- the training forward: the same kernels with SAVE, every intermediate in the caller's `saved` buffer
+extern "C" size_t daco_transformer_saved_floats(int G, int n) {
+  if (G <= 0 || n <= 0) return 0;
+  return (size_t)G * n * SV_TOKEN + 2 * (size_t)G;
+}
+
+int tf_check_train_args(const char *who, int G, int n, int feats, size_t param_floats, size_t saved_floats,
+                        bool needs_workspace, size_t workspace_bytes) {
+  if (feats < 1 || feats > TF_MAX_FEATS) { set_error("%s: 1 <= feats <= %d (feats=%d)", who, TF_MAX_FEATS, feats); return DACO_E_BADARG; }
+  if (n > TF_MAX_TOKENS || G > 65535) { set_error("%s: n=%d tokens exceed %d (or G=%d > 65535)", who, n, TF_MAX_TOKENS, G); return DACO_E_TOOLARGE; }
+  if (param_floats != daco_transformer_param_floats(feats)) { set_error("%s: %zu parameter floats, the layout has %zu", who, param_floats, daco_transformer_param_floats(feats)); return DACO_E_BADARG; }
+  if (saved_floats < daco_transformer_saved_floats(G, n)) { set_error("%s: saved buffer %zu < %zu floats", who, saved_floats, daco_transformer_saved_floats(G, n)); return DACO_E_WORKSPACE; }
+  const size_t need = needs_workspace ? daco_transformer_train_workspace_bytes(G, n) : 0;
+  if (workspace_bytes < need) { set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need); return DACO_E_WORKSPACE; }
+  return DACO_OK;
+}
+
+extern "C" int daco_transformer_forward_train(void *stream, int G, int n, int feats, const float *src, const float *params,
+                                              size_t param_floats, float *out, float *saved, size_t saved_floats,
+                                              void *workspace, size_t workspace_bytes) {
+  if (G <= 0 || n <= 0 || !src || !params || !out || !saved) { set_error("daco_transformer_forward_train: bad argument (G=%d n=%d)", G, n); return DACO_E_BADARG; }
+  const int rc = tf_check_train_args("daco_transformer_forward_train", G, n, feats, param_floats, saved_floats, false, workspace_bytes);
+  (void)workspace;                                       // X and QKV live in `saved`: the forward needs no scratch
+  if (rc != DACO_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t N = (size_t)G * n;
+  const SavedHead hd = saved_head(saved, N, G);
+  dim3 grid((unsigned)((n + 127) / 128), (unsigned)G), block(128);
+  for (int l = 0; l < TLAYERS; ++l) {
+    const float *lp = params + t_layer_off(feats, l);
+    const SavedLayer sv = saved_layer(saved, N, l);
+    float *Xout = l + 1 < TLAYERS ? saved_layer(saved, N, l + 1).X : hd.X;
+    hipLaunchKernelGGL(tf_qkv_kernel, grid, block, 0, s, n, feats, l == 0 ? 1 : 0, src, params, lp, sv.X, sv.QKV);
+    hipLaunchKernelGGL(tf_attn_ffn_kernel<true>, grid, block, 0, s, n, lp, sv.QKV, sv.X, Xout, sv.O, sv.R1, sv.HPRE, sv.R2, sv.LSE);
+  }
+  hipLaunchKernelGGL(tf_head_kernel<true>, grid, block, 0, s, n, params + t_layer_off(feats, TLAYERS), hd.X, hd.RAW, hd.H1, hd.H2);
+  hipLaunchKernelGGL(tf_max_div_kernel<true>, dim3((unsigned)G), dim3(256), 0, s, n, hd.RAW, out, hd.MX, hd.AMAX);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error("transformer training kernels launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
   return DACO_OK;
 }

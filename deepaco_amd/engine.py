@@ -680,6 +680,52 @@ def transformer_forward(src, params):
     return out
 
 
+def _transformer_args(src, params):
+    _require_gpu(src, params)
+    src, params = _f32c(src), _f32c(params)
+    if src.dim() != 3:
+        raise _lib.DacoError(f"transformer: src [G, n, feats] expected, got {tuple(src.shape)}")
+    return src, params
+
+
+def transformer_forward_train(src, params):
+    """The forward of transformer_forward -- the same [G, n] output, bit for bit -- that also keeps what the backward needs
+    (include/deepaco_hip.h daco_transformer_forward_train) -> (out [G, n], saved).  `saved` is a tensor of its own (871 floats
+    per token), to be handed to transformer_backward; nothing of the shared scratch carries over."""
+    src, params = _transformer_args(src, params)
+    G, n, feats = src.shape
+    dev = src.device
+    L = _lib.lib()
+    with _on(dev):
+        out = torch.empty((G, n), dtype=torch.float32, device=dev)
+        saved = torch.empty((L.daco_transformer_saved_floats(G, n),), dtype=torch.float32, device=dev)
+        rc = L.daco_transformer_forward_train(_stream(dev), G, n, feats, src.data_ptr(), params.data_ptr(), params.numel(),
+                                              out.data_ptr(), saved.data_ptr(), saved.numel(), None, 0)    # (needs no scratch)
+    _lib.check(rc, "daco_transformer_forward_train")
+    return out, saved
+
+
+def transformer_backward(src, params, saved, grad_out):
+    """Gradient of sum(grad_out * out) w.r.t. the flat parameter block, in the block's layout (daco_transformer_backward);
+    src / params as given to transformer_forward_train, `saved` as it returned it, grad_out [G, n].  No gradient for src."""
+    src, params = _transformer_args(src, params)
+    _require_gpu(saved, grad_out)
+    G, n, feats = src.shape
+    grad_out = _f32c(grad_out)
+    if tuple(grad_out.shape) != (G, n) or saved.dtype != torch.float32 or not saved.is_contiguous():
+        raise _lib.DacoError(f"transformer_backward: grad_out [{G}, {n}] and a contiguous float32 saved buffer expected")
+    dev = src.device
+    L = _lib.lib()
+    with _on(dev):
+        grad = torch.empty((params.numel(),), dtype=torch.float32, device=dev)
+        ws = _workspace(dev, L.daco_transformer_train_workspace_bytes(G, n), "transformer_train")
+        rc = L.daco_transformer_backward(_stream(dev), G, n, feats, src.data_ptr(), params.data_ptr(), params.numel(),
+                                         saved.data_ptr(), saved.numel(), grad_out.data_ptr(), grad.data_ptr(),
+                                         ws.data_ptr(), ws.numel())
+    _lib.check(rc, "daco_transformer_backward")
+    return grad
+
+
 class BatchedMKPVec:
     """B colonies of mkp_transformer/aco.py iterated side by side without a host synchronisation: per iteration one
     construction launch (objectives fused) and one launch for best tracking + pheromone update.

@@ -226,3 +226,41 @@ def infer_mkp_transformer_batch(price, weight, n_ants, t_aco, net=None):
         out[i] = col.alltime_best_obj
     col.check_feasible()
     return out, col
+
+
+def _mkp_transformer_loss(net, price, weight, n_ants, seed=0, it=0, noise=None, ant_gid0=0):
+    """The loss of mkp_transformer/train.py:15-30 for B instances: reformat -> network `+ 1e-10` -> B colonies sampled with
+    log-probabilities (one launch) -> per instance sum((mean(objs) - objs) * sum_t log_probs) / n_ants, averaged over the
+    instances.  Private: the body of train_mkp_transformer_batch, with what the tests need to compare a batch with single
+    instances.  noise: recorded Exp(1) draws [B, L, A, n+1] instead of the in-kernel stream; ant_gid0: the id of the first
+    ant (instance b of a batch draws what a single colony with ant_gid0 = b * n_ants draws).  -> (loss, colony)"""
+    from .autograd import MkpvBatchSampleFn
+    B = price.shape[0]
+    src = torch.cat((price.unsqueeze(2), weight.transpose(1, 2)), dim=2)              # reformat: [B, n, m+1]
+    heu = net.forward_batch(src) + 1e-10
+    col = engine.BatchedMKPVec(price, weight, n_ants, heuristic=heu.detach(), seed=seed, ant_gid0=ant_gid0)
+    col.iteration = int(it)
+    heu1 = torch.cat((heu, torch.full((B, 1), 1e-8, device=heu.device)), dim=1)       # the dummy item (aco.py:64)
+    sols, logp, lens, objs, flags = MkpvBatchSampleFn.apply(heu1, col, noise)
+    col.flags |= flags
+    # the reference's loop ends with the instance's longest ant (aco.py:130): rows past it do not exist there, and hold the
+    # padding's log(1 - eps) here -- masked on the device instead of trimmed, which would need the length on the host
+    rows = torch.arange(logp.shape[1], device=logp.device).view(1, -1, 1)
+    logp = logp * (rows < lens.max(dim=1).values.view(B, 1, 1))
+    loss = (((objs.mean(dim=1, keepdim=True) - objs) * logp.sum(dim=1)).sum(dim=1) / n_ants).mean()
+    return loss, col
+
+
+def train_mkp_transformer_batch(net, optimizer, price, weight, n_ants, seed=0, it=0, *, _noise=None):
+    """One optimiser step of mkp_transformer/train.py:15-31 (`train_instance`) for B instances at once, without a host
+    synchronisation: one network forward for the batch (HIP), B colonies in one launch, the REINFORCE loss of every instance
+    averaged over the instances, one backward (daco_mkpv_backward, daco_transformer_backward) and one optimizer.step().
+    price [B, n], weight [B, m, n].  Returns the loss tensor.  `_noise` is a test hook, not part of the surface: recorded
+    draws [B, L, A, n+1] instead of the in-kernel stream, as mkp_vec.ACO.gen_sol's `_noise`.  The colonies' feasibility flags
+    are not read here: that would synchronise."""
+    net.train()
+    loss, _ = _mkp_transformer_loss(net, price, weight, n_ants, seed, it, _noise)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    return loss.detach()

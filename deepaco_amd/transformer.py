@@ -6,10 +6,12 @@ unchanged:
     linear1.*, linear2.*, norm1.*, norm2.*}, encoder.*, decoder_heu._dummy (empty, frozen), decoder_heu.lins.{0,1,2}.*
 
 With gradients disabled the forward is the HIP encoder (csrc/daco_transformer.hip through engine.transformer_forward; a
-missing library is an error, there is no fall-back).  With gradients enabled it runs on torch ops built from the same
-parameters, so that mkp_transformer/train.py's loss.backward() works through torch autograd; a HIP backward for the encoder
-is the follow-up.  `forward(src)` takes the reference's [n, 1, m+1] and returns [n]; `forward_batch` takes
-[B, n, m+1] and returns [B, n], every sequence divided by its own maximum.
+missing library is an error, there is no fall-back).  With gradients enabled it is the same encoder's training forward and
+mkp_transformer/train.py's loss.backward() runs csrc/daco_transformer_train.hip (autograd.TransformerFn):
+`grad_path = "hip"`, the default.  `grad_path = "torch"` runs `_torch_forward`, nn.TransformerEncoder on torch ops built from
+the same parameters: the comparator of the tests and of A/B timing.  No gradient reaches `src`.  `forward(src)` takes the
+reference's [n, 1, m+1] and returns [n]; `forward_batch` takes [B, n, m+1] and returns [B, n], every sequence divided by its
+own maximum.
 """
 import math
 
@@ -54,6 +56,7 @@ class ParNet(MLP):
 
 
 class TransformerModel(nn.Module):
+    grad_path = "hip"          # how a forward with gradients enabled runs: "hip" | "torch" (set on the class or an instance)
 
     def __init__(self, ntoken_input=6, d_model=32, nhead=2, d_hid=32, nlayers=3, dropout=0):
         super().__init__()
@@ -82,6 +85,10 @@ class TransformerModel(nn.Module):
         so nothing cheap tells a stale block from a fresh one; one cat of 44 small tensors is the price."""
         return torch.cat([p.detach().float().reshape(-1) for p in self._ordered_parameters()]).contiguous()
 
+    def packed_parameters_with_grad(self):
+        """The same block as a differentiable cat: its backward hands every parameter its slice of the block's gradient."""
+        return torch.cat([p.float().reshape(-1) for p in self._ordered_parameters()])
+
     def _torch_forward(self, src_n_B_f):
         x = self.encoder(src_n_B_f) * math.sqrt(self.d_model)
         heu = self.decoder_heu(self.transformer_encoder(x))            # [n, B]
@@ -92,7 +99,12 @@ class TransformerModel(nn.Module):
         if not src.is_cuda or not self.encoder.weight.is_cuda:
             raise engine._lib.DacoError("TransformerModel needs its input and parameters on a HIP device; there is no CPU path")
         if torch.is_grad_enabled():
-            return self._torch_forward(src.transpose(0, 1)).transpose(0, 1)
+            if self.grad_path == "torch":
+                return self._torch_forward(src.transpose(0, 1)).transpose(0, 1)
+            if self.grad_path != "hip":
+                raise ValueError(f"grad_path is 'hip' or 'torch', not {self.grad_path!r}")
+            from .autograd import TransformerFn
+            return TransformerFn.apply(src, self.packed_parameters_with_grad())
         return engine.transformer_forward(src, self.packed_parameters())
 
     def forward(self, src):

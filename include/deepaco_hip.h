@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 128 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward) */
 
 /* error codes */
 #define DACO_OK 0
@@ -694,6 +694,31 @@ size_t daco_transformer_param_floats(int feats);
 size_t daco_transformer_workspace_bytes(int G, int n);
 int daco_transformer_forward(void *stream, int G, int n, int feats, const float *src, const float *params,
                              size_t param_floats, float *out, void *workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_transformer_forward_train / daco_transformer_backward -- replace TransformerModel.forward with gradients enabled and
+ *   torch autograd through it (mkp_transformer/train.py:15-31, loss.backward()).
+ * forward_train: the arithmetic of daco_transformer_forward -- `out` is bit for bit the same -- and what the backward needs in
+ * the caller-owned `saved` (daco_transformer_saved_floats(G, n) = 871 G n + 2 G floats; layout in csrc/daco_transformer.h:
+ * per layer the input, q/k/v, the attention output, both LayerNorm inputs, the ReLU input; ParNet's hidden rows and the raw
+ * sigmoid; the log-sum-exp of every (layer, token, head); every sequence's maximum and the first index attaining it).
+ * backward: grad_out [G][n] -> grad_params, daco_transformer_param_floats(feats) floats in the layout of `params`,
+ * OVERWRITTEN (no need to clear).  No gradient for src.  src / params / saved as forward_train had / left them.  Flash-style
+ * attention backward (the n x n probabilities are recomputed, never written), weight gradients on v_mfma_f32_16x16x4_f32 as
+ * per-128-token partials merged in a fixed order: no atomics, no memset, two calls agree bit for bit.  20 launches.
+ * workspace: the backward takes daco_transformer_train_workspace_bytes(G, n) bytes of scratch (DACO_E_WORKSPACE below that);
+ * forward_train keeps everything in `saved` and needs none: its workspace may be NULL with 0 bytes.  Nothing passes from the
+ * forward to the backward but `saved`.  Checks and codes as daco_transformer_forward; a short `saved` is DACO_E_WORKSPACE.
+ * Arithmetic: float32, except two float64 accumulators per thread for the softmax row term of the backward.
+ */
+size_t daco_transformer_saved_floats(int G, int n);
+size_t daco_transformer_train_workspace_bytes(int G, int n);
+int daco_transformer_forward_train(void *stream, int G, int n, int feats, const float *src, const float *params,
+                                   size_t param_floats, float *out, float *saved, size_t saved_floats, void *workspace,
+                                   size_t workspace_bytes);
+int daco_transformer_backward(void *stream, int G, int n, int feats, const float *src, const float *params,
+                              size_t param_floats, const float *saved, size_t saved_floats, const float *grad_out,
+                              float *grad_params, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,10 @@ warm-up, written to profiles/mkp_transformer.json:
   * construction solutions/s and the update's time, `BatchedMKPVec.run` iterations/s;
   * the encoder forward's time for 1 and 64 sequences (next to the module's torch-op path), `infer_mkp_transformer_batch`
     instances/s;
+  * `--training`: forward + backward of sum(out * g) through the network for `grad_path` "hip" (csrc/daco_transformer_train.hip)
+    and "torch" (nn.TransformerEncoder on torch ops, the training path before the HIP backward) at 1 and 64 sequences of 300
+    and 500 tokens, and one `train_mkp_transformer_batch` step at 64 x 300 x 20 ants: median of five runs of 200 (steps: 50),
+    each path in two fresh processes started alternately, merged into the same file under `training`;
   * in the same run, the existing fused `mkp` construction (daco_sibling_sample, matrix rows per step) at the same n and ants;
   * `--reference DIR` (a host that has the reference's mkp_transformer/ directory; no GPU needed): the reference's own
     ACO.run(50) on that host's CPU with its default heuristic, merged into the same file under `reference_cpu` -- another
@@ -91,7 +95,9 @@ def network_rows():
             src = torch.cat((price.unsqueeze(2), weight.transpose(1, 2)), dim=2).to(dev)
             with torch.no_grad():
                 t_hip = timeit(lambda: net.forward_batch(src), 20)
+            net.grad_path = "torch"
             t_torch = timeit(lambda: net.forward_batch(src), 5)          # gradients enabled: the torch-op path
+            net.grad_path = "hip"
             rows.append({"n": n, "sequences": G, "encoder_forward_ms": t_hip * 1e3, "torch_op_forward_ms": t_torch * 1e3})
             print(json.dumps(rows[-1]))
         price, weight = instances(64, n)
@@ -100,6 +106,66 @@ def network_rows():
         rows.append({"n": n, "instances": 64, "ants": 20, "t_aco": [1, 5, 10, 20, 50], "infer_batch_ms": t_inf * 1e3,
                      "infer_instances_per_s": 64 / t_inf})
         print(json.dumps(rows[-1]))
+    return rows
+
+
+TRAIN_SHAPES = ((300, 1), (500, 1), (300, 64), (500, 64))
+
+
+def training_child(path):
+    """one process, one grad_path: [{n, sequences, fwd_bwd_us: five runs of 200}], then the batched step"""
+    from deepaco_amd.pipeline import train_mkp_transformer_batch
+    from deepaco_amd.transformer import TransformerModel
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    net = TransformerModel().to(dev).train()
+    net.grad_path = path
+    rows = []
+    for n, G in TRAIN_SHAPES:
+        price, weight = instances(G, n)
+        src = torch.cat((price.unsqueeze(2), weight.transpose(1, 2)), dim=2).to(dev)
+        g = torch.randn(G, n, generator=torch.Generator().manual_seed(1)).to(dev)
+
+        def fwd_bwd():
+            net.zero_grad(set_to_none=True)
+            (net.forward_batch(src) * g).sum().backward()
+        for _ in range(20):
+            fwd_bwd()
+        rows.append({"n": n, "sequences": G, "fwd_bwd_us": [timeit(fwd_bwd, 200) * 1e6 for _ in range(5)]})
+    price, weight = instances(64, 300)
+    price, weight = price.to(dev), weight.to(dev)
+    opt = torch.optim.AdamW(net.parameters(), lr=3e-4)
+    it = [0]
+
+    def step():
+        it[0] += 1
+        train_mkp_transformer_batch(net, opt, price, weight, 20, seed=1, it=it[0])
+    for _ in range(10):
+        step()
+    rows.append({"n": 300, "instances": 64, "ants": 20, "train_step_us": [timeit(step, 50) * 1e6 for _ in range(5)]})
+    print("TRAINING_CHILD " + json.dumps(rows))
+
+
+def training_rows():
+    """each path in two fresh processes, started alternately (this process never opens the device)"""
+    import statistics
+    import subprocess
+    runs = {"hip": [], "torch": []}
+    for _ in range(2):
+        for path in ("hip", "torch"):
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--training-child", path], check=True,
+                                 capture_output=True, text=True, timeout=900).stdout
+            runs[path].append(json.loads(next(l for l in out.splitlines() if l.startswith("TRAINING_CHILD "))[15:]))
+    rows = []
+    for i in range(len(TRAIN_SHAPES) + 1):
+        key = "fwd_bwd_us" if i < len(TRAIN_SHAPES) else "train_step_us"
+        row = {k: v for k, v in runs["hip"][0][i].items() if k != key}
+        for path in ("hip", "torch"):
+            meds = [statistics.median(r[i][key]) for r in runs[path]]
+            row[f"{key}_{path}"] = [round(m, 1) for m in meds]
+        row["torch_over_hip"] = round(statistics.mean(row[f"{key}_torch"]) / statistics.mean(row[f"{key}_hip"]), 3)
+        rows.append(row)
+        print(json.dumps(row))
     return rows
 
 
@@ -123,10 +189,16 @@ def reference_rows(ref_dir):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", help="directory of the reference's mkp_transformer/ module: measure its CPU run instead")
+    ap.add_argument("--training", action="store_true", help="measure forward + backward and the batched training step only")
+    ap.add_argument("--training-child", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT, help="file to write (an existing one is merged into)")
     args = ap.parse_args()
+    if args.training_child:
+        return training_child(args.training_child)
     data = json.load(open(args.out)) if os.path.exists(args.out) else {}
-    if args.reference:
+    if args.training:
+        data["training"] = training_rows()
+    elif args.reference:
         data["reference_cpu"] = reference_rows(args.reference)
     else:
         data["device"] = torch.cuda.get_device_name(0)
