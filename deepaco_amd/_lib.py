@@ -86,6 +86,12 @@ SIGNATURES = {
     "daco_transformer_train_workspace_bytes": (_sz, [_i, _i]),
     "daco_transformer_forward_train": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz]),
     "daco_transformer_backward": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz]),
+    "daco_rcpsp_schedule": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "daco_rcpsp_workspace_bytes": (_sz, [_i, _i]),
+    "daco_rcpsp_sample": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _f, _f,
+                               C.c_double, C.c_double, _i, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "daco_rcpsp_backward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _l, _f, _f, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "daco_rcpsp_track": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "daco_tsp_nls": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _l, _vp, _vp, _vp]),
 }
 

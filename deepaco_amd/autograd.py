@@ -166,3 +166,27 @@ class TransformerFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         src, flat, saved = ctx.saved_tensors
         return None, engine.transformer_backward(src, flat, saved, grad_out)
+
+
+class RcpspSampleFn(torch.autograd.Function):
+    """Project-scheduling construction + schedule (rcpsp/aco.py:176-236) for the B colonies of an engine.BatchedRCPSP whose
+    log-probabilities carry gradient to the heuristic [B, n, n]: daco_rcpsp_sample forward, daco_rcpsp_backward (a replay of
+    each ant's route under the colony's evaluation rule) backward.
+    -> (routes [B,n,A], log_probs [B,n-1,A], starts [B,n,A], costs [B,A], flags [B])."""
+
+    @staticmethod
+    def forward(ctx, heuristic, colony, noise):
+        colony.heuristic = heuristic.detach().float().reshape(colony.B, colony.n, colony.n).contiguous()
+        routes, logp, rowsum, starts, costs, flags = colony.sample(require_prob=True, noise=noise)
+        ctx.save_for_backward(colony.pheromone.clone(), colony.heuristic, routes, rowsum)
+        ctx.meta = (colony.inst, colony.alpha, colony.beta, colony.gamma, colony.c, heuristic.shape)
+        ctx.mark_non_differentiable(routes, starts, costs, flags)
+        return routes, logp, starts, costs, flags
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _gr, glogp, _gs, _gc, _gf):
+        tau, eta, routes, rowsum = ctx.saved_tensors
+        inst, alpha, beta, gamma, c, shape = ctx.meta
+        grad = engine.rcpsp_backward(inst, tau, eta, alpha, beta, gamma, c, routes, rowsum, glogp.contiguous())
+        return grad.reshape(shape), None, None

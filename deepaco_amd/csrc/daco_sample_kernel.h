@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "daco_device.h"
+#include "daco_rcpsp.h"
 #include "../../include/deepaco_hip.h"
 
 namespace daco {
@@ -61,6 +62,7 @@ struct SampleParams {
   int row_vec = 0;                   // rows can be read as aligned 16-byte vectors (n % 4 == 0, aligned bases and strides)
   int nbr_grouped = 0;               // scan_sparse: nbr as [B][ceil(A/8)][n][8] (eight ants' entries of a node together) instead of [B][n][A]
   int lh_kl = 0, lh_kmax = 0;        // scan_sparse, LDS-heads variant: lane records per row kept in LDS, the caller's bound of live slots per row
+  RcpspDev rc;                       // PROB_RCPSP (daco_rcpsp.hip): the project, the evaluation rule, the decoder's outputs
 };
 
 template <class F, int... I>
@@ -81,6 +83,19 @@ __device__ inline void load_vec(const float *p, float (&out)[VEC]) {
     out[0] = t.x; out[1] = t.y;
   } else {
     out[0] = *p;
+  }
+}
+
+// dst[b][r][0..ld) = src[b][r][0..n) padded with `fill` (a template so that every file that pads a matrix holds the one definition)
+template <int UNUSED = 0>
+__global__ void __launch_bounds__(256)
+pad_matrix_kernel(int B, int n, int ld, const float *src, long src_bs, float *dst, float fill) {
+  const long total = (long)B * n * ld;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int k = (int)(i % ld);
+    const long row = i / ld;
+    const int b = (int)(row / n), r = (int)(row % n);
+    dst[i] = k < n ? src[b * src_bs + (long)r * n + k] : fill;
   }
 }
 
@@ -113,17 +128,21 @@ struct Visited {
   }
 };
 
-enum { PROB_TSP = 0, PROB_CVRP = 1, PROB_STEP = 2, PROB_SOP = 3, PROB_PCTSP = 4, PROB_OP = 5, PROB_MKP = 6, PROB_CVRP64 = 7 };
+enum { PROB_TSP = 0, PROB_CVRP = 1, PROB_STEP = 2, PROB_SOP = 3, PROB_PCTSP = 4, PROB_OP = 5, PROB_MKP = 6, PROB_CVRP64 = 7, PROB_RCPSP = 8 };
 
 // PROB_TSP: whole closed tour; PROB_CVRP: whole capacity-constrained route sequence; PROB_CVRP64: the same with the load
 // bookkeeping of cvrp_nls/aco.py:254-272 in float64 (used = used + demand[cur]; demand > capacity - used, all double there:
 // with demands k/50 a customer that fits exactly is common, and whether it passes is a matter of the last bit);
 // PROB_STEP: ONE draw per ant from an externally maintained mask (ACO.pick_move for the sibling
 // problems, whose feasibility logic stays with the caller).
+// PROB_RCPSP (rcpsp/aco.py:176-213): PROB_SOP's precedence bookkeeping on the project's adjacency matrix -- with the direct
+// rule it IS that construction, draw for draw -- plus the summation / balanced evaluation of Merkle et al. (a running
+// vector s <- gamma s + tau[prev] per ant, in registers next to the row) and, where the LDS plan fits, the decoding of the
+// finished route into a schedule (daco_rcpsp.h).
 template <int VEC, int CH, int MODE, bool LOGP, int PROB>
 __global__ void __launch_bounds__(256)
 tsp_sample_kernel(const SampleParams p) {
-  constexpr bool CVRP = PROB == PROB_CVRP || PROB == PROB_CVRP64, DEM64 = PROB == PROB_CVRP64, STEP = PROB == PROB_STEP, SOP = PROB == PROB_SOP,
+  constexpr bool CVRP = PROB == PROB_CVRP || PROB == PROB_CVRP64, DEM64 = PROB == PROB_CVRP64, STEP = PROB == PROB_STEP, RCPSP = PROB == PROB_RCPSP, SOP = PROB == PROB_SOP || RCPSP,
                  PCTSP = PROB == PROB_PCTSP, OP = PROB == PROB_OP, MKP = PROB == PROB_MKP;
   constexpr bool VARLEN = CVRP || PCTSP || OP || MKP;   // solution length differs between ants
   constexpr bool DUMMY = OP || MKP;                     // last node = absorbing dummy, never drawn
@@ -173,6 +192,19 @@ tsp_sample_kernel(const SampleParams p) {
   prev = __builtin_amdgcn_readfirstlane(prev);
   const int first = prev;
 
+  // RCPSP: the wave's slice of LDS (route first) when the kernel decodes its own routes
+  unsigned char *rc_lds = nullptr;
+  if constexpr (RCPSP) { if (p.rc.fused) rc_lds = reinterpret_cast<unsigned char *>(epi_lds) + (size_t)wave * rcpsp_wave_lds(p.n, p.rc.R, p.rc.H); }
+  float ssum[RCPSP ? CH : 1][VEC] = {};                 // RCPSP: the summation rule's running vector
+  auto own_value = [&](const float (&arr)[CH][VEC], int ch) {   // arr's entry of candidate ch (wave-uniform), from its owner lane
+    const unsigned vi = (unsigned)ch / VEC;
+    const int jj = (int)(vi >> 6) * VEC + (int)((unsigned)ch % VEC);
+    float sel = 0.0f;
+    static_for<NJ>([&](auto J) { constexpr int j = J; sel = j == jj ? arr[j / VEC][j % VEC] : sel; });
+    return readlane_f(sel, (int)(vi & 63u));
+  };
+  (void)own_value; (void)ssum;
+
   Visited vis;
   auto mark = [&](int k) {                              // k wave-uniform, >= 0
     const unsigned vi = (unsigned)k / VEC;
@@ -182,6 +214,7 @@ tsp_sample_kernel(const SampleParams p) {
   int own_lane = -1, own_bit = 0;                       // SCAN: owner of the last choice, known without division
   if constexpr (PROB == PROB_TSP || SOP || OP || MKP) mark(prev);
   if (lane == 0 && !STEP) { if constexpr (EPI) tour[0] = (uint16_t)prev; else path_out[0] = prev; }
+  if constexpr (RCPSP) { if (rc_lds && lane == 0) reinterpret_cast<uint16_t *>(rc_lds)[0] = (uint16_t)prev; }
 
   // per-candidate constants / counters of the constrained problems (this lane's candidates):
   //   CVRP demand, SOP number of unvisited predecessors, OP distance back to the depot
@@ -318,6 +351,34 @@ tsp_sample_kernel(const SampleParams p) {
     const float *rp = (MODE == DACO_RACE_PHILOX ? Rb : Pb) + (unsigned)prev * (unsigned)ld;
 #pragma unroll
     for (int c = 0; c < CH; ++c) load_vec<VEC>(rp + c * 64 * VEC, row[c]);
+    float wrow[RCPSP ? CH : 1][VEC];                      // RCPSP, summation / balanced: the step's weights (PHILOX: row = 1 / w)
+    bool rc_rule = false;
+    (void)wrow; (void)rc_rule;
+    if constexpr (RCPSP) {
+      rc_rule = p.rc.rule != 0;
+      if (rc_rule) {
+        // rcpsp/aco.py:193-206: s_k = sum_i gamma^(t-i) tau[route_i][k] as the recurrence s <- gamma s + tau[prev];
+        // w = (s mask)^alpha eta[prev]^beta, balanced: c (P[prev] mask) + (1 - c) w.  Two roundings per product, no fma.
+        const size_t ro = ((size_t)b * n + (unsigned)prev) * (unsigned)ld + lane * VEC;
+        float tr[CH][VEC], er[CH][VEC], pd[CH][VEC];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          load_vec<VEC>(p.rc.taup + ro + c * 64 * VEC, tr[c]);
+          load_vec<VEC>(p.rc.etab + ro + c * 64 * VEC, er[c]);
+          if (MODE == DACO_RACE_PHILOX) load_vec<VEC>(Pb + (unsigned)prev * (unsigned)ld + c * 64 * VEC, pd[c]);
+        }
+        static_for<NJ>([&](auto J) {
+          constexpr int j = J, c = j / VEC, v = j % VEC;
+          if constexpr (MODE != DACO_RACE_PHILOX) pd[c][v] = row[c][v];
+          ssum[c][v] = p.rc.gamma * ssum[c][v] + tr[c][v];
+          const bool closed = blk.template test<j>();
+          float w = pw(closed ? 0.0f : ssum[c][v], p.alpha) * er[c][v];
+          if (p.rc.rule == 2) w = p.rc.cdir * (closed ? 0.0f : pd[c][v]) + p.rc.csum * w;
+          wrow[c][v] = w;
+          row[c][v] = MODE == DACO_RACE_PHILOX ? 1.0f / w : w;
+        });
+      }
+    }
 
     int choice;
     float pchoice = 0.0f, S = 0.0f;
@@ -368,7 +429,7 @@ tsp_sample_kernel(const SampleParams p) {
         }
         choice = (int)((((unsigned)jsel / VEC) * 64u + (unsigned)L) * VEC + ((unsigned)jsel % VEC));
         own_lane = L; own_bit = jsel;
-        if constexpr (LOGP) pchoice = p.P[((size_t)b * n + prev) * ld + choice];
+        if constexpr (LOGP) pchoice = (RCPSP && rc_rule) ? own_value(row, choice) : p.P[((size_t)b * n + prev) * ld + choice];
       }
     } else if constexpr (MODE == DACO_RACE_PHILOX) {
       float bk = __builtin_inff();
@@ -392,12 +453,15 @@ tsp_sample_kernel(const SampleParams p) {
         float pr[CH][VEC];
 #pragma unroll
         for (int c = 0; c < CH; ++c) load_vec<VEC>(pp + c * 64 * VEC, pr[c]);
+        if constexpr (RCPSP) {
+          if (rc_rule) static_for<NJ>([&](auto J) { constexpr int j = J; pr[j / VEC][j % VEC] = wrow[j / VEC][j % VEC]; });
+        }
         static_for<NJ>([&](auto J) {
           constexpr int j = J;
           part = part + (blk.template test<j>() ? 0.0f : pr[j / VEC][j % VEC]);
         });
         S = wave_sum(part);
-        pchoice = p.P[((size_t)b * n + prev) * ld + choice];
+        pchoice = (RCPSP && rc_rule) ? own_value(pr, choice) : p.P[((size_t)b * n + prev) * ld + choice];
       }
     } else {  // DACO_RACE_NOISE: the arithmetic of torch.multinomial's one-sample path
       const float *q = p.noise + (((size_t)b * (VARLEN ? p.noise_steps : (STEP ? 1 : n - 1)) + (t - t0)) * A + a) * n;
@@ -481,6 +545,7 @@ tsp_sample_kernel(const SampleParams p) {
       else mark(choice);
     }
     if (lane == 0) { if constexpr (EPI) tour[t] = (uint16_t)choice; else path_out[STEP ? 0 : (size_t)t * A] = choice; }
+    if constexpr (RCPSP) { if (rc_lds && lane == 0) reinterpret_cast<uint16_t *>(rc_lds)[t] = (uint16_t)choice; }
     if (dist_b) {                                        // fused gen_path_costs (wave-uniform)
       cost = cost + dpend;
       // TSP: d[u_t][u_{t-1}] (tsp/aco.py:127); CVRP: d[u_{t-1}][u_t] (cvrp/aco.py:135); scalar load
@@ -525,6 +590,18 @@ tsp_sample_kernel(const SampleParams p) {
     else { nbr_a[(size_t)prev * A] = (uint32_t)pprev | ((uint32_t)first << 16); nbr_a[(size_t)first * A] = (uint32_t)prev | ((uint32_t)second << 16); }
   }
   if (infeasible && p.flags && lane == 0) atomicOr(p.flags + b, 1);
+  if constexpr (RCPSP) {
+    if (rc_lds) {                                        // the route just drawn (every entry a node id), decoded by the same wave
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      int c_out = 0;
+      const int f = ssgs_wave(p.rc, n, b, A, rc_lds, lane, p.rc.starts ? p.rc.starts + (size_t)b * n * A + a : nullptr, &c_out);
+      if (lane == 0) {
+        p.rc.costs[(size_t)b * A + a] = c_out;
+        if (f && p.flags) atomicOr(p.flags + b, f);
+      }
+    }
+  }
   if constexpr (EPI) {
     // ---- the workgroup's (up to) 4 tours leave LDS together (see tsp_scan32_kernel): paths in 32-byte runs per step
     // row, tour lengths from 64-edge gathers summed in step order by one lane, the neighbour table through an

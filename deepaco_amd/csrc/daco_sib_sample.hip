@@ -16,22 +16,6 @@
 // steps do (the dummy is then the only open node, probability 1).
 #include "daco_sample_kernel.h"
 
-namespace daco {
-
-// dst[b][r][0..ld) = src[b][r][0..n) padded with `fill`
-__global__ void __launch_bounds__(256)
-pad_matrix_kernel(int B, int n, int ld, const float *src, long src_bs, float *dst, float fill) {
-  const long total = (long)B * n * ld;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int k = (int)(i % ld);
-    const long row = i / ld;
-    const int b = (int)(row / n), r = (int)(row % n);
-    dst[i] = k < n ? src[b * src_bs + (long)r * n + k] : fill;
-  }
-}
-
-}  // namespace daco
-
 using namespace daco;
 
 extern "C" size_t daco_sibling_workspace_bytes(int B, int n, int mode) {
@@ -72,7 +56,7 @@ extern "C" int daco_sibling_sample(void *stream, int kind, int B, int n, int A, 
   if (blocks > 8192) blocks = 8192;
   launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, P, R, s);
   if (aux_mat)
-    hipLaunchKernelGGL(pad_matrix_kernel, dim3(blocks), dim3(256), 0, s, B, n, ld, aux_mat, aux_mat_bstride, auxp, 0.0f);
+    hipLaunchKernelGGL(pad_matrix_kernel<0>, dim3(blocks), dim3(256), 0, s, B, n, ld, aux_mat, aux_mat_bstride, auxp, 0.0f);
   SampleParams sp;
   sp.B = B; sp.n = n; sp.A = A; sp.ld = ld; sp.CH = CH;
   sp.P = P; sp.R = R; sp.norm_passes = 1; sp.start = start; sp.fixed_start = 0;

@@ -264,3 +264,20 @@ def train_mkp_transformer_batch(net, optimizer, price, weight, n_ants, seed=0, i
     loss.backward()
     optimizer.step()
     return loss.detach()
+
+
+@torch.no_grad()
+def infer_rcpsp_batch(instances, n_ants, t_aco, heuristic=None, seed=0, sampler="scan", best_route="copy", **acoparam):
+    """The protocol of rcpsp/test.ipynb (`infer_instance` / `test`) for B projects of equal size at once: one colony per
+    project, the best makespan read at every checkpoint of t_aco (e.g. [1, 10, 20]).  instances: a list of
+    rcpsp.RCPSPInstance (or stacked RcpspTensors with a heuristic); heuristic [B, n, n] or None for the reference's default
+    (nWRUP(0.3) / max * nGRPWA); acoparam: the notebook's dict(elitist=True, min_max=True) and anything else
+    engine.BatchedRCPSP takes.  Returns (best costs [len(t_aco), B] int32, colony)."""
+    colony = engine.BatchedRCPSP(instances, n_ants=n_ants, heuristic=heuristic, seed=seed, sampler=sampler, best_route=best_route,
+                                 **acoparam)
+    out, done = [], 0
+    for t in t_aco:
+        colony.run(t - done)
+        done = t
+        out.append(colony.best_cost.clone())
+    return torch.stack(out), colony

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded) */
 
 /* error codes */
 #define DACO_OK 0
@@ -719,6 +719,77 @@ int daco_transformer_forward_train(void *stream, int G, int n, int feats, const 
 int daco_transformer_backward(void *stream, int G, int n, int feats, const float *src, const float *params,
                               size_t param_floats, const float *saved, size_t saved_floats, const float *grad_out,
                               float *grad_params, void *workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_rcpsp_* -- the project-scheduling colony of rcpsp/aco.py (Merkle, Middendorf, Schmeck 2002)
+ *
+ * A project: n activities (0 = source, n-1 = sink), R renewable resources.  Per instance b, dense:
+ *   duration [B][n], resources [B][n][R], capacity [B][R], earliest_start / latest_start [B][n], all int32;
+ *   succ_ptr [B][n+1] / succ_idx [B][E] int32: the successor lists as CSR (E = entries allocated per instance, the lists of
+ *   an instance occupy succ_idx[b][0 .. succ_ptr[b][n]));
+ *   horizon: the time slots a usage timeline needs, max(latest_start + duration) over the batch.
+ * Limits (DACO_E_TOOLARGE beyond): n <= DACO_RCPSP_MAX_N, R <= DACO_RCPSP_MAX_R, horizon <= DACO_RCPSP_MAX_HORIZON; capacities
+ * <= 65535.  The caller vouches that an activity of duration 0 needs no resource (the reference's event queue and the usage
+ * timeline used here could part there; deepaco_amd.rcpsp.RCPSPInstance.validate checks it on the host).
+ *
+ * daco_rcpsp_schedule -- replaces SSGS_ordered (rcpsp/aco.py:42-63) for every ant of update_cost (:222-227)
+ *   routes [B][n][A] int64 (activity lists) -> starts [B][n][A] int32 (start time per ACTIVITY; may be NULL) and costs [B][A]
+ *   int32 = start of activity n-1.  The reference's rule exactly: start = min(max(first time from the resources' last request
+ *   on at which every needed resource has room, ends of the predecessors [earliest_start without any]), latest_start); a
+ *   resource with requirement 0 is neither consulted nor advanced; no back-filling before a resource's last request.
+ *   flags [B] or NULL (caller zeroes): DACO_RCPSP_FLAG_ORDER = a route is not a topological order of all activities (entries
+ *   outside [0, n): that ant is not decoded, cost -1); DACO_RCPSP_FLAG_RESOURCE = a requirement exceeds its capacity, or the
+ *   clamp to latest_start broke a resource constraint (the reference raises in request() there), or a time left the horizon.
+ *
+ * daco_rcpsp_sample -- construct_solutions + update_cost (:176-236) in one call
+ *   n-1 draws from activity 0; open = not visited and every direct predecessor visited.  indegree [B][n] f32 and adjacency
+ *   [B][n][n] f32 (1 where k is a direct successor of i) are the precedence data in daco_sibling_sample(DACO_SIB_SOP)'s form.
+ *   The rule is chosen as the reference chooses it: direct p_k = tau[prev][k]^alpha eta[prev][k]^beta when float(gamma) < 0.05
+ *   or c == 1 (then the routes are DACO_SIB_SOP's, draw for draw); otherwise s <- gamma s + tau[prev] (one running vector per
+ *   ant) and w_k = (s_k mask_k)^alpha eta[prev][k]^beta, summation p = w when c == 0, balanced p = c p_direct + (1 - c) w
+ *   else.  alpha > 0 for those two.  mode, noise [B][n-1][A][n], seed / iter / ant_gid0, logp / rowsum [B][n-1][A] (or NULL):
+ *   as daco_sibling_sample.  starts (or NULL), costs, flags as daco_rcpsp_schedule, plus bit 0 of flags (a draw had no
+ *   open candidate).  workspace: daco_rcpsp_workspace_bytes(B, n).
+ *
+ * daco_rcpsp_backward -- gradient of sum(grad_logp * logp) w.r.t. eta for routes drawn by daco_rcpsp_sample with the same
+ *   tau / eta / alpha / beta / gamma / c: grad_eta[b][prev][k] += g beta ([k = pick] / eta - w_k / (eta S)), 0 where the
+ *   probability was clamped, daco_sample_backward's conventions at eta = 0.  grad_eta [B][n][n] is accumulated into.
+ *
+ * daco_rcpsp_track -- the record keeping of update_cost (:228-236) and the deposit list of update_pheromone (:242-252)
+ *   best_cost [B] int32 in/out (start at INT32_MAX), best_idx [B] int32 in/out, best_route [B][n] int64, best_schedule [B][n]
+ *   int32 (or NULL).  alias = 0: best_route is a copy made when the record fell.  alias = 1: the reference's behaviour, whose
+ *   best_solution.route is a view of row best_idx of the colony's route tensor and so shows what THAT ANT drew last.
+ *   Out, for daco_pheromone_update(len = n, A = C, symmetric = 0, hub = -1, elitist = 0, weights = upd_weights): upd_routes
+ *   [B][n][C] int64 and upd_weights [B][C], C = 2 (elitist: best-so-far, iteration best) or A + 1 (best-so-far, every ant);
+ *   weights f32(Q / best_cost in float64) and f32(Q) / f32(cost); min_max: clamp_min [B] = tmin, clamp_max [B] = f32(Q n /
+ *   best_cost in float64), raised to tmin where below it.
+ */
+#define DACO_RCPSP_MAX_N 256
+#define DACO_RCPSP_MAX_R 8
+#define DACO_RCPSP_MAX_HORIZON 8192
+#define DACO_RCPSP_FLAG_ORDER 4
+#define DACO_RCPSP_FLAG_RESOURCE 8
+int daco_rcpsp_schedule(void *stream, int B, int n, int A, int R, int horizon, int E, const int32_t *duration,
+                        const int32_t *resources, const int32_t *capacity, const int32_t *earliest_start,
+                        const int32_t *latest_start, const int32_t *succ_ptr, const int32_t *succ_idx,
+                        const int64_t *routes, int32_t *starts, int32_t *costs, int32_t *flags);
+size_t daco_rcpsp_workspace_bytes(int B, int n);
+int daco_rcpsp_sample(void *stream, int B, int n, int A, int R, int horizon, int E, const int32_t *duration,
+                      const int32_t *resources, const int32_t *capacity, const int32_t *earliest_start,
+                      const int32_t *latest_start, const int32_t *succ_ptr, const int32_t *succ_idx,
+                      const float *indegree, const float *adjacency, const float *tau, long tau_bstride,
+                      const float *eta, long eta_bstride, float alpha, float beta, double gamma, double c, int mode,
+                      const float *noise, uint64_t seed, uint64_t iter, uint32_t ant_gid0, int64_t *routes,
+                      float *logp, float *rowsum, int32_t *starts, int32_t *costs, int32_t *flags, void *workspace,
+                      size_t workspace_bytes);
+int daco_rcpsp_backward(void *stream, int B, int n, int A, const float *indegree, const float *adjacency,
+                        const float *tau, long tau_bstride, const float *eta, long eta_bstride, float alpha, float beta,
+                        double gamma, double c, const int64_t *routes, const float *rowsum, const float *grad_logp,
+                        float *grad_eta);
+int daco_rcpsp_track(void *stream, int B, int n, int A, const int64_t *routes, const int32_t *starts, const int32_t *costs,
+                     double Q, int elitist, int alias, int min_max, float tmin, int32_t *best_cost, int32_t *best_idx,
+                     int64_t *best_route, int32_t *best_schedule, int64_t *upd_routes, float *upd_weights,
+                     float *clamp_min, float *clamp_max);
 
 #ifdef __cplusplus
 }
