@@ -77,10 +77,13 @@ def ssgs_queue(inst, route):
     return np.array(start, dtype=np.int32)
 
 
-def ssgs_timeline(inst, route, want_flags=False):
+def ssgs_timeline(inst, route, want_flags=False, stats=None):
     """The same rule on usage timelines, as the kernel computes it: per resource the units in use per time slot and the time
     of its last request; the first t >= last with usage[t] <= capacity - v; the request adds v to [t, t + duration).
-    flags: 4 = not a topological order of all activities, 8 = a resource rule of the reference's request() broken."""
+    flags: 4 = not a topological order of all activities, 8 = a resource rule of the reference's request() broken.
+    stats (a dict, optional) counts what sends the kernel's two 64-slot loops on a second trip: "long_search", the searches
+    whose answer lies at least 64 slots past the resource's last request, and "long_request", the requests of more than 64
+    slots."""
     n, R = inst["resources"].shape
     H = int(inst["horizon"])
     usage = np.zeros((R, H), dtype=np.int64)
@@ -108,6 +111,8 @@ def ssgs_timeline(inst, route, want_flags=False):
             t = last[r]
             while t < H and usage[r, t] > room:
                 t += 1
+            if stats is not None and t - last[r] >= 64:
+                stats["long_search"] = stats.get("long_search", 0) + 1
             arrange = max(arrange, t)
         est = ready[j] if ready[j] >= 0 else (0 if ready[j] == -1 else int(inst["earliest_start"][j]))
         arrange = min(max(arrange, est), int(inst["latest_start"][j]))
@@ -118,6 +123,8 @@ def ssgs_timeline(inst, route, want_flags=False):
             if arrange < last[r]:
                 flags |= 8
             last[r] = arrange
+            if stats is not None and d > 64:
+                stats["long_request"] = stats.get("long_request", 0) + 1
             if arrange + d > H:
                 flags |= 8
             usage[r, arrange:min(arrange + d, H)] += v
@@ -204,7 +211,8 @@ def construct(inst, tau, eta, noise, alpha=1.0, beta=2.0, gamma=0.0, c=0.6):
 # ------------------------------------------------------------------ the update
 def update(tau, best_route, best_cost, routes, costs, Q=1.0, decay=0.975, elitist=False, min_max=False, tmin=0.1, tmax=np.inf):
     """update_pheromone (rcpsp/aco.py:238-256), float32: decay, the best-so-far route with f32(Q / best_cost) (a float64
-    quotient), the iteration best (elitist) or every ant in index order with the float32 quotient Q / cost, the two clamps."""
+    quotient), the iteration best (elitist) or every ant in index order with the float32 quotient Q / cost, the two clamps:
+    from above first, then from below, so tmax < tmin (Q n / best_cost below the floor) leaves tmin everywhere."""
     tau = (np.asarray(tau, dtype=F) * F(decay)).astype(F)
 
     def deposit(route, w):
@@ -257,32 +265,72 @@ def reinforce_weights(costs, n, A):
     return np.broadcast_to(w, (n - 1, A)).copy()
 
 
-def grad_closed_form(tau, eta, routes, opens, grad_logp, alpha=1.0, beta=2.0, gamma=0.0, c=0.6):
-    """d sum(grad_logp * log_probs) / d eta in float64.  Every term of a rule's weight is base_k * eta[prev][k]^beta, so
-    d log p / d eta[prev][k] = beta ([k = pick] / eta - w_k / (eta S)); 0 where the probability is clamped."""
+def _rule_weights(tau, eta, s, prev, mask, rule, alpha, beta, c):
+    """float64 weights of one step: (base, w) with w = base * eta[prev]^beta on the open candidates, 0 elsewhere"""
+    direct = tau[prev] ** alpha
+    summ = np.where(mask, s, 0.0) ** alpha
+    base = direct if rule == 0 else (summ if rule == 1 else float(F(c)) * direct + float(F(1.0 - c)) * summ)
+    return base, np.where(mask, base * eta[prev] ** beta, 0.0)
+
+
+def logp_f64(tau, eta, routes, opens, alpha=1.0, beta=2.0, gamma=0.0, c=0.6):
+    """The log-probabilities [n-1, A] of given routes in float64 (the clamp thresholds are float32's, as in the reference run
+    in float64): max |construct()["log_probs"] - this| is the distance the r1 fixtures store as logp_f64_dist."""
     tau, eta = np.asarray(tau, dtype=np.float64), np.asarray(eta, dtype=np.float64)
     n = tau.shape[0]
     A = routes.shape[0]
     rule = rule_of(gamma, c)
-    g = np.zeros((n, n))
+    out = np.zeros((n - 1, A))
     for a in range(A):
         s = np.zeros(n)
         for t in range(n - 1):
             prev, pick = int(routes[a, t]), int(routes[a, t + 1])
             s = float(F(gamma)) * s + tau[prev]
+            _, w = _rule_weights(tau, eta, s, prev, opens[t, a], rule, alpha, beta, c)
+            out[t, a] = np.log(np.clip(w[pick] / w.sum(), float(EPS), 1.0 - float(EPS)))
+    return out
+
+
+GRAD_MUTANTS = ("drop64", "no_decay", "no_memory", "last_ant")
+
+
+def grad_closed_form(tau, eta, routes, opens, grad_logp, alpha=1.0, beta=2.0, gamma=0.0, c=0.6, dtype=np.float64, mutant=None,
+                     probs=None):
+    """d sum(grad_logp * log_probs) / d eta in float64.  Every term of a rule's weight is base_k * eta[prev][k]^beta, so
+    d log p / d eta[prev][k] = beta ([k = pick] / eta - w_k / (eta S)); 0 where the probability is clamped.
+    dtype = float32 evaluates the same closed form in float32 (what a test may derive a wider bound from).  probs (a list,
+    optional) receives (probability of the pick, number of open candidates with positive weight) of every step.
+    mutant: a deliberately wrong variant, for the tests that prove a case list can fail -- "drop64" the candidates k >= 64 are
+    missing from S, "no_decay" the running vector is not multiplied by gamma, "no_memory" it forgets every row but the
+    current one, "last_ant" the last ant contributes nothing."""
+    if mutant is not None and mutant not in GRAD_MUTANTS:
+        raise ValueError(f"no such mutant: {mutant}")
+    tau, eta = np.asarray(tau, dtype=dtype), np.asarray(eta, dtype=dtype)
+    n = tau.shape[0]
+    A = routes.shape[0]
+    rule = rule_of(gamma, c)
+    g = np.zeros((n, n), dtype=dtype)
+    gam = dtype(F(gamma))
+    for a in range(A - 1 if mutant == "last_ant" else A):
+        s = np.zeros(n, dtype=dtype)
+        for t in range(n - 1):
+            prev, pick = int(routes[a, t]), int(routes[a, t + 1])
+            s = (s if mutant == "no_decay" else (0 * s if mutant == "no_memory" else gam * s)) + tau[prev]
             mask = opens[t, a]
-            direct = tau[prev] ** alpha
-            summ = np.where(mask, s, 0.0) ** alpha
-            base = direct if rule == 0 else (summ if rule == 1 else float(F(c)) * direct + float(F(1.0 - c)) * summ)
-            w = np.where(mask, base * eta[prev] ** beta, 0.0)
-            S = w.sum()
-            pr = w[pick] / S
-            if not (EPS < pr < 1 - EPS):
-                continue
-            e = eta[prev]
+            direct = tau[prev] ** dtype(alpha)
+            summ = np.where(mask, s, dtype(0)) ** dtype(alpha)
+            base = direct if rule == 0 else (summ if rule == 1 else dtype(F(c)) * direct + dtype(F(1.0 - c)) * summ)
+            w = np.where(mask, base * eta[prev] ** dtype(beta), dtype(0))
+            S = w[:64].sum() if mutant == "drop64" else w.sum()
             with np.errstate(divide="ignore", invalid="ignore"):
-                dw = np.where(e != 0, beta * w / e, base if beta == 1 else (0.0 if beta > 1 else np.inf))
-            row = -grad_logp[t, a] / S * np.where(mask, dw, 0.0)
-            row[pick] += grad_logp[t, a] * beta / e[pick]
-            g[prev] += row
+                pr = w[pick] / S
+                if probs is not None:
+                    probs.append((float(pr), int((w > 0).sum())))
+                if not (EPS < pr < 1 - EPS):
+                    continue
+                e = eta[prev]
+                dw = np.where(e != 0, dtype(beta) * w / e, base if beta == 1 else (0.0 if beta > 1 else np.inf)).astype(dtype)
+                row = -dtype(grad_logp[t, a]) / S * np.where(mask, dw, dtype(0))
+                row[pick] += dtype(grad_logp[t, a]) * dtype(beta) / e[pick]
+                g[prev] += row
     return g
