@@ -162,10 +162,32 @@ __device__ inline float sp_at_least_denorm(float x) {     // max(x, denorm_min) 
 // live slots per row) with the tail total moved into the first slot no row uses (slot kmax, whose id stays `dead`: its term is
 // T x 0 = 0 as before) -- 500 rows x 312 bytes at k = 50.  The step then reads its head row from LDS; values, order of the
 // additions, uniforms and decisions are those of the kernel above, so the tours are the same bit for bit.
-template <int CHD, bool RACE, int SPL, bool LH = false>
-__global__ void __launch_bounds__(256, LH ? 1 : (CHD == 2 ? (RACE ? 4 : 6) : 5))
+//
+// ST ("split tours"; CHD = 2, scan draw, four slots per lane, not LH): the launch that is just too large for one round of the
+// kernel above (more than six, at most eight workgroups per CU: sparse_many_workgroups; the headline shape).  With whole tours in LDS a
+// workgroup takes 25.4 KB and six fit a CU, so the headline's 2 048 workgroups ran in 1.33 rounds, the last third of them two per
+// CU at the latency of a bare chain.  Here the tours live in a WINDOW of SP_W = 352 entries per ant: with
+// TE = max(0, roundup16(n - SP_W)), entry t sits at index t while t0 < TE and at t - TE afterwards; at the chunk boundary t0 == TE
+// each wavefront writes its own four ants' entries 0 .. TE-1 to their rows of tours16 (one burst of 2 TE bytes per ant and tour,
+// no workgroup barrier, nothing else added to the loop: the offset is folded into the ant's window pointer at that boundary, so a
+// step's instructions are those of the kernel above).  20 KB per workgroup and 64 registers: eight workgroups per CU, one round.
+// The epilogue copies the early parts back (L2 lines the workgroup wrote itself) into the dead flag array and reads a tour
+// through a two-piece accessor; cost staging and the inverse table share what is left of that array (SP_TOUR, DSW, NI below).
+constexpr int SP_W = 352;                                // ST: window entries per ant
+constexpr int SP_EW = 160;                               // ST: early entries per ant at most (n <= 512: TE <= 160)
+constexpr int SP_ST_DEAD = 16 * (512 + 16) + 4 * 128 + 256;   // ST: flags, bitmaps and spare bytes in front of the window (dead after the loop)
+constexpr int SP_ST_LDS = SP_ST_DEAD + 16 * SP_W * 2;    // ST: the whole block, an eighth of a CU's 160 KB
+static_assert(SP_ST_LDS <= 160 * 1024 / 8 && SP_ST_DEAD % 16 == 0, "ST: eight workgroups per CU");
+static_assert(SP_ST_DEAD >= 16 * SP_EW * 2 + 4 * 512 * 2, "ST: early parts and the inverse table of four ants inside the dead bytes");
+
+// (ST's epilogue reads `p` again from the start of the kernel-argument segment: `p` must stay the kernel's FIRST explicit
+// argument, and every launch passes exactly this struct -- sample_sparse_impl is the only launch site.)
+static_assert(std::is_trivially_copyable<SampleParams>::value, "SampleParams is read back from the kernel-argument segment as plain bytes");
+template <int CHD, bool RACE, int SPL, bool LH = false, bool ST = false>
+__global__ void __launch_bounds__(256, LH ? 1 : (ST ? 8 : (CHD == 2 ? (RACE ? 4 : 6) : 5)))
 scan_sparse_kernel(const SampleParams p) {
   static_assert(!LH || (CHD == 2 && !RACE && SPL == 4), "the LDS-heads variant: n <= 512, scan draw, 64-slot heads");
+  static_assert(!ST || (CHD == 2 && !RACE && SPL == 4 && !LH), "the split-tour variant: n <= 512, scan draw, 64-slot heads, not LH");
   constexpr int APW = 4, APB = LH ? 4 : 16;
   constexpr int LS = sp_lane_bytes(SPL);                 // bytes per lane of a head row
   constexpr int LAST = SPL - 1;                          // (lane 15: the slot of the tail total)
@@ -175,7 +197,10 @@ scan_sparse_kernel(const SampleParams p) {
                                                          // four ants of a wavefront (and the sixteen of the epilogue) fall on different banks
   constexpr uint32_t ROWB = 16u * LS;                    // bytes of a head row: lane s holds {SPL f32 values, SPL u16 ids} at s * LS
   // LDS (one dynamic block): visited flags as BYTES (1 while node k is unvisited, node order) and
-  //   n <= 512: the u16 tours -- 1.5 KB per ant, six workgroups per CU (all outputs leave in the epilogue below);
+  //   n <= 512, ST: the tail-walk bitmaps, then a window of SP_W entries of each u16 tour -- 20 KB per workgroup, eight per CU;
+  //   entries 0 .. TE-1 go to tours16 once per tour and come back into the flag array for the epilogue (above);
+  //   n <= 512 otherwise (race, 128-slot heads, LH): the whole u16 tours -- 1.5 KB per ant, six workgroups per CU (all outputs
+  //   leave in the epilogue below);
   //   n > 512 (TG): a 16-step window of each tour only.  The tours go to global memory 32 bytes per ant every 16 steps and come
   //   back eight at a time for the epilogue, which reuses the block: 3.1 KB per ant would allow three workgroups per CU, 32 KB
   //   per workgroup allow four, and at this size the launch time follows the occupancy (two instead of three: 6.5 -> 8.6 ms at
@@ -183,11 +208,12 @@ scan_sparse_kernel(const SampleParams p) {
   constexpr bool TG = CHD == 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char sparse_dyn[];
   uint8_t *flag_mem = sparse_dyn;                                                   // [APB][FLP]
-  uint16_t *tour_mem = reinterpret_cast<uint16_t *>(sparse_dyn + APB * FLP);      // !TG: [APB][FL]; TG: [APB][16], the window
+  uint16_t *tour_mem = reinterpret_cast<uint16_t *>(sparse_dyn + (ST ? SP_ST_DEAD : APB * FLP));   // !TG: [APB][FLT]; TG: [APB][16], ST: [APB][SP_W], the windows
   // tail walk: the head of the row as a bitmap over the nodes, one per wavefront (inside the block at n > 512, so that five
-  // workgroups of 32 KB fill a CU's LDS)
-  __shared__ uint32_t bm_static[TG ? 1 : (LH ? 1 : 4)][32];
-  uint32_t (*bm_s)[32] = TG ? reinterpret_cast<uint32_t (*)[32]>(sparse_dyn + APB * FLP + APB * 32) : bm_static;
+  // workgroups of 32 KB fill a CU's LDS; ST: behind the flags)
+  __shared__ uint32_t bm_static[TG || ST ? 1 : (LH ? 1 : 4)][32];
+  uint32_t (*bm_s)[32] = TG ? reinterpret_cast<uint32_t (*)[32]>(sparse_dyn + APB * FLP + APB * 32)
+                            : ST ? reinterpret_cast<uint32_t (*)[32]>(sparse_dyn + APB * FLP) : bm_static;
   // LH: the head table behind the flags and the tours: [n][kl] lane records of LS bytes, then one empty record
   unsigned char *lh_tab = sparse_dyn + APB * FLP + APB * FLT * 2;
   static_assert(!LH || ((APB * FLP + APB * FLT * 2) % 16 == 0), "LH: table aligned");
@@ -210,9 +236,11 @@ scan_sparse_kernel(const SampleParams p) {
   uint32_t sls = (uint32_t)s * LS;
   asm volatile("" : "+v"(sls));                          // (kept in a register: the loop adds it to the row offset)
   uint8_t *fl = flag_mem + (wave * APW + q) * FLP;
-  uint16_t *tour = tour_mem + (wave * APW + q) * (TG ? 16 : FLT);
+  uint16_t *tour = tour_mem + (wave * APW + q) * (TG ? 16 : ST ? SP_W : FLT);
   // TG: tour entry t lives at tour[t & 15] until its chunk is flushed to the workgroup's rows of tours16 [B][A][FL]
-  uint16_t *t16b = TG ? p.tours16 + ((size_t)b * A + abase) * FL : nullptr;
+  // ST: at tour[t]; `tour` steps back by TE entries when entries 0 .. TE-1 have gone to those rows
+  uint16_t *t16b = TG || ST ? p.tours16 + ((size_t)b * A + abase) * FL : nullptr;
+  const int TE = ST ? (n > SP_W ? (n - SP_W + 15) & ~15 : 0) : 0;
   const uint32_t t16o = (uint32_t)((wave * APW + q) * FL + s);
 #define SP_T(t) (TG ? ((t) & 15) : (t))
   bool infeasible = false;
@@ -289,6 +317,24 @@ scan_sparse_kernel(const SampleParams p) {
     // profiles/r06_fused_head_rows.txt.)
     for (int t0 = 0; t0 < n; t0 += 16) {
       int t = t0;
+      if constexpr (ST) {
+        if (t0 == TE && t0 != 0) {
+          // entries 0 .. TE-1 of the wavefront's four ants leave the window: 16 bytes per lane, sixteen lanes per ant
+          // (the row's address is formed here, from a copy of the lane number the compiler cannot see through: hoisted out of the
+          // loop it would take two more registers for the whole tour)
+          int lf = lane;
+          asm volatile("" : "+v"(lf) :: "memory");
+          const int qf = lf >> 4;
+          const uint4 *src = reinterpret_cast<const uint4 *>(tour);
+          uint4 *dst = reinterpret_cast<uint4 *>(t16b + (size_t)(wave * APW + qf) * FL);
+          for (int j = lf & 15; j < (TE >> 3); j += 16) {
+            const uint4 v = src[j];
+            if (a0 + qf < A) dst[j] = v;
+          }
+          asm volatile("" ::: "memory");
+          tour -= TE;
+        }
+      }
       if constexpr (!RACE) {
         // uniform of step t: component (t>>4)&3 of Philox block ((t>>6)<<4) + (t&15); lane s computes the one of step
         // t0 + 15 - s, the row is rotated by one lane per step so that lane 15 holds the current one
@@ -529,9 +575,16 @@ scan_sparse_kernel(const SampleParams p) {
 #undef SP_LAST_POSITIVE
 #undef SP_ID
 #undef SP_IDW
-  if (infeasible && p.flags && lane == 0) atomicOr(p.flags + b, 1);
-  if (p.stats && lane == 0 && (n_dense | n_tail | n_rej)) {
-    atomicAdd(p.stats + 0, n_dense); atomicAdd(p.stats + 1, n_tail); atomicAdd(p.stats + 2, n_rej);
+  // ST: what follows reads the kernel's arguments again from the argument segment (the one SampleParams at its start) through
+  // a pointer the compiler cannot trace back: two dozen scalars that the loop does not use then do not live through it -- they
+  // were spilled into lanes of a second vector register, which the rare ways of the step had to make room for in scratch memory
+  typedef const __attribute__((address_space(4))) SampleParams *sp_args_t;
+  sp_args_t pe = (sp_args_t)__builtin_amdgcn_kernarg_segment_ptr();
+  if constexpr (ST) asm volatile("" : "+s"(pe));
+#define SP_E(x) (ST ? pe->x : p.x)
+  if (infeasible && SP_E(flags) && lane == 0) atomicOr(SP_E(flags) + b, 1);
+  if (SP_E(stats) && lane == 0 && (n_dense | n_tail | n_rej)) {
+    atomicAdd(SP_E(stats) + 0, n_dense); atomicAdd(SP_E(stats) + 1, n_tail); atomicAdd(SP_E(stats) + 2, n_rej);
   }
 
   // ------------------------------------------------------------------ epilogue: the workgroup's 16 tours leave
@@ -539,45 +592,73 @@ scan_sparse_kernel(const SampleParams p) {
   if constexpr (!TG) {
     uint16_t (*tour_s)[FLT] = reinterpret_cast<uint16_t (*)[FLT]>(tour_mem);
     __syncthreads();
+    // ST: entry t of tour k is early_s[k][t] (t < TE) or late_s[k][t - TE]
+    uint16_t (*early_s)[SP_EW] = reinterpret_cast<uint16_t (*)[SP_EW]>(sparse_dyn);
+    uint16_t (*late_s)[SP_W] = reinterpret_cast<uint16_t (*)[SP_W]>(tour_mem);
+#define SP_TOUR(k, t) (ST ? ((t) < TE ? early_s[k][t] : late_s[k][(t) - TE]) : tour_s[k][t])
+    if constexpr (ST) {
+      if (TE > 0) {
+        // the early parts come back from this workgroup's rows of tours16 (its own stores: visible after the barrier, as in the
+        // TG epilogue); a spare group's early part is that of ant A-1, whose tour it built again
+        const int V = TE >> 3;                               // 16-byte pieces per ant
+        for (int e = threadIdx.x; e < APB * V; e += 256) {
+          const int k = e / V, j = e - k * V;
+          reinterpret_cast<uint4 *>(early_s[k])[j] = reinterpret_cast<const uint4 *>(t16b + (size_t)(k < nant ? k : nant - 1) * FL)[j];
+        }
+        __syncthreads();
+      }
+    }
     const int k16 = threadIdx.x & (APB - 1);
     constexpr int TSTEP = 256 / APB;
-    if (p.paths && k16 < nant) {
-      int64_t *pb = p.paths + (size_t)b * n * A + abase;
-      for (int t = threadIdx.x / APB; t < n; t += TSTEP) pb[(size_t)t * A + k16] = (int64_t)tour_s[k16][t];
+    if (SP_E(paths) && k16 < nant) {
+      int64_t *pb = SP_E(paths) + (size_t)b * n * A + abase;
+      for (int t = threadIdx.x / APB; t < n; t += TSTEP) pb[(size_t)t * A + k16] = (int64_t)SP_TOUR(k16, t);
     }
-    if (!p.paths && p.tours16) {
+    if constexpr (ST) {
+      if (!SP_E(paths) && SP_E(tours16)) {
+        // compact tours: the early parts are at their place already, the windows follow them (entries TE .. TE + SP_W - 1)
+        uint32_t *tb = reinterpret_cast<uint32_t *>(SP_E(tours16) + ((size_t)b * A + abase) * FL + TE);
+        const int wl = (TE + SP_W < FL ? SP_W : FL - TE) / 2;
+        for (int e = threadIdx.x; e < nant * (SP_W / 2); e += 256) {
+          const int k = e / (SP_W / 2), j = e - k * (SP_W / 2);
+          if (j < wl) tb[(size_t)k * (FL / 2) + j] = reinterpret_cast<const uint32_t *>(late_s[k])[j];
+        }
+      }
+    } else if (!SP_E(paths) && SP_E(tours16)) {
       // no int64 paths asked for: the tours leave as they are, u16 rows of FL entries per ant in the workspace (a quarter of
       // the bytes: 32 MB instead of 131 at the headline shape; daco_track_best_tours16 reads the best one)
-      uint32_t *tb = reinterpret_cast<uint32_t *>(p.tours16 + ((size_t)b * A + abase) * FL);
+      uint32_t *tb = reinterpret_cast<uint32_t *>(SP_E(tours16) + ((size_t)b * A + abase) * FL);
       for (int e = threadIdx.x; e < nant * (FL / 2); e += 256) {
         const int k = e / (FL / 2), j = e - k * (FL / 2);
         tb[(size_t)k * (FL / 2) + j] = reinterpret_cast<const uint32_t *>(tour_s[k])[j];
       }
     }
-    if (p.costs) {
+    if (SP_E(costs)) {
       // tour lengths (tsp/aco.py:121-132): sum_k d[u_k][u_{k-1}], then the closing edge -- f32, that order.  64 edges of each
       // of the wave's four ants are gathered with every lane active and staged in the (dead) flag array.
       __syncthreads();
-      const float *dist_b = p.dist + (size_t)b * p.dist_bs;
+      const float *dist_b = SP_E(dist) + (size_t)b * SP_E(dist_bs);
       // (LH: the flag array is four ants' worth; the head table is dead by now and holds the staging rows and the inverse table)
-      float (*dstage)[APW][64] = reinterpret_cast<float (*)[APW][64]>(LH ? lh_tab : flag_mem);
+      // (ST: 32 edges of each ant per pass, staged behind the early parts; the sum takes them in the same order)
+      constexpr int DSW = ST ? 32 : 64;
+      float (*dstage)[APW][DSW] = reinterpret_cast<float (*)[APW][DSW]>(LH ? lh_tab : ST ? sparse_dyn + APB * SP_EW * 2 : flag_mem);
       if (active) {
         float cost = 0.0f;
         const float *mine_d = dstage[wave][q];
         // (Round 6, last session, measured and not kept: four chunks' gathers in flight together -- sixteen loads per lane -- made
         // the headline launch SLOWER, 0.522 -> 0.532 ms on one box: the phase is bound by the L2's line rate, as DESIGN 9.1 says,
         // and deeper bursts only disturb the loops of the workgroups still building tours.)
-        for (int base = 1; base < n; base += 64) {
-          const int t = base + lane;
+        for (int base = 1; base < n; base += DSW) {
+          const int t = base + (lane & (DSW - 1));
 #pragma unroll
-          for (int r4 = 0; r4 < APW; ++r4) {
-            const uint16_t *tr = tour_s[wave * APW + r4];
-            dstage[wave][r4][lane] = t < n ? dist_b[(uint32_t)tr[t] * (uint32_t)n + tr[t - 1]] : 0.0f;
+          for (int r4 = 0; r4 < APW; r4 += 64 / DSW) {
+            const int kr = wave * APW + r4 + lane / DSW;
+            dstage[wave][r4 + lane / DSW][lane & (DSW - 1)] = t < n ? dist_b[(uint32_t)SP_TOUR(kr, t) * (uint32_t)n + SP_TOUR(kr, t - 1)] : 0.0f;
           }
           __builtin_amdgcn_wave_barrier();
           if (s == 0) {
 #pragma unroll
-            for (int v4 = 0; v4 < 16; ++v4) {
+            for (int v4 = 0; v4 < DSW / 4; ++v4) {
               const float4 v = *(const float4 *)(mine_d + 4 * v4);
               cost = cost + v.x; cost = cost + v.y; cost = cost + v.z; cost = cost + v.w;
             }
@@ -585,40 +666,45 @@ scan_sparse_kernel(const SampleParams p) {
           __builtin_amdgcn_wave_barrier();
         }
         if (s == 0 && a0 + q < A) {
-          const uint16_t *tm = tour_s[wave * APW + q];
-          cost = cost + dist_b[(uint32_t)tm[0] * (uint32_t)n + tm[n - 1]];
-          p.costs[(size_t)b * A + a0 + q] = cost;
+          const int km = wave * APW + q;
+          cost = cost + dist_b[(uint32_t)SP_TOUR(km, 0) * (uint32_t)n + SP_TOUR(km, n - 1)];
+          SP_E(costs)[(size_t)b * A + a0 + q] = cost;
         }
       }
     }
-    if (p.nbr) {
-      // the update's table through an inverse-permutation table in the (dead) flag array, eight ants at a time
-      uint16_t (*inv)[FL] = reinterpret_cast<uint16_t (*)[FL]>(LH ? lh_tab + 4096 : flag_mem);
-      static_assert(LH || APB * FLP >= 8 * FL * (int)sizeof(uint16_t), "inverse table of eight ants inside the flag array");
-      const int k8 = threadIdx.x & 7;
-      for (int half = 0; half < 2; ++half) {
-        const int nh = nant - half * 8 < 8 ? nant - half * 8 : 8;
+    if (SP_E(nbr)) {
+      // the update's table through an inverse-permutation table in the (dead) flag array, eight ants at a time (ST: four, behind
+      // the early parts)
+      constexpr int NI = ST ? 4 : 8;
+      uint16_t (*inv)[FL] = reinterpret_cast<uint16_t (*)[FL]>(LH ? lh_tab + 4096 : ST ? sparse_dyn + APB * SP_EW * 2 : flag_mem);
+      static_assert(LH || ST || APB * FLP >= 8 * FL * (int)sizeof(uint16_t), "inverse table of eight ants inside the flag array");
+      const int k8 = threadIdx.x & (NI - 1);
+      for (int half = 0; half < 16 / NI; ++half) {
+        const int nh = nant - half * NI < NI ? nant - half * NI : NI;
         __syncthreads();
         if (nh <= 0) break;
-        for (int e = threadIdx.x; e < 8 * FL / 8; e += 256) ((uint4 *)&inv[0][0])[e] = make_uint4(0, 0, 0, 0);
+        for (int e = threadIdx.x; e < NI * FL / 8; e += 256) ((uint4 *)&inv[0][0])[e] = make_uint4(0, 0, 0, 0);
         __syncthreads();
-        const uint16_t *tk = tour_s[half * 8 + (k8 < nh ? k8 : 0)];
+        const int kt = half * NI + (k8 < nh ? k8 : 0);
         if (k8 < nh)
-          for (int t = threadIdx.x >> 3; t < n; t += 32) inv[k8][tk[t]] = (uint16_t)t;
+          for (int t = threadIdx.x / NI; t < n; t += 256 / NI) inv[k8][SP_TOUR(kt, t)] = (uint16_t)t;
         __syncthreads();
         // classic layout [B][n][A]: one 32-byte run per node; grouped (nbr_grouped: [B][ceil(A/8)][n][8]): the eight ants' entries
         // of consecutive nodes are consecutive -- the 256 threads of a pass write 1 KB in one piece
-        const int a8 = abase + half * 8;
-        uint32_t *nb = p.nbr_grouped ? p.nbr + (((size_t)b * ((A + 7) >> 3) + (a8 >> 3)) * n) * 8 + (a8 & 7) : p.nbr + (size_t)b * n * A + a8;
-        const size_t nstride = p.nbr_grouped ? 8 : (size_t)A;
+        const int a8 = abase + half * NI;
+        uint32_t *nb = SP_E(nbr_grouped) ? SP_E(nbr) + (((size_t)b * ((A + 7) >> 3) + (a8 >> 3)) * n) * 8 + (a8 & 7) : SP_E(nbr) + (size_t)b * n * A + a8;
+        const size_t nstride = SP_E(nbr_grouped) ? 8 : (size_t)A;
         if (k8 < nh)
-          for (int node = threadIdx.x >> 3; node < n; node += 32) {
+          for (int node = threadIdx.x / NI; node < n; node += 256 / NI) {
             const int t = inv[k8][node];
-            const uint32_t pv = tk[t == 0 ? n - 1 : t - 1], nx = tk[t == n - 1 ? 0 : t + 1];
+            const int tp = t == 0 ? n - 1 : t - 1, tn = t == n - 1 ? 0 : t + 1;
+            const uint32_t pv = SP_TOUR(kt, tp), nx = SP_TOUR(kt, tn);
             nb[(size_t)node * nstride + k8] = pv | (nx << 16);
           }
       }
     }
+#undef SP_TOUR
+#undef SP_E
   } else {
     // TG: eight tours at a time, global -> LDS (this workgroup wrote them: its stores are visible after the barrier's release /
     // acquire), into the block the loop no longer needs: [8][FL] tours | [8][FL] inverse table (cost staging before it is built)
@@ -732,6 +818,49 @@ static bool sparse_rows_vec4(int n, const float *tau, long tau_bstride, const fl
   return (n & 3) == 0 && (tau_bstride & 3) == 0 && (eta_bstride & 3) == 0 && (((uintptr_t)tau | (uintptr_t)eta) & 15) == 0;
 }
 
+// the instantiation of scan_sparse_kernel and its dynamic LDS for a launch that is not the LDS-heads case: flags + tours (n <= 512;
+// the split-tour variant for the scan draw on 64-slot heads: SP_ST_LDS); the larger of flags + window and eight tours + their
+// inverse table (n > 512).
+// many: the launch does not fit one round of the whole-tour kernel (six workgroups per CU) but fits one round of the split-tour
+// variant (eight).  Only then does the variant turn a second, badly filled round into none.  A launch that fits six per CU has no
+// tail, and the variant's epilogue (copy-back, four inverse-table passes instead of two) costs it 5 % (B = 48: 0.41 against
+// 0.39 ms); a launch of several rounds runs its epilogues under other workgroups' loops either way, and the whole-tour kernel
+// is 1 % ahead there (B = 128: 1.02 against 1.03 ms).  profiles/resident_round_ab.txt.
+constexpr int SP_WHOLE_TOUR_PER_CU = 6, SP_SPLIT_TOUR_PER_CU = 8;
+static int sparse_split_mode = -1;                       // -1: by the size of the launch; 0 / 1: never / always (tests, A/B runs)
+extern "C" int daco_tsp_sparse_split_tours(int mode) {
+  const int old = sparse_split_mode;
+  if (mode >= -1 && mode <= 1) sparse_split_mode = mode;
+  return old;
+}
+static bool sparse_many_workgroups(long workgroups) {
+  if (sparse_split_mode >= 0) return sparse_split_mode == 1;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return true; }
+  return workgroups > (long)SP_WHOLE_TOUR_PER_CU * cus && workgroups <= (long)SP_SPLIT_TOUR_PER_CU * cus;
+}
+
+struct SparseVariant { const void *fn; size_t lds; };
+static SparseVariant sparse_variant(int ld, bool race, int spl, bool many) {
+#define DACO_SPARSE_LDS(C) ((C) == 2 ? 16 * ((C) * 256 + 16) + 16 * ((C) * 256 + 2) * 2 : 2 * 8 * (C) * 256 * 2)
+#define DACO_SPARSE_V(C, R, S) SparseVariant{reinterpret_cast<const void *>(&scan_sparse_kernel<C, R, S>), (size_t)DACO_SPARSE_LDS(C)}
+  if (ld <= 512 && !race && spl == 4 && many) return SparseVariant{reinterpret_cast<const void *>(&scan_sparse_kernel<2, false, 4, false, true>), (size_t)SP_ST_LDS};
+  if (ld <= 512) return race ? (spl == 4 ? DACO_SPARSE_V(2, true, 4) : DACO_SPARSE_V(2, true, 8)) : (spl == 4 ? DACO_SPARSE_V(2, false, 4) : DACO_SPARSE_V(2, false, 8));
+  return race ? (spl == 4 ? DACO_SPARSE_V(4, true, 4) : DACO_SPARSE_V(4, true, 8)) : (spl == 4 ? DACO_SPARSE_V(4, false, 4) : DACO_SPARSE_V(4, false, 8));
+#undef DACO_SPARSE_V
+#undef DACO_SPARSE_LDS
+}
+
+// workgroups of that launch a CU holds at a time, for a launch of more than six and at most eight workgroups per CU (0: bad
+// arguments or the query failed)
+extern "C" int daco_tsp_sparse_resident_per_cu(int n, int head_slots, int race) {
+  if (n <= 128 || n > 1024 || (head_slots != 64 && head_slots != 128)) return 0;
+  const SparseVariant v = sparse_variant(n <= 512 ? 512 : 1024, race != 0, head_slots / 16, true);
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, v.fn, 256, v.lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  return nb;
+}
+
 static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, int nbr_grouped, const char *what, void *stream, int B, int n, int A, const float *tau, long tau_bstride, const float *eta,
                                       long eta_bstride, float alpha, float beta, const uint16_t *head_id, int head_slots, const int64_t *start,
                                       int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
@@ -807,21 +936,17 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   }
   const int bpi = lh ? (A + 3) / 4 : (A + 15) / 16;
   const dim3 grid((unsigned)(B * bpi));
-  // dynamic LDS: flags + tours (n <= 512); the larger of flags + window and eight tours + their inverse table (n > 512)
-#define DACO_SPARSE_LDS(C) ((C) == 2 ? 16 * ((C) * 256 + 16) + 16 * ((C) * 256 + 2) * 2 : 2 * 8 * (C) * 256 * 2)
-#define DACO_SPARSE_LAUNCH(C, R, S) hipLaunchKernelGGL((scan_sparse_kernel<C, R, S>), grid, dim3(256), DACO_SPARSE_LDS(C), s, sp)
-#define DACO_SPARSE_PICK(C, R) do { if (spl == 4) DACO_SPARSE_LAUNCH(C, R, 4); else DACO_SPARSE_LAUNCH(C, R, 8); } while (0)
   if (lh) {
     // (more than 64 KB of dynamic LDS has to be asked for; per call: the attribute belongs to the current device's copy of the
     // kernel and a process may drive several devices)
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_sparse_kernel<2, false, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024 - 128) != hipSuccess) { set_error("%s: hipFuncSetAttribute(dynamic LDS) failed", what); return DACO_E_HIP; }
     hipLaunchKernelGGL((scan_sparse_kernel<2, false, 4, true>), grid, dim3(256), lh_lds, s, sp);
-  } else if (ld <= 512) { if (race) DACO_SPARSE_PICK(2, true); else DACO_SPARSE_PICK(2, false); }
-  else { if (race) DACO_SPARSE_PICK(4, true); else DACO_SPARSE_PICK(4, false); }
-#undef DACO_SPARSE_PICK
-#undef DACO_SPARSE_LDS
-#undef DACO_SPARSE_LAUNCH
+  } else {
+    const SparseVariant v = sparse_variant(ld, race, spl, sparse_many_workgroups((long)B * bpi));
+    void *args[] = {&sp};                               // (the one argument: the split-tour variant's epilogue reads it back from offset 0 of the segment)
+    if (hipLaunchKernel(v.fn, grid, dim3(256), args, v.lds, s) != hipSuccess) { set_error("%s: scan_sparse_kernel launch failed", what); return DACO_E_HIP; }
+  }
   e = hipGetLastError();
   if (e != hipSuccess) { set_error("scan_sparse_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
   if (ev_end && hipEventRecord((hipEvent_t)ev_end, s) != hipSuccess) { set_error("hipEventRecord(ev_end) failed"); return DACO_E_HIP; }

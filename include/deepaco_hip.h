@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel) */
 
 /* error codes */
 #define DACO_OK 0
@@ -151,6 +151,20 @@ size_t daco_tsp_sparse_workspace_bytes_general(int B, int n, int A);
  * its iteration asks for no int64 [B][n][A] tensor (131 MB per iteration at TSP-500 x 512 x 64) and hands these rows to
  * daco_track_best_tours16. */
 size_t daco_tsp_sparse_tours_offset(int B, int n, int A);
+/* daco_tsp_sparse_resident_per_cu -- how many workgroups of the construction kernel a compute unit holds at a time
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor) for the instantiation and the dynamic LDS that daco_tsp_sample_sparse / _race_head /
+ * _heads launch for these arguments when the launch has more than six and at most eight workgroups of 16 ants per compute unit
+ * (another launch of the scan draw on 64-slot heads at n <= 512 has no badly filled second round to remove and keeps whole tours
+ * in LDS, six workgroups per compute unit; few ants of one instance take the LDS-heads variant).  The scan draw on 64-slot
+ * heads at n <= 512 keeps a 352-entry window of each tour in LDS and parks the first max(0, roundup16(n - 352)) entries in the
+ * workspace's tours16 rows (also in a call that returns int64 paths), so that eight workgroups fit: 2 048 workgroups -- TSP-500 x 512
+ * ants x 64 instances -- are resident at once on 256 compute units.  0: bad arguments, or the query failed. */
+int daco_tsp_sparse_resident_per_cu(int n, int head_slots, int race);
+/* daco_tsp_sparse_split_tours -- which launches of the scan draw on 64-slot heads at n <= 512 take the split-tour variant:
+ * -1 (default) those with more than six and at most eight workgroups per compute unit, 0 none, 1 all of them (what the tests of the variant and
+ * A/B runs set; the tours are the same either way).  Process-wide, not thread-safe against concurrent launches.  Returns the
+ * previous mode; any other argument only queries. */
+int daco_tsp_sparse_split_tours(int mode);
 int daco_tsp_sample_sparse(void *stream, int B, int n, int A,
                            const float *tau, long tau_bstride, const float *eta, long eta_bstride,
                            float alpha, float beta, const uint16_t *head_id, int head_slots,

@@ -23,14 +23,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 # workload directory -> (kernel substring, key in counters.json / hbm_traffic.json)
+# (scan_sparse_kernel<CHD, RACE, SPL, LH, ST>: the headline launch is the split-tour variant)
 WORKLOADS = {
     "headline": ("tsp_scan32_kernel", "tsp500_a512_b64_scan"),
-    "scan_sparse": ("scan_sparse_kernel<2, false, 4, false>", "tsp500_a512_b64_scan_sparse"),
-    "c5_sparse": ("scan_sparse_kernel<4, false, 8, false>", "tsp1000_a2048_b64_scan_sparse"),
-    "b1_lds_heads": ("scan_sparse_kernel<2, false, 4, true>", "tsp500_a512_b1_scan_sparse"),
+    "scan_sparse": ("scan_sparse_kernel<2, false, 4, false, true>", "tsp500_a512_b64_scan_sparse"),
+    "c5_sparse": ("scan_sparse_kernel<4, false, 8, false, false>", "tsp1000_a2048_b64_scan_sparse"),
+    "b1_lds_heads": ("scan_sparse_kernel<2, false, 4, true, false>", "tsp500_a512_b1_scan_sparse"),
     "deposit_heads": ("deposit_rows_kernel<true, 1, true>", "tsp500_a512_b64_update_heads"),
     "race": ("tsp_sample_kernel", "tsp500_a512_b64_race"),
-    "race_head": ("scan_sparse_kernel<2, true, 4, false>", "tsp500_a512_b64_race_head"),
+    "race_head": ("scan_sparse_kernel<2, true, 4, false, false>", "tsp500_a512_b64_race_head"),
     "c2": ("scan16_kernel", "tsp100_a512_b256_scan"),
     "c4": ("scan16_kernel", "cvrp100_a512_b256_scan"),
     "c5": ("tsp_scan32_kernel", "tsp1000_a2048_b64_scan"),
@@ -55,10 +56,10 @@ def main():
     from deepaco_amd import _lib
     version = _lib.ABI_VERSION
     counters = {"daco_version": version,
-                "source": "profiles/r06_pmc_*.txt (tools/profile.sh + tools/make_counters.py: rocprofv3 --pmc, one pass per counter "
+                "source": "the pmc_<workload>.txt summaries kept under profiles/ (tools/profile.sh + tools/make_counters.py: rocprofv3 --pmc, one pass per counter "
                           "group, mean per launch of the workload's dominant kernel, all of this library version)"}
     traffic = {"daco_version": version,
-               "source": "profiles/r06_pmc_*.txt (tools/profile.sh: FETCH_SIZE KiB x 1024 x 2 [gfx950 correction] + WRITE_SIZE KiB x "
+               "source": "the pmc_<workload>.txt summaries kept under profiles/ (tools/profile.sh: FETCH_SIZE KiB x 1024 x 2 [gfx950 correction] + WRITE_SIZE KiB x "
                          "1024, mean per launch of the dominant kernel)"}
     if "--merge" in sys.argv[2:]:
         for name, cur in (("counters.json", counters), ("hbm_traffic.json", traffic)):

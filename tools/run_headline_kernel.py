@@ -11,6 +11,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepaco_amd import engine  # noqa: E402
 
+if os.environ.get("SPARSE_SPLIT"):                      # -1 / 0 / 1: daco_tsp_sparse_split_tours (the split-tour variant by size / never / always)
+    from deepaco_amd import _lib
+    _lib.lib().daco_tsp_sparse_split_tours(int(os.environ["SPARSE_SPLIT"]))
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 A = int(sys.argv[3]) if len(sys.argv) > 3 else 512
