@@ -1,0 +1,22 @@
+"""Batched functional layer over the C ABI: B instances x A ants per call.
+
+Every function takes torch tensors that live on a HIP device, enqueues the kernels on the
+current torch stream and returns torch tensors; nothing here synchronises with the host.
+Layouts follow the reference with a leading batch dimension:
+paths [B, n, A] int64, log_probs [B, n-1, A] f32, costs [B, A] f32.
+"""
+from .. import _lib  # noqa: F401
+from .colonies import (BatchedCVRP, BatchedTSP, StreamedTSP, ant_sharded_cvrp, ant_sharded_tsp, run_kept_colony,  # noqa: F401
+                       same_state)
+from .common import MODES, RACE_NOISE, RACE_PHILOX, SCAN, SCAN_WAVE, _f32c, _stream, _workspace, stage_to_hip  # noqa: F401
+from .cvrp_ops import cvrp_sample, sample_backward  # noqa: F401
+from .local_search import (HgsTables, TspLocalSearch, TwoOptTables, cvrp_local_search_, heuristic_dist, hgs_local_search_,  # noqa: F401
+                           nls_, transposed_for_two_opt, two_opt_, two_opt_tables)
+from .mkp_ops import (BatchedMKPVec, mkpv_backward, mkpv_check_flags, mkpv_sample, mkpv_update_, transformer_backward,  # noqa: F401
+                      transformer_forward, transformer_forward_train)
+from .rcpsp_ops import (RCPSP_FLAG_ORDER, RCPSP_FLAG_RESOURCE, RCPSP_MAX_HORIZON, RCPSP_MAX_N, RCPSP_MAX_R, BatchedRCPSP,  # noqa: F401
+                        rcpsp_backward, rcpsp_check_flags, rcpsp_sample, rcpsp_schedule)
+from .sibling_ops import SIB_KINDS, PickService, sibling_backward, sibling_sample  # noqa: F401
+from .tsp_ops import (SPARSE_MAX_N, SPARSE_MIN_N, auto_head_k, head_table, heu_matrix, resolve_sampler, sparse_head,  # noqa: F401
+                      sparse_tours16, sparse_workspace, take_auto_top, tsp_knn_graph, tsp_sample, tsp_sample_sparse)
+from .update import pheromone_update_, tour_costs, track_best_  # noqa: F401

@@ -1,0 +1,308 @@
+"""TSP construction: the dense and race samplers, the head-row samplers with their head tables, the k-nn graph."""
+import torch
+
+from .. import _lib
+from .common import MODES, RACE_NOISE, _bstride, _f32c, _on, _ptr, _require_gpu, _stream, _workspace
+
+
+def tsp_sample(tau, eta, n_ants, alpha=1.0, beta=1.0, mode="scan", norm_passes=1, start=None,
+               fixed_start=-1, noise=None, seed=0, it=0, ant_gid0=0, require_prob=False, batch=None,
+               events=None, dist=None, want_nbr=False, iter_dev=None, ant_gid_bstride=0, flags=None):
+    """ACO.gen_path for a batch (tsp/aco.py:134-177, tsp_nls/aco.py:184-220).
+
+    tau, eta: [B,n,n] or [n,n] (shared).  Returns (paths, log_probs|None, rowsum|None, flags).
+    events: optional (begin, end) torch.cuda.Event pair (already recorded once, so the handles
+    exist) re-recorded around the tour-construction kernel only.
+    dist: if given, tour costs are fused into the kernel and returned; want_nbr: also return the
+    neighbour table the pheromone update consumes.  With either, the return value is
+    (paths, log_probs, rowsum, flags, costs|None, nbr|None)."""
+    _require_gpu(tau, eta, start, noise)
+    n = tau.shape[-1]
+    B = batch or (tau.shape[0] if tau.dim() == 3 else (eta.shape[0] if eta.dim() == 3 else 1))
+    dev = tau.device
+    tau, tbs = _bstride(tau, n)
+    eta, ebs = _bstride(eta, n)
+    m = MODES[mode] if isinstance(mode, str) else int(mode)
+    L = _lib.lib()
+    with _on(dev):
+        paths = torch.empty((B, n, n_ants), dtype=torch.int64, device=dev)
+        logp = torch.empty((B, n - 1, n_ants), dtype=torch.float32, device=dev) if require_prob else None
+        rowsum = torch.empty((B, n - 1, n_ants), dtype=torch.float32, device=dev) if require_prob else None
+        if flags is None:                                    # (a caller's own flag words are OR-ed into: no fill launch per call)
+            flags = torch.zeros((B,), dtype=torch.int32, device=dev)
+        if start is not None:
+            start = start.to(torch.int64).contiguous().view(B, n_ants)
+        if noise is not None:      # race_noise: the reference's q tensors; scan modes: injected uniforms [B, n-1, A]
+            noise = _f32c(noise).view(B, n - 1, n_ants, n) if m == RACE_NOISE else _f32c(noise).view(B, n - 1, n_ants)
+        costs, dbs = None, 0
+        if dist is not None:
+            _require_gpu(dist)
+            dist, dbs = _bstride(dist, n)
+            costs = torch.empty((B, n_ants), dtype=torch.float32, device=dev)
+        nbr = torch.empty((B, n, n_ants), dtype=torch.int32, device=dev) if want_nbr else None
+        ws = _workspace(dev, L.daco_tsp_sample_workspace_bytes(B, n, m), "sample")
+        rc = L.daco_tsp_sample(_stream(dev), B, n, n_ants, tau.data_ptr(), tbs, eta.data_ptr(), ebs,
+                               float(alpha), float(beta), m, int(norm_passes),
+                               start.data_ptr() if start is not None else None, int(fixed_start),
+                               noise.data_ptr() if noise is not None else None,
+                               int(seed) & (2 ** 64 - 1), int(it), iter_dev.data_ptr() if iter_dev is not None else None,
+                               int(ant_gid0) & 0xFFFFFFFF, int(ant_gid_bstride),
+                               paths.data_ptr(), logp.data_ptr() if require_prob else None,
+                               rowsum.data_ptr() if require_prob else None, flags.data_ptr(),
+                               dist.data_ptr() if dist is not None else None, dbs,
+                               costs.data_ptr() if costs is not None else None,
+                               nbr.data_ptr() if nbr is not None else None,
+                               ws.data_ptr(), ws.numel(),
+                               events[0].cuda_event if events else None,
+                               events[1].cuda_event if events else None)
+    _lib.check(rc, "daco_tsp_sample")
+    if dist is not None or want_nbr:
+        return paths, logp, rowsum, flags, costs, nbr
+    return paths, logp, rowsum, flags
+
+
+def sparse_head(weights, k, top=None):
+    """Head table of scan_sparse for `weights` [B,n,n] or [n,n] (the colony passes its heuristic): per row the k (<= 127)
+    largest entries, ids ascending (ties at the k-th value: the smaller id) -- [B,n,S] int16 holding uint16 ids with S = 64
+    slots for k <= 63, else 128; the unused slots 0, the last slot = k (include/deepaco_hip.h daco_tsp_sample_sparse;
+    oracle.sparse_head_ids is the same rule).
+    top: the rows' largest values in descending order, at least k of them ([.., m >= k], e.g. what auto_head_k computed for the
+    same matrix): the one torch.topk this function needs is then skipped."""
+    _require_gpu(weights)
+    w = weights if weights.dim() == 3 else weights.unsqueeze(0)
+    B, n, _ = w.shape
+    assert 1 <= k <= 127 and k <= n
+    slots = 64 if k <= 63 else 128
+    # the k largest by (value descending, id ascending), without sorting the rows: everything above the k-th value,
+    # and of the entries equal to it the smallest ids.  The chosen ids ascending = the chosen columns in column order: their
+    # running count is the slot (the others go to a spare slot that is cut off).
+    v = w.detach().to(torch.float32)
+    if top is not None and top.shape[-1] >= k:
+        kth = (top if top.dim() == 3 else top.unsqueeze(0))[:, :, k - 1:k].to(torch.float32)     # ([1,n,1] broadcasts over B)
+    else:
+        kth = torch.topk(v, k, dim=2).values[:, :, k - 1:k]
+    greater = v > kth
+    eq = v == kth
+    room = k - greater.sum(dim=2, keepdim=True)
+    chosen = greater | (eq & (torch.cumsum(eq, dim=2, dtype=torch.int32) <= room))
+    slot = torch.where(chosen, torch.cumsum(chosen, dim=2, dtype=torch.int32) - 1, slots).to(torch.int64)
+    ids = torch.zeros((B, n, slots + 1), dtype=torch.int16, device=w.device)
+    ids.scatter_(2, slot, torch.arange(n, device=w.device, dtype=torch.int16).view(1, 1, n).expand(B, n, n))
+    ids = ids[:, :, :slots].contiguous()                 # (bit pattern of uint16: ids < 32768 here, n <= 1024)
+    ids[:, :, slots - 1] = k
+    return ids
+
+
+SPARSE_MIN_N, SPARSE_MAX_N = 129, 1024        # sizes daco_tsp_sample_sparse / _race_head cover
+
+
+def auto_head_k(heuristic, mass=0.98, want_top=False):
+    """Head size for sampler='auto' on a heuristic nobody sparsified by hand: 63 or 127 if that many largest entries hold at
+    least `mass` of (nearly) every row (the learned heuristic is k-sparse by construction: tsp/net.py:94-102 scatters k values per row
+    into zeros, + 1e-10), else None.  One reduction and one host read per heuristic object.
+    mass = 0.98: a step that has to leave the head re-reads the whole row for its ants (each such step stops four
+    ants for a row walk); with a fifth of the mass in the tail (plain 1/d at n = 200: 0.85 in the best 127) the head rows lose.
+    want_top: also return the rows' 127 largest values (descending), which sparse_head takes instead of its own torch.topk."""
+    h = heuristic.detach()
+    n = h.shape[-1]
+    if not (SPARSE_MIN_N <= n <= SPARSE_MAX_N):
+        return (None, None) if want_top else None
+    h = h.to(torch.float32)
+    top = torch.topk(h, min(127, n - 1), dim=-1).values
+    tot = h.sum(dim=-1)
+    # "every row" up to one row in twenty: a network output can leave single rows flat (all live entries ~1e-13 against the
+    # 1e-10 floor); those rows cost a dense step when an ant stands on them, the colony still gains on the others
+    ok63 = ((top[..., :63].sum(dim=-1) / tot) >= mass).float().mean()
+    ok127 = ((top.sum(dim=-1) / tot) >= mass).float().mean()
+    # Round 6: a head that leaves a slot free AND fits a CU's LDS next to four ants (n x ceil((k + 1) / 4) lanes x 24 bytes: k <= 51 at
+    # n = 500, <= 62 below n = 410) lets a launch of few ants -- one instance, the reference's own call pattern, tsp/test.ipynb:66-68 --
+    # keep its head rows in LDS; taken when it holds practically ALL of the mass (1 - 1e-4: the network's output has
+    # exactly the graph's k live entries per row, so k = 50 -> a head of 51), since whatever it left out would be walked as tail
+    lanes = min(16, (160 * 1024 - 128 - 4 * 528 - 4 * 514 * 2 - 32) // (n * 24))
+    k_lds = min(62, 4 * lanes - 1, top.shape[-1])
+    ok_lds = ((top[..., :k_lds].sum(dim=-1) / tot) >= 1.0 - 1e-4).float().mean() if k_lds >= 8 else torch.zeros((), device=h.device)
+    ok63, ok127, ok_lds = (float(x) for x in torch.stack((ok63, ok127, ok_lds)).tolist())          # (one host read)
+    k = k_lds if ok_lds >= 0.95 else (63 if ok63 >= 0.95 else (127 if ok127 >= 0.95 else None))
+    return (k, top if k else None) if want_top else k
+
+
+_warned_sparse_range = False
+
+
+def resolve_sampler(sampler, n, head_k, heuristic, cache):
+    """('scan' | 'scan_wave' | 'race' | 'scan_sparse', head size) for a colony of n nodes.
+    'auto': head / tail rows (scan_sparse: the same categorical as 'scan', 384 / 768 bytes per step instead of a row) whenever
+    they apply -- after sparsify(k), or when auto_head_k finds the heuristic concentrated -- and 129 <= n <= 1024; else the dense
+    scan.  An explicit 'scan_sparse' outside that range falls back to 'scan' with one warning.
+    cache: a dict of the colony (the concentration test is repeated only when the heuristic object changes)."""
+    global _warned_sparse_range
+    in_range = SPARSE_MIN_N <= n <= SPARSE_MAX_N
+    if sampler == "scan_sparse" and not in_range:
+        if not _warned_sparse_range:
+            _warned_sparse_range = True
+            import warnings
+            warnings.warn(f"sampler='scan_sparse' covers {SPARSE_MIN_N} <= n <= {SPARSE_MAX_N}; n = {n} runs the dense scan "
+                          f"(the same distribution)", RuntimeWarning, stacklevel=3)
+        return "scan", None
+    if sampler != "auto":
+        return sampler, head_k
+    if not in_range:
+        return "scan", None
+    if head_k is not None:
+        return "scan_sparse", head_k
+    hit = cache.get("auto_head")
+    if hit is None or hit[0] is not heuristic:
+        k, top = auto_head_k(heuristic, want_top=True)
+        hit = cache["auto_head"] = (heuristic, k)
+        cache["auto_top"] = (heuristic, top)            # (taken -- and dropped -- by the colony's next head table)
+    return ("scan_sparse", hit[1]) if hit[1] else ("scan", None)
+
+
+def take_auto_top(cache, heuristic):
+    """The sorted top values resolve_sampler left in a colony's cache for this heuristic object (None if there are none); they
+    are handed over once: 16 MB per 64 x 500 rows that nothing needs after the head table is built."""
+    hit = cache.pop("auto_top", None) if cache else None
+    return hit[1] if hit is not None and hit[0] is heuristic else None
+
+
+def head_table(heuristic, k, B, cache=None):
+    """sparse_head(.., k) of a colony's heuristic object ([n,n] shared, or [B,n,n]) for its B instances; cache: the colony's
+    resolve_sampler cache, whose sorted top values for this object are taken (take_auto_top)."""
+    h = heuristic.detach()
+    h = h if h.dim() == 3 else h.unsqueeze(0).expand(B, *h.shape)
+    return sparse_head(_f32c(h), k, top=take_auto_top(cache, heuristic))
+
+
+def sparse_workspace(device, B, n, n_ants, unit_exponents=True):
+    """A scratch tensor of the head-row samplers that a colony KEEPS (daco_tsp_sparse_workspace_bytes: the iteration's head rows
+    and, for n > 512, the tours as they are built): pheromone_update_(heads=...) writes the next iteration's head rows into it and
+    tsp_sample_sparse(heads_ready=True) reads them, so it must not be the per-stream scratch other colonies share."""
+    L = _lib.lib()
+    nbytes = (L.daco_tsp_sparse_workspace_bytes if unit_exponents else L.daco_tsp_sparse_workspace_bytes_general)(B, n, n_ants)
+    if nbytes == 0:
+        raise ValueError(f"scan_sparse serves 129 <= n <= 1024 (n = {n})")
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def sparse_tours16(workspace, B, n, n_ants):
+    """The tours of the last tsp_sample_sparse call on `workspace` in their compact form: an int16-typed view [B, A, ld] of the
+    workspace (ld = 512 for n <= 512, else 1024; entry t of ant a = the node visited at step t, entries >= n undefined; node ids are
+    below 32768, so the sign bit is never set).  Written by calls with n > 512 and by calls with want_paths=False
+    (include/deepaco_hip.h daco_tsp_sparse_tours_offset)."""
+    off = int(_lib.lib().daco_tsp_sparse_tours_offset(B, n, n_ants))
+    ld = 512 if n <= 512 else 1024
+    return workspace[off:off + B * n_ants * ld * 2].view(torch.int16).view(B, n_ants, ld)
+
+
+def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, fixed_start=-1, seed=0, it=0, ant_gid0=0,
+                      batch=None, events=None, dist=None, want_nbr=False, iter_dev=None, ant_gid_bstride=0, want_stats=False,
+                      want_paths=True, race=False, workspace=None, heads_ready=False, head_live_max=0, nbr_grouped=False, flags=None):
+    """ACO.gen_path on head / tail rows (sampler "scan_sparse", include/deepaco_hip.h daco_tsp_sample_sparse): the
+    distribution of tsp_sample(mode="scan"), 384 / 768 bytes per step instead of a row while the head has a live candidate.
+    head: sparse_head(heuristic, k).  Returns (paths, flags, costs|None, nbr|None[, stats]).
+    race=True: daco_tsp_sample_race_head -- the exponential race of mode="race" on the head rows, with the tours of the dense
+    race kernel (same seed), one variate per head slot and step instead of n.
+    workspace: a sparse_workspace() tensor the caller keeps (default: the per-stream scratch); heads_ready=True: it already holds
+    this iteration's head rows (pheromone_update_(heads=...) wrote them for these very tensors) and the pass over tau is skipped
+    (include/deepaco_hip.h daco_tsp_sample_heads) -- the same tours.
+    head_live_max: the k the head table was built with (sparse_head(.., k)), or 0: lets a launch of few ants (one instance, a few
+    hundred ants) keep the head rows in LDS -- the same tours, about half the time at TSP-500 x 512 ants x 1 instance.
+    nbr_grouped: the update's table as [B, ceil(A/8), n, 8] (written in 1 KB pieces; pheromone_update_(heads={..., "nbr_grouped": True})
+    takes it) instead of [B, n, A]; the returned tensor keeps the shape [B, n, A] either way (same bytes, opaque to the caller)."""
+    _require_gpu(tau, eta, start, head, workspace)
+    assert not heads_ready or workspace is not None
+    n = tau.shape[-1]
+    B = batch or (tau.shape[0] if tau.dim() == 3 else (eta.shape[0] if eta.dim() == 3 else 1))
+    dev = tau.device
+    tau, tbs = _bstride(tau, n)
+    eta, ebs = _bstride(eta, n)
+    assert head.dtype == torch.int16 and head.is_contiguous() and tuple(head.shape) in ((B, n, 64), (B, n, 128))
+    L = _lib.lib()
+    with _on(dev):
+        paths = torch.empty((B, n, n_ants), dtype=torch.int64, device=dev) if want_paths else None
+        if flags is None:                                    # (a caller that keeps its flag words -- they are OR-ed into -- saves a fill launch per call)
+            flags = torch.zeros((B,), dtype=torch.int32, device=dev)
+        if start is not None:
+            start = start.to(torch.int64).contiguous().view(B, n_ants)
+        costs, dbs = None, 0
+        if dist is not None:
+            _require_gpu(dist)
+            dist, dbs = _bstride(dist, n)
+            costs = torch.empty((B, n_ants), dtype=torch.float32, device=dev)
+        assert not (want_nbr and nbr_grouped) or n_ants % 8 == 0, "the grouped table wants a multiple of eight ants"
+        nbr = torch.empty((B, n, n_ants), dtype=torch.int32, device=dev) if want_nbr else None
+        stats = torch.zeros(3, dtype=torch.int64, device=dev) if want_stats else None
+        unit = float(alpha) == 1.0 and float(beta) == 1.0       # (other exponents: tau^alpha, eta^beta are formed in the workspace first)
+        nbytes = (L.daco_tsp_sparse_workspace_bytes if unit else L.daco_tsp_sparse_workspace_bytes_general)(B, n, n_ants)
+        if nbytes == 0:
+            raise ValueError(f"scan_sparse serves 129 <= n <= 1024 (n = {n})")
+        ws = workspace if workspace is not None else _workspace(dev, nbytes, "sample_sparse")
+        assert ws.numel() >= nbytes
+        rc = L.daco_tsp_sample_heads(_stream(dev), int(bool(race)), int(bool(heads_ready)), int(head_live_max), int(bool(nbr_grouped)), B, n, n_ants, tau.data_ptr(), tbs, eta.data_ptr(), ebs, float(alpha),
+                                      float(beta), head.data_ptr(), int(head.shape[2]), start.data_ptr() if start is not None else None,
+                                      int(fixed_start), int(seed) & (2 ** 64 - 1), int(it),
+                                      iter_dev.data_ptr() if iter_dev is not None else None, int(ant_gid0) & 0xFFFFFFFF,
+                                      int(ant_gid_bstride), paths.data_ptr() if paths is not None else None, flags.data_ptr(),
+                                      dist.data_ptr() if dist is not None else None, dbs,
+                                      costs.data_ptr() if costs is not None else None,
+                                      nbr.data_ptr() if nbr is not None else None,
+                                      stats.data_ptr() if stats is not None else None, ws.data_ptr(), ws.numel(),
+                                      events[0].cuda_event if events else None, events[1].cuda_event if events else None)
+    _lib.check(rc, "daco_tsp_sample_heads")
+    out = (paths, flags, costs, nbr)
+    return out + (stats,) if want_stats else out
+
+
+def tsp_knn_graph(coords, k_sparse, diag=1e9, want_dist=True):
+    """Batched gen_pyg_data (tsp/utils.py:16-36): coords [B,n,2] -> (dist [B,n,n] | None, edge_index [B,2,n*k],
+    edge_attr [B,n*k,1]) in one launch.  The same launch writes the batch as one block-diagonal int32 graph (the form the
+    network's kernels take); it rides on the returned edge_index as `_daco_csr`, and Net.forward_batch(..., k_sparse=k) uses it
+    instead of deriving it again (valid as long as that tensor object is not written to: its version counter is checked)."""
+    _require_gpu(coords)
+    coords = _f32c(coords)
+    B, n, _ = coords.shape
+    dev = coords.device
+    E = n * int(k_sparse)
+    with _on(dev):
+        dist = torch.empty((B, n, n), dtype=torch.float32, device=dev) if want_dist else None
+        ei = torch.empty((B, 2, E), dtype=torch.int64, device=dev)
+        ea = torch.empty((B, E, 1), dtype=torch.float32, device=dev)
+        src32 = torch.empty((B * E,), dtype=torch.int32, device=dev)
+        dst32 = torch.empty((B * E,), dtype=torch.int32, device=dev)
+        # src / dst rows of one instance are the two halves of its [2, E] block
+        src = ei[:, 0]
+        dst = ei[:, 1]
+        if B > 1:                       # the kernel writes [B][E] arrays: use separate contiguous buffers
+            src_c = torch.empty((B, E), dtype=torch.int64, device=dev)
+            dst_c = torch.empty((B, E), dtype=torch.int64, device=dev)
+        else:
+            src_c, dst_c = src, dst
+        rc = _lib.lib().daco_tsp_knn_graph_csr(_stream(dev), B, n, int(k_sparse), coords.data_ptr(), float(diag),
+                                               _ptr(dist), src_c.data_ptr(), dst_c.data_ptr(),
+                                               ea.data_ptr(), src32.data_ptr(), dst32.data_ptr())
+        if B > 1:
+            ei[:, 0], ei[:, 1] = src_c, dst_c
+    _lib.check(rc, "daco_tsp_knn_graph_csr")
+    ei._daco_csr = (src32, dst32, n, int(k_sparse), ei._version)
+    return dist, ei, ea
+
+
+def heu_matrix(n, edge_index, heu, fill=0.0, add=0.0, check=False):
+    """Net.reshape for a batch (tsp/net.py:94-102) with its callers' `+ eps`: edge_index [B,2,E] int64 (graph-local ids),
+    heu [B,E] f32 -> [B,n,n] f32 = `fill` everywhere, heu + add at [src, dst].  check=True: raise if an id lies outside
+    [0, n) (the reference's indexed assignment would; this syncs) -- otherwise such edges are skipped."""
+    _require_gpu(edge_index, heu)
+    B, E = heu.shape
+    assert edge_index.shape == (B, 2, E) and edge_index.dtype == torch.int64
+    ei = edge_index.contiguous()
+    heu = _f32c(heu.detach())
+    dev = heu.device
+    with _on(dev):
+        out = torch.empty((B, n, n), dtype=torch.float32, device=dev)
+        bad = torch.zeros((1,), dtype=torch.int32, device=dev) if check else None
+        rc = _lib.lib().daco_heu_matrix(_stream(dev), B, n, E, ei.data_ptr(), heu.data_ptr(), float(fill), float(add),
+                                        out.data_ptr(), _ptr(bad))
+    _lib.check(rc, "daco_heu_matrix")
+    if check and int(bad.item()):
+        raise IndexError(f"heu_matrix: {int(bad.item())} edge(s) with a node id outside [0, {n})")
+    return out

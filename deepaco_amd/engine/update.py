@@ -1,0 +1,104 @@
+"""Tour costs, the best-so-far record and the pheromone deposit."""
+import torch
+
+from .. import _lib
+from .common import _bstride, _f32c, _on, _require_gpu, _stream, _workspace
+
+
+def tour_costs(dist, paths, closed=True):
+    """ACO.gen_path_costs for a batch (tsp/aco.py:121-132; closed=False: cvrp/aco.py:133-136)."""
+    _require_gpu(dist, paths)
+    n = dist.shape[-1]
+    B, length, A = paths.shape
+    dist, dbs = _bstride(dist, n)
+    paths = paths.contiguous()
+    dev = paths.device
+    with _on(dev):
+        costs = torch.empty((B, A), dtype=torch.float32, device=dev)
+        rc = _lib.lib().daco_tour_costs(_stream(dev), B, n, length, A, dist.data_ptr(), dbs, paths.data_ptr(),
+                                        int(closed), costs.data_ptr())
+    _lib.check(rc, "daco_tour_costs")
+    return costs
+
+
+def track_best_(costs, paths, lowest, shortest=None, mmas_scale=None, tours16=None):
+    """Best-so-far bookkeeping of ACO.run on the device (tsp/aco.py:78-88): updates lowest [B] and shortest
+    [B,len] in place where this iteration's first-minimum cost beats the record.  mmas_scale (= problem size):
+    also returns the MMAS upper bound n / lowest_cost [B] (computed like the reference's rtruediv).
+    tours16 (with paths=None): the tours as sparse_tours16() rows [B, A, ld] instead of int64 paths [B, len, A]; len = shortest's."""
+    _require_gpu(costs, paths, lowest, shortest, tours16)
+    assert costs.dtype == torch.float32 and costs.is_contiguous()
+    B, A = costs.shape
+    assert lowest.dtype == torch.float32 and lowest.is_contiguous() and lowest.numel() == B
+    dev = costs.device
+    with _on(dev):
+        mx = torch.empty((B,), dtype=torch.float32, device=dev) if mmas_scale is not None else None
+        if paths is None:
+            assert tours16 is not None and tours16.dtype == torch.int16 and tours16.is_contiguous() and shortest is not None
+            assert tuple(tours16.shape[:2]) == (B, A)
+            rc = _lib.lib().daco_track_best_tours16(_stream(dev), B, int(shortest.shape[1]), A, int(tours16.shape[2]), costs.data_ptr(),
+                                                    tours16.data_ptr(), lowest.data_ptr(), shortest.data_ptr(), None,
+                                                    mx.data_ptr() if mx is not None else None,
+                                                    float(mmas_scale) if mmas_scale is not None else 0.0)
+            _lib.check(rc, "daco_track_best_tours16")
+            return mx
+        length = paths.shape[1]
+        assert paths.is_contiguous() and tuple(paths.shape) == (B, length, A)
+        rc = _lib.lib().daco_track_best(_stream(dev), B, length, A, costs.data_ptr(), paths.data_ptr(), lowest.data_ptr(),
+                                        shortest.data_ptr() if shortest is not None else None, None,
+                                        mx.data_ptr() if mx is not None else None,
+                                        float(mmas_scale) if mmas_scale is not None else 0.0)
+    _lib.check(rc, "daco_track_best")
+    return mx
+
+
+def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, clamp_min=None,
+                      clamp_max=None, floor=0.0, nbr=None, weights=None, hub=0, heads=None):
+    """In-place ACO.update_pheronome for a batch (tsp/aco.py:95-118, cvrp/aco.py:107-130).
+
+    tau [B,n,n] f32 contiguous (modified in place); clamp_min/clamp_max: [B] f32 tensors or None.
+    weights [B,A]: explicit deposit per ant (default 1/cost); hub: see include/deepaco_hip.h.
+    heads (symmetric only): dict(eta, alpha, beta, head, race, workspace) of a colony whose next construction is
+    tsp_sample_sparse(..., workspace=workspace, heads_ready=True): the update also writes that call's head rows
+    (daco_pheromone_update_heads: tau is read once per iteration instead of twice)."""
+    _require_gpu(tau, paths, costs, clamp_min, clamp_max)
+    assert tau.dim() == 3 and tau.dtype == torch.float32 and tau.is_contiguous()
+    B, n, _ = tau.shape
+    if paths is None:                                        # (the table is all the deposit reads)
+        assert nbr is not None and symmetric
+        length, A = n, costs.shape[-1]
+    else:
+        _, length, A = paths.shape
+        paths = paths.contiguous()
+    pptr = paths.data_ptr() if paths is not None else None
+    costs = _f32c(costs)
+    if weights is not None:
+        weights = _f32c(weights)
+    dev = tau.device
+    L = _lib.lib()
+    with _on(dev):
+        ws = _workspace(dev, L.daco_pheromone_update_workspace_bytes(B, n, length, A), "update")
+        if heads is not None:
+            assert symmetric and length == n
+            eta, ebs = _bstride(heads["eta"], n)
+            head, sws = heads["head"], heads["workspace"]
+            _require_gpu(eta, head, sws)
+            rc = L.daco_pheromone_update_heads(_stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
+                                               int(bool(elitist)), clamp_min.data_ptr() if clamp_min is not None else None,
+                                               clamp_max.data_ptr() if clamp_max is not None else None, float(floor),
+                                               nbr.data_ptr() if nbr is not None else None,
+                                               weights.data_ptr() if weights is not None else None, ws.data_ptr(), ws.numel(),
+                                               eta.data_ptr(), ebs, float(heads["alpha"]), float(heads["beta"]), head.data_ptr(),
+                                               int(head.shape[2]), int(bool(heads.get("race", False))),
+                                               int(bool(heads.get("nbr_grouped", False))) if nbr is not None else 0, sws.data_ptr(), sws.numel())
+            _lib.check(rc, "daco_pheromone_update_heads")
+            return tau
+        rc = L.daco_pheromone_update(_stream(dev), B, n, length, A, tau.data_ptr(), pptr,
+                                     costs.data_ptr(), float(decay), int(bool(elitist)), int(bool(symmetric)),
+                                     clamp_min.data_ptr() if clamp_min is not None else None,
+                                     clamp_max.data_ptr() if clamp_max is not None else None,
+                                     float(floor), nbr.data_ptr() if nbr is not None else None,
+                                     weights.data_ptr() if weights is not None else None, int(hub),
+                                     ws.data_ptr(), ws.numel())
+    _lib.check(rc, "daco_pheromone_update")
+    return tau

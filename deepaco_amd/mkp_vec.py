@@ -20,7 +20,7 @@ items (no dummy padding).
 import torch
 from torch.distributions import Categorical
 
-from . import engine
+from . import _lib, engine
 from .autograd import MkpvSampleFn
 
 
@@ -30,7 +30,7 @@ class ACO:
                  heuristic=None, min=None, device='cpu', *, sampler='scan', seed=None):
         for t in (price, weight, pheromone, heuristic):
             if torch.is_tensor(t) and not t.is_cuda:
-                raise engine._lib.DacoError(f"{type(self).__module__}.ACO needs tensors on a HIP device; there is no CPU path")
+                raise _lib.DacoError(f"{type(self).__module__}.ACO needs tensors on a HIP device; there is no CPU path")
         self.n, self.m = len(price), len(weight)
         self.n_ants, self.decay, self.alpha, self.beta = n_ants, decay, alpha, beta
         self.elitist, self.min_max = elitist, min_max

@@ -7,7 +7,7 @@ and nothing synchronises with the host until the caller reads the result.
 """
 import torch
 
-from . import engine
+from . import _lib, engine
 
 EPS = 1e-10        # added to the learned heuristic (tsp/train.ipynb:35, tsp_nls/test.py:28)
 
@@ -114,7 +114,7 @@ class TspNlsTrainer:
                  optimizer=None, device=None):
         dev = torch.device(device) if device is not None else next(net.parameters()).device
         if dev.type != "cuda":
-            raise engine._lib.DacoError("TspNlsTrainer runs on a HIP device only")
+            raise _lib.DacoError("TspNlsTrainer runs on a HIP device only")
         self.net, self.B, self.n, self.n_ants, self.k = net, int(B), int(n), int(n_ants), int(k_sparse)
         self.seed, self.max_norm, self.local_search, self.use_graph = int(seed), float(max_norm), local_search, bool(graph)
         self.block = net.flatten_parameters()

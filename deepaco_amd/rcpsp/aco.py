@@ -14,6 +14,7 @@ except ImportError:
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
     from deepaco_amd import _lib, engine
 from deepaco_amd.autograd import RcpspSampleFn
+from deepaco_amd.engine.common import _f32c
 from deepaco_amd.rcpsp.rcpsp_inst import (RCPSPInstance, default_heuristic, nGRPWA_heuristic, nLFT_heuristic,  # noqa: F401
                                          nWRUP_heuristic)
 
@@ -103,7 +104,7 @@ class ACO_RCPSP:
 
     @pheromone.setter
     def pheromone(self, value):
-        self._col.pheromone = engine._f32c(value).reshape(1, self.n, self.n).clone()
+        self._col.pheromone = _f32c(value).reshape(1, self.n, self.n).clone()
 
     @property
     def max(self):
@@ -131,7 +132,7 @@ class ACO_RCPSP:
             self._take(routes, starts, costs, flags)
             return logp[0]
         with torch.no_grad():
-            self._col.heuristic = engine._f32c(self.heuristic.detach()).reshape(1, self.n, self.n)
+            self._col.heuristic = _f32c(self.heuristic.detach()).reshape(1, self.n, self.n)
             routes, _, _, starts, costs, flags = self._col.sample(noise=self._next_noise())
         self._take(routes, starts, costs, flags)
 

@@ -21,7 +21,7 @@ reference's solutions bit for bit.
 """
 import torch
 
-from . import engine
+from . import _lib, engine
 
 
 class _PickFn(torch.autograd.Function):
@@ -79,7 +79,7 @@ class _Base:
     def _require_gpu(self, *ts):
         for t in ts:
             if torch.is_tensor(t) and not t.is_cuda:
-                raise engine._lib.DacoError(f"{type(self).__module__}.ACO needs tensors on a HIP device; there is no CPU path")
+                raise _lib.DacoError(f"{type(self).__module__}.ACO needs tensors on a HIP device; there is no CPU path")
 
     def _begin(self):
         self._svc = engine.PickService(self.pheromone.detach().float(), self.heuristic.detach().float(), self.n_ants,

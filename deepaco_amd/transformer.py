@@ -19,7 +19,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
-from . import engine
+from . import _lib, engine
 
 _LAYER_ORDER = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
                 "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias",
@@ -97,7 +97,7 @@ class TransformerModel(nn.Module):
     def forward_batch(self, src):
         """src [B, n, m+1] -> [B, n]"""
         if not src.is_cuda or not self.encoder.weight.is_cuda:
-            raise engine._lib.DacoError("TransformerModel needs its input and parameters on a HIP device; there is no CPU path")
+            raise _lib.DacoError("TransformerModel needs its input and parameters on a HIP device; there is no CPU path")
         if torch.is_grad_enabled():
             if self.grad_path == "torch":
                 return self._torch_forward(src.transpose(0, 1)).transpose(0, 1)

@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: the shared library loads without a GPU, exports every
 symbol include/deepaco_hip.h declares, the ctypes table covers them all, and argument validation
 answers with error codes (no compute is launched here)."""
+import ctypes as C
 import os
 import re
 
@@ -28,8 +29,65 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(L, s), f"{s} declared in include/deepaco_hip.h but not exported"
 
 
+_C_SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+              "uint64_t": C.c_uint64, "uint32_t": C.c_uint32, "int32_t": C.c_int32, "int64_t": C.c_int64}
+
+
+def header_signatures():
+    """name -> (restype, argtypes) of every prototype in include/deepaco_hip.h, in ctypes: any pointer argument a c_void_p,
+    a `const char *` return a c_char_p, the scalar types by name."""
+    text = open(os.path.join(ROOT, "include", "deepaco_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^\s*#[^\n]*(\\\n[^\n]*)*", "", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', "", text)
+    sigs = {}
+    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(daco_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        ret = " ".join(ret.replace("*", " * ").split())
+        res = C.c_char_p if ret == "const char *" else _C_SCALARS[ret]
+        argtypes = []
+        for a in ([] if args.strip() in ("", "void") else args.split(",")):
+            words = [w for w in a.replace("*", " * ").split() if w != "const"]
+            argtypes.append(C.c_void_p if "*" in words else _C_SCALARS[words[0]])
+        assert name not in sigs, f"{name} declared twice"
+        sigs[name] = (res, argtypes)
+    return sigs
+
+
+def signature_mismatches(table, header):
+    """One line per function of `header` whose row of `table` differs: the function and the first differing position."""
+    out = []
+    for name, (res, args) in sorted(header.items()):
+        if name not in table:
+            out.append(f"{name}: no row")
+            continue
+        tres, targs = table[name]
+        if tres is not res:
+            out.append(f"{name}: returns {res.__name__} in the header, {tres.__name__} in the table")
+            continue
+        for i, (h, t) in enumerate(zip(args, targs)):
+            if h is not t:
+                out.append(f"{name}: argument {i} is {h.__name__} in the header, {t.__name__} in the table")
+                break
+        else:
+            if len(args) != len(targs):
+                out.append(f"{name}: {len(args)} arguments in the header, {len(targs)} in the table")
+    return out
+
+
 def test_ctypes_table_matches_header():
     assert sorted(_lib.SIGNATURES) == header_symbols()
+    header = header_signatures()
+    assert sorted(header) == header_symbols()                        # (the prototype parser misses no declaration)
+    assert signature_mismatches(_lib.SIGNATURES, header) == []
+    # the comparison can fail: one row with a float where the header says double, one with its last argument dropped
+    res, args = _lib.SIGNATURES["daco_rcpsp_sample"]
+    at = args.index(C.c_double)
+    wrong = dict(_lib.SIGNATURES, daco_rcpsp_sample=(res, args[:at] + [C.c_float] + args[at + 1:]),
+                 daco_tour_costs=(_lib.SIGNATURES["daco_tour_costs"][0], _lib.SIGNATURES["daco_tour_costs"][1][:-1]))
+    assert signature_mismatches(wrong, header) == [
+        f"daco_rcpsp_sample: argument {at} is c_double in the header, c_float in the table",
+        "daco_tour_costs: 10 arguments in the header, 9 in the table"]
 
 
 def test_version_and_layout_helpers_agree_with_oracle():

@@ -49,7 +49,7 @@ def test_resolution_rules():
     assert engine.resolve_sampler("auto", 300, None, 1 / d, cache) == ("scan", None)
     assert engine.resolve_sampler("auto", 100, 10, h[:100, :100], {}) == ("scan", None)
     assert engine.resolve_sampler("auto", 2000, 100, h, {}) == ("scan", None)
-    engine._warned_sparse_range = False
+    engine.tsp_ops._warned_sparse_range = False
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         assert engine.resolve_sampler("scan_sparse", 100, 10, h, {}) == ("scan", None)

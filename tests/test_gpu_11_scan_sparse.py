@@ -261,7 +261,7 @@ def test_auto_sampler_picks_head_rows_where_they_apply():
     assert col.resolved_sampler() == ("scan", None)
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
-        engine._warned_sparse_range = False
+        engine.tsp_ops._warned_sparse_range = False
         f = engine.BatchedTSP(small, n_ants=16, seed=1, sampler="scan_sparse")
         f.sparsify(10)
         f.run(2)

@@ -27,8 +27,8 @@ with torch.no_grad():
 out = {}
 for label in ("candidate_lists", "dense_only"):
     if label == "dense_only":
-        keep = engine.two_opt_tables
-        engine.two_opt_tables = lambda *a, **kw: None
+        keep = engine.local_search.two_opt_tables
+        engine.local_search.two_opt_tables = lambda *a, **kw: None
     aco = ACO(n_ants=A, heuristic=heu.cpu(), distances=dist.cpu(), device="cpu", local_search="nls", seed=1)
     aco.run(1, inference=True)
     torch.cuda.synchronize()
@@ -38,5 +38,5 @@ for label in ("candidate_lists", "dense_only"):
     dt = (time.perf_counter() - t0) / iters
     out[label] = {"seconds_per_iteration": dt, "best_cost": float(best)}
     if label == "dense_only":
-        engine.two_opt_tables = keep
+        engine.local_search.two_opt_tables = keep
 print(json.dumps({"workload": f"one TSP-{n} instance, {A} ants, NLS inference (maxt = 10000), class surface", **out}))
