@@ -10,10 +10,8 @@
 // reference, adds to different elements never interact, and no atomics are needed
 // (probe-verified bit-identical).  Evaporation is fused into the
 // LDS fill and the MMAS clamp / floor into the write-back, so tau makes one round trip.
-#include "daco_device.h"
-#include "daco_head_rows.h"
+#include "daco_host.h"
 #include <cstdlib>
-#include "../../include/deepaco_hip.h"
 
 namespace daco {
 
@@ -475,8 +473,6 @@ deposit_hub_kernel(int n, int A, int W, int hub, float *tau, const uint32_t *hub
 
 using namespace daco;
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" int daco_tour_costs(void *stream, int B, int n, int len, int A, const float *dist,
                                long dist_bstride, const int64_t *paths, int closed, float *costs) {
   if (B <= 0 || n <= 0 || len <= 0 || A <= 0 || !dist || !paths || !costs) {
@@ -490,9 +486,7 @@ extern "C" int daco_tour_costs(void *stream, int B, int n, int len, int A, const
   else
     hipLaunchKernelGGL(tour_costs_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, n,
                        len, A, dist, dist_bstride, paths, closed, costs);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("tour_costs_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("tour_costs_kernel");
 }
 
 extern "C" int daco_track_best(void *stream, int B, int len, int A, const float *costs, const int64_t *paths,
@@ -503,9 +497,7 @@ extern "C" int daco_track_best(void *stream, int B, int len, int A, const float 
   }
   hipLaunchKernelGGL(track_best_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, len, A, costs, paths, lowest, shortest,
                      best_idx, mmas_max, mmas_scale);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("track_best_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("track_best_kernel");
 }
 
 extern "C" int daco_track_best_tours16(void *stream, int B, int len, int A, int ld, const float *costs, const uint16_t *tours16,
@@ -516,23 +508,18 @@ extern "C" int daco_track_best_tours16(void *stream, int B, int len, int A, int 
   }
   hipLaunchKernelGGL(track_best_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, len, A, costs, (const int64_t *)nullptr, lowest, shortest,
                      best_idx, mmas_max, mmas_scale, tours16, ld);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("track_best_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("track_best_kernel");
 }
 
 extern "C" size_t daco_directed_table_bytes(int B, int n, int A) {
   if (B <= 0 || n <= 0 || A <= 0) return 0;
-  // successor per (node, ant) | per-ant set of depot successors | per-ant route length
-  return align256((size_t)B * n * A * sizeof(uint32_t)) + align256((size_t)B * A * ((n + 31) / 32) * sizeof(uint32_t)) +
-         align256((size_t)B * A * sizeof(int32_t));
+  return DirectedTable::bytes(B, n, A);
 }
 
 extern "C" size_t daco_pheromone_update_workspace_bytes(int B, int n, int len, int A) {
   if (B <= 0 || n <= 0 || A <= 0 || len <= 0) return 0;
   // nbr table | best-ant index | (directed) per-ant bitmap of the nodes that follow the hub
-  return align256((size_t)B * A * n * sizeof(uint32_t)) + align256((size_t)B * sizeof(int)) +
-         align256((size_t)B * A * ((n + 31) / 32) * sizeof(uint32_t));
+  return align256(DirectedTable::next_bytes(B, n, A)) + align256((size_t)B * sizeof(int)) + align256(DirectedTable::hubmask_bytes(B, n, A));
 }
 
 // rows per workgroup from an LDS budget: smaller slabs mean more workgroups per CU moving tau while others run
@@ -573,17 +560,18 @@ static int pheromone_update_impl(void *stream, int B, int n, int len, int A, flo
   if (workspace_bytes < need) { set_error("daco_pheromone_update: workspace %zu < %zu", workspace_bytes, need); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
   const uint32_t *nbr = nbr_in ? nbr_in : (const uint32_t *)workspace;
-  int *best = (int *)((char *)workspace + align256((size_t)B * A * n * sizeof(uint32_t)));
+  int *best = (int *)((char *)workspace + align256(DirectedTable::next_bytes(B, n, A)));
   if (!symmetric) {
     const int W = (n + 31) / 32;
     const uint32_t *hubmask = (const uint32_t *)((char *)best + align256((size_t)B * sizeof(int)));
     const int32_t *tab_lens = nullptr;
     if (nbr_in) {
-      hubmask = (const uint32_t *)((const char *)nbr_in + align256((size_t)B * n * A * sizeof(uint32_t)));
-      tab_lens = (const int32_t *)((const char *)hubmask + align256((size_t)B * A * W * sizeof(uint32_t)));
+      const DirectedTable tab = DirectedTable::carve(nbr_in, B, n, A);
+      hubmask = tab.hubmask;
+      tab_lens = tab.lens;
     } else {
-      if (hipMemsetAsync((void *)hubmask, 0, (size_t)B * A * W * sizeof(uint32_t), s) != hipSuccess) { set_error("hipMemsetAsync failed"); return DACO_E_HIP; }
-      if (hipMemsetAsync(workspace, 0xFF, (size_t)B * A * n * sizeof(uint32_t), s) != hipSuccess) { set_error("hipMemsetAsync failed"); return DACO_E_HIP; }
+      if (hipMemsetAsync((void *)hubmask, 0, DirectedTable::hubmask_bytes(B, n, A), s) != hipSuccess) { set_error("hipMemsetAsync failed"); return DACO_E_HIP; }
+      if (hipMemsetAsync(workspace, 0xFF, DirectedTable::next_bytes(B, n, A), s) != hipSuccess) { set_error("hipMemsetAsync failed"); return DACO_E_HIP; }
       const long total = (long)B * (len - 1) * A;
       int blocks = (int)((total + 255) / 256);
       if (blocks > 16384) blocks = 16384;
@@ -598,9 +586,7 @@ static int pheromone_update_impl(void *stream, int B, int n, int len, int A, flo
     hipLaunchKernelGGL((deposit_rows_kernel<false, 0>), dim3(B * bpi), dim3(256), deposit_lds_bytes(R, n), s, n, A, R, hub, tau,
                        nbr, costs, weights, decay, elitist ? best : nullptr, clamp_min, clamp_max,
                        floor_val, he);
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) { set_error("directed pheromone update launch: %s", hipGetErrorString(e2)); return DACO_E_HIP; }
-    return DACO_OK;
+    return launch_status("directed pheromone update");
   }
   if (!nbr_in) {
     const long total = (long)B * n * A;
@@ -620,9 +606,7 @@ static int pheromone_update_impl(void *stream, int B, int n, int len, int A, flo
   else DACO_DEPOSIT_SYM(2);
 #undef DACO_DEPOSIT_SYM
 #undef DACO_DEPOSIT_SYM_G
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("pheromone update launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("pheromone update");
 }
 
 extern "C" int daco_pheromone_update(void *stream, int B, int n, int len, int A, float *tau,
@@ -633,8 +617,6 @@ extern "C" int daco_pheromone_update(void *stream, int B, int n, int len, int A,
   return pheromone_update_impl(stream, B, n, len, A, tau, paths, costs, decay, elitist, symmetric, clamp_min, clamp_max, floor_val, nbr_in,
                                weights, hub, workspace, workspace_bytes, HeadEmit{});
 }
-
-extern "C" size_t daco_tsp_sparse_workspace_bytes(int B, int n, int A);
 
 extern "C" int daco_pheromone_update_heads(void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,
                                            float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,
@@ -647,15 +629,14 @@ extern "C" int daco_pheromone_update_heads(void *stream, int B, int n, int A, fl
   if (alpha != 1.0f || beta != 1.0f) { set_error("daco_pheromone_update_heads: alpha = beta = 1 only (the rows of tau are formed here; other exponents take the sampler's own pass)"); return DACO_E_BADARG; }
   const size_t need = daco_tsp_sparse_workspace_bytes(B, n, A);
   if (sparse_workspace_bytes < need) { set_error("daco_pheromone_update_heads: sparse workspace %zu < %zu bytes", sparse_workspace_bytes, need); return DACO_E_WORKSPACE; }
+  const HeadWs ws = HeadWs::carve(sparse_workspace, B, n, A);                // (the sampler's layout: dense rows, then head rows)
   HeadEmit he;
   he.eta = eta; he.eta_bs = eta_bstride; he.hid = head_id;
-  he.P = (float *)sparse_workspace;                                     // (the sampler's layout: dense rows, then head rows)
-  he.hrow = (char *)sparse_workspace + align256((size_t)B * n * (n <= 512 ? 512 : 1024) * sizeof(float));
+  he.P = ws.P; he.hrow = ws.hrow;
   he.spl = head_slots / 16; he.race = race ? 1 : 0; he.nbr_grouped = nbr_grouped ? 1 : 0;
-  const int ld = n <= 512 ? 512 : 1024;
-  he.dead = ld;
-  const bool vec4 = (n & 3) == 0 && (eta_bstride & 3) == 0 && (((uintptr_t)eta | (uintptr_t)tau) & 15) == 0;
-  he.ch = vec4 ? ld / 256 : -(ld / 256);
+  he.dead = ws.ld;
+  const bool vec4 = rows_vec4(n, tau, (long)n * n, eta, eta_bstride);
+  he.ch = vec4 ? ws.ld / 256 : -(ws.ld / 256);
   return pheromone_update_impl(stream, B, n, n, A, tau, paths, costs, decay, elitist, 1, clamp_min, clamp_max, floor_val, nbr_in, weights, 0,
                                workspace, workspace_bytes, he);
 }

@@ -51,8 +51,7 @@
 // Bookkeeping per move is wave-parallel: route ids from ballots over 64 positions at a time, one lane per route for the
 // (sequential, f64) loads and reversal sums, the new sequence gathered by all threads through a table of at most six source
 // ranges, empty routes squeezed out with ballots.
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_host.h"
 
 namespace daco {
 
@@ -430,7 +429,5 @@ extern "C" int daco_cvrp_local_search(void *stream, int B, int n, int A, int Lma
   } while (0)
   if (stage) DACO_LS_LAUNCH(true, 512); else DACO_LS_LAUNCH(false, 256);
 #undef DACO_LS_LAUNCH
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("cvrp_ls_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("cvrp_ls_kernel");
 }

@@ -13,6 +13,9 @@ namespace daco {
 // ------------------------------------------------------------------ error plumbing (host)
 void set_error(const char *fmt, ...);
 
+// every part of a workspace or table starts on a 256-byte boundary
+__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 // ------------------------------------------------------------------ candidate layout
 // A row of n candidates is dealt to the 64 lanes in vectors of VEC floats: candidate
 // k = (c*64 + lane)*VEC + v.  Rows are padded to ld = roundup(n, 64*VEC) so every lane's
@@ -37,13 +40,12 @@ __device__ inline int xcd_remap(int orig, int nwg) {
 struct NbrEntry { float d; uint32_t id; };
 
 constexpr size_t NBR_HEADER = 256;            // per-instance header: [0] bits of M = max off-diagonal |d|, [1] ~ordered(min off-diagonal d)
-__host__ __device__ inline size_t nbr_align(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ __device__ inline size_t nbr_instance_bytes(int n) {
-  return NBR_HEADER + nbr_align((size_t)n * n * sizeof(NbrEntry)) + nbr_align((size_t)n * n * sizeof(uint16_t));
+  return NBR_HEADER + align256((size_t)n * n * sizeof(NbrEntry)) + align256((size_t)n * n * sizeof(uint16_t));
 }
 __device__ inline const NbrEntry *nbr_nb(const unsigned char *tab) { return reinterpret_cast<const NbrEntry *>(tab + NBR_HEADER); }
 __device__ inline const uint16_t *nbr_rk(const unsigned char *tab, int n) {
-  return reinterpret_cast<const uint16_t *>(tab + NBR_HEADER + nbr_align((size_t)n * n * sizeof(NbrEntry)));
+  return reinterpret_cast<const uint16_t *>(tab + NBR_HEADER + align256((size_t)n * n * sizeof(NbrEntry)));
 }
 
 

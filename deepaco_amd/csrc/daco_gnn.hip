@@ -14,8 +14,8 @@
 // Activations ping-pong between two workspace buffers.  The head (3 linears, silu, silu, sigmoid)
 // chains three MFMA GEMMs per 32-edge tile with an LDS transpose between them.
 // Everything is f32 (bf16/fp16 MFMA would break 1e-5 parity through 12 residual layers).
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_gnn.h"
+#include "daco_host.h"
 
 #include <cstdlib>
 
@@ -24,16 +24,6 @@ namespace daco {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int U = 32;                       // units
 
-// ---- parameter block layout (floats), built by the host (deepaco_amd/net.py pack_params)
-// [0]               v_lin0.W [32][feats] | v_lin0.b [32]
-// then              e_lin0.W [32]        | e_lin0.b [32]
-// then 12 x layer:  WvT [32 c][128 c']  (x1|x2|x3|x4 outputs, transposed) | bv [128]
-//                   We [32 o][32 c] | be [32] | bn_v scale[32] shift[32] | bn_e scale[32] shift[32]
-// then head:        W1 [32][32] b1 [32] W2 [32][32] b2 [32] W3 [32] b3 [1]
-constexpr int LAYER_FLOATS = 32 * 128 + 128 + 32 * 32 + 32 + 4 * 32;
-__host__ __device__ inline size_t off_layer(int feats, int l) { return (size_t)32 * feats + 32 + 64 + (size_t)l * LAYER_FLOATS; }
-__host__ __device__ inline size_t off_head(int feats) { return off_layer(feats, 12); }
-constexpr int HEAD_FLOATS = 2 * (32 * 32 + 32) + 32 + 1;
 constexpr int GNN_SPLIT_MIN_EDGES = 200000;   // above this a layer is two launches (edge | node), below it one
 
 // Activations.  e^-x in six full-rate instructions instead of libm's twelve (the two activations are evaluated 2*E*32 times
@@ -132,8 +122,7 @@ __device__ inline f32x16 tile_gemm(const float *row, const float *Wm, int lane) 
   for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bw[kk], acc, 0, 0, 0);
   return acc;
 }
-// MFMA 32x32 output layout: register r of lane l holds D[row][col], col = l & 31,
-__device__ inline int drow(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+// MFMA 32x32 output layout: register r of lane l holds D[row][col], col = l & 31, row = drow(r, l) (daco_gnn.h)
 
 // ---------------- edge update: 4 waves, one 32-edge tile each.
 // The MFMA result (lane = channel, 16 edge rows per lane) is turned through a wave-private LDS tile
@@ -924,8 +913,6 @@ gnn_head_kernel(int E, int feats, const float *params, const float *w, float *he
 
 using namespace daco;
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" size_t daco_gnn_param_floats(int feats) { return off_head(feats) + HEAD_FLOATS; }
 
 extern "C" size_t daco_gnn_workspace_bytes(int n, int E) {
@@ -1010,7 +997,5 @@ extern "C" int daco_gnn_forward(void *stream, int n, int E, int feats, const flo
   // (a head that walks several tiles per wave with the next rows in flight, W1 / W2 in LDS, was measured: 139 us against
   // this kernel's 131 at 64 x TSP-500 -- not kept)
   if (!head_fused) hipLaunchKernelGGL(gnn_head_kernel, dim3(edge_blocks), dim3(256), 0, s, E, feats, params, wb[wcur], heu);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("gnn kernels launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("gnn kernels");
 }

@@ -26,22 +26,18 @@
 // slots holding d/dgamma, d/dbeta.
 #include <cstdlib>
 
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_gnn.h"
+#include "daco_host.h"
 
 namespace daco {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int TU = 32;
-constexpr int T_LAYER_FLOATS = 32 * 128 + 128 + 32 * 32 + 32 + 4 * 32;
 constexpr float BN_EPS = 1e-5f;
-__host__ __device__ inline size_t t_off_layer(int feats, int l) { return (size_t)32 * feats + 32 + 64 + (size_t)l * T_LAYER_FLOATS; }
-__host__ __device__ inline size_t t_off_head(int feats) { return t_off_layer(feats, 12); }
 
 __device__ inline float t_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + expf(-x)); }
 __device__ inline float t_silu(float x) { return x * t_sigmoid(x); }
 __device__ inline float t_dsilu(float x) { const float s = t_sigmoid(x); return s * (1.0f + x * (1.0f - s)); }
-__device__ inline int t_drow(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // D[i][j] += sum_k A[i][k] * B[k][j] over k = 0..31 with v_mfma_f32_32x32x2_f32; lane l supplies A[l%32][k] and
 // B[k][l%32] for k = (l/32)*16 + kk.  a(kk) / b(kk) are functors returning those elements.
@@ -129,7 +125,7 @@ gnn_t_edge_pre(int E, int Eg, const int *src, const int *dst, const float *We, c
                             [&](int kk) { const float4 w4 = wev[kk >> 2]; return (kk & 3) == 0 ? w4.x : (kk & 3) == 1 ? w4.y : (kk & 3) == 2 ? w4.z : w4.w; });
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
-  for (int r = 0; r < 16; ++r) tile[t_drow(r, lane)][o] = acc[r];
+  for (int r = 0; r < 16; ++r) tile[drow(r, lane)][o] = acc[r];
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -266,7 +262,7 @@ gnn_t_node_init(int n, int feats, const float *xin, const float *params, float *
   xs[il][o] = v;
   __syncthreads();
   if (i >= n) return;
-  const float *WT = params + t_off_layer(feats, 0), *bv = WT + 32 * 128;
+  const float *WT = params + off_layer(feats, 0), *bv = WT + 32 * 128;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     float acc = bv[q * 32 + o];
@@ -302,12 +298,12 @@ gnn_t_head_fwd(int E, const float *hp, const float *w, float *heu) {
   f32x16 acc = mfma32(ZERO16, [&](int kk) { return t[o][h * 16 + kk]; }, [&](int kk) { return W1[o * TU + h * 16 + kk]; });
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
-  for (int r = 0; r < 16; ++r) t[t_drow(r, lane)][o] = t_silu(acc[r] + b1[o]);
+  for (int r = 0; r < 16; ++r) t[drow(r, lane)][o] = t_silu(acc[r] + b1[o]);
   __builtin_amdgcn_wave_barrier();
   acc = mfma32(ZERO16, [&](int kk) { return t[o][h * 16 + kk]; }, [&](int kk) { return W2[o * TU + h * 16 + kk]; });
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
-  for (int r = 0; r < 16; ++r) t[t_drow(r, lane)][o] = t_silu(acc[r] + b2[o]) * W3[o];
+  for (int r = 0; r < 16; ++r) t[drow(r, lane)][o] = t_silu(acc[r] + b2[o]) * W3[o];
   __builtin_amdgcn_wave_barrier();
   if (lane < 32) {
     float s = 0.0f;
@@ -326,10 +322,10 @@ __device__ inline void flush_acc(float *dstM, const f32x16 &acc, int lane) {
   float t = 0.0f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) t += acc[r];
-  unsafeAtomicAdd(dstM + t_drow(0, lane) * TU + j, t);
+  unsafeAtomicAdd(dstM + drow(0, lane) * TU + j, t);
 #else
 #pragma unroll
-  for (int r = 0; r < 16; ++r) unsafeAtomicAdd(dstM + t_drow(r, lane) * TU + j, acc[r]);
+  for (int r = 0; r < 16; ++r) unsafeAtomicAdd(dstM + drow(r, lane) * TU + j, acc[r]);
 #endif
 }
 
@@ -345,7 +341,7 @@ __device__ inline void flush_acc_wg(float *dstM, const f32x16 &acc, float *red) 
   for (int i = tid; i < 1024; i += 256) red[i] = 0.0f;
   __syncthreads();
 #pragma unroll
-  for (int r = 0; r < 16; ++r) atomicAdd(&red[t_drow(r, lane) * TU + j], acc[r]);
+  for (int r = 0; r < 16; ++r) atomicAdd(&red[drow(r, lane) * TU + j], acc[r]);
   __syncthreads();
   for (int i = tid; i < 1024; i += 256) unsafeAtomicAdd(dstM + i, red[i]);
   __syncthreads();
@@ -393,14 +389,14 @@ gnn_t_head_bwd(int E, const float *hp, const float *w, const float *heu, const f
       win[q] = *reinterpret_cast<const float4 *>(w + (size_t)e * TU + c0);
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { const int e = min(e0 + t_drow(r, lane), E - 1); hvr[r] = heu[e]; ghr[r] = gheu[e]; }
+    for (int r = 0; r < 16; ++r) { const int e = min(e0 + drow(r, lane), E - 1); hvr[r] = heu[e]; ghr[r] = gheu[e]; }
 #pragma unroll
     for (int q = 0; q < 4; ++q) *reinterpret_cast<float4 *>(&tin[q * 8 + (lane >> 3)][c0]) = win[q];
     __builtin_amdgcn_wave_barrier();
     // a1 = w W1^T + b1 -> ta (pre-activation), h1 = silu(a1) -> tg (temporarily)
     f32x16 acc = mfma32(ZERO16, [&](int kk) { return tin[o][h * 16 + kk]; }, [&](int kk) { return w1r[kk]; });
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { const float a = acc[r] + b1o; ta[t_drow(r, lane)][o] = a; tg[t_drow(r, lane)][o] = t_silu(a); }
+    for (int r = 0; r < 16; ++r) { const float a = acc[r] + b1o; ta[drow(r, lane)][o] = a; tg[drow(r, lane)][o] = t_silu(a); }
     __builtin_amdgcn_wave_barrier();
     // a2 = h1 W2^T + b2; h2 = silu(a2); gs = gheu * heu * (1 - heu) per edge
     acc = mfma32(ZERO16, [&](int kk) { return tg[o][h * 16 + kk]; }, [&](int kk) { return w2r[kk]; });
@@ -408,7 +404,7 @@ gnn_t_head_bwd(int E, const float *hp, const float *w, const float *heu, const f
     float a2r[16], gsr[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int e = e0 + t_drow(r, lane);
+      const int e = e0 + drow(r, lane);
       float gs = 0.0f;
       if (e < E) { const float hv = hvr[r]; gs = ghr[r] * hv * (1.0f - hv); }
       a2r[r] = acc[r] + b2o; gsr[r] = gs;
@@ -432,7 +428,7 @@ gnn_t_head_bwd(int E, const float *hp, const float *w, const float *heu, const f
     for (int q = 0; q < 4; ++q) wsave[q] = *reinterpret_cast<const float4 *>(&tin[q * 8 + (lane >> 3)][c0]);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tin[t_drow(r, lane)][o] = ga2[r];                 // tin := g_a2 [edge][ch]
+    for (int r = 0; r < 16; ++r) tin[drow(r, lane)][o] = ga2[r];                 // tin := g_a2 [edge][ch]
     __builtin_amdgcn_wave_barrier();
     aW2 = mfma32(aW2, [&](int kk) { return tin[h * 16 + kk][o]; }, [&](int kk) { return tg[h * 16 + kk][o]; });
     // g_h1 = g_a2 W2 : D[e][c] = sum_o g_a2[e][o] W2[o][c]
@@ -440,7 +436,7 @@ gnn_t_head_bwd(int E, const float *hp, const float *w, const float *heu, const f
     __builtin_amdgcn_wave_barrier();
     // g_a1 = g_h1 * dsilu(a1) -> tg
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { const float g = acc[r] * t_dsilu(ta[t_drow(r, lane)][o]); tg[t_drow(r, lane)][o] = g; ab1 += g; }
+    for (int r = 0; r < 16; ++r) { const float g = acc[r] * t_dsilu(ta[drow(r, lane)][o]); tg[drow(r, lane)][o] = g; ab1 += g; }
     __builtin_amdgcn_wave_barrier();
     // restore the w tile, gW1 += g_a1^T w, gw = g_a1 W1
 #pragma unroll
@@ -450,7 +446,7 @@ gnn_t_head_bwd(int E, const float *hp, const float *w, const float *heu, const f
     acc = mfma32(ZERO16, [&](int kk) { return tg[o][h * 16 + kk]; }, [&](int kk) { return w1c[kk]; });
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) ta[t_drow(r, lane)][o] = acc[r];
+    for (int r = 0; r < 16; ++r) ta[drow(r, lane)][o] = acc[r];
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -662,7 +658,7 @@ gnn_t_edge_bwd(int E, int Eg, const int *src, const int *dst, const float *We, c
     const f32x16 acc = mfma32(ZERO16, [&](int kk) { return tg[o][h * 16 + kk]; }, [&](int kk) { return wecol[kk]; });
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tw[t_drow(r, lane)][o] = acc[r];
+    for (int r = 0; r < 16; ++r) tw[drow(r, lane)][o] = acc[r];
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -822,7 +818,7 @@ gnn_t_node_lin_bwd(int n, const float *WT, const float *x0, const float *gX, flo
     }
     float gold[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { const int i = i0 + t_drow(r, lane); gold[r] = gx[(size_t)(i < n ? i : n - 1) * TU + o]; }
+    for (int r = 0; r < 16; ++r) { const int i = i0 + drow(r, lane); gold[r] = gx[(size_t)(i < n ? i : n - 1) * TU + o]; }
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -850,7 +846,7 @@ gnn_t_node_lin_bwd(int n, const float *WT, const float *x0, const float *gX, flo
                    [&](int kk) { const float4 w4 = wv[q][kk >> 2]; return (kk & 3) == 0 ? w4.x : (kk & 3) == 1 ? w4.y : (kk & 3) == 2 ? w4.z : w4.w; });
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = i0 + t_drow(r, lane);
+      const int i = i0 + drow(r, lane);
       if (i < n) gx[(size_t)i * TU + o] = gold[r] + acc[r];
     }
     __builtin_amdgcn_wave_barrier();
@@ -862,7 +858,7 @@ gnn_t_node_lin_bwd(int n, const float *WT, const float *x0, const float *gX, flo
   for (int q = 0; q < 4; ++q) {
     const int j = lane & 31;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) unsafeAtomicAdd(gWT + t_drow(r, lane) * 128 + q * 32 + j, aW[q][r]);
+    for (int r = 0; r < 16; ++r) unsafeAtomicAdd(gWT + drow(r, lane) * 128 + q * 32 + j, aW[q][r]);
     unsafeAtomicAdd(gbv + q * 32 + o, ab[q]);
   }
 }
@@ -937,8 +933,6 @@ __global__ void gnn_t_export_stats(int G, int count_e, int count_v, const double
   out[(size_t)idx * 2 + 1] = (float)(v < 0.0 ? 0.0 : v);
 }
 
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct TrainWs {
   float *a0, *x[13], *X[12], *w[13], *ze[12], *zv[12];
   double *fsums;   // [12][2][G][32][2]
@@ -954,7 +948,7 @@ struct TrainWs {
 static TrainWs carve(void *base, int n, int E, int G) {
   TrainWs t;
   char *p = (char *)base;
-  auto take = [&](size_t bytes) { char *r = p; p += al256(bytes); return r; };
+  auto take = [&](size_t bytes) { char *r = p; p += align256(bytes); return r; };
   t.a0 = (float *)take((size_t)n * 32 * 4);
   for (int l = 0; l <= 12; ++l) t.x[l] = (float *)take((size_t)n * 32 * 4);
   for (int l = 0; l < 12; ++l) t.X[l] = (float *)take((size_t)n * 128 * 4);
@@ -1011,7 +1005,7 @@ extern "C" int daco_gnn_train_forward(void *stream, int n, int E, int feats, int
   hipLaunchKernelGGL(gnn_t_node_init, dim3(node_blocks), dim3(256), 0, s, n, feats, x, params, t.a0, t.x[0], t.X[0]);
   hipLaunchKernelGGL(gnn_t_edge_init, dim3(ew_blocks), dim3(256), 0, s, E, feats, edge_attr, params, t.w[0]);
   for (int l = 0; l < 12; ++l) {
-    const float *lp = params + t_off_layer(feats, l);
+    const float *lp = params + off_layer(feats, l);
     const float *We = lp + 32 * 128 + 128, *be = We + 1024, *gv = be + 32, *bv_ = gv + 32, *ge = bv_ + 32, *bee = ge + 32;
     double *fe = t.fsums + ((size_t)l * 2 + 0) * G * 64, *fv = t.fsums + ((size_t)l * 2 + 1) * G * 64;
     float2 *fte = t.ftab + ((size_t)l * 2 + 0) * G * 32, *ftv = t.ftab + ((size_t)l * 2 + 1) * G * 32;
@@ -1024,16 +1018,14 @@ extern "C" int daco_gnn_train_forward(void *stream, int n, int E, int feats, int
       hipLaunchKernelGGL(gnn_t_stat_table, dim3(tb), dim3(256), 0, s, G, Eg, ng, fe, fte, 0);      // (fv / ftv follow fe / fte)
     }
     hipLaunchKernelGGL(gnn_t_edge_post, dim3(ew_blocks), dim3(256), 0, s, E, Eg, ge, bee, fte, t.w[l], t.ze[l], t.w[l + 1]);
-    const float *WTn = l < 11 ? params + t_off_layer(feats, l + 1) : nullptr;
+    const float *WTn = l < 11 ? params + off_layer(feats, l + 1) : nullptr;
     hipLaunchKernelGGL(gnn_t_node_post, dim3(node_blocks), dim3(256), 0, s, n, ng, gv, bv_, ftv, t.x[l], t.zv[l], t.x[l + 1], WTn,
                        WTn ? WTn + 32 * 128 : nullptr, l < 11 ? t.X[l + 1] : nullptr);
   }
-  hipLaunchKernelGGL(gnn_t_head_fwd, dim3(tile_blocks), dim3(256), 0, s, E, params + t_off_head(feats), t.w[12], heu);
+  hipLaunchKernelGGL(gnn_t_head_fwd, dim3(tile_blocks), dim3(256), 0, s, E, params + off_head(feats), t.w[12], heu);
   if (stats_out)
     hipLaunchKernelGGL(gnn_t_export_stats, dim3((12 * 2 * G * 32 + 255) / 256), dim3(256), 0, s, G, Eg, ng, t.fsums, stats_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("gnn train forward launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("gnn train forward");
 }
 
 extern "C" int daco_gnn_train_backward(void *stream, int n, int E, int feats, int G, const float *x, const int32_t *src,
@@ -1051,7 +1043,7 @@ extern "C" int daco_gnn_train_backward(void *stream, int n, int E, int feats, in
   const int etiles = (E + 31) / 32, ntiles = (n + 31) / 32;
   // (at most one workgroup per CU: the waves walk more tiles, and fewer workgroups add into the same words of the gradient)
   const int egrid = etiles / 4 + 1 < 256 ? etiles / 4 + 1 : 256, ngrid = ntiles / 4 + 1 < 512 ? ntiles / 4 + 1 : 512;
-  const size_t pfloats = t_off_head(feats) + 2 * (1024 + 32) + 32 + 1;
+  const size_t pfloats = off_head(feats) + HEAD_FLOATS;
   // (kernels, not memset nodes: daco_device.h zero_async)
   if (zero_async(grad_params, pfloats * 4, s) != hipSuccess || zero_async(t.gx, (size_t)n * 32 * 4, s) != hipSuccess ||
       zero_async(t.bsums, (size_t)12 * 2 * G * 64 * 8, s) != hipSuccess) { set_error("zero fill failed"); return DACO_E_HIP; }
@@ -1069,12 +1061,12 @@ extern "C" int daco_gnn_train_backward(void *stream, int n, int E, int feats, in
     rowptr_dst = t.csr_rowptr;
     perm_dst = t.csr_perm;
   }
-  hipLaunchKernelGGL(gnn_t_head_bwd, dim3(egrid), dim3(256), 0, s, E, params + t_off_head(feats), t.w[12], heu, grad_heu, t.gw,
-                     grad_params + t_off_head(feats));
+  hipLaunchKernelGGL(gnn_t_head_bwd, dim3(egrid), dim3(256), 0, s, E, params + off_head(feats), t.w[12], heu, grad_heu, t.gw,
+                     grad_params + off_head(feats));
   for (int l = 11; l >= 0; --l) {
-    const float *lp = params + t_off_layer(feats, l);
+    const float *lp = params + off_layer(feats, l);
     const float *WT = lp, *We = lp + 32 * 128 + 128, *gv = We + 1024 + 32, *bv_ = gv + 32, *ge = bv_ + 32, *bee = ge + 32;
-    float *glp = grad_params + t_off_layer(feats, l);
+    float *glp = grad_params + off_layer(feats, l);
     float *gWT = glp, *gbv = glp + 32 * 128, *gWe = gbv + 128, *gbe = gWe + 1024, *ggv = gbe + 32, *gbv_ = ggv + 32, *gge = gbv_ + 32, *gbee = gge + 32;
     double *be_s = t.bsums + (size_t)l * 2 * G * 64, *bv_s = be_s + (size_t)G * 64;
     // the gather path pays four small CSR kernels per call and one gather launch per layer: it wins from ~100 k edges
@@ -1107,7 +1099,5 @@ extern "C" int daco_gnn_train_backward(void *stream, int n, int E, int feats, in
   // (at most 128 workgroups: each adds once into the same 64 words, and the adds to one word are serial)
   hipLaunchKernelGGL(gnn_t_edge_init_bwd, dim3(E / 64 + 1 < 128 ? E / 64 + 1 : 128), dim3(256), 0, s, E, edge_attr, W0e, W0e + 32, t.gw,
                      grad_params + 32 * feats + 32, grad_params + 32 * feats + 64);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("gnn train backward launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("gnn train backward");
 }

@@ -7,8 +7,7 @@
 // is one launch for B instances: one wavefront per node builds its distance row (kept in registers,
 // lane l owns columns l, l+64, ...) and extracts the k nearest by k rounds of a wave arg-min
 // (ties -> smaller index).  Output order = ascending distance, like topk's sorted result.
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_host.h"
 
 namespace daco {
 
@@ -110,9 +109,7 @@ static int knn_graph_launch(const char *what, void *stream, int B, int n, int k,
   else if (cpl <= 32) DACO_KNN(32);
   else DACO_KNN(64);
 #undef DACO_KNN
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("knn_graph_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("knn_graph_kernel");
 }
 
 extern "C" int daco_tsp_knn_graph(void *stream, int B, int n, int k, const float *coords, float diag, float *dist,
@@ -142,7 +139,5 @@ extern "C" int daco_heu_matrix(void *stream, int B, int n, int E, const int64_t 
   if (E > 0)                                                // (the scatter follows the fill on the same stream)
     hipLaunchKernelGGL(heu_scatter_kernel, dim3((unsigned)(((size_t)B * E + 255) / 256)), dim3(256), 0, s, B, n, E, edge_index, heu, add,
                        out, bad);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("daco_heu_matrix launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("daco_heu_matrix");
 }

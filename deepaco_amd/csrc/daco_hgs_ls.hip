@@ -22,8 +22,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "../../include/deepaco_hip.h"
-#include "daco_device.h"
+#include "daco_host.h"
 
 namespace daco {
 
@@ -45,7 +44,7 @@ struct HgsLayout {
     off = len + a16(2 * (size_t)n);
     ent = off + a16(4 * (size_t)n);
     bits = ent + a16(2 * (size_t)2 * g * nc);
-    total = (bits + a16(4 * (size_t)n * words) + 255) & ~(size_t)255;
+    total = align256(bits + a16(4 * (size_t)n * words));
   }
 };
 struct HgsHeader { double maxDist; uint32_t rng_state; uint32_t entries; };
@@ -899,9 +898,7 @@ extern "C" int daco_hgs_prepare(void *stream, int B, int n, const double *matrix
   }
   hipLaunchKernelGGL(hgs_prepare_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, n, nb_granular, matrix, bstride,
                      (unsigned char *)tables, HgsLayout(n, nb_granular).total);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("hgs_prepare_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("hgs_prepare_kernel");
 }
 
 // wavefronts per SIMD the kernel is compiled for: 168 registers.  Measured at CVRP-100 x 512 ants: two (198 registers) 232 k, three
@@ -986,9 +983,7 @@ extern "C" int daco_hgs_local_search(void *stream, int B, int n, int A, int Lmax
       // (the scratch stride was sized for hgs_grid's wavefronts: one wavefront per workgroup here, never more workgroups than that)
       const long lm_grid = items < (long)grid * waves ? items : (long)grid * waves;
       hipLaunchKernelGGL((hgs_ls_kernel<1, 1, true>), dim3((unsigned)lm_grid), dim3(64), lm_lds, st, p);
-      e = hipGetLastError();
-      if (e != hipSuccess) { set_error("hgs_ls_kernel (latency mode) launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-      return DACO_OK;
+      return launch_status("hgs_ls_kernel (latency mode)");
     }
   }
 #define DACO_HGS_LAUNCH(W_, S_)                                                                                                   \
@@ -1003,7 +998,5 @@ extern "C" int daco_hgs_local_search(void *stream, int B, int n, int A, int Lmax
   else if (waves == 2) DACO_HGS_LAUNCH(2, HGS_WPS);
   else DACO_HGS_LAUNCH(1, HGS_WPS);
 #undef DACO_HGS_LAUNCH
-  e = hipGetLastError();
-  if (e != hipSuccess) { set_error("hgs_ls_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("hgs_ls_kernel");
 }

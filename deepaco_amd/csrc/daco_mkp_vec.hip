@@ -464,8 +464,7 @@ extern "C" int daco_mkpv_sample(void *stream, int B, int n, int A, int m, const 
   p.sols = sols; p.lens = lens; p.logp = logp; p.rowsum = rowsum; p.objs = price ? objs : nullptr; p.flags = flags;
   hipStream_t s = (hipStream_t)stream;
   const hipError_t e = n <= 256 ? launch_mkpv_sample<1>(p, mode, s) : (n <= 512 ? launch_mkpv_sample<2>(p, mode, s) : launch_mkpv_sample<4>(p, mode, s));
-  if (e != hipSuccess) { set_error("mkpv_sample_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status(e, "mkpv_sample_kernel");
 }
 
 extern "C" int daco_mkpv_backward(void *stream, int B, int n, int A, int m, int rows, const float *tau, long tau_bstride,
@@ -487,9 +486,7 @@ extern "C" int daco_mkpv_backward(void *stream, int B, int n, int A, int m, int 
   if (CH == 1) hipLaunchKernelGGL(mkpv_backward_kernel<1>, grid, block, dyn, s, p);
   else if (CH == 2) hipLaunchKernelGGL(mkpv_backward_kernel<2>, grid, block, dyn, s, p);
   else hipLaunchKernelGGL(mkpv_backward_kernel<4>, grid, block, dyn, s, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("mkpv_backward_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("mkpv_backward_kernel");
 }
 
 extern "C" int daco_mkpv_update(void *stream, int B, int n, int A, int rows, const int64_t *sols, const int32_t *lens,
@@ -505,7 +502,5 @@ extern "C" int daco_mkpv_update(void *stream, int B, int n, int A, int rows, con
   p.B = B; p.n = n; p.A = A; p.rows = rows; p.sols = sols; p.lens = lens; p.objs = objs; p.Q = Q; p.decay = decay;
   p.elitist = elitist; p.min_max = min_max; p.tmin = tmin; p.tmax = tmax; p.tau = tau; p.best_obj = best_obj; p.best_sol = best_sol;
   hipLaunchKernelGGL(mkpv_update_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("mkpv_update_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("mkpv_update_kernel");
 }

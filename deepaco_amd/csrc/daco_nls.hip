@@ -27,8 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_host.h"
 
 namespace daco {
 
@@ -517,6 +516,5 @@ extern "C" int daco_tsp_nls(void *stream, int B, int T, int n, const float *dist
             "wait %.3f reduce %.3f apply %.3f | cycles per tour %.0f, evaluation rounds per tour %.1f\n", B * T, h[0] / tot, h[1] / tot,
             h[2] / tot, h[3] / tot, h[4] / tot, h[5] / tot, h[6] / tot, tot / (B * T), (double)h[7] / (B * T));
   }
-  if (e != hipSuccess) { set_error("nls_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status(e, "nls_kernel");
 }

@@ -257,14 +257,12 @@ extern "C" int daco_rcpsp_schedule(void *stream, int B, int n, int A, int R, int
     return DACO_E_BADARG;
   }
   const RcpspDev q = rcpsp_dev(R, horizon, E, duration, resources, capacity, earliest_start, latest_start, succ_ptr, succ_idx, starts, costs);
-  const hipError_t e = launch_schedule(q, B, n, A, routes, flags, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error("rcpsp_schedule_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status(launch_schedule(q, B, n, A, routes, flags, (hipStream_t)stream), "rcpsp_schedule_kernel");
 }
 
 extern "C" size_t daco_rcpsp_workspace_bytes(int B, int n) {
   if (B <= 0 || n < 2 || n > DACO_RCPSP_MAX_N) return 0;
-  return 5 * align256((size_t)B * n * ld_alloc(n) * sizeof(float));     // P | 1/P | adjacency | tau | eta^beta, padded rows
+  return RcpspWs::bytes(B, n);
 }
 
 extern "C" int daco_rcpsp_sample(void *stream, int B, int n, int A, int R, int horizon, int E, const int32_t *duration,
@@ -292,42 +290,33 @@ extern "C" int daco_rcpsp_sample(void *stream, int B, int n, int A, int R, int h
   if (workspace_bytes < need) { set_error("daco_rcpsp_sample: workspace %zu < %zu bytes", workspace_bytes, need); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
   const int vec = vec_for_n(n), ld = ld_alloc(n);
-  const size_t mat = need / 5;
-  float *P = (float *)workspace, *Rm = (float *)((char *)workspace + mat), *adjp = (float *)((char *)workspace + 2 * mat);
-  float *taup = (float *)((char *)workspace + 3 * mat), *etab = (float *)((char *)workspace + 4 * mat);
+  const RcpspWs ws = RcpspWs::carve(workspace, B, n);
+  float *const Rm = mode == DACO_RACE_PHILOX ? ws.R : nullptr;
   const long total = (long)B * n * ld;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
-  launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, P, mode == DACO_RACE_PHILOX ? Rm : nullptr, s);
-  hipLaunchKernelGGL(pad_matrix_kernel<0>, dim3(blocks), dim3(256), 0, s, B, n, ld, adjacency, (long)n * n, adjp, 0.0f);
+  launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, ws.P, Rm, s);
+  hipLaunchKernelGGL(pad_matrix_kernel<0>, dim3(blocks), dim3(256), 0, s, B, n, ld, adjacency, (long)n * n, ws.adj, 0.0f);
   if (rule != 0) {                                      // x^1 = x and x^0 = 1 exactly (pw): tau itself and eta^beta, padded
-    launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, 1.0f, 0.0f, taup, nullptr, s);
-    launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, 0.0f, beta, etab, nullptr, s);
+    launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, 1.0f, 0.0f, ws.tau, nullptr, s);
+    launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, 0.0f, beta, ws.etab, nullptr, s);
   }
-  SampleParams sp;
-  sp.B = B; sp.n = n; sp.A = A; sp.ld = ld; sp.CH = 1;
-  sp.P = P; sp.R = mode == DACO_RACE_PHILOX ? Rm : nullptr; sp.norm_passes = 1; sp.start = nullptr; sp.fixed_start = 0;
-  sp.noise = noise; sp.seed = seed; sp.iter = iter; sp.iter_dev = nullptr; sp.ant_gid0 = ant_gid0; sp.gid_bstride = 0;
-  sp.paths = routes; sp.logp = logp; sp.rowsum = rowsum; sp.flags = flags;
-  sp.dist = nullptr; sp.dist_bs = 0; sp.costs = nullptr; sp.nbr = nullptr; sp.hubmask = nullptr; sp.tab_lens = nullptr;
-  sp.demand = nullptr; sp.capacity = 0.0f; sp.demand64 = nullptr; sp.capacity64 = 0.0; sp.Lmax = n; sp.noise_steps = n - 1; sp.lens = nullptr;
-  sp.mask = nullptr; sp.step = 0;
-  sp.aux_vec = indegree; sp.aux_mat = adjp; sp.scalar0 = 0.0f; sp.wts = nullptr; sp.m = 0;
+  if (const int rc = launch_status("prob_matrix_kernel / pad_matrix_kernel")) return rc;
+  SampleParams sp = sample_params(B, n, A, ld, 1, ws.P, Rm, noise, seed, iter, ant_gid0, routes, logp, rowsum, flags);
+  sp.norm_passes = 1; sp.Lmax = n; sp.noise_steps = n - 1;
+  sp.aux_vec = indegree; sp.aux_mat = ws.adj;
   sp.alpha = alpha; sp.beta = beta;
   sp.rc = rcpsp_dev(R, horizon, E, duration, resources, capacity, earliest_start, latest_start, succ_ptr, succ_idx, starts, costs);
-  sp.rc.rule = rule; sp.rc.gamma = g32; sp.rc.cdir = cdir; sp.rc.csum = csum; sp.rc.taup = taup; sp.rc.etab = etab;
+  sp.rc.rule = rule; sp.rc.gamma = g32; sp.rc.cdir = cdir; sp.rc.csum = csum; sp.rc.taup = ws.tau; sp.rc.etab = ws.etab;
   const size_t dyn4 = 4 * rcpsp_wave_lds(n, R, horizon);
   sp.rc.fused = dyn4 <= RCPSP_LDS_PLAIN;
   const size_t dyn = sp.rc.fused ? dyn4 : 0;
   const bool lp = logp != nullptr;
   hipError_t e = vec == 1 ? launch_rcpsp_sample<1>(sp, mode, lp, dyn, s)
                : (vec == 2 ? launch_rcpsp_sample<2>(sp, mode, lp, dyn, s) : launch_rcpsp_sample<4>(sp, mode, lp, dyn, s));
-  if (e != hipSuccess) { set_error("rcpsp construction kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  if (!sp.rc.fused) {
-    e = launch_schedule(sp.rc, B, n, A, routes, flags, s);
-    if (e != hipSuccess) { set_error("rcpsp_schedule_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  }
-  return DACO_OK;
+  if (const int rc = launch_status(e, "rcpsp construction kernel")) return rc;
+  if (sp.rc.fused) return DACO_OK;
+  return launch_status(launch_schedule(sp.rc, B, n, A, routes, flags, s), "rcpsp_schedule_kernel");
 }
 
 extern "C" int daco_rcpsp_backward(void *stream, int B, int n, int A, const float *indegree, const float *adjacency,
@@ -344,9 +333,7 @@ extern "C" int daco_rcpsp_backward(void *stream, int B, int n, int A, const floa
   if (!rcpsp_rule(gamma, c, &rule, &g32, &cdir, &csum)) { set_error("daco_rcpsp_backward: gamma >= 0 and 0 <= c <= 1 required"); return DACO_E_BADARG; }
   hipLaunchKernelGGL(rcpsp_backward_kernel, dim3((unsigned)(B * ((A + 3) / 4))), dim3(256), 0, (hipStream_t)stream, B, n, A, indegree,
                      adjacency, tau, tau_bstride, eta, eta_bstride, alpha, beta, rule, g32, cdir, csum, routes, rowsum, grad_logp, grad_eta);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("rcpsp_backward_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("rcpsp_backward_kernel");
 }
 
 extern "C" int daco_rcpsp_track(void *stream, int B, int n, int A, const int64_t *routes, const int32_t *starts, const int32_t *costs,
@@ -361,7 +348,5 @@ extern "C" int daco_rcpsp_track(void *stream, int B, int n, int A, const int64_t
   hipLaunchKernelGGL(rcpsp_track_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, n, A, routes, starts, costs, Q, elitist,
                      alias, tmin, best_cost, best_idx, best_route, best_schedule, upd_routes, upd_weights,
                      min_max ? clamp_min : nullptr, min_max ? clamp_max : nullptr);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("rcpsp_track_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("rcpsp_track_kernel");
 }

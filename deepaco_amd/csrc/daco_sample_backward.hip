@@ -16,8 +16,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_host.h"
 
 namespace daco {
 
@@ -310,9 +309,7 @@ extern "C" int daco_sibling_backward(void *stream, int kind, int B, int n, int A
     case DACO_SIB_MKP: hipLaunchKernelGGL(sibling_backward_kernel<DACO_SIB_MKP>, grid, block, 0, s, sp); break;
     default: set_error("daco_sibling_backward: unknown kind %d", kind); return DACO_E_BADARG;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("sibling_backward_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("sibling_backward_kernel");
 }
 
 
@@ -340,7 +337,5 @@ extern "C" int daco_sample_backward(void *stream, int B, int n, int A, int rows,
   dim3 grid((unsigned)(B * ((A + 3) / 4) * segs)), block(256);
   if (cvrp) hipLaunchKernelGGL(sample_backward_kernel<true>, grid, block, 0, (hipStream_t)stream, bp);
   else hipLaunchKernelGGL(sample_backward_kernel<false>, grid, block, 0, (hipStream_t)stream, bp);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("sample_backward_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("sample_backward_kernel");
 }

@@ -6,9 +6,8 @@
 #include <type_traits>
 #include <utility>
 
-#include "daco_device.h"
+#include "daco_host.h"
 #include "daco_rcpsp.h"
-#include "../../include/deepaco_hip.h"
 
 namespace daco {
 
@@ -64,6 +63,17 @@ struct SampleParams {
   int lh_kl = 0, lh_kmax = 0;        // scan_sparse, LDS-heads variant: lane records per row kept in LDS, the caller's bound of live slots per row
   RcpspDev rc;                       // PROB_RCPSP (daco_rcpsp.hip): the project, the evaluation rule, the decoder's outputs
 };
+
+// What every sampler sets: sizes, the probability rows, the RNG words, the outputs.  Every other field is zero / null (or the
+// default written above); an entry point then assigns only what its problem uses.
+inline SampleParams sample_params(int B, int n, int A, int ld, int CH, const float *P, const float *R, const float *noise, uint64_t seed,
+                                  uint64_t iter, uint32_t ant_gid0, int64_t *paths, float *logp, float *rowsum, int32_t *flags) {
+  SampleParams sp{};
+  sp.B = B; sp.n = n; sp.A = A; sp.ld = ld; sp.CH = CH;
+  sp.P = P; sp.R = R; sp.noise = noise; sp.seed = seed; sp.iter = iter; sp.ant_gid0 = ant_gid0;
+  sp.paths = paths; sp.logp = logp; sp.rowsum = rowsum; sp.flags = flags;
+  return sp;
+}
 
 template <class F, int... I>
 __device__ inline void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
@@ -689,17 +699,6 @@ static hipError_t dispatch_sample(const SampleParams &sp, int vec, int CH, int m
     default: return launch_sample<4, 16, CVRP>(sp, mode, lp, s);
   }
 }
-
-// chunks per lane actually instantiated (compile-time loop bounds): the row is padded with
-// zeros up to the next instantiated size; zero padding never changes a sum or a draw.
-inline int inst_chunks(int n) {
-  const int vec = vec_for_n(n), need = ld_for_n(n) / (64 * vec);
-  static const int avail[] = {1, 2, 3, 4, 6, 8, 12, 16};
-  for (int c : avail) if (c >= need) return c;
-  return -1;
-}
-inline int ld_alloc(int n) { return inst_chunks(n) * 64 * vec_for_n(n); }
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- shared by the several-ants-per-wavefront kernels (daco_tsp_scan32.hip, daco_scan16.hip)
 constexpr int FCMP_OLT = 4;   // LLVM predicate for __builtin_amdgcn_fcmpf

@@ -795,28 +795,11 @@ pow_pair_kernel(long count_t, const float *tau, float alpha, float *tau_out, lon
   if (i < count_e) eta_out[i] = pw(eta[i], beta);
 }
 
-// workspace: the dense rows P [B][n][ld], the head rows (daco_pheromone_update_heads writes both), then the u16 tours [B][A][ld]
-// (n > 512: as they are built; n <= 512: written by a call that asks for no int64 paths)
-extern "C" size_t daco_tsp_sparse_tours_offset(int B, int n, int A) {
-  if (B <= 0 || A <= 0 || n <= 128 || n > 1024) return 0;
-  const int ld = n <= 512 ? 512 : 1024;                  // (the row walks of the kernel's two instantiations read 512 / 1024 candidates)
-  return align256((size_t)B * n * ld * sizeof(float)) + align256((size_t)B * n * sp_head_row_bytes(SP_KH_MAX / 16));
-}
-extern "C" size_t daco_tsp_sparse_workspace_bytes(int B, int n, int A) {
-  if (B <= 0 || A <= 0 || n <= 128 || n > 1024) return 0;
-  const int ld = n <= 512 ? 512 : 1024;
-  return daco_tsp_sparse_tours_offset(B, n, A) + align256(((size_t)B * A + 16) * ld * sizeof(uint16_t));
-}
-
-// ... and, for exponents other than 1, tau^alpha [B][n][n] and eta^beta [B or 1][n][n] behind it
-extern "C" size_t daco_tsp_sparse_workspace_bytes_general(int B, int n, int A) {
-  const size_t base = daco_tsp_sparse_workspace_bytes(B, n, A);
-  return base ? base + 2 * align256((size_t)B * n * n * sizeof(float)) : 0;
-}
-
-static bool sparse_rows_vec4(int n, const float *tau, long tau_bstride, const float *eta, long eta_bstride) {
-  return (n & 3) == 0 && (tau_bstride & 3) == 0 && (eta_bstride & 3) == 0 && (((uintptr_t)tau | (uintptr_t)eta) & 15) == 0;
-}
+// the workspace (daco_host.h HeadWs): dense rows | head rows | u16 tours, and for exponents other than 1 the two powered matrices
+static bool sparse_sizes_ok(int B, int n, int A) { return B > 0 && A > 0 && n > 128 && n <= 1024; }
+extern "C" size_t daco_tsp_sparse_tours_offset(int B, int n, int A) { return sparse_sizes_ok(B, n, A) ? HeadWs::tours_offset(B, n) : 0; }
+extern "C" size_t daco_tsp_sparse_workspace_bytes(int B, int n, int A) { return sparse_sizes_ok(B, n, A) ? HeadWs::bytes(B, n, A) : 0; }
+extern "C" size_t daco_tsp_sparse_workspace_bytes_general(int B, int n, int A) { return sparse_sizes_ok(B, n, A) ? HeadWs::bytes_general(B, n, A) : 0; }
 
 // the instantiation of scan_sparse_kernel and its dynamic LDS for a launch that is not the LDS-heads case: flags + tours (n <= 512;
 // the split-tour variant for the scan draw on 64-slot heads: SP_ST_LDS); the larger of flags + window and eight tours + their
@@ -855,7 +838,7 @@ static SparseVariant sparse_variant(int ld, bool race, int spl, bool many) {
 // arguments or the query failed)
 extern "C" int daco_tsp_sparse_resident_per_cu(int n, int head_slots, int race) {
   if (n <= 128 || n > 1024 || (head_slots != 64 && head_slots != 128)) return 0;
-  const SparseVariant v = sparse_variant(n <= 512 ? 512 : 1024, race != 0, head_slots / 16, true);
+  const SparseVariant v = sparse_variant(HeadWs::ld_for(n), race != 0, head_slots / 16, true);
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, v.fn, 256, v.lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
   return nb;
@@ -879,9 +862,8 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   const size_t need = daco_tsp_sparse_workspace_bytes(B, n, A);
   if (workspace_bytes < need) { set_error("%s: workspace %zu < %zu bytes", what, workspace_bytes, need); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
-  const int ld = n <= 512 ? 512 : 1024;
-  float *P = (float *)workspace;
-  char *hrow = (char *)workspace + align256((size_t)B * n * ld * sizeof(float));
+  const HeadWs ws = HeadWs::carve(workspace, B, n, A);
+  const int ld = ws.ld;
   const int spl = head_slots / 16;
   if (alpha != 1.0f || beta != 1.0f) {
     // the kernels take unit exponents: the powers are applied to the matrices first, into the tail of a `general` workspace
@@ -891,39 +873,35 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
       return DACO_E_WORKSPACE;
     }
     if (heads_ready) { set_error("%s: heads_ready needs alpha = beta = 1 (daco_pheromone_update_heads forms the rows of tau itself)", what); return DACO_E_BADARG; }
-    float *tp = (float *)((char *)workspace + need), *ep = tp + align256((size_t)B * n * n * sizeof(float)) / sizeof(float);
     if ((tau_bstride != 0 && tau_bstride != (long)n * n) || (eta_bstride != 0 && eta_bstride != (long)n * n)) {
       set_error("%s: exponents other than 1 need dense matrices (stride n * n between instances, or 0 for a shared one)", what);
       return DACO_E_BADARG;
     }
     const long ct = (tau_bstride ? (long)B : 1L) * n * n, ce = (eta_bstride ? (long)B : 1L) * n * n;
     const long cm = ct > ce ? ct : ce;
-    hipLaunchKernelGGL(pow_pair_kernel, dim3((unsigned)((cm + 255) / 256)), dim3(256), 0, s, ct, tau, alpha, tp, ce, eta, beta, ep);
-    tau = tp; eta = ep;
+    hipLaunchKernelGGL(pow_pair_kernel, dim3((unsigned)((cm + 255) / 256)), dim3(256), 0, s, ct, tau, alpha, ws.tau_pow, ce, eta, beta, ws.eta_pow);
+    tau = ws.tau_pow; eta = ws.eta_pow;
     alpha = beta = 1.0f;
   }
-  const bool vec4 = sparse_rows_vec4(n, tau, tau_bstride, eta, eta_bstride);
+  const bool vec4 = rows_vec4(n, tau, tau_bstride, eta, eta_bstride);
   if (!heads_ready) {
     const dim3 pg((unsigned)(((long)B * n + 3) / 4));
 #define DACO_PREPASS_C(R, V, C) hipLaunchKernelGGL((sparse_prepass_kernel<R, V, C>), pg, dim3(256), 0, s, B, n, ld / 256, tau, tau_bstride, eta, eta_bstride, \
-                                                   head_id, P, hrow, spl, ld)
+                                                   head_id, ws.P, ws.hrow, spl, ld)
 #define DACO_PREPASS(R, V) do { if (ld <= 512) DACO_PREPASS_C(R, V, 2); else DACO_PREPASS_C(R, V, 4); } while (0)
     if (race) { if (vec4) DACO_PREPASS(true, true); else DACO_PREPASS(true, false); }
     else { if (vec4) DACO_PREPASS(false, true); else DACO_PREPASS(false, false); }
 #undef DACO_PREPASS
 #undef DACO_PREPASS_C
   }
-  SampleParams sp{};
-  sp.B = B; sp.n = n; sp.A = A; sp.ld = ld; sp.CH = ld / 256;
-  sp.P = P; sp.start = start; sp.fixed_start = fixed_start;
+  if (const int rc = launch_status("sparse_prepass_kernel")) return rc;
+  SampleParams sp = sample_params(B, n, A, ld, ld / 256, ws.P, nullptr, nullptr, seed, iter, ant_gid0, paths, nullptr, nullptr, flags);
+  sp.start = start; sp.fixed_start = fixed_start;
   sp.tau = tau; sp.tau_bs = tau_bstride; sp.eta = eta; sp.eta_bs = eta_bstride; sp.alpha = alpha; sp.beta = beta; sp.row_vec = vec4 ? 1 : 0;
-  sp.seed = seed; sp.iter = iter; sp.iter_dev = iter_offset; sp.ant_gid0 = ant_gid0; sp.gid_bstride = ant_gid_bstride;
-  sp.paths = paths; sp.flags = flags; sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr; sp.nbr_grouped = nbr_grouped ? 1 : 0;
-  sp.hval = (const float *)hrow; sp.hid = head_id; sp.stats = stats;
-  sp.tours16 = (uint16_t *)(hrow + align256((size_t)B * n * sp_head_row_bytes(SP_KH_MAX / 16)));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("%s pre-pass: %s", what, hipGetErrorString(e)); return DACO_E_HIP; }
-  if (ev_begin && hipEventRecord((hipEvent_t)ev_begin, s) != hipSuccess) { set_error("hipEventRecord(ev_begin) failed"); return DACO_E_HIP; }
+  sp.iter_dev = iter_offset; sp.gid_bstride = ant_gid_bstride;
+  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr; sp.nbr_grouped = nbr_grouped ? 1 : 0;
+  sp.hval = (const float *)ws.hrow; sp.hid = head_id; sp.stats = stats; sp.tours16 = ws.tours16;
+  if (const int rc = record_event(ev_begin, s, "ev_begin")) return rc;
   // few ants (no more workgroups of four than the chip has CUs) and a head table that fits a CU's LDS: the LDS-heads variant
   bool lh = false;
   size_t lh_lds = 0;
@@ -947,10 +925,8 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
     void *args[] = {&sp};                               // (the one argument: the split-tour variant's epilogue reads it back from offset 0 of the segment)
     if (hipLaunchKernel(v.fn, grid, dim3(256), args, v.lds, s) != hipSuccess) { set_error("%s: scan_sparse_kernel launch failed", what); return DACO_E_HIP; }
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) { set_error("scan_sparse_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  if (ev_end && hipEventRecord((hipEvent_t)ev_end, s) != hipSuccess) { set_error("hipEventRecord(ev_end) failed"); return DACO_E_HIP; }
-  return DACO_OK;
+  if (const int rc = launch_status("scan_sparse_kernel")) return rc;
+  return record_event(ev_end, s, "ev_end");
 }
 
 #define DACO_SPARSE_ARGS stream, B, n, A, tau, tau_bstride, eta, eta_bstride, alpha, beta, head_id, head_slots, start, fixed_start, seed, iter, \

@@ -20,7 +20,7 @@ using namespace daco;
 
 extern "C" size_t daco_sibling_workspace_bytes(int B, int n, int mode) {
   if (B <= 0 || n <= 0 || n > DACO_MAX_NODES) return 0;
-  return daco_tsp_sample_workspace_bytes(B, n, mode) + align256((size_t)B * n * ld_alloc(n) * sizeof(float));
+  return ProbWs::bytes(B, n, mode, true);
 }
 
 extern "C" int daco_sibling_sample(void *stream, int kind, int B, int n, int A, const float *tau, long tau_bstride,
@@ -47,25 +47,17 @@ extern "C" int daco_sibling_sample(void *stream, int kind, int B, int n, int A, 
   if (workspace_bytes < need) { set_error("daco_sibling_sample: workspace %zu < %zu bytes", workspace_bytes, need); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
   const int vec = vec_for_n(n), CH = inst_chunks(n), ld = ld_alloc(n);
-  const size_t pbytes = daco_tsp_sample_workspace_bytes(B, n, mode);
-  float *P = (float *)workspace;
-  float *R = mode == DACO_RACE_PHILOX ? (float *)((char *)workspace + pbytes / 2) : nullptr;
-  float *auxp = (float *)((char *)workspace + pbytes);
+  const ProbWs ws = ProbWs::carve(workspace, B, n, mode);
   const long total = (long)B * n * ld;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
-  launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, P, R, s);
+  launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, ws.P, ws.R, s);
   if (aux_mat)
-    hipLaunchKernelGGL(pad_matrix_kernel<0>, dim3(blocks), dim3(256), 0, s, B, n, ld, aux_mat, aux_mat_bstride, auxp, 0.0f);
-  SampleParams sp;
-  sp.B = B; sp.n = n; sp.A = A; sp.ld = ld; sp.CH = CH;
-  sp.P = P; sp.R = R; sp.norm_passes = 1; sp.start = start; sp.fixed_start = 0;
-  sp.noise = noise; sp.seed = seed; sp.iter = iter; sp.iter_dev = nullptr; sp.ant_gid0 = ant_gid0; sp.gid_bstride = 0;
-  sp.paths = paths; sp.logp = logp; sp.rowsum = rowsum; sp.flags = flags;
-  sp.dist = nullptr; sp.dist_bs = 0; sp.costs = nullptr; sp.nbr = nullptr; sp.hubmask = nullptr; sp.tab_lens = nullptr;
-  sp.demand = nullptr; sp.capacity = 0.0f; sp.Lmax = Lmax; sp.noise_steps = noise_steps; sp.lens = lens;
-  sp.mask = nullptr; sp.step = 0;
-  sp.aux_vec = aux_vec; sp.aux_mat = auxp; sp.scalar0 = scalar0; sp.wts = item_weights; sp.m = m;
+    hipLaunchKernelGGL(pad_matrix_kernel<0>, dim3(blocks), dim3(256), 0, s, B, n, ld, aux_mat, aux_mat_bstride, ws.aux, 0.0f);
+  if (const int rc = launch_status("prob_matrix_kernel / pad_matrix_kernel")) return rc;
+  SampleParams sp = sample_params(B, n, A, ld, CH, ws.P, ws.R, noise, seed, iter, ant_gid0, paths, logp, rowsum, flags);
+  sp.norm_passes = 1; sp.start = start; sp.Lmax = Lmax; sp.noise_steps = noise_steps; sp.lens = lens;
+  sp.aux_vec = aux_vec; sp.aux_mat = ws.aux; sp.scalar0 = scalar0; sp.wts = item_weights; sp.m = m;
   const bool lp = logp != nullptr;
   hipError_t e;
   switch (kind) {
@@ -75,6 +67,5 @@ extern "C" int daco_sibling_sample(void *stream, int kind, int B, int n, int A, 
     case DACO_SIB_MKP: e = dispatch_sample<PROB_MKP>(sp, vec, CH, mode, lp, s); break;
     default: set_error("daco_sibling_sample: unknown kind %d", kind); return DACO_E_BADARG;
   }
-  if (e != hipSuccess) { set_error("sibling sample kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status(e, "sibling sample kernel");
 }

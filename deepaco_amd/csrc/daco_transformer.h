@@ -1,8 +1,7 @@
 // daco_transformer.h -- what daco_transformer.hip (forward, training forward) and daco_transformer_train.hip (backward) share:
 // the layout of the flat parameter block, the layout of the `saved` buffer of the training forward, the per-token helpers.
 #pragma once
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_host.h"
 
 namespace daco {
 

@@ -269,9 +269,7 @@ extern "C" int daco_transformer_forward(void *stream, int G, int n, int feats, c
   }
   hipLaunchKernelGGL(tf_head_kernel<false>, grid, block, 0, s, n, params + t_layer_off(feats, TLAYERS), X, raw, nullptr, nullptr);
   hipLaunchKernelGGL(tf_max_div_kernel<false>, dim3((unsigned)G), dim3(256), 0, s, n, raw, out, nullptr, nullptr);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("transformer kernels launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("transformer kernels");
 }
 
 // ---- the training forward: the same kernels with SAVE, every intermediate in the caller's `saved` buffer
@@ -311,7 +309,5 @@ extern "C" int daco_transformer_forward_train(void *stream, int G, int n, int fe
   }
   hipLaunchKernelGGL(tf_head_kernel<true>, grid, block, 0, s, n, params + t_layer_off(feats, TLAYERS), hd.X, hd.RAW, hd.H1, hd.H2);
   hipLaunchKernelGGL(tf_max_div_kernel<true>, dim3((unsigned)G), dim3(256), 0, s, n, hd.RAW, out, hd.MX, hd.AMAX);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("transformer training kernels launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("transformer training kernels");
 }

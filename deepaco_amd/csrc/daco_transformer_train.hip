@@ -463,7 +463,5 @@ extern "C" int daco_transformer_backward(void *stream, int G, int n, int feats, 
   jobs.j[0] = tf_job(dX, 32, 32, src, feats, feats, 0, 0, (size_t)32 * feats);
   hipLaunchKernelGGL(tfb_wgrad_kernel, dim3((unsigned)ntiles, 1), b256, 0, s, N, jobs, partials, P);
   hipLaunchKernelGGL(tfb_merge_kernel, dim3((unsigned)((P + 255) / 256)), b256, 0, s, ntiles, P, partials, grad_params);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("transformer backward kernels launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("transformer backward kernels");
 }

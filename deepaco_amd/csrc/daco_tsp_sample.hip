@@ -55,8 +55,7 @@ void launch_prob_matrix(int B, int n, int ld, const float *tau, long tau_bs, con
                                float beta, float *P, float *R, hipStream_t s) {
   const long rows = (long)B * n;
   const int blocks = (int)(rows < 16384 ? rows : 16384);
-  const bool vec4 = (n & 3) == 0 && (tau_bs & 3) == 0 && (eta_bs & 3) == 0 && (((uintptr_t)tau | (uintptr_t)eta) & 15) == 0;
-  if (vec4) hipLaunchKernelGGL(prob_matrix_kernel<true>, dim3(blocks), dim3(256), 0, s, B, n, ld, tau, tau_bs, eta, eta_bs, alpha, beta, P, R);
+  if (rows_vec4(n, tau, tau_bs, eta, eta_bs)) hipLaunchKernelGGL(prob_matrix_kernel<true>, dim3(blocks), dim3(256), 0, s, B, n, ld, tau, tau_bs, eta, eta_bs, alpha, beta, P, R);
   else hipLaunchKernelGGL(prob_matrix_kernel<false>, dim3(blocks), dim3(256), 0, s, B, n, ld, tau, tau_bs, eta, eta_bs, alpha, beta, P, R);
 }
 
@@ -70,8 +69,7 @@ extern "C" int daco_ld_for_n(int n) { return ld_for_n(n); }
 
 extern "C" size_t daco_tsp_sample_workspace_bytes(int B, int n, int mode) {
   if (B <= 0 || n <= 0 || n > DACO_MAX_NODES) return 0;
-  const size_t mat = align256((size_t)B * n * ld_alloc(n) * sizeof(float));
-  return mode == DACO_RACE_PHILOX ? 2 * mat : mat;
+  return ProbWs::bytes(B, n, mode);
 }
 
 extern "C" int daco_tsp_sample(void *stream, int B, int n, int A, const float *tau, long tau_bstride,
@@ -100,29 +98,18 @@ extern "C" int daco_tsp_sample(void *stream, int B, int n, int A, const float *t
   if (workspace_bytes < need) { set_error("daco_tsp_sample: workspace %zu < %zu bytes", workspace_bytes, need); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
   const int vec = vec_for_n(n), CH = inst_chunks(n), ld = ld_alloc(n);
-  float *P = (float *)workspace;
-  float *R = mode == DACO_RACE_PHILOX ? (float *)((char *)workspace + need / 2) : nullptr;
-  {
-    launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, P, R, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("prob_matrix_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  }
-  SampleParams sp;
-  sp.B = B; sp.n = n; sp.A = A; sp.ld = ld; sp.CH = CH;
-  sp.P = P; sp.R = R; sp.norm_passes = norm_passes; sp.start = start; sp.fixed_start = fixed_start;
-  sp.noise = noise; sp.seed = seed; sp.iter = iter; sp.iter_dev = iter_offset; sp.ant_gid0 = ant_gid0; sp.gid_bstride = ant_gid_bstride;
-  sp.paths = paths; sp.logp = logp; sp.rowsum = rowsum; sp.flags = flags;
-  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr; sp.hubmask = nullptr; sp.tab_lens = nullptr;
-  sp.demand = nullptr; sp.capacity = 0.0f; sp.Lmax = 0; sp.noise_steps = 0; sp.lens = nullptr; sp.demand64 = nullptr; sp.capacity64 = 0.0;
-  sp.mask = nullptr; sp.step = 0;
-  sp.aux_vec = nullptr; sp.aux_mat = nullptr; sp.scalar0 = 0.0f; sp.wts = nullptr; sp.m = 0;
+  const ProbWs ws = ProbWs::carve(workspace, B, n, mode);
+  launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, ws.P, ws.R, s);
+  if (const int rc = launch_status("prob_matrix_kernel")) return rc;
+  SampleParams sp = sample_params(B, n, A, ld, CH, ws.P, ws.R, noise, seed, iter, ant_gid0, paths, logp, rowsum, flags);
+  sp.norm_passes = norm_passes; sp.start = start; sp.fixed_start = fixed_start;
+  sp.iter_dev = iter_offset; sp.gid_bstride = ant_gid_bstride;
+  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr;
   const bool lp = logp != nullptr;
-  hipError_t e;
-  if (ev_begin && hipEventRecord((hipEvent_t)ev_begin, s) != hipSuccess) { set_error("hipEventRecord(ev_begin) failed"); return DACO_E_HIP; }
-  e = four_per_wave ? launch_tsp_scan16(sp, lp, s) : two_per_wave ? launch_tsp_scan32(sp, lp, s) : dispatch_sample<PROB_TSP>(sp, vec, CH, mode, lp, s);
-  if (e != hipSuccess) { set_error("tsp_sample_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  if (ev_end && hipEventRecord((hipEvent_t)ev_end, s) != hipSuccess) { set_error("hipEventRecord(ev_end) failed"); return DACO_E_HIP; }
-  return DACO_OK;
+  if (const int rc = record_event(ev_begin, s, "ev_begin")) return rc;
+  const hipError_t e = four_per_wave ? launch_tsp_scan16(sp, lp, s) : two_per_wave ? launch_tsp_scan32(sp, lp, s) : dispatch_sample<PROB_TSP>(sp, vec, CH, mode, lp, s);
+  if (const int rc = launch_status(e, "tsp_sample_kernel")) return rc;
+  return record_event(ev_end, s, "ev_end");
 }
 
 extern "C" int daco_cvrp_sample(void *stream, int B, int n, int A, const float *tau, long tau_bstride,
@@ -151,42 +138,31 @@ extern "C" int daco_cvrp_sample(void *stream, int B, int n, int A, const float *
   const size_t need = daco_tsp_sample_workspace_bytes(B, n, mode);
   if (workspace_bytes < need) { set_error("daco_cvrp_sample: workspace %zu < %zu bytes", workspace_bytes, need); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
-  uint32_t *hubmask = nullptr;
-  int32_t *tab_lens = nullptr;
+  DirectedTable tab{};
   if (next_table) {
     // "no successor" everywhere, empty depot sets; the kernel fills in what each ant really does
-    const size_t tab = ((size_t)B * n * A * sizeof(uint32_t) + 255) & ~(size_t)255;
-    hubmask = (uint32_t *)((char *)next_table + tab);
-    tab_lens = (int32_t *)((char *)hubmask + (((size_t)B * A * ((n + 31) / 32) * sizeof(uint32_t) + 255) & ~(size_t)255));
-    if (hipMemsetAsync(next_table, 0xFF, (size_t)B * n * A * sizeof(uint32_t), s) != hipSuccess ||
-        hipMemsetAsync(hubmask, 0, (size_t)B * A * ((n + 31) / 32) * sizeof(uint32_t), s) != hipSuccess) {
+    tab = DirectedTable::carve(next_table, B, n, A);
+    if (hipMemsetAsync(tab.next, 0xFF, DirectedTable::next_bytes(B, n, A), s) != hipSuccess ||
+        hipMemsetAsync(tab.hubmask, 0, DirectedTable::hubmask_bytes(B, n, A), s) != hipSuccess) {
       set_error("daco_cvrp_sample: hipMemsetAsync failed");
       return DACO_E_HIP;
     }
   }
   const int vec = vec_for_n(n), CH = inst_chunks(n), ld = ld_alloc(n);
-  float *P = (float *)workspace;
-  float *R = mode == DACO_RACE_PHILOX ? (float *)((char *)workspace + need / 2) : nullptr;
-  {
-    launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, P, R, s);
-  }
-  SampleParams sp;
-  sp.B = B; sp.n = n; sp.A = A; sp.ld = ld; sp.CH = CH;
-  sp.P = P; sp.R = R; sp.norm_passes = 1; sp.start = nullptr; sp.fixed_start = 0;
-  sp.noise = noise; sp.seed = seed; sp.iter = iter; sp.iter_dev = iter_offset; sp.ant_gid0 = ant_gid0; sp.gid_bstride = ant_gid_bstride;
-  sp.paths = paths; sp.logp = logp; sp.rowsum = rowsum; sp.flags = flags;
-  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = (uint32_t *)next_table; sp.hubmask = hubmask; sp.tab_lens = tab_lens;
+  const ProbWs ws = ProbWs::carve(workspace, B, n, mode);
+  launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, ws.P, ws.R, s);
+  if (const int rc = launch_status("prob_matrix_kernel")) return rc;
+  SampleParams sp = sample_params(B, n, A, ld, CH, ws.P, ws.R, noise, seed, iter, ant_gid0, paths, logp, rowsum, flags);
+  sp.norm_passes = 1; sp.iter_dev = iter_offset; sp.gid_bstride = ant_gid_bstride;
+  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = tab.next; sp.hubmask = tab.hubmask; sp.tab_lens = tab.lens;
   sp.demand = demand; sp.capacity = capacity; sp.Lmax = Lmax; sp.noise_steps = noise_steps; sp.lens = lens;
   sp.demand64 = demand64; sp.capacity64 = capacity64;
-  sp.mask = nullptr; sp.step = 0;
-  sp.aux_vec = nullptr; sp.aux_mat = nullptr; sp.scalar0 = 0.0f; sp.wts = nullptr; sp.m = 0;
-  if (ev_begin && hipEventRecord((hipEvent_t)ev_begin, s) != hipSuccess) { set_error("hipEventRecord(ev_begin) failed"); return DACO_E_HIP; }
-  hipError_t e = four_per_wave ? launch_cvrp_scan16(sp, logp != nullptr, s)
-               : demand64     ? dispatch_sample<PROB_CVRP64>(sp, vec, CH, mode, logp != nullptr, s)
-                              : dispatch_sample<PROB_CVRP>(sp, vec, CH, mode, logp != nullptr, s);
-  if (e != hipSuccess) { set_error("cvrp sample kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  if (ev_end && hipEventRecord((hipEvent_t)ev_end, s) != hipSuccess) { set_error("hipEventRecord(ev_end) failed"); return DACO_E_HIP; }
-  return DACO_OK;
+  if (const int rc = record_event(ev_begin, s, "ev_begin")) return rc;
+  const hipError_t e = four_per_wave ? launch_cvrp_scan16(sp, logp != nullptr, s)
+                     : demand64     ? dispatch_sample<PROB_CVRP64>(sp, vec, CH, mode, logp != nullptr, s)
+                                    : dispatch_sample<PROB_CVRP>(sp, vec, CH, mode, logp != nullptr, s);
+  if (const int rc = launch_status(e, "cvrp sample kernel")) return rc;
+  return record_event(ev_end, s, "ev_end");
 }
 
 // ------------------------------------------------------------------ step-wise API (sibling problems)
@@ -197,13 +173,9 @@ extern "C" int daco_prob_matrix(void *stream, int B, int n, const float *tau, lo
   if (n > DACO_MAX_NODES) { set_error("daco_prob_matrix: n=%d exceeds DACO_MAX_NODES", n); return DACO_E_TOOLARGE; }
   const size_t need = daco_tsp_sample_workspace_bytes(B, n, mode);
   if (workspace_bytes < need) { set_error("daco_prob_matrix: workspace %zu < %zu bytes", workspace_bytes, need); return DACO_E_WORKSPACE; }
-  const int ld = ld_alloc(n);
-  float *P = (float *)workspace;
-  float *R = mode == DACO_RACE_PHILOX ? (float *)((char *)workspace + need / 2) : nullptr;
-  launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, P, R, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("prob_matrix_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  const ProbWs ws = ProbWs::carve(workspace, B, n, mode);
+  launch_prob_matrix(B, n, ld_alloc(n), tau, tau_bstride, eta, eta_bstride, alpha, beta, ws.P, ws.R, (hipStream_t)stream);
+  return launch_status("prob_matrix_kernel");
 }
 
 extern "C" int daco_pick_move(void *stream, int B, int n, int A, const void *prob_workspace, size_t workspace_bytes,
@@ -221,17 +193,9 @@ extern "C" int daco_pick_move(void *stream, int B, int n, int A, const void *pro
   const size_t need = daco_tsp_sample_workspace_bytes(B, n, mode);
   if (workspace_bytes < need) { set_error("daco_pick_move: workspace %zu < %zu bytes", workspace_bytes, need); return DACO_E_WORKSPACE; }
   const int vec = vec_for_n(n), CH = inst_chunks(n), ld = ld_alloc(n);
-  SampleParams sp;
-  sp.B = B; sp.n = n; sp.A = A; sp.ld = ld; sp.CH = CH;
-  sp.P = (const float *)prob_workspace;
-  sp.R = mode == DACO_RACE_PHILOX ? (const float *)((const char *)prob_workspace + need / 2) : nullptr;
-  sp.norm_passes = 1; sp.start = prev; sp.fixed_start = -1; sp.noise = noise; sp.seed = seed; sp.iter = iter; sp.iter_dev = nullptr; sp.gid_bstride = 0;
-  sp.ant_gid0 = ant_gid0; sp.paths = actions; sp.logp = logp; sp.rowsum = rowsum; sp.flags = flags;
-  sp.dist = nullptr; sp.dist_bs = 0; sp.costs = nullptr; sp.nbr = nullptr;
-  sp.demand = nullptr; sp.capacity = 0.0f; sp.Lmax = 0; sp.noise_steps = 1; sp.lens = nullptr; sp.demand64 = nullptr; sp.capacity64 = 0.0;
+  const ProbWs ws = ProbWs::carve(prob_workspace, B, n, mode);
+  SampleParams sp = sample_params(B, n, A, ld, CH, ws.P, ws.R, noise, seed, iter, ant_gid0, actions, logp, rowsum, flags);
+  sp.norm_passes = 1; sp.start = prev; sp.fixed_start = -1; sp.noise_steps = 1;
   sp.mask = mask; sp.step = step;
-  sp.aux_vec = nullptr; sp.aux_mat = nullptr; sp.scalar0 = 0.0f; sp.wts = nullptr; sp.m = 0;
-  hipError_t e = dispatch_sample<PROB_STEP>(sp, vec, CH, mode, logp != nullptr, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error("pick_move kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status(dispatch_sample<PROB_STEP>(sp, vec, CH, mode, logp != nullptr, (hipStream_t)stream), "pick_move kernel");
 }

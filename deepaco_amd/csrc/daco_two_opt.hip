@@ -13,8 +13,7 @@
 // each wave owns a contiguous chunk of rows i (equal pair counts), lanes stride j.
 #include <cstdlib>
 
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_host.h"
 
 namespace daco {
 
@@ -612,9 +611,7 @@ extern "C" int daco_two_opt(void *stream, int B, int T, int n, const float *dist
     default: DACO_2OPT(4, true); break;
   }
 #undef DACO_2OPT
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("two_opt_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("two_opt_kernel");
 }
 
 namespace daco {
@@ -661,7 +658,5 @@ extern "C" int daco_two_opt_auto(void *stream, int B, int T, int n, const float 
                      (const unsigned char *)tables_T, tables_bytes_per_instance(n), (int)w_back);
   rc = launch_two_opt_nbr(s, B, T, n, dist, dist_bstride, tables, tables_T, tours, max_iterations, nullptr, sweeps, 0xffffffffu, 1);
   if (rc != DACO_OK) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("two_opt_auto launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("two_opt_auto");
 }

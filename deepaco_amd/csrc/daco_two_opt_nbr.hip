@@ -28,8 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "daco_device.h"
-#include "../../include/deepaco_hip.h"
+#include "daco_host.h"
 
 namespace daco {
 
@@ -386,9 +385,7 @@ extern "C" int daco_two_opt_prepare(void *stream, int B, int n, const float *dis
   while (P2 < n) P2 <<= 1;
   hipLaunchKernelGGL(nbr_maxabs_kernel, dim3(16, B), dim3(256), 0, s, n, dist, dist_bstride, tabs, stride);
   hipLaunchKernelGGL(nbr_sort_rows_kernel, dim3((unsigned)B * n), dim3(256), (size_t)P2 * 8, s, n, P2, dist, dist_bstride, tabs, stride);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("two_opt table kernels launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("two_opt table kernels");
 }
 
 namespace daco {
@@ -407,9 +404,7 @@ int launch_two_opt_nbr(hipStream_t s, int B, int T, int n, const float *dist, lo
   if (tables == tables_T) { if (wide) DACO_NBR_LAUNCH(true, 1024); else DACO_NBR_LAUNCH(true, 256); }
   else { if (wide) DACO_NBR_LAUNCH(false, 1024); else DACO_NBR_LAUNCH(false, 256); }
 #undef DACO_NBR_LAUNCH
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("two_opt_nbr_kernel launch: %s", hipGetErrorString(e)); return DACO_E_HIP; }
-  return DACO_OK;
+  return launch_status("two_opt_nbr_kernel");
 }
 }  // namespace daco
 
