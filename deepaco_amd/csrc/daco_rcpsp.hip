@@ -5,8 +5,9 @@
 //     interpreted Python through per-resource event queues re-sorted on every request (rcpsp_inst.py:57-90)
 //     -> rcpsp_schedule_kernel, or the tail of the construction kernel: one wavefront per (project, ant), daco_rcpsp.h;
 //   construct_solutions (:176-213): n-1 draws from activity 0 under precedence constraints, with the direct, summation and
-//     balanced evaluation of Merkle et al. (:190-206) -> PROB_RCPSP of the construction template (daco_sample_kernel.h): the
-//     draw code, modes, noise layout and Philox counters are those of daco_sibling_sample;
+//     balanced evaluation of Merkle et al. (:190-206) -> PROB_RCPSP of the construction template (daco_sample_kernel.h),
+//     launched through its launch_sample with the decoder's LDS plan; the draw code, modes, noise layout and Philox counters
+//     are those of daco_sibling_sample;
 //   the best-so-far bookkeeping of update_cost and the deposit list of update_pheromone (:238-256) -> rcpsp_track_kernel, which
 //     lays out [best-so-far route | iteration-best ant or every ant] with their weights for daco_pheromone_update
 //     (symmetric = 0, hub = -1), whose sequential per-row adds reproduce the reference's index_put order bit for bit;
@@ -60,17 +61,6 @@ static hipError_t launch_schedule(const RcpspDev &q, int B, int n, int A, const 
     (void)hipFuncSetAttribute((const void *)rcpsp_schedule_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
   const long waves = (long)B * A;
   hipLaunchKernelGGL(rcpsp_schedule_kernel, dim3((unsigned)((waves + wpb - 1) / wpb)), dim3(64 * wpb), dyn, s, q, B, n, A, routes, flags);
-  return hipGetLastError();
-}
-
-template <int VEC>
-static hipError_t launch_rcpsp_sample(const SampleParams &sp, int mode, bool logp, size_t dyn, hipStream_t s) {
-  dim3 grid((unsigned)(sp.B * ((sp.A + 3) / 4))), block(256);
-#define DACO_LAUNCH(M, L) hipLaunchKernelGGL((tsp_sample_kernel<VEC, 1, M, L, PROB_RCPSP>), grid, block, dyn, s, sp)
-  if (mode == DACO_SCAN) { if (logp) DACO_LAUNCH(DACO_SCAN, true); else DACO_LAUNCH(DACO_SCAN, false); }
-  else if (mode == DACO_RACE_PHILOX) { if (logp) DACO_LAUNCH(DACO_RACE_PHILOX, true); else DACO_LAUNCH(DACO_RACE_PHILOX, false); }
-  else { if (logp) DACO_LAUNCH(DACO_RACE_NOISE, true); else DACO_LAUNCH(DACO_RACE_NOISE, false); }
-#undef DACO_LAUNCH
   return hipGetLastError();
 }
 
@@ -292,11 +282,8 @@ extern "C" int daco_rcpsp_sample(void *stream, int B, int n, int A, int R, int h
   const int vec = vec_for_n(n), ld = ld_alloc(n);
   const RcpspWs ws = RcpspWs::carve(workspace, B, n);
   float *const Rm = mode == DACO_RACE_PHILOX ? ws.R : nullptr;
-  const long total = (long)B * n * ld;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
   launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, ws.P, Rm, s);
-  hipLaunchKernelGGL(pad_matrix_kernel<0>, dim3(blocks), dim3(256), 0, s, B, n, ld, adjacency, (long)n * n, ws.adj, 0.0f);
+  launch_pad_matrix(B, n, ld, adjacency, (long)n * n, ws.adj, 0.0f, s);
   if (rule != 0) {                                      // x^1 = x and x^0 = 1 exactly (pw): tau itself and eta^beta, padded
     launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, 1.0f, 0.0f, ws.tau, nullptr, s);
     launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, 0.0f, beta, ws.etab, nullptr, s);
@@ -312,8 +299,8 @@ extern "C" int daco_rcpsp_sample(void *stream, int B, int n, int A, int R, int h
   sp.rc.fused = dyn4 <= RCPSP_LDS_PLAIN;
   const size_t dyn = sp.rc.fused ? dyn4 : 0;
   const bool lp = logp != nullptr;
-  hipError_t e = vec == 1 ? launch_rcpsp_sample<1>(sp, mode, lp, dyn, s)
-               : (vec == 2 ? launch_rcpsp_sample<2>(sp, mode, lp, dyn, s) : launch_rcpsp_sample<4>(sp, mode, lp, dyn, s));
+  hipError_t e = vec == 1 ? launch_sample<1, 1, PROB_RCPSP>(sp, mode, lp, s, dyn)          // n <= 256: one chunk per lane
+               : (vec == 2 ? launch_sample<2, 1, PROB_RCPSP>(sp, mode, lp, s, dyn) : launch_sample<4, 1, PROB_RCPSP>(sp, mode, lp, s, dyn));
   if (const int rc = launch_status(e, "rcpsp construction kernel")) return rc;
   if (sp.rc.fused) return DACO_OK;
   return launch_status(launch_schedule(sp.rc, B, n, A, routes, flags, s), "rcpsp_schedule_kernel");

@@ -1,6 +1,6 @@
 // daco_sample_kernel.h -- the tour-construction kernel template shared by daco_tsp_sample.hip (TSP, CVRP,
-// step-wise draws) and daco_sib_sample.hip (fused sibling-problem constructions).  See daco_tsp_sample.hip
-// for the design notes.
+// step-wise draws), daco_sib_sample.hip (fused sibling-problem constructions) and daco_rcpsp.hip (project
+// scheduling), with its host dispatch (launch_sample / dispatch_sample).  See daco_tsp_sample.hip for the design notes.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -96,23 +96,12 @@ __device__ inline void load_vec(const float *p, float (&out)[VEC]) {
   }
 }
 
-// dst[b][r][0..ld) = src[b][r][0..n) padded with `fill` (a template so that every file that pads a matrix holds the one definition)
-template <int UNUSED = 0>
-__global__ void __launch_bounds__(256)
-pad_matrix_kernel(int B, int n, int ld, const float *src, long src_bs, float *dst, float fill) {
-  const long total = (long)B * n * ld;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int k = (int)(i % ld);
-    const long row = i / ld;
-    const int b = (int)(row / n), r = (int)(row % n);
-    dst[i] = k < n ? src[b * src_bs + (long)r * n + k] : fill;
-  }
-}
-
 // P = tau^alpha * eta^beta with zero padding; R = 1/P with +inf padding (optional): launches prob_matrix_kernel
 // (daco_tsp_sample.hip)
 void launch_prob_matrix(int B, int n, int ld, const float *tau, long tau_bs, const float *eta, long eta_bs, float alpha,
                         float beta, float *P, float *R, hipStream_t s);
+// dst[b][r][0..ld) = src[b][r][0..n) padded with `fill`: launches pad_matrix_kernel (daco_tsp_sample.hip)
+void launch_pad_matrix(int B, int n, int ld, const float *src, long src_bs, float *dst, float fill, hipStream_t s);
 
 // visited bitset: bit (c*VEC+v) of a 64-bit word kept as two 32-bit halves so every test is a
 // single 32-bit v_and/v_cmp (the upper half folds away when CH*VEC <= 32)
@@ -668,15 +657,15 @@ tsp_sample_kernel(const SampleParams p) {
 }
 
 // ------------------------------------------------------------------ host dispatch
-template <int VEC, int CH, int CVRP>
-static hipError_t launch_sample(const SampleParams &sp, int mode, bool logp, hipStream_t s) {
+template <int VEC, int CH, int PROB>
+static hipError_t launch_sample(const SampleParams &sp, int mode, bool logp, hipStream_t s, size_t dyn_lds = 0) {
   const int bpi = (sp.A + 3) / 4;
   dim3 grid((unsigned)(sp.B * bpi)), block(256);
-  // PROB_TSP keeps the workgroup's tours (+ the inverse table and a staging row per wave) in LDS
-  const size_t dyn = CVRP == PROB_TSP ? (size_t)8 * ((sp.n + 7) & ~7) * sizeof(uint16_t) + 4 * 64 * sizeof(float) : 0;
+  // PROB_TSP keeps the workgroup's tours (+ the inverse table and a staging row per wave) in LDS; dyn_lds: what another problem asks for (the RCPSP decoder)
+  const size_t dyn = PROB == PROB_TSP ? (size_t)8 * ((sp.n + 7) & ~7) * sizeof(uint16_t) + 4 * 64 * sizeof(float) : dyn_lds;
 #define DACO_LAUNCH(M, L) do { \
-    if (dyn > 64 * 1024) (void)hipFuncSetAttribute((const void *)tsp_sample_kernel<VEC, CH, M, L, CVRP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); \
-    hipLaunchKernelGGL((tsp_sample_kernel<VEC, CH, M, L, CVRP>), grid, block, dyn, s, sp); } while (0)
+    if (dyn > 64 * 1024) (void)hipFuncSetAttribute((const void *)tsp_sample_kernel<VEC, CH, M, L, PROB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); \
+    hipLaunchKernelGGL((tsp_sample_kernel<VEC, CH, M, L, PROB>), grid, block, dyn, s, sp); } while (0)
   if (mode == DACO_SCAN) { if (logp) DACO_LAUNCH(DACO_SCAN, true); else DACO_LAUNCH(DACO_SCAN, false); }
   else if (mode == DACO_RACE_PHILOX) { if (logp) DACO_LAUNCH(DACO_RACE_PHILOX, true); else DACO_LAUNCH(DACO_RACE_PHILOX, false); }
   else { if (logp) DACO_LAUNCH(DACO_RACE_NOISE, true); else DACO_LAUNCH(DACO_RACE_NOISE, false); }
@@ -684,19 +673,19 @@ static hipError_t launch_sample(const SampleParams &sp, int mode, bool logp, hip
   return hipGetLastError();
 }
 
-template <int CVRP>
+template <int PROB>
 static hipError_t dispatch_sample(const SampleParams &sp, int vec, int CH, int mode, bool lp, hipStream_t s) {
-  if (vec == 1) return launch_sample<1, 1, CVRP>(sp, mode, lp, s);
-  if (vec == 2) return launch_sample<2, 1, CVRP>(sp, mode, lp, s);
+  if (vec == 1) return launch_sample<1, 1, PROB>(sp, mode, lp, s);
+  if (vec == 2) return launch_sample<2, 1, PROB>(sp, mode, lp, s);
   switch (CH) {
-    case 1: return launch_sample<4, 1, CVRP>(sp, mode, lp, s);
-    case 2: return launch_sample<4, 2, CVRP>(sp, mode, lp, s);
-    case 3: return launch_sample<4, 3, CVRP>(sp, mode, lp, s);
-    case 4: return launch_sample<4, 4, CVRP>(sp, mode, lp, s);
-    case 6: return launch_sample<4, 6, CVRP>(sp, mode, lp, s);
-    case 8: return launch_sample<4, 8, CVRP>(sp, mode, lp, s);
-    case 12: return launch_sample<4, 12, CVRP>(sp, mode, lp, s);
-    default: return launch_sample<4, 16, CVRP>(sp, mode, lp, s);
+    case 1: return launch_sample<4, 1, PROB>(sp, mode, lp, s);
+    case 2: return launch_sample<4, 2, PROB>(sp, mode, lp, s);
+    case 3: return launch_sample<4, 3, PROB>(sp, mode, lp, s);
+    case 4: return launch_sample<4, 4, PROB>(sp, mode, lp, s);
+    case 6: return launch_sample<4, 6, PROB>(sp, mode, lp, s);
+    case 8: return launch_sample<4, 8, PROB>(sp, mode, lp, s);
+    case 12: return launch_sample<4, 12, PROB>(sp, mode, lp, s);
+    default: return launch_sample<4, 16, PROB>(sp, mode, lp, s);
   }
 }
 

@@ -48,12 +48,8 @@ extern "C" int daco_sibling_sample(void *stream, int kind, int B, int n, int A, 
   hipStream_t s = (hipStream_t)stream;
   const int vec = vec_for_n(n), CH = inst_chunks(n), ld = ld_alloc(n);
   const ProbWs ws = ProbWs::carve(workspace, B, n, mode);
-  const long total = (long)B * n * ld;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
   launch_prob_matrix(B, n, ld, tau, tau_bstride, eta, eta_bstride, alpha, beta, ws.P, ws.R, s);
-  if (aux_mat)
-    hipLaunchKernelGGL(pad_matrix_kernel<0>, dim3(blocks), dim3(256), 0, s, B, n, ld, aux_mat, aux_mat_bstride, ws.aux, 0.0f);
+  if (aux_mat) launch_pad_matrix(B, n, ld, aux_mat, aux_mat_bstride, ws.aux, 0.0f, s);
   if (const int rc = launch_status("prob_matrix_kernel / pad_matrix_kernel")) return rc;
   SampleParams sp = sample_params(B, n, A, ld, CH, ws.P, ws.R, noise, seed, iter, ant_gid0, paths, logp, rowsum, flags);
   sp.norm_passes = 1; sp.start = start; sp.Lmax = Lmax; sp.noise_steps = noise_steps; sp.lens = lens;

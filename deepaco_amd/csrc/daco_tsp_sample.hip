@@ -51,6 +51,24 @@ prob_matrix_kernel(int B, int n, int ld, const float *tau, long tau_bs, const fl
   }
 }
 
+// dst[b][r][0..ld) = src[b][r][0..n) padded with `fill` (a template: the kernel keeps the name it had in every file that padded a matrix)
+template <int UNUSED = 0>
+__global__ void __launch_bounds__(256)
+pad_matrix_kernel(int B, int n, int ld, const float *src, long src_bs, float *dst, float fill) {
+  const long total = (long)B * n * ld;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int k = (int)(i % ld);
+    const long row = i / ld;
+    const int b = (int)(row / n), r = (int)(row % n);
+    dst[i] = k < n ? src[b * src_bs + (long)r * n + k] : fill;
+  }
+}
+
+void launch_pad_matrix(int B, int n, int ld, const float *src, long src_bs, float *dst, float fill, hipStream_t s) {
+  const long blocks = ((long)B * n * ld + 255) / 256;
+  hipLaunchKernelGGL(pad_matrix_kernel<0>, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, s, B, n, ld, src, src_bs, dst, fill);
+}
+
 void launch_prob_matrix(int B, int n, int ld, const float *tau, long tau_bs, const float *eta, long eta_bs, float alpha,
                                float beta, float *P, float *R, hipStream_t s) {
   const long rows = (long)B * n;
