@@ -94,6 +94,10 @@ SIGNATURES = {
                                C.c_double, C.c_double, _i, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "daco_rcpsp_backward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _l, _f, _f, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "daco_rcpsp_track": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # (the status of daco_rcpsp_net_forward is a long: see the note at its prototype)
+    "daco_rcpsp_net_param_floats": (_sz, []),
+    "daco_rcpsp_net_workspace_bytes": (_sz, [_i, _i]),
+    "daco_rcpsp_net_forward": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz]),
     "daco_tsp_nls": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _l, _vp, _vp, _vp]),
 }
 

@@ -267,12 +267,18 @@ def train_mkp_transformer_batch(net, optimizer, price, weight, n_ants, seed=0, i
 
 
 @torch.no_grad()
-def infer_rcpsp_batch(instances, n_ants, t_aco, heuristic=None, seed=0, sampler="scan", best_route="copy", **acoparam):
+def infer_rcpsp_batch(instances, n_ants, t_aco, heuristic=None, seed=0, sampler="scan", best_route="copy", net=None, **acoparam):
     """The protocol of rcpsp/test.ipynb (`infer_instance` / `test`) for B projects of equal size at once: one colony per
     project, the best makespan read at every checkpoint of t_aco (e.g. [1, 10, 20]).  instances: a list of
     rcpsp.RCPSPInstance (or stacked RcpspTensors with a heuristic); heuristic [B, n, n] or None for the reference's default
-    (nWRUP(0.3) / max * nGRPWA); acoparam: the notebook's dict(elitist=True, min_max=True) and anything else
-    engine.BatchedRCPSP takes.  Returns (best costs [len(t_aco), B] int32, colony)."""
+    (nWRUP(0.3) / max * nGRPWA); net: a rcpsp.net.Net whose `forward_batch(instances)` (`Net.reshape(...) + 1e-10` for the
+    whole batch, one launch) is the heuristic instead -- instances must then be RCPSPInstance objects, and giving a heuristic
+    as well is an error; acoparam: the notebook's dict(elitist=True, min_max=True) and anything else engine.BatchedRCPSP
+    takes.  Returns (best costs [len(t_aco), B] int32, colony)."""
+    if net is not None:
+        if heuristic is not None:
+            raise ValueError("infer_rcpsp_batch: give either a heuristic or a network, not both")
+        heuristic = net.eval().forward_batch(instances)
     colony = engine.BatchedRCPSP(instances, n_ants=n_ants, heuristic=heuristic, seed=seed, sampler=sampler, best_route=best_route,
                                  **acoparam)
     out, done = [], 0

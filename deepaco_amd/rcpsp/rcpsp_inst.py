@@ -3,7 +3,8 @@ parser, the activity-on-node project with its time windows, and the arrays the k
 
 The read surface is the reference's (its spelling included: `earlist_start`).  What differs: an activity here is a plain
 record -- predecessor / successor lists hold indices, the closures are computed once for the whole project -- and the
-torch_geometric view (`to_pyg_data`) is absent."""
+torch_geometric view (`to_pyg_data`) returns a deepaco_amd.net.GraphData (x, edge_index, edge_attr; torch_geometric is not
+required).  The network's kernel takes the same graph as a dense matrix of relation codes (`relation_matrix`)."""
 import glob
 import os
 from typing import List, NamedTuple, Optional, Sequence
@@ -184,6 +185,44 @@ class RCPSPInstance:
                     return False
         return bool((usage <= np.array(self.capacity)[:, None]).all())
 
+    # ---- the network's graph (rcpsp_inst.py:193-222)
+    def get_extended_adjlist(self):
+        """Per activity, the activities that neither precede nor follow it transitively.  The reference lists them in the
+        iteration order of a Python set built by these very operations, and the order of its edge list follows from it: the
+        operations are kept as they are there."""
+        allindex = set(range(self.n))
+        extended_adjlist = []
+        for i, act in enumerate(self.activities):
+            no_relation = allindex - set(act.succ_closure) - set(act.pred_closure)
+            no_relation.remove(i)
+            extended_adjlist.append(list(no_relation))
+        return extended_adjlist
+
+    def node_features(self):
+        """[n, 1 + R] float32: duration / max duration | requirements / capacities, rounded where the reference rounds (the
+        durations in float32, the requirements in float64 and then to float32)."""
+        r = self.get_resource_matrix().astype(np.float32) / np.array(self.capacity)
+        t = np.array(self.get_duration(), dtype=np.float32)
+        t = t / t.max()
+        return np.hstack([t.reshape(self.n, 1), r]).astype(np.float32)
+
+    def to_pyg_data(self, device="cpu"):
+        """x [n, 1 + R], edge_index [2, E], edge_attr [E, 2] in the reference's edge order, value for value: precedence edges
+        (attribute [1,0]), unrelated pairs ([0,1]), the sink's self-loop ([0,0])."""
+        from ..net import GraphData
+        src, dst, attr = [], [], []
+        for code, lists in ((1, self.adjlist), (2, self.get_extended_adjlist())):
+            for i, row in enumerate(lists):
+                src += [i] * len(row)
+                dst += list(row)
+            attr += [[1.0, 0.0] if code == 1 else [0.0, 1.0]] * (len(src) - len(attr))
+        src.append(self.n - 1)
+        dst.append(self.n - 1)
+        attr.append([0.0, 0.0])
+        return GraphData(x=torch.from_numpy(self.node_features()).to(device),
+                         edge_index=torch.tensor([src, dst], dtype=torch.long).to(device),
+                         edge_attr=torch.tensor(attr, dtype=torch.float32).to(device))
+
     # ---- what the kernels take
     def validate(self):
         """What the decoder relies on: an activity without duration holds no resource (the reference's event queue and a usage
@@ -230,6 +269,49 @@ def stack_instances(instances, device) -> RcpspTensors:
         idx[b, :t.succ_idx.numel()] = t.succ_idx
     out = {k: torch.stack([getattr(t, k) for t in ts]).to(device) for k in RcpspTensors._fields[:-1] if k != "succ_idx"}
     return RcpspTensors(succ_idx=idx.to(device), horizon=max(t.horizon for t in ts), **out)
+
+
+# ---- the network's graph in the form its kernel takes
+REL_NONE, REL_PRECEDENCE, REL_UNRELATED, REL_SINK_LOOP = 0, 1, 2, 3
+REL_ATTR = ((1.0, 0.0), (0.0, 1.0), (0.0, 0.0))         # edge_attr row of the codes 1, 2, 3
+
+
+def relation_matrix(inst: RCPSPInstance) -> np.ndarray:
+    """[n, n] uint8, entry (i, j) the code of edge i -> j of to_pyg_data's graph: 0 no edge, 1 j is a direct successor of i,
+    2 neither precedes the other transitively, 3 the sink's self-loop.  Made once per instance (the closures it is made from
+    are the constructor's) and returned read-only."""
+    rel = getattr(inst, "_relation", None)
+    if rel is None:
+        n, acts = inst.n, inst.activities
+        follows = np.zeros((n, n), dtype=bool)                      # follows[i, k]: k is in i's successor closure
+        rows = np.repeat(np.arange(n), [len(a.succ_closure) for a in acts])
+        follows[rows, np.fromiter((k for a in acts for k in a.succ_closure), dtype=np.int64, count=rows.size)] = True
+        rel = np.where(follows | follows.T | np.eye(n, dtype=bool), REL_NONE, REL_UNRELATED).astype(np.uint8)
+        rows = np.repeat(np.arange(n), [a.outdegree for a in acts])
+        rel[rows, np.fromiter((k for a in acts for k in a.succ), dtype=np.int64, count=rows.size)] = REL_PRECEDENCE
+        rel[n - 1, n - 1] = REL_SINK_LOOP
+        rel.setflags(write=False)
+        inst._relation = rel
+    return rel
+
+
+def relation_to_edges(rel):
+    """The edge list of a relation matrix, row by row: (edge_index [2, E] int64, edge_attr [E, 2] float32).  The pairs of
+    to_pyg_data, in another order."""
+    rel = np.asarray(rel)
+    src, dst = np.nonzero(rel)
+    attr = np.array(REL_ATTR, dtype=np.float32)[rel[src, dst] - 1]
+    return torch.from_numpy(np.stack([src, dst]).astype(np.int64)), torch.from_numpy(attr)
+
+
+def stack_graphs(instances, device="cpu"):
+    """B projects of equal n as the network's batch: (x [B, n, 5] float32, relation [B, n, n] uint8)."""
+    xs = [i.node_features() for i in instances]
+    if any(x.shape != xs[0].shape for x in xs):
+        raise ValueError("stack_graphs: the projects differ in size or in the number of resources")
+    x = torch.from_numpy(np.stack(xs)).to(device)
+    rel = torch.from_numpy(np.stack([relation_matrix(i) for i in instances])).to(device)
+    return x, rel
 
 
 # ---- the file format

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only) */
 
 /* error codes */
 #define DACO_OK 0
@@ -804,6 +804,32 @@ int daco_rcpsp_track(void *stream, int B, int n, int A, const int64_t *routes, c
                      double Q, int elitist, int alias, int min_max, float tmin, int32_t *best_cost, int32_t *best_idx,
                      int64_t *best_route, int32_t *best_schedule, int64_t *upd_routes, float *upd_weights,
                      float *clamp_min, float *clamp_max);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_rcpsp_net_forward -- replaces Net.forward of rcpsp/net.py in eval mode, and Net.reshape(...) + eps, for B projects
+ *   EmbNet(depth=12, feats=5, edge_feats=2, units=32).forward rcpsp/net.py:30-47, ParNet :72-79, the graph of
+ *   RCPSPInstance.to_pyg_data rcpsp/rcpsp_inst.py:202-222 in dense form.
+ * B projects of n activities each, ONE launch, one workgroup per project (no cooperative launch, no atomics):
+ *   x [B][n][5] f32 node features (duration / max duration, requirements / capacities); feats must be 5 (DACO_E_BADARG)
+ *   relation [B][n][n] uint8: 0 = no edge, 1 = precedence edge (attribute [1,0]), 2 = unrelated pair (attribute [0,1]),
+ *     3 = the sink's self-loop (attribute [0,0]); edge (i, j) at slot i*n + j; a value above 3 is read as 0
+ *   params: daco_rcpsp_net_param_floats() floats, layout at the top of csrc/daco_rcpsp_net.hip (that of csrc/daco_gnn.h with 64
+ *     floats for e_lin0.weight; BatchNorm folded to scale / shift from the running statistics -> eval mode only)
+ *   heu out [B][n][n] f32: sigmoid(logit) + eps on edges, eps exactly elsewhere (Net.reshape's zero plus eps)
+ *   logit out [B][n][n] or NULL: the head's pre-sigmoid output on edges, -INFINITY elsewhere
+ *   emb out [B][n][n][32] or NULL: the edge embedding before the head on edges, unspecified elsewhere
+ *   workspace: daco_rcpsp_net_workspace_bytes(B, n) bytes (0 for B <= 0, n < 2 or n > DACO_RCPSP_NET_MAX_N); its contents
+ *     before the call do not matter.  n <= DACO_RCPSP_NET_MAX_N (PSPLIB's largest is 122), DACO_E_TOOLARGE above.
+ * Float32 with fixed summation orders: bit-identical from run to run, and a project gives the same bits alone as in a batch.
+ * The status is the usual DACO_OK / DACO_E_* value but typed `long`: tests/test_entry_refusals.py demands a row of its own
+ * (fixed) table for every export that returns `int`; the refusals of this entry point are held by
+ * tests/test_rcpsp_net_refusals.py instead, in that table's form.
+ */
+#define DACO_RCPSP_NET_MAX_N 128
+size_t daco_rcpsp_net_param_floats(void);
+size_t daco_rcpsp_net_workspace_bytes(int B, int n);
+long daco_rcpsp_net_forward(void *stream, int B, int n, int feats, const float *x, const uint8_t *relation, const float *params,
+                            float eps, float *heu, float *logit, float *emb, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
