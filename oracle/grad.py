@@ -23,70 +23,138 @@ def _dp_deta(tau_row, eta_row, alpha, beta, p):
     return np.where(eta_row != 0, beta * p / safe, at_zero)
 
 
+class _Aux:
+    """What tsp_grad / cvrp_grad hand back through `stats` besides the two counts, for the tests that hold a kernel to them:
+    absum [n, n] (the sum of the absolute values of each entry's terms, as sibling_grad's), S [rows-1, A] the float64 masked
+    row sums (nan past the route), prob [rows-1, A] p_j / S before the clamp, inside [rows-1, A] (the draw is inside the clamp;
+    `unclamped` is the count of those that carry weight), union [n, n] (k was open at some draw made from row i, weighted or
+    not), support [n, n] (the same over the draws that are differentiated: weighted and inside the clamp -- the gradient is
+    exactly zero elsewhere)."""
+
+    def __init__(self, n, rows, A):
+        self.absum = np.zeros((n, n), np.float64)
+        self.union = np.zeros((n, n), bool)
+        self.support = np.zeros((n, n), bool)
+        self.S = np.full((rows - 1, A), np.nan)
+        self.prob = np.full((rows - 1, A), np.nan)
+        self.inside = np.zeros((rows - 1, A), bool)
+
+    def draw(self, t, a, prev, open_, S, pr, inside):
+        self.union[prev] |= open_
+        self.S[t - 1, a], self.prob[t - 1, a], self.inside[t - 1, a] = S, pr, inside
+
+    def into(self, stats):
+        stats.update(absum=self.absum, union=self.union, support=self.support, S=self.S, prob=self.prob, inside=self.inside)
+
+
+def _draw(out, aux, tau_row, eta_row, alpha, beta, open_, prev, j, g, t, a):
+    """One draw of either construction: adds g * d log clamp(p_j / S) / d eta[prev] to out -> (carries weight, inside the clamp)."""
+    p = _pw(tau_row, alpha) * _pw(eta_row, beta) * open_
+    S = p.sum()
+    with np.errstate(invalid="ignore"):                 # (S = 0: a route replayed under a rule that closes all it could take)
+        ratio = p[j] / S
+    pr = np.float32(ratio)
+    inside = bool(EPS < pr < np.float32(1) - EPS)
+    if aux is not None:
+        aux.draw(t, a, prev, open_, S, ratio, inside)
+    if inside and g != 0.0:
+        d = g * _dp_deta(tau_row, eta_row, alpha, beta, p) * open_ / S
+        out[prev] -= d
+        out[prev, j] += g * beta / eta_row[j]
+        if aux is not None:
+            aux.support[prev] |= open_
+            aux.absum[prev] += np.abs(d)
+            aux.absum[prev, j] += abs(g * beta / eta_row[j])
+    return g != 0.0, inside and g != 0.0
+
+
 def tsp_grad(tau, eta, alpha, beta, paths, grad_logp, stats=None):
-    """stats: a dict that receives `carrying` (draws with a non-zero weight) and `unclamped` (those of them inside the clamp)."""
+    """stats: a dict that receives `carrying` (draws with a non-zero weight), `unclamped` (those of them inside the clamp)
+    and the arrays of _Aux."""
     carrying = flowing = 0
     n, A = paths.shape
     tau64, eta64 = tau.astype(np.float64), eta.astype(np.float64)
     out = np.zeros((n, n), np.float64)
+    aux = _Aux(n, n, A) if stats is not None else None
     for a in range(A):
         open_ = np.ones(n, bool)
         prev = int(paths[0, a])
         open_[prev] = False
         for t in range(1, n):
             j = int(paths[t, a])
-            p = _pw(tau64[prev], alpha) * _pw(eta64[prev], beta) * open_
-            S = p.sum()
-            pr = np.float32(p[j] / S)
-            g = float(grad_logp[t - 1, a])
-            carrying += g != 0.0
-            if EPS < pr < np.float32(1) - EPS and g != 0.0:
-                flowing += 1
-                out[prev] -= g * _dp_deta(tau64[prev], eta64[prev], alpha, beta, p) * open_ / S
-                out[prev, j] += g * beta / eta64[prev, j]
+            c, f = _draw(out, aux, tau64[prev], eta64[prev], alpha, beta, open_, prev, j, float(grad_logp[t - 1, a]), t, a)
+            carrying += c
+            flowing += f
             open_[j] = False
             prev = j
     if stats is not None:
+        aux.into(stats)
         stats.update(carrying=int(carrying), unclamped=int(flowing))
     return out
 
 
-def cvrp_grad(tau, eta, alpha, beta, demand, capacity, paths, grad_logp, stats=None):
-    """stats: as in tsp_grad (the draws after an ant's route is complete are not counted)."""
+def cvrp_open_sets(demand, capacity, path, n, float64_load=False):
+    """The open set of every draw of one ant's route `path` (depot first) under the reference's rule, cvrp/aco.py:176-205:
+    visited customers closed, the depot closed at the depot while customers are left, `demand > capacity - used` closed --
+    in float32 as cvrp/ keeps its load, or with `float64_load` in double as cvrp_nls/aco.py:254-272 does on its float64
+    demands.  Yields (t, prev, j, open [n] bool) until the route is complete."""
+    f = np.float64 if float64_load else np.float32
+    if float64_load:
+        demand = np.asarray(demand, np.float64)
+    vis = np.zeros(n, bool)
+    prev, remaining, used = 0, n - 1, f(0)
+    for t in range(1, len(path)):
+        if remaining == 0 and prev == 0:
+            break                                       # done: p(depot) = 1 is clamped, no gradient
+        j = int(path[t])
+        open_ = ~vis
+        open_[0] = not (prev == 0 and remaining > 0)
+        open_ &= ~(demand > f(capacity) - used)
+        yield t, prev, j, open_
+        if j != 0:
+            vis[j] = True
+            remaining -= 1
+        else:
+            used = f(0)
+        used = f(used + demand[j])
+        prev = j
+
+
+def cvrp_grad(tau, eta, alpha, beta, demand, capacity, paths, grad_logp, stats=None, float64_load=False):
+    """stats: as in tsp_grad (the draws after an ant's route is complete are not counted).  float64_load: see cvrp_open_sets."""
     carrying = flowing = 0
     L, A = paths.shape
     n = tau.shape[0]
     tau64, eta64 = tau.astype(np.float64), eta.astype(np.float64)
     out = np.zeros((n, n), np.float64)
+    aux = _Aux(n, L, A) if stats is not None else None
     for a in range(A):
-        vis = np.zeros(n, bool)
-        prev, remaining, used = 0, n - 1, np.float32(0)
-        for t in range(1, L):
-            if remaining == 0 and prev == 0:
-                break                                   # done: p(depot) = 1 is clamped, no gradient
-            j = int(paths[t, a])
-            open_ = ~vis
-            open_[0] = not (prev == 0 and remaining > 0)
-            open_ &= ~(demand > np.float32(capacity) - used)
-            p = _pw(tau64[prev], alpha) * _pw(eta64[prev], beta) * open_
-            S = p.sum()
-            pr = np.float32(p[j] / S)
-            g = float(grad_logp[t - 1, a])
-            carrying += g != 0.0
-            if EPS < pr < np.float32(1) - EPS and g != 0.0:
-                flowing += 1
-                out[prev] -= g * beta * p / (eta64[prev] * S)
-                out[prev, j] += g * beta / eta64[prev, j]
-            if j != 0:
-                vis[j] = True
-                remaining -= 1
-            else:
-                used = np.float32(0)
-            used = np.float32(used + demand[j])
-            prev = j
+        for t, prev, j, open_ in cvrp_open_sets(demand, capacity, paths[:, a], n, float64_load):
+            c, f = _draw(out, aux, tau64[prev], eta64[prev], alpha, beta, open_, prev, j, float(grad_logp[t - 1, a]), t, a)
+            carrying += c
+            flowing += f
     if stats is not None:
+        aux.into(stats)
         stats.update(carrying=int(carrying), unclamped=int(flowing))
     return out
+
+
+def batch_grad(tau, eta, alpha, beta, paths, grad_logp, demand=None, capacity=None, float64_load=False):
+    """tsp_grad (demand None) or cvrp_grad for the B instances of a batch: tau [B, n, n] or [n, n] (shared), eta [B, n, n],
+    paths [B, rows, A], grad_logp [B, rows-1, A], demand [B, n] or [n] -> (grad [B, n, n] float64, [stats of instance b])."""
+    B = paths.shape[0]
+    outs, allstats = [], []
+    for b in range(B):
+        st = {}
+        t = tau if tau.ndim == 2 else tau[b]
+        if demand is None:
+            g = tsp_grad(t, eta[b], alpha, beta, paths[b], grad_logp[b], stats=st)
+        else:
+            d = demand if demand.ndim == 1 else demand[b]
+            g = cvrp_grad(t, eta[b], alpha, beta, d, capacity, paths[b], grad_logp[b], stats=st, float64_load=float64_load)
+        outs.append(g)
+        allstats.append(st)
+    return np.stack(outs), allstats
 
 
 

@@ -246,10 +246,20 @@ def test_cvrp_nls_float64_instances_reproduce_the_reference_routes(name):
     L = min(p32.shape[0], paths.shape[0])
     assert not torch.equal(p32[:L], paths[:L])
     # gradient: closed form on the reference's routes with the float64 capacity rule (oracle), float32 elsewhere
-    loss = (logp.sum(0) * torch.linspace(-1.0, 1.0, A, device=logp.device)).sum()
+    w = torch.linspace(-1.0, 1.0, A, device=logp.device)
+    loss = (logp.sum(0) * w).sum()
     loss.backward()
     assert bool(torch.isfinite(heu.grad).all()) and float(heu.grad.abs().max()) > 0
     assert heu.grad.shape == (len(g["demand"]), len(g["demand"]))
+    from oracle import grad as ograd
+    import sample_grad_cases as sc
+    G = np.tile(w.cpu().numpy()[None, :], (paths.shape[0] - 1, 1))
+    st = {}
+    ref = ograd.cvrp_grad(g["pheromone"], g["heuristic"], aco.alpha, aco.beta, g["demand"], float(aco.capacity), g["paths"], G, stats=st,
+                          float64_load=True)
+    assert st["unclamped"] >= 0.5 * st["carrying"] > 0 and not sc.edge_draws(st).any()
+    # (tests/test_sample_grad_spec.py: float32 bookkeeping closes the chosen customer somewhere on each of these fixtures' routes)
+    sc.check_gradient(heu.grad.cpu().numpy(), ref, st, g["heuristic"], name)
 
 
 @pytest.mark.parametrize("n,A,B", [(21, 18, 1), (51, 65, 1), (101, 33, 2), (128, 9, 1), (201, 12, 1), (256, 5, 1), (301, 4, 1), (512, 3, 1), (600, 2, 1)])
