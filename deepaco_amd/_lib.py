@@ -98,6 +98,10 @@ SIGNATURES = {
     "daco_rcpsp_net_param_floats": (_sz, []),
     "daco_rcpsp_net_workspace_bytes": (_sz, [_i, _i]),
     "daco_rcpsp_net_forward": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz]),
+    "daco_rcpsp_net_train_saved_bytes": (_sz, [_i, _i]),
+    "daco_rcpsp_net_train_workspace_bytes": (_sz, [_i, _i]),
+    "daco_rcpsp_net_train_forward": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz]),
+    "daco_rcpsp_net_train_backward": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz]),
     "daco_tsp_nls": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _l, _i, _l, _vp, _vp, _vp]),
 }
 

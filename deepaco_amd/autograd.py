@@ -190,3 +190,32 @@ class RcpspSampleFn(torch.autograd.Function):
         inst, alpha, beta, gamma, c, shape = ctx.meta
         grad = engine.rcpsp_backward(inst, tau, eta, alpha, beta, gamma, c, routes, rowsum, glogp.contiguous())
         return grad.reshape(shape), None, None
+
+
+class RcpspNetFn(torch.autograd.Function):
+    """The RCPSP heuristic network in training mode on HIP with gradients: flat (the parameter block of
+    rcpsp.net.Net.pack_params_train, a differentiable torch.cat whose own backward hands every tensor its slice), x [B, n, 5],
+    relation [B, n, n] uint8 -> (heu [B, n, n] = sigmoid + eps on the graph and eps off it, stats for the running statistics).
+    daco_rcpsp_net_train_forward forward, daco_rcpsp_net_train_backward backward; the context holds the forward's `saved`
+    block, which one backward consumes.  No gradient for x (instance data)."""
+
+    @staticmethod
+    def forward(ctx, flat, x, relation, eps):
+        flat, x = flat.detach(), x.detach()
+        heu, _, stats, saved = engine.rcpsp_net_forward_train(x, relation, flat, eps)
+        ctx.save_for_backward(flat, x, relation)
+        ctx.saved_block = saved
+        ctx.mark_non_differentiable(stats)
+        return heu, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_heu, _gstats):
+        if ctx.saved_block is None:
+            raise RuntimeError("rcpsp.Net (HIP training path): the saved activations of this forward were already consumed by a "
+                               "backward pass -- backward through the same forward a second time is not supported "
+                               "(run the forward again)")
+        flat, x, relation = ctx.saved_tensors
+        grad = engine.rcpsp_net_backward(x, relation, flat, ctx.saved_block, grad_heu)
+        ctx.saved_block = None
+        return grad, None, None, None

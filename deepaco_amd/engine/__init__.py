@@ -15,7 +15,8 @@ from .local_search import (HgsTables, TspLocalSearch, TwoOptTables, cvrp_local_s
 from .mkp_ops import (BatchedMKPVec, mkpv_backward, mkpv_check_flags, mkpv_sample, mkpv_update_, transformer_backward,  # noqa: F401
                       transformer_forward, transformer_forward_train)
 from .rcpsp_ops import (RCPSP_FLAG_ORDER, RCPSP_FLAG_RESOURCE, RCPSP_MAX_HORIZON, RCPSP_MAX_N, RCPSP_MAX_R, RCPSP_NET_MAX_N,  # noqa: F401
-                        BatchedRCPSP, rcpsp_backward, rcpsp_check_flags, rcpsp_net_forward, rcpsp_sample, rcpsp_schedule)
+                        BatchedRCPSP, rcpsp_backward, rcpsp_check_flags, rcpsp_net_backward, rcpsp_net_forward,
+                        rcpsp_net_forward_train, rcpsp_sample, rcpsp_schedule)
 from .sibling_ops import SIB_KINDS, PickService, sibling_backward, sibling_sample  # noqa: F401
 from .tsp_ops import (SPARSE_MAX_N, SPARSE_MIN_N, auto_head_k, head_table, heu_matrix, resolve_sampler, sparse_head,  # noqa: F401
                       sparse_tours16, sparse_workspace, take_auto_top, tsp_knn_graph, tsp_sample, tsp_sample_sparse)

@@ -141,6 +141,64 @@ def rcpsp_net_forward(x, relation, params, eps=1e-10, want_logit=False, want_emb
     return heu, logit, emb
 
 
+def _rcpsp_net_args(who, x, relation, params):
+    _require_gpu(x, relation, params)
+    if x.dim() != 3 or relation.dim() != 3 or relation.dtype != torch.uint8 or relation.shape[0] != x.shape[0] \
+            or tuple(relation.shape[1:]) != (x.shape[1], x.shape[1]):
+        raise _lib.DacoError(f"{who}: x [B, n, {RCPSP_NET_FEATS}] and relation [B, n, n] uint8 expected, got "
+                             f"{tuple(x.shape)} and {tuple(relation.shape)} {relation.dtype}")
+    P = _lib.lib().daco_rcpsp_net_param_floats()
+    if params.dtype != torch.float32 or params.numel() != P:
+        raise _lib.DacoError(f"{who}: {P} float32 parameters expected, got {params.numel()} {params.dtype}")
+    return _f32c(x), relation.contiguous(), params.contiguous()
+
+
+def rcpsp_net_forward_train(x, relation, params, eps=1e-10, want_logit=False):
+    """The training-mode forward of rcpsp/net.py for B projects in one launch (include/deepaco_hip.h
+    daco_rcpsp_net_train_forward): every project is normalised with its own BatchNorm statistics.  params: the flat block of
+    rcpsp.net.Net.pack_params_train (gamma / beta in the BatchNorm slots).  Returns (heu [B, n, n] as rcpsp_net_forward,
+    logit [B, n, n] | None, stats [12, 2 (edge, node), B, 32, 2 (mean, biased variance)], saved: the uint8 block
+    rcpsp_net_backward reads)."""
+    x, relation, params = _rcpsp_net_args("rcpsp_net_forward_train", x, relation, params)
+    B, n, feats = x.shape
+    L = _lib.lib()
+    dev = x.device
+    with _on(dev):
+        heu = torch.empty((B, n, n), dtype=torch.float32, device=dev)
+        logit = torch.empty((B, n, n), dtype=torch.float32, device=dev) if want_logit else None
+        stats = torch.empty((12, 2, B, 32, 2), dtype=torch.float32, device=dev)
+        saved = torch.empty(L.daco_rcpsp_net_train_saved_bytes(B, n), dtype=torch.uint8, device=dev)
+        rc = L.daco_rcpsp_net_train_forward(_stream(dev), B, n, feats, x.data_ptr(), relation.data_ptr(), params.data_ptr(),
+                                            float(eps), heu.data_ptr(), _ptr(logit), stats.data_ptr(), saved.data_ptr(),
+                                            saved.numel())
+    _lib.check(rc, "daco_rcpsp_net_train_forward")
+    return heu, logit, stats, saved
+
+
+def rcpsp_net_backward(x, relation, params, saved, grad_heu, want_per_project=False):
+    """d sum(grad_heu * heu) / d params for a forward of rcpsp_net_forward_train (daco_rcpsp_net_train_backward): the flat
+    gradient in the parameter block's layout, summed over the projects in ascending order.  grad_heu [B, n, n]; entries off the
+    graph are ignored.  `saved` is only read.  want_per_project: -> (gradient, [B, P] every project's own block)."""
+    x, relation, params = _rcpsp_net_args("rcpsp_net_backward", x, relation, params)
+    _require_gpu(saved, grad_heu)
+    B, n, feats = x.shape
+    grad_heu = _f32c(grad_heu)
+    if tuple(grad_heu.shape) != (B, n, n) or saved.dtype != torch.uint8:
+        raise _lib.DacoError(f"rcpsp_net_backward: grad_heu [{B}, {n}, {n}] and the forward's uint8 `saved` expected, got "
+                             f"{tuple(grad_heu.shape)} and {saved.dtype}")
+    L = _lib.lib()
+    dev = x.device
+    with _on(dev):
+        grad = torch.empty_like(params)
+        blocks = torch.empty((B, params.numel()), dtype=torch.float32, device=dev) if want_per_project else None
+        ws = _workspace(dev, L.daco_rcpsp_net_train_workspace_bytes(B, n), "rcpsp_net_train")
+        rc = L.daco_rcpsp_net_train_backward(_stream(dev), B, n, feats, x.data_ptr(), relation.data_ptr(), params.data_ptr(),
+                                             saved.data_ptr(), saved.numel(), grad_heu.data_ptr(), grad.data_ptr(), _ptr(blocks),
+                                             ws.data_ptr(), ws.numel())
+    _lib.check(rc, "daco_rcpsp_net_train_backward")
+    return (grad, blocks) if want_per_project else grad
+
+
 def rcpsp_check_flags(flags):
     """Raise for the flag words of rcpsp_sample / rcpsp_schedule (one per project)."""
     if flags.numel():

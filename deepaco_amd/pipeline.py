@@ -287,3 +287,36 @@ def infer_rcpsp_batch(instances, n_ants, t_aco, heuristic=None, seed=0, sampler=
         done = t
         out.append(colony.best_cost.clone())
     return torch.stack(out), colony
+
+
+def _rcpsp_loss(net, instances, n_ants, seed=0, it=0, noise=None, **acoparam):
+    """The loss of rcpsp/train.ipynb's train_instance for B projects of equal n: one HIP training forward -> B colonies sampled
+    and scheduled with log-probabilities (one launch) -> per project sum_a (cost - mean cost) sum_t logp / n_ants / n, averaged
+    over the projects.  Private: the body of train_rcpsp_batch, with what the tests need.  noise: recorded draws
+    [B, n-1, A, n] instead of the in-kernel stream.  -> (loss, colony, (routes, starts, costs))"""
+    from .autograd import RcpspSampleFn
+    heu = net.forward_batch_train(instances, eps=EPS)
+    col = engine.BatchedRCPSP(instances, n_ants=n_ants, heuristic=heu.detach(), seed=seed, device=heu.device, **acoparam)
+    col.iteration = int(it)
+    routes, logp, starts, costs, flags = RcpspSampleFn.apply(heu, col, noise)
+    col.flags |= flags
+    cost = costs.float()
+    loss = (((cost - cost.mean(dim=1, keepdim=True)) * logp.sum(dim=1)).sum(dim=1) / n_ants / col.n).mean()
+    return loss, col, (routes, starts, costs)
+
+
+def train_rcpsp_batch(net, optimizer, instances, n_ants, seed=0, it=0, *, _noise=None, max_norm=1.0, **acoparam):
+    """One optimiser step of rcpsp/train.ipynb (`train_instance`) for B projects of equal n at once, without a host
+    synchronisation: one training forward of the network for the batch (HIP, whatever net.grad_path says), B colonies
+    constructed and scheduled in one launch, the REINFORCE loss of every project averaged over the projects, one backward
+    (daco_rcpsp_backward, daco_rcpsp_net_train_backward), clip_grad_norm_(max_norm=1.0) as the notebook has it, and one
+    optimizer.step().  instances: a list of rcpsp.RCPSPInstance; acoparam: what engine.BatchedRCPSP takes.  Returns the
+    detached loss.  `_noise` is a test hook, not part of the surface (recorded draws [B, n-1, A, n]); the colonies' feasibility
+    flags are not read here: that would synchronise."""
+    net.train()
+    loss, _, _ = _rcpsp_loss(net, instances, n_ants, seed, it, _noise, **acoparam)
+    optimizer.zero_grad()
+    loss.backward()
+    torch.nn.utils.clip_grad_norm_(parameters=net.parameters(), max_norm=max_norm, norm_type=2)
+    optimizer.step()
+    return loss.detach()

@@ -7,10 +7,14 @@ forward(pyg, require_heu=True) -> (None, heu [E]) in the caller's edge order:
     (csrc/daco_rcpsp_net.hip).  The kernel takes the graph as a dense matrix of relation codes, derived here from
     edge_index / edge_attr (duplicate pairs and attribute rows other than [1,0], [0,1], [0,0] are refused), and the values
     are gathered back into the caller's edge order.
-  * training mode, or a gradient required -> the module tree as torch ops on the tensors' device (a HIP device: there is no
-    CPU compute path in the product, the CPU tests call the module tree as the comparator only).  This is what
-    train.ipynb's train_instance runs on, through autograd.RcpspSampleFn; a HIP backward for this network is a later change.
+  * training mode with `grad_path = "hip"` -> autograd.RcpspNetFn: daco_rcpsp_net_train_forward / _backward
+    (csrc/daco_rcpsp_net_train.hip), one launch per direction, BatchNorm on the project's own statistics, the running
+    statistics updated as the reference's forward leaves them.  pipeline.train_rcpsp_batch always takes this path.
+  * training mode with `grad_path = "torch"` (the default), or eval mode with a gradient required (either setting: gradients
+    with fixed statistics have no kernel) -> the module tree as torch ops on the tensors' device (a HIP device: there is no
+    CPU compute path in the product, the CPU tests call the module tree as the comparator only).
 forward_batch(instances, eps=1e-10) -> [B, n, n]: `Net.reshape(pyg, heu) + eps` for B projects of equal n in one launch.
+forward_batch_train(instances, eps=1e-10) -> the same in training mode, with a graph (HIP path whatever grad_path says).
 Only R = 4 resources (feats = 5, fixed by the checkpoints): the reference's padding branch for fewer cannot run."""
 import torch
 from torch import nn
@@ -53,8 +57,13 @@ def relation_from_edges(n, edge_index, edge_attr):
 
 
 class Net(nn.Module):
-    def __init__(self):
+    GRAD_PATHS = ("torch", "hip")
+
+    def __init__(self, grad_path="torch"):
         super().__init__()
+        if grad_path not in self.GRAD_PATHS:
+            raise ValueError(f"rcpsp.Net: grad_path is one of {self.GRAD_PATHS}")
+        self.grad_path = grad_path
         self.emb_net = EmbNet()
         self.par_net_heu = ParNet()
         self._packed = None
@@ -67,6 +76,8 @@ class Net(nn.Module):
         if not require_heu:
             return None, None
         needs_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if self.training and self.grad_path == "hip":
+            return None, self.forward_train_hip(pyg)
         if self.training or needs_graph:
             return None, self.forward_torch(pyg)
         return None, self.forward_hip(pyg)
@@ -87,6 +98,101 @@ class Net(nn.Module):
         matrix = torch.zeros(size=(n_nodes, n_nodes), device=pyg.x.device, dtype=vector.dtype)
         matrix[pyg.edge_index[0], pyg.edge_index[1]] = vector
         return matrix
+
+    # ------------------------------------------------------------------ HIP training path
+    def pack_params_train(self):
+        """Flat parameter block for the training kernels (the layout of csrc/daco_rcpsp_net.hip with gamma / beta in the
+        BatchNorm slots), built from the live parameters with differentiable ops, so that autograd hands the flat gradient back
+        to every nn.Parameter.  The last layer's node update (v_lins1.11, v_lins2.11, v_bns.11) feeds nothing: those slices
+        enter detached, so their .grad stays None as on the torch-op path (AdamW decays a parameter whose gradient is zero
+        and skips one whose gradient is None)."""
+        e = self.emb_net
+        parts = [e.v_lin0.weight.reshape(-1), e.v_lin0.bias, e.e_lin0.weight.reshape(-1), e.e_lin0.bias]
+        for i in range(DEPTH):
+            live = (lambda t: t) if i < DEPTH - 1 else (lambda t: t.detach())
+            Wv = torch.cat([live(e.v_lins1[i].weight), live(e.v_lins2[i].weight), e.v_lins3[i].weight, e.v_lins4[i].weight], 0)
+            bv = torch.cat([live(e.v_lins1[i].bias), live(e.v_lins2[i].bias), e.v_lins3[i].bias, e.v_lins4[i].bias], 0)
+            parts += [Wv.t().reshape(-1), bv, e.e_lins0[i].weight.reshape(-1), e.e_lins0[i].bias,
+                      live(e.v_bns[i].module.weight), live(e.v_bns[i].module.bias), e.e_bns[i].module.weight, e.e_bns[i].module.bias]
+        for lin in self.par_net_heu.lins:
+            parts += [lin.weight.reshape(-1), lin.bias]
+        return torch.cat([p.float().reshape(-1) for p in parts])
+
+    @torch.no_grad()
+    def _update_running_stats(self, stats, count_e, n):
+        """BatchNorm1d's training-mode side effect for all 24 BatchNorms (v_bns.11 included: the reference calls it, its output
+        is dead), from the statistics the kernel reports, as B successive single-project reference forwards would leave
+        them -- the rule of deepaco_amd.net.Net._update_running_stats with every project's own edge count.  stats
+        [12, 2, B, 32, 2], count_e [B]."""
+        e = self.emb_net
+        bns = [(i, w, (e.e_bns[i] if w == 0 else e.v_bns[i]).module) for i in range(DEPTH) for w in (0, 1)]
+        cfg = {(bool(bn.track_running_stats and bn.running_mean is not None), bn.momentum) for _, _, bn in bns}
+        if len(cfg) != 1:
+            raise _lib.DacoError("rcpsp.Net: the BatchNorm modules of one network must share track_running_stats / momentum")
+        tracks, momentum = next(iter(cfg))
+        if not tracks:
+            return
+        B = stats.shape[2]
+        ce = count_e.to(torch.float32).view(B, 1)
+        mean = stats[..., 0]                                                              # [12, 2, B, 32]
+        var = torch.stack((stats[:, 0, :, :, 1] * (ce / (ce - 1).clamp(min=1)),
+                           stats[:, 1, :, :, 1] * (n / max(n - 1, 1))), dim=1)             # unbiased, as BatchNorm1d tracks it
+        rm, rv = [bn.running_mean for _, _, bn in bns], [bn.running_var for _, _, bn in bns]
+        nbt = [bn.num_batches_tracked for _, _, bn in bns]
+        if momentum is None:
+            k = float(nbt[0])
+            add_m, add_v = mean.sum(2) / (k + B), var.sum(2) / (k + B)
+            keep = k / (k + B)
+        else:
+            m = momentum
+            decay = ((1 - m) ** torch.arange(B - 1, -1, -1, device=stats.device, dtype=torch.float32)).view(1, 1, B, 1)
+            add_m, add_v = m * (decay * mean).sum(2), m * (decay * var).sum(2)
+            keep = (1 - m) ** B
+        torch._foreach_mul_(rm + rv, keep)
+        torch._foreach_add_(rm, [add_m[i, w] for i, w, _ in bns])
+        torch._foreach_add_(rv, [add_v[i, w] for i, w, _ in bns])
+        torch._foreach_add_(nbt, B)
+
+    def forward_relation_train(self, x, relation, eps=1e-10):
+        """x [B, n, 5], relation [B, n, n] uint8 on a HIP device -> heu [B, n, n] of the training-mode network, differentiable
+        with respect to the parameters (autograd.RcpspNetFn); updates the BatchNorm running statistics."""
+        from ..autograd import RcpspNetFn
+        if not self.training:
+            raise _lib.DacoError("rcpsp.Net: the HIP gradient path is the training-mode network (batch statistics): call .train()")
+        if not x.is_cuda:
+            raise _lib.DacoError("deepaco_amd.rcpsp.Net runs on a HIP device only (got CPU tensors)")
+        self._check_feats(x.shape[-1])
+        if x.shape[1] > engine.RCPSP_NET_MAX_N:
+            raise _lib.DacoTooLarge(f"rcpsp.Net: n={x.shape[1]} exceeds {engine.RCPSP_NET_MAX_N}")
+        flat = self.pack_params_train()
+        if flat.device != x.device:
+            raise _lib.DacoError(f"rcpsp.Net: parameters on {flat.device}, graph on {x.device}")
+        heu, stats = RcpspNetFn.apply(flat, x, relation, float(eps))
+        self._update_running_stats(stats, ((relation != 0) & (relation < 4)).sum(dim=(1, 2)), x.shape[1])   # (a code above 3 is no edge)
+        return heu
+
+    def forward_train_hip(self, pyg):
+        """One graph through the training kernels; the values come back in the caller's edge order, gathered from the dense
+        output with ordinary indexing (autograd scatters the gradient back)."""
+        x = pyg.x
+        if not x.is_cuda:
+            raise _lib.DacoError("deepaco_amd.rcpsp.Net runs on a HIP device only (got CPU tensors)")
+        n = x.shape[0]
+        self._check_feats(x.shape[1])
+        if n > engine.RCPSP_NET_MAX_N:
+            raise _lib.DacoTooLarge(f"rcpsp.Net: n={n} exceeds {engine.RCPSP_NET_MAX_N}")
+        rel = relation_from_edges(n, pyg.edge_index, pyg.edge_attr)
+        heu = self.forward_relation_train(x.unsqueeze(0), rel.unsqueeze(0), 0.0)
+        return heu[0][pyg.edge_index[0], pyg.edge_index[1]]
+
+    def forward_batch_train(self, instances, eps=1e-10):
+        """`Net.reshape(pyg, heu) + eps` of every project of a list of RCPSPInstance of equal n in training mode -> [B, n, n]
+        with a graph, one launch, on the parameters' device."""
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise _lib.DacoError("deepaco_amd.rcpsp.Net runs on a HIP device only (the parameters are on the CPU)")
+        x, rel = rcpsp_inst.stack_graphs(instances, dev)
+        return self.forward_relation_train(x, rel, eps)
 
     # ------------------------------------------------------------------ HIP inference path
     @staticmethod

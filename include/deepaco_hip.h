@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*) */
 
 /* error codes */
 #define DACO_OK 0
@@ -830,6 +830,33 @@ size_t daco_rcpsp_net_param_floats(void);
 size_t daco_rcpsp_net_workspace_bytes(int B, int n);
 long daco_rcpsp_net_forward(void *stream, int B, int n, int feats, const float *x, const uint8_t *relation, const float *params,
                             float eps, float *heu, float *logit, float *emb, void *workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_rcpsp_net_train_forward / _backward -- Net.forward of rcpsp/net.py in TRAINING mode (gnn.BatchNorm normalises every
+ * project with its own statistics: the edge BatchNorms over the project's E edges, the node BatchNorms over its n nodes,
+ * biased variance, eps 1e-5) and its gradient with respect to the parameters.  Arguments as daco_rcpsp_net_forward, except:
+ *   params: the same layout with gamma | beta (not folded scale | shift) in the BatchNorm slots
+ *   stats out [12][2 (edge, node)][B][32][2 (mean, biased variance)]: what the running statistics are updated from
+ *   saved: daco_rcpsp_net_train_saved_bytes(B, n) bytes the forward fills and the backward only reads (layout at the top of
+ *     csrc/daco_rcpsp_net_train.hip; (25 n^2 + 24 n) * 128 + 6144 bytes per project, rounded up to 256: 50.4 MB at n = 128)
+ *   grad_heu [B][n][n]: d loss / d heu; entries off the graph are not read
+ *   grad_params out: daco_rcpsp_net_param_floats() floats, the sum over the projects in ascending b, d/dgamma and d/dbeta in the
+ *     BatchNorm slots; grad_blocks out [B][param_floats] or NULL: every project's own block
+ *   workspace (backward): daco_rcpsp_net_train_workspace_bytes(B, n) bytes; contents before the call do not matter
+ * One launch per direction, one workgroup per project, plus one small launch that adds the blocks; float64 workgroup sums in
+ * a fixed order: bit-identical from call to call, and a project's block is the same alone as in a batch.  Refusals (before any
+ * HIP call): bad argument / null pointer DACO_E_BADARG, n > DACO_RCPSP_NET_MAX_N DACO_E_TOOLARGE, short saved or workspace
+ * DACO_E_WORKSPACE.  Both size functions give 0 for B <= 0, n < 2 or n > DACO_RCPSP_NET_MAX_N.  The status is a `long`, as
+ * daco_rcpsp_net_forward's; its rows are in tests/test_rcpsp_net_train_refusals.py.
+ */
+size_t daco_rcpsp_net_train_saved_bytes(int B, int n);
+size_t daco_rcpsp_net_train_workspace_bytes(int B, int n);
+long daco_rcpsp_net_train_forward(void *stream, int B, int n, int feats, const float *x, const uint8_t *relation,
+                                  const float *params, float eps, float *heu, float *logit, float *stats, void *saved,
+                                  size_t saved_bytes);
+long daco_rcpsp_net_train_backward(void *stream, int B, int n, int feats, const float *x, const uint8_t *relation,
+                                   const float *params, const void *saved, size_t saved_bytes, const float *grad_heu,
+                                   float *grad_params, float *grad_blocks, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
