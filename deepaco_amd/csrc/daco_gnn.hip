@@ -26,22 +26,8 @@ constexpr int U = 32;                       // units
 
 constexpr int GNN_SPLIT_MIN_EDGES = 200000;   // above this a layer is two launches (edge | node), below it one
 
-// Activations.  e^-x in six full-rate instructions instead of libm's twelve (the two activations are evaluated 2*E*32 times
-// per layer and were most of a layer's VALU work): t = -x*log2(e) as the rounded product plus its exact residual (two fmas,
-// the second adds the low word of log2 e), 2^t on the hardware exponential (its range reduction is exact), first-order
-// correction for the residual: ~1 ulp, like libm.  1/(1+e^-x) with the hardware reciprocal (1 ulp).  The two-wide
-// versions are the same arithmetic on v_pk_* instructions.
+// The two-wide versions of the activations of daco_gnn.h: the same arithmetic on v_pk_* instructions.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.92596299e-8f, LN2F = 0.693147182464599609375f;
-__device__ inline float exp_neg(float x) {
-  const float nx = fminf(-x, 87.0f);                      // beyond: e^-x > 1e37, sigmoid and silu are 0 to f32 either way
-  const float t = nx * L2E_HI;
-  const float lo = fmaf(nx, L2E_LO, fmaf(nx, L2E_HI, -t));
-  const float e = __builtin_amdgcn_exp2f(t);
-  return fmaf(e, lo * LN2F, e);
-}
-__device__ inline float sigmoidf(float x) { return __builtin_amdgcn_rcpf(1.0f + exp_neg(x)); }
-__device__ inline float silu(float x) { return x * sigmoidf(x); }
 __device__ inline f32x2 sigmoid2(f32x2 x) {
   f32x2 nx;
   nx.x = fminf(-x.x, 87.0f); nx.y = fminf(-x.y, 87.0f);

@@ -1,10 +1,12 @@
 // daco_rcpsp_net_train.hip -- the heuristic network of rcpsp/net.py in TRAINING mode (gnn.BatchNorm on the statistics of each
 // project), forward and backward, on the dense relation form of daco_rcpsp_net.hip: B projects of equal n, one workgroup of
 // 512 threads per project, ONE launch per direction (+ one small launch that adds the B per-project gradient blocks in ascending
-// b).  No cooperative launch, no grid barrier, no atomics.  The device code of daco_rcpsp_net.hip is not shared but defined
-// again here (that translation unit stays byte-identical).
+// b).  No cooperative launch, no grid barrier, no atomics.  This file holds the `saved` and workspace layouts, the reductions,
+// the training layer, the backward and the entry points; the parameter block's layout, the LDS carve (with its float64
+// reduction block and row counts), the device helpers that the forward shares with the eval-mode kernel (input linears, row and
+// column compaction, node linears, head) and the host side's refusals are in daco_rcpsp_net.h.
 //
-// ---- parameter block: the layout of daco_rcpsp_net.hip with gamma | beta in the BatchNorm slots (bn_v, then bn_e).  The
+// ---- parameter block: the layout of daco_rcpsp_net.h with gamma | beta in the BatchNorm slots (bn_v, then bn_e).  The
 // gradient block has the same layout, d/dgamma and d/dbeta in those slots.
 //
 // ---- `saved`, per project (floats; the per-project stride is rounded up to 256 bytes), written by the forward, read-only to
@@ -34,47 +36,23 @@
 //            sigmoid(w_ij) / count_i -> gX[:, 32:64].  No atomics: the order is fixed.
 //   node B : gWvT = xs^T gX, gbv, gxs += gX WvT^T
 // then v_lin0, e_lin0 (three per-code sums of gw through silu') -- plain f32 FMAs, a lane per channel, as the forward.
-#include "daco_gnn.h"
-#include "daco_host.h"
+#include "daco_rcpsp_net.h"
 
 namespace daco {
 namespace {
 
-constexpr int RT_FEATS = 5, RT_THREADS = 512, RT_WAVES = RT_THREADS / 64, RT_SLOTS = 16, RT_DEPTH = 12;
-constexpr int RT_OFF_ELIN = 32 * RT_FEATS + 32;
-constexpr int RT_OFF_LAYER0 = RT_OFF_ELIN + 64 + 32;
-constexpr int RT_OFF_HEAD = RT_OFF_LAYER0 + RT_DEPTH * LAYER_FLOATS;
-constexpr int RT_PARAM_FLOATS = RT_OFF_HEAD + HEAD_FLOATS;
-constexpr int RT_L_BV = 32 * 128, RT_L_WE = RT_L_BV + 128, RT_L_BE = RT_L_WE + 1024, RT_L_BNV = RT_L_BE + 32, RT_L_BNE = RT_L_BNV + 64;
-constexpr int RT_H_B1 = 1024, RT_H_W2 = 1056, RT_H_B2 = 2080, RT_H_W3 = 2112, RT_H_B3 = 2144;
-constexpr size_t RT_LDS_PLAIN = 64 * 1024, RT_LDS_MAX = 160 * 1024;
 constexpr double RT_BN_EPS = 1e-5;
-
-constexpr float RT_L2E_HI = 1.44269502162933349609375f, RT_L2E_LO = 1.92596299e-8f, RT_LN2F = 0.693147182464599609375f;
-__device__ inline float rt_exp_neg(float x) {
-  const float nx = fminf(-x, 87.0f);
-  const float t = nx * RT_L2E_HI;
-  const float lo = fmaf(nx, RT_L2E_LO, fmaf(nx, RT_L2E_HI, -t));
-  const float e = __builtin_amdgcn_exp2f(t);
-  return fmaf(e, lo * RT_LN2F, e);
-}
-__device__ inline float rt_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + rt_exp_neg(x)); }
-__device__ inline float rt_silu(float x) { return x * rt_sigmoid(x); }
-__device__ inline float rt_dsilu(float x) {
-  const float s = rt_sigmoid(x);
-  return s * fmaf(x, 1.0f - s, 1.0f);
-}
 
 // per-project pieces of `saved` and of the backward's workspace (floats)
 struct RtSaved {
   size_t n2, nu;
   __host__ __device__ explicit RtSaved(int n) : n2((size_t)n * n * 32), nu((size_t)n * 32) {}
   __host__ __device__ size_t w(int l) const { return (size_t)l * n2; }
-  __host__ __device__ size_t ze(int l) const { return (size_t)(13 + l) * n2; }
-  __host__ __device__ size_t xs(int l) const { return 25 * n2 + (size_t)l * nu; }
-  __host__ __device__ size_t zv(int l) const { return 25 * n2 + (size_t)(12 + l) * nu; }
-  __host__ __device__ size_t bn(int l) const { return 25 * n2 + 24 * nu + (size_t)l * 128; }
-  __host__ __device__ size_t floats() const { return 25 * n2 + 24 * nu + 12 * 128; }
+  __host__ __device__ size_t ze(int l) const { return (size_t)(RN_DEPTH + 1 + l) * n2; }
+  __host__ __device__ size_t xs(int l) const { return (2 * RN_DEPTH + 1) * n2 + (size_t)l * nu; }
+  __host__ __device__ size_t zv(int l) const { return (2 * RN_DEPTH + 1) * n2 + (size_t)(RN_DEPTH + l) * nu; }
+  __host__ __device__ size_t bn(int l) const { return (2 * RN_DEPTH + 1) * n2 + 2 * RN_DEPTH * nu + (size_t)l * 128; }
+  __host__ __device__ size_t floats() const { return bn(RN_DEPTH); }
   __host__ __device__ size_t stride_bytes() const { return align256(floats() * sizeof(float)); }
 };
 struct RtWork {
@@ -85,57 +63,10 @@ struct RtWork {
   __host__ __device__ size_t gX() const { return 2 * n2; }
   __host__ __device__ size_t gxs() const { return 2 * n2 + n * 128; }
   __host__ __device__ size_t part() const { return 2 * n2 + n * 160; }                  // [2][16][1024]
-  __host__ __device__ size_t block() const { return part() + 2 * RT_SLOTS * 1024; }
-  __host__ __device__ size_t floats() const { return block() + RT_PARAM_FLOATS; }
+  __host__ __device__ size_t block() const { return part() + 2 * RN_SLOTS * 1024; }
+  __host__ __device__ size_t floats() const { return block() + RN_PARAM_FLOATS; }
   __host__ __device__ size_t stride_bytes() const { return align256(floats() * sizeof(float)); }
 };
-
-// dynamic LDS: floats, then the float64 reduction block, then ints, then bytes
-struct RtLds {
-  float *xs, *X, *W, *e0, *stage;
-  double *red;
-  int *rowcnt;
-  uint8_t *rel, *cols;
-  __host__ __device__ static size_t floats(int n) { return (size_t)n * 160 + LAYER_FLOATS + 96 + RT_WAVES * 2 * 96; }
-  __host__ __device__ static size_t bytes(int n) {
-    return floats(n) * sizeof(float) + RT_SLOTS * 32 * 2 * sizeof(double) + 128 * sizeof(int) + (((size_t)n * n + 15) & ~(size_t)15) +
-           RT_WAVES * 128;
-  }
-  __device__ static RtLds carve(float *base, int n) {
-    RtLds s;
-    s.xs = base; s.X = s.xs + n * 32; s.W = s.X + n * 128; s.e0 = s.W + LAYER_FLOATS; s.stage = s.e0 + 96;
-    s.red = reinterpret_cast<double *>(s.stage + RT_WAVES * 2 * 96);
-    s.rowcnt = reinterpret_cast<int *>(s.red + RT_SLOTS * 32 * 2);
-    s.rel = reinterpret_cast<uint8_t *>(s.rowcnt + 128);
-    s.cols = s.rel + ((n * n + 15) & ~15);
-    return s;
-  }
-};
-static_assert((LAYER_FLOATS + 96 + RT_WAVES * 2 * 96) % 2 == 0, "the float64 block must be 8-byte aligned");
-
-// the non-zero entries of a row (stride 1) or a column (stride n), ascending, into this wavefront's list; returns their number
-__device__ inline int rt_compact(const uint8_t *first, int stride, int n, uint8_t *list, int lane) {
-  const int c0 = lane < n ? first[lane * stride] : 0, c1 = lane + 64 < n ? first[(lane + 64) * stride] : 0;
-  const unsigned long long m0 = __ballot(c0 != 0), m1 = __ballot(c1 != 0);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  const int cnt0 = __popcll(m0);
-  if (c0) list[__popcll(m0 & below)] = (uint8_t)lane;
-  if (c1) list[cnt0 + __popcll(m1 & below)] = (uint8_t)(lane + 64);
-  return cnt0 + __popcll(m1);
-}
-
-__device__ inline float rt_dot32(const float *st, const float (&wr)[32]) {
-  float acc = 0.0f;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const float4 v = *reinterpret_cast<const float4 *>(st + q * 4);
-    acc = fmaf(v.x, wr[q * 4 + 0], acc);
-    acc = fmaf(v.y, wr[q * 4 + 1], acc);
-    acc = fmaf(v.z, wr[q * 4 + 2], acc);
-    acc = fmaf(v.w, wr[q * 4 + 3], acc);
-  }
-  return acc;
-}
 
 // acc[c] += g * st[c]: the outer product row this lane owns
 __device__ inline void rt_outer32(const float *st, float g, float (&acc)[32]) {
@@ -157,7 +88,7 @@ __device__ inline void rt_reduce2(double *red, double &a, double &b) {
   red[(slot * 32 + o) * 2 + 1] = b;
   __syncthreads();
   double sa = 0.0, sb = 0.0;
-  for (int s = 0; s < RT_SLOTS; ++s) {
+  for (int s = 0; s < RN_SLOTS; ++s) {
     sa += red[(s * 32 + o) * 2 + 0];
     sb += red[(s * 32 + o) * 2 + 1];
   }
@@ -168,41 +99,20 @@ __device__ inline void rt_reduce2(double *red, double &a, double &b) {
 
 // the 16 slots' partial [32][32] matrices (part [16][1024], global) added in slot order into dst [1024]; between barriers
 __device__ inline void rt_reduce_matrix(const float *part, float *dst) {
-  for (int e = threadIdx.x; e < 1024; e += RT_THREADS) {
+  for (int e = threadIdx.x; e < 1024; e += RN_THREADS) {
     float acc = 0.0f;
-    for (int s = 0; s < RT_SLOTS; ++s) acc += part[s * 1024 + e];
+    for (int s = 0; s < RN_SLOTS; ++s) acc += part[s * 1024 + e];
     dst[e] = acc;
   }
 }
 
-__device__ inline void rt_node_linears(const RtLds &s, int n) {
-  const int col = threadIdx.x & 127;
-  const float *WT = s.W, *bv = s.W + RT_L_BV;
-  for (int i = threadIdx.x >> 7; i < n; i += RT_THREADS / 128) {
-    float acc = bv[col];
-#pragma unroll 8
-    for (int c = 0; c < 32; ++c) acc = fmaf(s.xs[i * 32 + c], WT[c * 128 + col], acc);
-    s.X[i * 128 + col] = acc;
-  }
-}
-
 // relation codes, the rows' edge counts, silu(e_lin0(attr)) for the three attribute rows; returns E.  Ends behind a barrier.
-__device__ inline int rt_load_graph(const RtLds &s, int n, const uint8_t *relation, const float *params) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int t = tid; t < n * n; t += RT_THREADS) {
-    const uint8_t c = relation[t];
-    s.rel[t] = c > 3 ? 0 : c;
-  }
-  if (tid < 96) {
-    const int code = tid >> 5, o = tid & 31;
-    const float *W = params + RT_OFF_ELIN, *bb = W + 64;
-    float v = bb[o];
-    v = fmaf(code == 0 ? 1.0f : 0.0f, W[o * 2 + 0], v);
-    v = fmaf(code == 1 ? 1.0f : 0.0f, W[o * 2 + 1], v);
-    s.e0[tid] = rt_silu(v);
-  }
+__device__ inline int rt_load_graph(const RnLds &s, int n, const uint8_t *relation, const float *params) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  rn_load_relation(s, n, relation);
+  rn_edge_init(s, params);
   __syncthreads();
-  for (int i = wave; i < n; i += RT_WAVES) {
+  for (int i = wave; i < n; i += RN_WAVES) {
     const uint8_t *rrow = s.rel + i * n;
     const int c0 = lane < n ? rrow[lane] : 0, c1 = lane + 64 < n ? rrow[lane + 64] : 0;
     const int cnt = __popcll(__ballot(c0 != 0)) + __popcll(__ballot(c1 != 0));
@@ -214,28 +124,24 @@ __device__ inline int rt_load_graph(const RtLds &s, int n, const uint8_t *relati
   return E;
 }
 
-__device__ inline void rt_load_floats(float *dst, const float *src, int count) {
-  for (int t = threadIdx.x; t < count; t += RT_THREADS) dst[t] = src[t];
-}
-
 // ------------------------------------------------------------------------------------------------ forward
-__device__ inline void rt_fwd_layer(const RtLds &s, int n, int E, const float *__restrict__ wl, float *__restrict__ wnext,
+__device__ inline void rt_fwd_layer(const RnLds &s, int n, int E, const float *__restrict__ wl, float *__restrict__ wnext,
                                     float *__restrict__ ze, float *__restrict__ xs_save, float *__restrict__ zv_save,
                                     float *__restrict__ bn_save, float *__restrict__ stats_e, float *__restrict__ stats_v) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, o = lane & 31;
-  const float *We = s.W + RT_L_WE;
+  const float *We = s.W + RN_L_WE;
   float wr[32];
 #pragma unroll
   for (int c = 0; c < 32; ++c) wr[c] = We[o * 32 + c];
-  const float beo = s.W[RT_L_BE + o];
-  const float gv = s.W[RT_L_BNV + o], bv = s.W[RT_L_BNV + 32 + o], ge = s.W[RT_L_BNE + o], bbe = s.W[RT_L_BNE + 32 + o];
+  const float beo = s.W[RN_L_BE + o];
+  const float gv = s.W[RN_L_BNV + o], bv = s.W[RN_L_BNV + 32 + o], ge = s.W[RN_L_BNE + o], bbe = s.W[RN_L_BNE + 32 + o];
   float *st = s.stage + (wave * 2 + h) * 96;
   uint8_t *cols = s.cols + wave * 128;
-  for (int t = tid; t < n * 32; t += RT_THREADS) xs_save[t] = s.xs[t];
+  for (int t = tid; t < n * 32; t += RN_THREADS) xs_save[t] = s.xs[t];
   double s1 = 0.0, s2 = 0.0, v1 = 0.0, v2 = 0.0;
-  for (int i = wave; i < n; i += RT_WAVES) {
+  for (int i = wave; i < n; i += RN_WAVES) {
     const uint8_t *rrow = s.rel + i * n;
-    const int cnt = rt_compact(rrow, 1, n, cols, lane);
+    const int cnt = rn_compact(rrow, 1, n, cols, lane);
     const float *wrow = wl + (size_t)i * n * 32;
     float *zrow = ze + (size_t)i * n * 32;
     const float x3 = s.X[i * 128 + 64 + o];
@@ -254,8 +160,8 @@ __device__ inline void rt_fwd_layer(const RtLds &s, int n, int E, const float *_
         if (jj[q] >= 0) {
           const int j = jj[q];
           st[o] = w0[q];
-          const float g = rt_dot32(st, wr);
-          part = fmaf(rt_sigmoid(w0[q]), s.X[j * 128 + 32 + o], part);
+          const float g = rn_dot32(st, wr);
+          part = fmaf(sigmoidf(w0[q]), s.X[j * 128 + 32 + o], part);
           const float z = g + beo + x3 + s.X[j * 128 + 96 + o];
           zrow[j * 32 + o] = z;
           s1 += (double)z;
@@ -284,117 +190,65 @@ __device__ inline void rt_fwd_layer(const RtLds &s, int n, int E, const float *_
     bn_save[64 + o * 2 + 0] = mean_v; bn_save[64 + o * 2 + 1] = rstd_v;
   }
   // walk 2 (the barriers of the reductions made every ze and zv of walk 1 visible)
-  for (int i = wave; i < n; i += RT_WAVES) {
+  for (int i = wave; i < n; i += RN_WAVES) {
     const uint8_t *rrow = s.rel + i * n;
-    const int cnt = rt_compact(rrow, 1, n, cols, lane);
+    const int cnt = rn_compact(rrow, 1, n, cols, lane);
     const size_t row = (size_t)i * n * 32;
 #pragma unroll 4
     for (int k = h; k < cnt; k += 2) {
       const size_t at = row + cols[k] * 32 + o;
       const float y = fmaf((ze[at] - mean_e) * rstd_e, ge, bbe);
-      wnext[at] = wl[at] + rt_silu(y);
+      wnext[at] = wl[at] + silu(y);
     }
   }
-  for (int t = tid; t < n * 32; t += RT_THREADS) {          // t & 31 == o
+  for (int t = tid; t < n * 32; t += RN_THREADS) {          // t & 31 == o
     const float y = fmaf((zv_save[t] - mean_v) * rstd_v, gv, bv);
-    s.xs[t] += rt_silu(y);
+    s.xs[t] += silu(y);
   }
 }
 
-__device__ inline void rt_fwd_head(const RtLds &s, int n, const float *w, float eps, float *heu, float *logit) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, o = lane & 31;
-  const float *W1 = s.W, *b1 = W1 + RT_H_B1, *W2 = s.W + RT_H_W2, *b2 = s.W + RT_H_B2, *W3 = s.W + RT_H_W3, *b3 = s.W + RT_H_B3;
-  float w1r[32], w2r[32];
-#pragma unroll
-  for (int c = 0; c < 32; ++c) { w1r[c] = W1[o * 32 + c]; w2r[c] = W2[o * 32 + c]; }
-  const float b1o = b1[o], b2o = b2[o], b3v = b3[0];
-  float *st = s.stage + (wave * 2 + h) * 96;
-  uint8_t *cols = s.cols + wave * 128;
-  for (int i = wave; i < n; i += RT_WAVES) {
-    const uint8_t *rrow = s.rel + i * n;
-    for (int j = lane; j < n; j += 64)
-      if (!rrow[j]) {
-        heu[i * n + j] = eps;
-        if (logit) logit[i * n + j] = -__builtin_inff();
-      }
-    const int cnt = rt_compact(rrow, 1, n, cols, lane);
-    const float *wrow = w + (size_t)i * n * 32;
-    for (int k = h; k < cnt; k += 2) {
-      const int j = cols[k];
-      st[o] = wrow[j * 32 + o];
-      const float a1 = rt_silu(rt_dot32(st, w1r) + b1o);
-      st[32 + o] = a1;
-      const float a2 = rt_silu(rt_dot32(st + 32, w2r) + b2o);
-      st[64 + o] = a2;
-      float sum = 0.0f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float4 v = *reinterpret_cast<const float4 *>(st + 64 + q * 4);
-        const float4 u = *reinterpret_cast<const float4 *>(W3 + q * 4);
-        sum = fmaf(v.x, u.x, sum); sum = fmaf(v.y, u.y, sum); sum = fmaf(v.z, u.z, sum); sum = fmaf(v.w, u.w, sum);
-      }
-      if (o == 0) {
-        const float z = sum + b3v;
-        heu[i * n + j] = rt_sigmoid(z) + eps;
-        if (logit) logit[i * n + j] = z;
-      }
-    }
-  }
-}
-
-__device__ inline void rt_input_nodes(const RtLds &s, int n, const float *x, const float *params) {
-  for (int t = threadIdx.x; t < n * 32; t += RT_THREADS) {
-    const int i = t >> 5, o = t & 31;
-    const float *W = params, *bb = params + 32 * RT_FEATS;
-    float v = bb[o];
-#pragma unroll
-    for (int f = 0; f < RT_FEATS; ++f) v = fmaf(x[i * RT_FEATS + f], W[o * RT_FEATS + f], v);
-    s.xs[t] = rt_silu(v);
-  }
-}
-
-__global__ void __launch_bounds__(RT_THREADS)
+__global__ void __launch_bounds__(RN_THREADS)
 rcpsp_net_train_forward_kernel(int B, int n, const float *x, const uint8_t *relation, const float *params, float eps, float *heu,
                                float *logit, float *stats, float *saved_base, size_t saved_stride) {
   extern __shared__ __attribute__((aligned(16))) float rt_lds[];
-  const RtLds s = RtLds::carve(rt_lds, n);
+  const RnLds s = RnLds::carve(rt_lds, n, true);
   const RtSaved sv(n);
   const int b = blockIdx.x, tid = threadIdx.x;
-  x += (size_t)b * n * RT_FEATS;
+  x += (size_t)b * n * RN_FEATS;
   relation += (size_t)b * n * n;
   heu += (size_t)b * n * n;
   if (logit) logit += (size_t)b * n * n;
   float *saved = saved_base + (size_t)b * saved_stride;
 
   const int E = rt_load_graph(s, n, relation, params);
-  rt_load_floats(s.W, params + RT_OFF_LAYER0, LAYER_FLOATS);
-  rt_input_nodes(s, n, x, params);
+  rn_load_floats(s.W, params + RN_OFF_LAYER0, LAYER_FLOATS);
+  rn_input_nodes(s, n, x, params);
   {                                                     // w of layer 0: one of the three initial vectors
     float *w0 = saved + sv.w(0);
     const int o = tid & 31;
-    for (int t = tid >> 5; t < n * n; t += RT_THREADS / 32) {
+    for (int t = tid >> 5; t < n * n; t += RN_THREADS / 32) {
       const int c = s.rel[t];
       if (c) w0[(size_t)t * 32 + o] = s.e0[(c - 1) * 32 + o];
     }
   }
   __syncthreads();
-  rt_node_linears(s, n);
+  rn_node_linears(s, n);
   __syncthreads();
-  for (int l = 0; l < RT_DEPTH; ++l) {
+  for (int l = 0; l < RN_DEPTH; ++l) {
     float *st_e = stats + ((((size_t)l * 2 + 0) * B + b) * 32) * 2, *st_v = stats + ((((size_t)l * 2 + 1) * B + b) * 32) * 2;
     rt_fwd_layer(s, n, E, saved + sv.w(l), saved + sv.w(l + 1), saved + sv.ze(l), saved + sv.xs(l), saved + sv.zv(l),
                  saved + sv.bn(l), st_e, st_v);
     __syncthreads();
-    if (l < RT_DEPTH - 1) {
-      rt_load_floats(s.W, params + RT_OFF_LAYER0 + (size_t)(l + 1) * LAYER_FLOATS, LAYER_FLOATS);
+    if (l < RN_DEPTH - 1) {
+      rn_load_floats(s.W, params + RN_OFF_LAYER0 + (size_t)(l + 1) * LAYER_FLOATS, LAYER_FLOATS);
       __syncthreads();
-      rt_node_linears(s, n);
+      rn_node_linears(s, n);
     } else {
-      rt_load_floats(s.W, params + RT_OFF_HEAD, HEAD_FLOATS);
+      rn_load_floats(s.W, params + RN_OFF_HEAD, HEAD_FLOATS);
     }
     __syncthreads();
   }
-  rt_fwd_head(s, n, saved + sv.w(RT_DEPTH), eps, heu, logit);
+  rn_head(s, n, saved + sv.w(RN_DEPTH), eps, heu, logit, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -402,11 +256,11 @@ rcpsp_net_train_forward_kernel(int B, int n, const float *x, const uint8_t *rela
 //   A: recompute the two hidden layers per edge; gW2, gb2, gW3, gb3, gb1; g_h1 (the gradient at the first layer's
 //      pre-activation) -> gh1 [n][n][32] (the gze block, free until the first layer of the reverse walk)
 //   B: gW1 += g_h1 (x) w, gw <- W1^T g_h1
-__device__ inline void rt_bwd_head(const RtLds &s, int n, const float *__restrict__ w, const float *__restrict__ gheu,
+__device__ inline void rt_bwd_head(const RnLds &s, int n, const float *__restrict__ w, const float *__restrict__ gheu,
                                    float *__restrict__ gw, float *__restrict__ gh1buf, float *__restrict__ part,
                                    float *__restrict__ gblock) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, o = lane & 31, slot = tid >> 5;
-  const float *W1 = s.W, *W2 = s.W + RT_H_W2, *W3 = s.W + RT_H_W3;
+  const float *W1 = s.W, *W2 = s.W + RN_H_W2, *W3 = s.W + RN_H_W3;
   float *st = s.stage + slot * 96;
   uint8_t *cols = s.cols + wave * 128;
   double gb1 = 0.0, gb2 = 0.0, gw3 = 0.0, gb3 = 0.0;
@@ -417,21 +271,21 @@ __device__ inline void rt_bwd_head(const RtLds &s, int n, const float *__restric
       w1r[c] = W1[o * 32 + c]; w2r[c] = W2[o * 32 + c]; w2c[c] = W2[c * 32 + o];
       acc[c] = 0.0f;
     }
-    const float b1o = s.W[RT_H_B1 + o], b2o = s.W[RT_H_B2 + o], b3v = s.W[RT_H_B3], w3o = W3[o];
-    for (int i = wave; i < n; i += RT_WAVES) {
+    const float b1o = s.W[RN_H_B1 + o], b2o = s.W[RN_H_B2 + o], b3v = s.W[RN_H_B3], w3o = W3[o];
+    for (int i = wave; i < n; i += RN_WAVES) {
       const uint8_t *rrow = s.rel + i * n;
-      const int cnt = rt_compact(rrow, 1, n, cols, lane);
+      const int cnt = rn_compact(rrow, 1, n, cols, lane);
       const size_t row = (size_t)i * n * 32;
       for (int k = h; k < cnt; k += 2) {
         const int j = cols[k];
         const float wv = w[row + j * 32 + o];
         const float gh = gheu[i * n + j];
         st[o] = wv;
-        const float h1 = rt_dot32(st, w1r) + b1o;
-        const float a1 = rt_silu(h1);
+        const float h1 = rn_dot32(st, w1r) + b1o;
+        const float a1 = silu(h1);
         st[32 + o] = a1;
-        const float h2 = rt_dot32(st + 32, w2r) + b2o;
-        const float a2 = rt_silu(h2);
+        const float h2 = rn_dot32(st + 32, w2r) + b2o;
+        const float a2 = silu(h2);
         st[64 + o] = a2;
         float sum = 0.0f;
 #pragma unroll
@@ -440,30 +294,30 @@ __device__ inline void rt_bwd_head(const RtLds &s, int n, const float *__restric
           const float4 u = *reinterpret_cast<const float4 *>(W3 + q * 4);
           sum = fmaf(v.x, u.x, sum); sum = fmaf(v.y, u.y, sum); sum = fmaf(v.z, u.z, sum); sum = fmaf(v.w, u.w, sum);
         }
-        const float sz = rt_sigmoid(sum + b3v);
+        const float sz = sigmoidf(sum + b3v);
         const float gz = gh * (sz * (1.0f - sz));
         gw3 += (double)(gz * a2);
         gb3 += (double)gz;
-        const float gh2 = gz * w3o * rt_dsilu(h2);
+        const float gh2 = gz * w3o * dsilu(h2);
         gb2 += (double)gh2;
         rt_outer32(st + 32, gh2, acc);                   // gW2[o][c] += gh2[o] a1[c]
         st[64 + o] = gh2;
-        const float ga1 = rt_dot32(st + 64, w2c);         // sum_o' gh2[o'] W2[o'][o]
-        const float gh1 = ga1 * rt_dsilu(h1);
+        const float ga1 = rn_dot32(st + 64, w2c);         // sum_o' gh2[o'] W2[o'][o]
+        const float gh1 = ga1 * dsilu(h1);
         gb1 += (double)gh1;
         gh1buf[row + j * 32 + o] = gh1;
       }
     }
 #pragma unroll
-    for (int c = 0; c < 32; ++c) part[(RT_SLOTS + slot) * 1024 + o * 32 + c] = acc[c];
+    for (int c = 0; c < 32; ++c) part[(RN_SLOTS + slot) * 1024 + o * 32 + c] = acc[c];
   }
   {
     float w1c[32], acc[32];
 #pragma unroll
     for (int c = 0; c < 32; ++c) { w1c[c] = W1[c * 32 + o]; acc[c] = 0.0f; }
-    for (int i = wave; i < n; i += RT_WAVES) {           // the rows this wavefront wrote in walk A
+    for (int i = wave; i < n; i += RN_WAVES) {           // the rows this wavefront wrote in walk A
       const uint8_t *rrow = s.rel + i * n;
-      const int cnt = rt_compact(rrow, 1, n, cols, lane);
+      const int cnt = rn_compact(rrow, 1, n, cols, lane);
       const size_t row = (size_t)i * n * 32;
 #pragma unroll 2
       for (int k = h; k < cnt; k += 2) {
@@ -472,7 +326,7 @@ __device__ inline void rt_bwd_head(const RtLds &s, int n, const float *__restric
         st[o] = w[at];
         rt_outer32(st, gh1, acc);                        // gW1[o][c] += gh1[o] w[c]
         st[32 + o] = gh1;
-        gw[at] = rt_dot32(st + 32, w1c);
+        gw[at] = rn_dot32(st + 32, w1c);
       }
     }
 #pragma unroll
@@ -480,23 +334,23 @@ __device__ inline void rt_bwd_head(const RtLds &s, int n, const float *__restric
   }
   rt_reduce2(s.red, gb1, gb2);
   rt_reduce2(s.red, gw3, gb3);
-  float *gh = gblock + RT_OFF_HEAD;
+  float *gh = gblock + RN_OFF_HEAD;
   rt_reduce_matrix(part, gh);
-  rt_reduce_matrix(part + RT_SLOTS * 1024, gh + RT_H_W2);
+  rt_reduce_matrix(part + RN_SLOTS * 1024, gh + RN_H_W2);
   if (tid < 32) {
-    gh[RT_H_B1 + o] = (float)gb1;
-    gh[RT_H_B2 + o] = (float)gb2;
-    gh[RT_H_W3 + o] = (float)gw3;
-    if (o == 0) gh[RT_H_B3] = (float)gb3;
+    gh[RN_H_B1 + o] = (float)gb1;
+    gh[RN_H_B2 + o] = (float)gb2;
+    gh[RN_H_W3 + o] = (float)gw3;
+    if (o == 0) gh[RN_H_B3] = (float)gb3;
   }
 }
 
-__device__ inline void rt_bwd_layer(const RtLds &s, int n, int E, const float *__restrict__ wl, const float *__restrict__ ze,
+__device__ inline void rt_bwd_layer(const RnLds &s, int n, int E, const float *__restrict__ wl, const float *__restrict__ ze,
                                     const float *__restrict__ zv, const float *__restrict__ bn, float *__restrict__ gw,
                                     float *__restrict__ gze, float *gX, float *gxs, float *__restrict__ part,
                                     float *__restrict__ gl) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, o = lane & 31, slot = tid >> 5;
-  const float gv = s.W[RT_L_BNV + o], bv = s.W[RT_L_BNV + 32 + o], ge = s.W[RT_L_BNE + o], bbe = s.W[RT_L_BNE + 32 + o];
+  const float gv = s.W[RN_L_BNV + o], bv = s.W[RN_L_BNV + 32 + o], ge = s.W[RN_L_BNE + o], bbe = s.W[RN_L_BNE + 32 + o];
   const float mean_e = bn[o * 2], rstd_e = bn[o * 2 + 1], mean_v = bn[64 + o * 2], rstd_v = bn[64 + o * 2 + 1];
   float *st = s.stage + slot * 96;
   uint8_t *cols = s.cols + wave * 128;
@@ -504,48 +358,48 @@ __device__ inline void rt_bwd_layer(const RtLds &s, int n, int E, const float *_
   // ---- node A
   {
     double a = 0.0, c = 0.0;
-    for (int t = tid; t < n * 32; t += RT_THREADS) {
+    for (int t = tid; t < n * 32; t += RN_THREADS) {
       const float zh = (zv[t] - mean_v) * rstd_v;
-      const float gy = gxs[t] * rt_dsilu(fmaf(zh, gv, bv));
+      const float gy = gxs[t] * dsilu(fmaf(zh, gv, bv));
       a += (double)gy;
       c += (double)gy * (double)zh;
     }
     rt_reduce2(s.red, a, c);
     const float m1 = (float)(a / (double)n), m2 = (float)(c / (double)n);
-    if (tid < 32) { gl[RT_L_BNV + o] = (float)c; gl[RT_L_BNV + 32 + o] = (float)a; }
-    for (int t = tid; t < n * 32; t += RT_THREADS) {
+    if (tid < 32) { gl[RN_L_BNV + o] = (float)c; gl[RN_L_BNV + 32 + o] = (float)a; }
+    for (int t = tid; t < n * 32; t += RN_THREADS) {
       const float zh = (zv[t] - mean_v) * rstd_v;
-      const float gy = gxs[t] * rt_dsilu(fmaf(zh, gv, bv));
+      const float gy = gxs[t] * dsilu(fmaf(zh, gv, bv));
       gX[(t >> 5) * 128 + o] = gv * rstd_v * (gy - m1 - zh * m2);
     }
   }
   // ---- edge 1: the two sums of the edge BatchNorm
   double e1 = 0.0, e2 = 0.0;
-  for (int i = wave; i < n; i += RT_WAVES) {
-    const int cnt = rt_compact(s.rel + i * n, 1, n, cols, lane);
+  for (int i = wave; i < n; i += RN_WAVES) {
+    const int cnt = rn_compact(s.rel + i * n, 1, n, cols, lane);
     const size_t row = (size_t)i * n * 32;
 #pragma unroll 4
     for (int k = h; k < cnt; k += 2) {
       const size_t at = row + cols[k] * 32 + o;
       const float zh = (ze[at] - mean_e) * rstd_e;
-      const float gy = gw[at] * rt_dsilu(fmaf(zh, ge, bbe));
+      const float gy = gw[at] * dsilu(fmaf(zh, ge, bbe));
       e1 += (double)gy;
       e2 += (double)gy * (double)zh;
     }
   }
   rt_reduce2(s.red, e1, e2);                              // (its barriers also publish node A's gX)
   const float m1 = (float)(e1 / (double)max(E, 1)), m2 = (float)(e2 / (double)max(E, 1));
-  if (tid < 32) { gl[RT_L_BNE + o] = (float)e2; gl[RT_L_BNE + 32 + o] = (float)e1; }
+  if (tid < 32) { gl[RN_L_BNE + o] = (float)e2; gl[RN_L_BNE + 32 + o] = (float)e1; }
   // ---- edge 2
   {
-    const float *We = s.W + RT_L_WE;
+    const float *We = s.W + RN_L_WE;
     float wcol[32], acc[32];
 #pragma unroll
     for (int c = 0; c < 32; ++c) { wcol[c] = We[c * 32 + o]; acc[c] = 0.0f; }
     double gbe = 0.0, unused = 0.0;
     const float scale = ge * rstd_e;
-    for (int i = wave; i < n; i += RT_WAVES) {
-      const int cnt = rt_compact(s.rel + i * n, 1, n, cols, lane);
+    for (int i = wave; i < n; i += RN_WAVES) {
+      const int cnt = rn_compact(s.rel + i * n, 1, n, cols, lane);
       const size_t row = (size_t)i * n * 32;
       const float gagg = gX[i * 128 + o] / (float)max(cnt, 1);
       float rows = 0.0f;
@@ -567,16 +421,16 @@ __device__ inline void rt_bwd_layer(const RtLds &s, int n, int E, const float *_
             const int j = jj[q];
             const size_t at = row + j * 32 + o;
             const float zh = (zq[q] - mean_e) * rstd_e;
-            const float gy = gq[q] * rt_dsilu(fmaf(zh, ge, bbe));
+            const float gy = gq[q] * dsilu(fmaf(zh, ge, bbe));
             const float gz = scale * (gy - m1 - zh * m2);
             gze[at] = gz;
             gbe += (double)gz;
             rows += gz;
             st[o] = gz;
-            const float back = rt_dot32(st, wcol);        // sum_o' gz[o'] We[o'][o]
+            const float back = rn_dot32(st, wcol);        // sum_o' gz[o'] We[o'][o]
             st[32 + o] = wq[q];
             rt_outer32(st + 32, gz, acc);                 // gWe[o][c] += gz[o] w[c]
-            const float sg = rt_sigmoid(wq[q]);
+            const float sg = sigmoidf(wq[q]);
             gw[at] = gq[q] + back + gagg * s.X[j * 128 + 32 + o] * (sg * (1.0f - sg));
           }
         }
@@ -587,19 +441,19 @@ __device__ inline void rt_bwd_layer(const RtLds &s, int n, int E, const float *_
 #pragma unroll
     for (int c = 0; c < 32; ++c) part[slot * 1024 + o * 32 + c] = acc[c];
     rt_reduce2(s.red, gbe, unused);
-    if (tid < 32) gl[RT_L_BE + o] = (float)gbe;
-    rt_reduce_matrix(part, gl + RT_L_WE);
+    if (tid < 32) gl[RN_L_BE + o] = (float)gbe;
+    rt_reduce_matrix(part, gl + RN_L_WE);
   }
   // ---- edge 3: the column sums (gze and gX[:, 0:32] are complete behind the barriers above)
-  for (int j = wave; j < n; j += RT_WAVES) {
-    const int cnt = rt_compact(s.rel + j, n, n, cols, lane);
+  for (int j = wave; j < n; j += RN_WAVES) {
+    const int cnt = rn_compact(s.rel + j, n, n, cols, lane);
     float a4 = 0.0f, a2 = 0.0f;
 #pragma unroll 4
     for (int k = h; k < cnt; k += 2) {
       const int i = cols[k];
       const size_t at = ((size_t)i * n + j) * 32 + o;
       a4 += gze[at];
-      a2 = fmaf(gX[i * 128 + o] / (float)max(s.rowcnt[i], 1), rt_sigmoid(wl[at]), a2);
+      a2 = fmaf(gX[i * 128 + o] / (float)max(s.rowcnt[i], 1), sigmoidf(wl[at]), a2);
     }
     a4 += __shfl_xor(a4, 32);
     a2 += __shfl_xor(a2, 32);
@@ -620,8 +474,8 @@ __device__ inline void rt_bwd_layer(const RtLds &s, int n, int E, const float *_
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) gl[(cg * 8 + q) * 128 + col] = acc[q];
-    if (cg == 0) gl[RT_L_BV + col] = sum;
-    for (int t = tid; t < n * 32; t += RT_THREADS) {
+    if (cg == 0) gl[RN_L_BV + col] = sum;
+    for (int t = tid; t < n * 32; t += RN_THREADS) {
       const int i = t >> 5;
       float a = 0.0f;
       for (int k = 0; k < 128; ++k) {
@@ -633,15 +487,15 @@ __device__ inline void rt_bwd_layer(const RtLds &s, int n, int E, const float *_
   }
 }
 
-__global__ void __launch_bounds__(RT_THREADS)
+__global__ void __launch_bounds__(RN_THREADS)
 rcpsp_net_train_backward_kernel(int n, const float *x, const uint8_t *relation, const float *params, const float *saved_base,
                                 size_t saved_stride, const float *gheu, float *work_base, size_t work_stride) {
   extern __shared__ __attribute__((aligned(16))) float rt_lds[];
-  const RtLds s = RtLds::carve(rt_lds, n);
+  const RnLds s = RnLds::carve(rt_lds, n, true);
   const RtSaved sv(n);
   const RtWork wk(n);
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, o = lane & 31, slot = tid >> 5;
-  x += (size_t)b * n * RT_FEATS;
+  x += (size_t)b * n * RN_FEATS;
   relation += (size_t)b * n * n;
   gheu += (size_t)b * n * n;
   const float *saved = saved_base + (size_t)b * saved_stride;
@@ -650,32 +504,32 @@ rcpsp_net_train_backward_kernel(int n, const float *x, const uint8_t *relation, 
   float *gblock = work + wk.block();
 
   const int E = rt_load_graph(s, n, relation, params);
-  rt_load_floats(s.W, params + RT_OFF_HEAD, HEAD_FLOATS);
-  for (int t = tid; t < n * 32; t += RT_THREADS) gxs[t] = 0.0f;          // nothing reads the node state after the last layer
+  rn_load_floats(s.W, params + RN_OFF_HEAD, HEAD_FLOATS);
+  for (int t = tid; t < n * 32; t += RN_THREADS) gxs[t] = 0.0f;          // nothing reads the node state after the last layer
   __syncthreads();
-  rt_bwd_head(s, n, saved + sv.w(RT_DEPTH), gheu, gw, gze, part, gblock);
+  rt_bwd_head(s, n, saved + sv.w(RN_DEPTH), gheu, gw, gze, part, gblock);
   __syncthreads();
-  for (int l = RT_DEPTH - 1; l >= 0; --l) {
-    rt_load_floats(s.W, params + RT_OFF_LAYER0 + (size_t)l * LAYER_FLOATS, LAYER_FLOATS);
-    rt_load_floats(s.xs, saved + sv.xs(l), n * 32);
+  for (int l = RN_DEPTH - 1; l >= 0; --l) {
+    rn_load_floats(s.W, params + RN_OFF_LAYER0 + (size_t)l * LAYER_FLOATS, LAYER_FLOATS);
+    rn_load_floats(s.xs, saved + sv.xs(l), n * 32);
     __syncthreads();
-    rt_node_linears(s, n);
+    rn_node_linears(s, n);
     __syncthreads();
     rt_bwd_layer(s, n, E, saved + sv.w(l), saved + sv.ze(l), saved + sv.zv(l), saved + sv.bn(l), gw, gze, gX, gxs, part,
-                 gblock + RT_OFF_LAYER0 + (size_t)l * LAYER_FLOATS);
+                 gblock + RN_OFF_LAYER0 + (size_t)l * LAYER_FLOATS);
     __syncthreads();
   }
   // ---- v_lin0: x0 = silu(W x + b)
   {
-    const float *W = params, *bb = params + 32 * RT_FEATS;
+    const float *W = params, *bb = params + 32 * RN_FEATS;
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = slot; i < n; i += RT_SLOTS) {
+    for (int i = slot; i < n; i += RN_SLOTS) {
       float v = bb[o];
 #pragma unroll
-      for (int f = 0; f < RT_FEATS; ++f) v = fmaf(x[i * RT_FEATS + f], W[o * RT_FEATS + f], v);
-      const float gp = gxs[i * 32 + o] * rt_dsilu(v);
+      for (int f = 0; f < RN_FEATS; ++f) v = fmaf(x[i * RN_FEATS + f], W[o * RN_FEATS + f], v);
+      const float gp = gxs[i * 32 + o] * dsilu(v);
 #pragma unroll
-      for (int f = 0; f < RT_FEATS; ++f) acc[f] += (double)(gp * x[i * RT_FEATS + f]);
+      for (int f = 0; f < RN_FEATS; ++f) acc[f] += (double)(gp * x[i * RN_FEATS + f]);
       acc[5] += (double)gp;
     }
     rt_reduce2(s.red, acc[0], acc[1]);
@@ -683,17 +537,17 @@ rcpsp_net_train_backward_kernel(int n, const float *x, const uint8_t *relation, 
     rt_reduce2(s.red, acc[4], acc[5]);
     if (tid < 32) {
 #pragma unroll
-      for (int f = 0; f < RT_FEATS; ++f) gblock[o * RT_FEATS + f] = (float)acc[f];
-      gblock[32 * RT_FEATS + o] = (float)acc[5];
+      for (int f = 0; f < RN_FEATS; ++f) gblock[o * RN_FEATS + f] = (float)acc[f];
+      gblock[32 * RN_FEATS + o] = (float)acc[5];
     }
   }
   // ---- e_lin0: w0 = silu(e_lin0(attr of the code)): three per-code sums of gw
   {
     double c0 = 0.0, c1 = 0.0, c2 = 0.0, unused = 0.0;
     uint8_t *cols = s.cols + wave * 128;
-    for (int i = wave; i < n; i += RT_WAVES) {
+    for (int i = wave; i < n; i += RN_WAVES) {
       const uint8_t *rrow = s.rel + i * n;
-      const int cnt = rt_compact(rrow, 1, n, cols, lane);
+      const int cnt = rn_compact(rrow, 1, n, cols, lane);
       const size_t row = (size_t)i * n * 32;
 #pragma unroll 4
       for (int k = h; k < cnt; k += 2) {
@@ -707,12 +561,12 @@ rcpsp_net_train_backward_kernel(int n, const float *x, const uint8_t *relation, 
     rt_reduce2(s.red, c0, c1);
     rt_reduce2(s.red, c2, unused);
     if (tid < 32) {
-      const float *W = params + RT_OFF_ELIN, *bb = W + 64;
+      const float *W = params + RN_OFF_ELIN, *bb = W + 64;
       const float p0 = fmaf(0.0f, W[o * 2 + 1], fmaf(1.0f, W[o * 2 + 0], bb[o]));
       const float p1 = fmaf(1.0f, W[o * 2 + 1], fmaf(0.0f, W[o * 2 + 0], bb[o]));
       const float p2 = bb[o];
-      const float g0 = (float)c0 * rt_dsilu(p0), g1 = (float)c1 * rt_dsilu(p1), g2 = (float)c2 * rt_dsilu(p2);
-      float *ge0 = gblock + RT_OFF_ELIN;
+      const float g0 = (float)c0 * dsilu(p0), g1 = (float)c1 * dsilu(p1), g2 = (float)c2 * dsilu(p2);
+      float *ge0 = gblock + RN_OFF_ELIN;
       ge0[o * 2 + 0] = g0;
       ge0[o * 2 + 1] = g1;
       ge0[64 + o] = g0 + g1 + g2;
@@ -724,11 +578,11 @@ rcpsp_net_train_backward_kernel(int n, const float *x, const uint8_t *relation, 
 __global__ void rcpsp_net_train_sum_kernel(int B, const float *work_base, size_t work_stride, size_t block_off, float *grad,
                                            float *blocks) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= RT_PARAM_FLOATS) return;
+  if (p >= RN_PARAM_FLOATS) return;
   float acc = 0.0f;
   for (int b = 0; b < B; ++b) {
     const float v = work_base[(size_t)b * work_stride + block_off + p];
-    if (blocks) blocks[(size_t)b * RT_PARAM_FLOATS + p] = v;
+    if (blocks) blocks[(size_t)b * RN_PARAM_FLOATS + p] = v;
     acc += v;
   }
   grad[p] = acc;
@@ -740,57 +594,28 @@ __global__ void rcpsp_net_train_sum_kernel(int B, const float *work_base, size_t
 using namespace daco;
 
 extern "C" size_t daco_rcpsp_net_train_saved_bytes(int B, int n) {
-  if (B <= 0 || n < 2 || n > DACO_RCPSP_NET_MAX_N) return 0;
+  if (!rn_sizes_ok(B, n)) return 0;
   return (size_t)B * RtSaved(n).stride_bytes();
 }
 
 extern "C" size_t daco_rcpsp_net_train_workspace_bytes(int B, int n) {
-  if (B <= 0 || n < 2 || n > DACO_RCPSP_NET_MAX_N) return 0;
+  if (!rn_sizes_ok(B, n)) return 0;
   return (size_t)B * RtWork(n).stride_bytes();
-}
-
-static long rt_check(const char *who, int B, int n, int feats, bool pointers) {
-  if (B <= 0 || n < 2 || feats != RT_FEATS) {
-    set_error("%s: bad argument (B=%d n=%d feats=%d; feats must be %d)", who, B, n, feats, RT_FEATS);
-    return DACO_E_BADARG;
-  }
-  if (!pointers) {
-    set_error("%s: null pointer", who);
-    return DACO_E_BADARG;
-  }
-  if (n > DACO_RCPSP_NET_MAX_N) {
-    set_error("%s: n=%d exceeds DACO_RCPSP_NET_MAX_N = %d", who, n, DACO_RCPSP_NET_MAX_N);
-    return DACO_E_TOOLARGE;
-  }
-  if (RtLds::bytes(n) > RT_LDS_MAX) {                    // (cannot happen for n <= 128: 133 KB at n = 128)
-    set_error("%s: n=%d needs %zu bytes of LDS, a workgroup has %zu", who, n, RtLds::bytes(n), RT_LDS_MAX);
-    return DACO_E_TOOLARGE;
-  }
-  return DACO_OK;
-}
-
-template <typename K>
-static long rt_lds_attr(K kernel, size_t dyn, const char *what) {
-  if (dyn > RT_LDS_PLAIN) {
-    const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    if (e != hipSuccess) return launch_status(e, what);
-  }
-  return DACO_OK;
 }
 
 extern "C" long daco_rcpsp_net_train_forward(void *stream, int B, int n, int feats, const float *x, const uint8_t *relation,
                                              const float *params, float eps, float *heu, float *logit, float *stats,
                                              void *saved, size_t saved_bytes) {
   const char *who = "daco_rcpsp_net_train_forward";
-  if (const long rc = rt_check(who, B, n, feats, x && relation && params && heu && stats && saved)) return rc;
+  if (const long rc = rn_check(who, B, n, feats, x && relation && params && heu && stats && saved, true)) return rc;
   const size_t need = daco_rcpsp_net_train_saved_bytes(B, n);
   if (saved_bytes < need) {
     set_error("%s: saved %zu < %zu bytes", who, saved_bytes, need);
     return DACO_E_WORKSPACE;
   }
-  const size_t dyn = RtLds::bytes(n);
-  if (const long rc = rt_lds_attr(rcpsp_net_train_forward_kernel, dyn, "rcpsp_net_train_forward_kernel (dynamic LDS)")) return rc;
-  hipLaunchKernelGGL(rcpsp_net_train_forward_kernel, dim3((unsigned)B), dim3(RT_THREADS), dyn, (hipStream_t)stream, B, n, x,
+  const size_t dyn = RnLds::bytes(n, true);
+  if (const long rc = rn_lds_attr(rcpsp_net_train_forward_kernel, dyn, "rcpsp_net_train_forward_kernel (dynamic LDS)")) return rc;
+  hipLaunchKernelGGL(rcpsp_net_train_forward_kernel, dim3((unsigned)B), dim3(RN_THREADS), dyn, (hipStream_t)stream, B, n, x,
                      relation, params, eps, heu, logit, stats, (float *)saved, need / B / sizeof(float));
   return launch_status("rcpsp_net_train_forward_kernel");
 }
@@ -799,7 +624,7 @@ extern "C" long daco_rcpsp_net_train_backward(void *stream, int B, int n, int fe
                                               const float *params, const void *saved, size_t saved_bytes, const float *grad_heu,
                                               float *grad_params, float *grad_blocks, void *workspace, size_t workspace_bytes) {
   const char *who = "daco_rcpsp_net_train_backward";
-  if (const long rc = rt_check(who, B, n, feats, x && relation && params && saved && grad_heu && grad_params && workspace)) return rc;
+  if (const long rc = rn_check(who, B, n, feats, x && relation && params && saved && grad_heu && grad_params && workspace, true)) return rc;
   const size_t need_s = daco_rcpsp_net_train_saved_bytes(B, n), need_w = daco_rcpsp_net_train_workspace_bytes(B, n);
   if (saved_bytes < need_s) {
     set_error("%s: saved %zu < %zu bytes", who, saved_bytes, need_s);
@@ -809,13 +634,13 @@ extern "C" long daco_rcpsp_net_train_backward(void *stream, int B, int n, int fe
     set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need_w);
     return DACO_E_WORKSPACE;
   }
-  const size_t dyn = RtLds::bytes(n);
-  if (const long rc = rt_lds_attr(rcpsp_net_train_backward_kernel, dyn, "rcpsp_net_train_backward_kernel (dynamic LDS)")) return rc;
+  const size_t dyn = RnLds::bytes(n, true);
+  if (const long rc = rn_lds_attr(rcpsp_net_train_backward_kernel, dyn, "rcpsp_net_train_backward_kernel (dynamic LDS)")) return rc;
   const size_t wstride = need_w / B / sizeof(float);
-  hipLaunchKernelGGL(rcpsp_net_train_backward_kernel, dim3((unsigned)B), dim3(RT_THREADS), dyn, (hipStream_t)stream, n, x, relation,
+  hipLaunchKernelGGL(rcpsp_net_train_backward_kernel, dim3((unsigned)B), dim3(RN_THREADS), dyn, (hipStream_t)stream, n, x, relation,
                      params, (const float *)saved, need_s / B / sizeof(float), grad_heu, (float *)workspace, wstride);
   if (const long rc = launch_status("rcpsp_net_train_backward_kernel")) return rc;
-  hipLaunchKernelGGL(rcpsp_net_train_sum_kernel, dim3((RT_PARAM_FLOATS + 255) / 256), dim3(256), 0, (hipStream_t)stream, B,
+  hipLaunchKernelGGL(rcpsp_net_train_sum_kernel, dim3((RN_PARAM_FLOATS + 255) / 256), dim3(256), 0, (hipStream_t)stream, B,
                      (const float *)workspace, wstride, RtWork(n).block(), grad_params, grad_blocks);
   return launch_status("rcpsp_net_train_sum_kernel");
 }

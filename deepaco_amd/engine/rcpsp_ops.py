@@ -113,34 +113,6 @@ def rcpsp_backward(inst, tau, eta, alpha, beta, gamma, c, routes, rowsum, grad_l
     return grad
 
 
-def rcpsp_net_forward(x, relation, params, eps=1e-10, want_logit=False, want_emb=False):
-    """The eval-mode forward of rcpsp/net.py for B projects in one launch (include/deepaco_hip.h daco_rcpsp_net_forward).
-    x [B, n, 5] f32, relation [B, n, n] uint8 (rcpsp.rcpsp_inst.relation_matrix), params: the flat block of
-    rcpsp.net.Net.pack_params.  Returns (heu [B, n, n] = sigmoid(logit) + eps on edges and eps elsewhere, logit [B, n, n] | None
-    with -inf off the graph, emb [B, n, n, 32] | None)."""
-    _require_gpu(x, relation, params)
-    if x.dim() != 3 or relation.dim() != 3 or relation.dtype != torch.uint8 or relation.shape[0] != x.shape[0] \
-            or tuple(relation.shape[1:]) != (x.shape[1], x.shape[1]):
-        raise _lib.DacoError(f"rcpsp_net_forward: x [B, n, {RCPSP_NET_FEATS}] and relation [B, n, n] uint8 expected, got "
-                             f"{tuple(x.shape)} and {tuple(relation.shape)} {relation.dtype}")
-    B, n, feats = x.shape
-    L = _lib.lib()
-    if params.dtype != torch.float32 or params.numel() != L.daco_rcpsp_net_param_floats():
-        raise _lib.DacoError(f"rcpsp_net_forward: {L.daco_rcpsp_net_param_floats()} float32 parameters expected, got "
-                             f"{params.numel()} {params.dtype}")
-    x, relation, params = _f32c(x), relation.contiguous(), params.contiguous()
-    dev = x.device
-    with _on(dev):
-        heu = torch.empty((B, n, n), dtype=torch.float32, device=dev)
-        logit = torch.empty((B, n, n), dtype=torch.float32, device=dev) if want_logit else None
-        emb = torch.empty((B, n, n, 32), dtype=torch.float32, device=dev) if want_emb else None
-        ws = _workspace(dev, L.daco_rcpsp_net_workspace_bytes(B, n), "rcpsp_net")
-        rc = L.daco_rcpsp_net_forward(_stream(dev), B, n, feats, x.data_ptr(), relation.data_ptr(), params.data_ptr(), float(eps),
-                                      heu.data_ptr(), _ptr(logit), _ptr(emb), ws.data_ptr(), ws.numel())
-    _lib.check(rc, "daco_rcpsp_net_forward")
-    return heu, logit, emb
-
-
 def _rcpsp_net_args(who, x, relation, params):
     _require_gpu(x, relation, params)
     if x.dim() != 3 or relation.dim() != 3 or relation.dtype != torch.uint8 or relation.shape[0] != x.shape[0] \
@@ -151,6 +123,26 @@ def _rcpsp_net_args(who, x, relation, params):
     if params.dtype != torch.float32 or params.numel() != P:
         raise _lib.DacoError(f"{who}: {P} float32 parameters expected, got {params.numel()} {params.dtype}")
     return _f32c(x), relation.contiguous(), params.contiguous()
+
+
+def rcpsp_net_forward(x, relation, params, eps=1e-10, want_logit=False, want_emb=False):
+    """The eval-mode forward of rcpsp/net.py for B projects in one launch (include/deepaco_hip.h daco_rcpsp_net_forward).
+    x [B, n, 5] f32, relation [B, n, n] uint8 (rcpsp.rcpsp_inst.relation_matrix), params: the flat block of
+    rcpsp.net.Net.pack_params.  Returns (heu [B, n, n] = sigmoid(logit) + eps on edges and eps elsewhere, logit [B, n, n] | None
+    with -inf off the graph, emb [B, n, n, 32] | None)."""
+    x, relation, params = _rcpsp_net_args("rcpsp_net_forward", x, relation, params)
+    B, n, feats = x.shape
+    L = _lib.lib()
+    dev = x.device
+    with _on(dev):
+        heu = torch.empty((B, n, n), dtype=torch.float32, device=dev)
+        logit = torch.empty((B, n, n), dtype=torch.float32, device=dev) if want_logit else None
+        emb = torch.empty((B, n, n, 32), dtype=torch.float32, device=dev) if want_emb else None
+        ws = _workspace(dev, L.daco_rcpsp_net_workspace_bytes(B, n), "rcpsp_net")
+        rc = L.daco_rcpsp_net_forward(_stream(dev), B, n, feats, x.data_ptr(), relation.data_ptr(), params.data_ptr(), float(eps),
+                                      heu.data_ptr(), _ptr(logit), _ptr(emb), ws.data_ptr(), ws.numel())
+    _lib.check(rc, "daco_rcpsp_net_forward")
+    return heu, logit, emb
 
 
 def rcpsp_net_forward_train(x, relation, params, eps=1e-10, want_logit=False):

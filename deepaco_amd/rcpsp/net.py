@@ -100,23 +100,30 @@ class Net(nn.Module):
         return matrix
 
     # ------------------------------------------------------------------ HIP training path
+    def _param_block(self, dead, bn_slots):
+        """One walk over the flat parameter block in the layout of csrc/daco_rcpsp_net.h: v_lin0, e_lin0, then
+        WvT | bv | We | be | bn_v | bn_e for the 12 layers, then the head.  dead(t): how a tensor of the last layer's node
+        update (v_lins1.11, v_lins2.11, v_bns.11: it feeds nothing) enters; bn_slots(bn): the two vectors of a BatchNorm slot."""
+        e = self.emb_net
+        parts = [e.v_lin0.weight, e.v_lin0.bias, e.e_lin0.weight, e.e_lin0.bias]
+        for i in range(DEPTH):
+            same = lambda t: t                                                                # noqa: E731
+            live = dead if i == DEPTH - 1 else same
+            lins = ((e.v_lins1[i], live), (e.v_lins2[i], live), (e.v_lins3[i], same), (e.v_lins4[i], same))
+            Wv = torch.cat([enter(m.weight) for m, enter in lins], 0)                        # [128, 32]
+            parts += [Wv.t(), torch.cat([enter(m.bias) for m, enter in lins], 0), e.e_lins0[i].weight, e.e_lins0[i].bias,
+                      *(live(t) for t in bn_slots(e.v_bns[i].module)), *bn_slots(e.e_bns[i].module)]
+        for lin in self.par_net_heu.lins:
+            parts += [lin.weight, lin.bias]
+        return torch.cat([p.float().reshape(-1) for p in parts])
+
     def pack_params_train(self):
-        """Flat parameter block for the training kernels (the layout of csrc/daco_rcpsp_net.hip with gamma / beta in the
+        """Flat parameter block for the training kernels (the layout of csrc/daco_rcpsp_net.h with gamma / beta in the
         BatchNorm slots), built from the live parameters with differentiable ops, so that autograd hands the flat gradient back
         to every nn.Parameter.  The last layer's node update (v_lins1.11, v_lins2.11, v_bns.11) feeds nothing: those slices
         enter detached, so their .grad stays None as on the torch-op path (AdamW decays a parameter whose gradient is zero
         and skips one whose gradient is None)."""
-        e = self.emb_net
-        parts = [e.v_lin0.weight.reshape(-1), e.v_lin0.bias, e.e_lin0.weight.reshape(-1), e.e_lin0.bias]
-        for i in range(DEPTH):
-            live = (lambda t: t) if i < DEPTH - 1 else (lambda t: t.detach())
-            Wv = torch.cat([live(e.v_lins1[i].weight), live(e.v_lins2[i].weight), e.v_lins3[i].weight, e.v_lins4[i].weight], 0)
-            bv = torch.cat([live(e.v_lins1[i].bias), live(e.v_lins2[i].bias), e.v_lins3[i].bias, e.v_lins4[i].bias], 0)
-            parts += [Wv.t().reshape(-1), bv, e.e_lins0[i].weight.reshape(-1), e.e_lins0[i].bias,
-                      live(e.v_bns[i].module.weight), live(e.v_bns[i].module.bias), e.e_bns[i].module.weight, e.e_bns[i].module.bias]
-        for lin in self.par_net_heu.lins:
-            parts += [lin.weight.reshape(-1), lin.bias]
-        return torch.cat([p.float().reshape(-1) for p in parts])
+        return self._param_block(lambda t: t.detach(), lambda bn: (bn.weight, bn.bias))
 
     @torch.no_grad()
     def _update_running_stats(self, stats, count_e, n):
@@ -159,11 +166,7 @@ class Net(nn.Module):
         from ..autograd import RcpspNetFn
         if not self.training:
             raise _lib.DacoError("rcpsp.Net: the HIP gradient path is the training-mode network (batch statistics): call .train()")
-        if not x.is_cuda:
-            raise _lib.DacoError("deepaco_amd.rcpsp.Net runs on a HIP device only (got CPU tensors)")
-        self._check_feats(x.shape[-1])
-        if x.shape[1] > engine.RCPSP_NET_MAX_N:
-            raise _lib.DacoTooLarge(f"rcpsp.Net: n={x.shape[1]} exceeds {engine.RCPSP_NET_MAX_N}")
+        self._check_graph(x)
         flat = self.pack_params_train()
         if flat.device != x.device:
             raise _lib.DacoError(f"rcpsp.Net: parameters on {flat.device}, graph on {x.device}")
@@ -175,12 +178,8 @@ class Net(nn.Module):
         """One graph through the training kernels; the values come back in the caller's edge order, gathered from the dense
         output with ordinary indexing (autograd scatters the gradient back)."""
         x = pyg.x
-        if not x.is_cuda:
-            raise _lib.DacoError("deepaco_amd.rcpsp.Net runs on a HIP device only (got CPU tensors)")
+        self._check_graph(x)
         n = x.shape[0]
-        self._check_feats(x.shape[1])
-        if n > engine.RCPSP_NET_MAX_N:
-            raise _lib.DacoTooLarge(f"rcpsp.Net: n={n} exceeds {engine.RCPSP_NET_MAX_N}")
         rel = relation_from_edges(n, pyg.edge_index, pyg.edge_attr)
         heu = self.forward_relation_train(x.unsqueeze(0), rel.unsqueeze(0), 0.0)
         return heu[0][pyg.edge_index[0], pyg.edge_index[1]]
@@ -200,27 +199,28 @@ class Net(nn.Module):
         if feats != FEATS:
             raise _lib.DacoError(f"rcpsp.Net: {feats} node features; the network takes {FEATS} (duration and R = 4 resources)")
 
+    def _check_graph(self, x):
+        """The refusals of every HIP path, of the node features x [..., n, 5]."""
+        if not x.is_cuda:
+            raise _lib.DacoError("deepaco_amd.rcpsp.Net runs on a HIP device only (got CPU tensors)")
+        self._check_feats(x.shape[-1])
+        if x.shape[-2] > engine.RCPSP_NET_MAX_N:
+            raise _lib.DacoTooLarge(f"rcpsp.Net: n={x.shape[-2]} exceeds {engine.RCPSP_NET_MAX_N}")
+
     def pack_params(self):
-        """Flat f32 parameter block in the layout csrc/daco_rcpsp_net.hip documents (BatchNorm folded)."""
+        """Flat f32 parameter block in the layout csrc/daco_rcpsp_net.h documents (BatchNorm folded), cached."""
         key = tuple(t._version for t in list(self.parameters()) + list(self.buffers())) + (next(self.parameters()).device,)
         if self._packed is not None and self._packed_key == key:
             return self._packed
-        e = self.emb_net
+
+        def folded(bn):
+            if not bn.track_running_stats or bn.running_mean is None:
+                raise _lib.DacoError("rcpsp.Net.pack_params folds the BatchNorm running statistics; this network tracks none")
+            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+            return scale, bn.bias - bn.running_mean * scale
+
         with torch.no_grad():
-            parts = [e.v_lin0.weight.reshape(-1), e.v_lin0.bias, e.e_lin0.weight.reshape(-1), e.e_lin0.bias]
-            for i in range(DEPTH):
-                lins = (e.v_lins1[i], e.v_lins2[i], e.v_lins3[i], e.v_lins4[i])
-                Wv = torch.cat([m.weight for m in lins], 0)                                  # [128, 32]
-                parts += [Wv.t().contiguous().reshape(-1), torch.cat([m.bias for m in lins], 0), e.e_lins0[i].weight.reshape(-1),
-                          e.e_lins0[i].bias]
-                for bn in (e.v_bns[i].module, e.e_bns[i].module):
-                    if not bn.track_running_stats or bn.running_mean is None:
-                        raise _lib.DacoError("rcpsp.Net.pack_params folds the BatchNorm running statistics; this network tracks none")
-                    scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-                    parts += [scale, bn.bias - bn.running_mean * scale]
-            for lin in self.par_net_heu.lins:
-                parts += [lin.weight.reshape(-1), lin.bias]
-            flat = torch.cat([p.float().reshape(-1) for p in parts]).contiguous()
+            flat = self._param_block(lambda t: t, folded)
         assert flat.numel() == _lib.lib().daco_rcpsp_net_param_floats()
         self._packed, self._packed_key = flat, key
         return flat
@@ -230,11 +230,7 @@ class Net(nn.Module):
         """x [B, n, 5], relation [B, n, n] uint8 on a HIP device -> engine.rcpsp_net_forward's tuple (eval mode only)."""
         if self.training:
             raise _lib.DacoError("rcpsp.Net: the kernel is an inference path (BatchNorm running statistics): call .eval()")
-        if not x.is_cuda:
-            raise _lib.DacoError("deepaco_amd.rcpsp.Net runs on a HIP device only (got CPU tensors)")
-        self._check_feats(x.shape[-1])
-        if x.shape[1] > engine.RCPSP_NET_MAX_N:
-            raise _lib.DacoTooLarge(f"rcpsp.Net: n={x.shape[1]} exceeds {engine.RCPSP_NET_MAX_N}")
+        self._check_graph(x)
         params = self.pack_params()
         if params.device != x.device:
             raise _lib.DacoError(f"rcpsp.Net: parameters on {params.device}, graph on {x.device}")
@@ -245,12 +241,8 @@ class Net(nn.Module):
         """One graph through the kernel; the values come back in the caller's edge order.  want: 'heu' (sigmoid, no eps),
         'logit', or 'emb' ([E, 32])."""
         x = pyg.x
-        if not x.is_cuda:
-            raise _lib.DacoError("deepaco_amd.rcpsp.Net runs on a HIP device only (got CPU tensors)")
+        self._check_graph(x)
         n = x.shape[0]
-        self._check_feats(x.shape[1])
-        if n > engine.RCPSP_NET_MAX_N:
-            raise _lib.DacoTooLarge(f"rcpsp.Net: n={n} exceeds {engine.RCPSP_NET_MAX_N}")
         rel = relation_from_edges(n, pyg.edge_index, pyg.edge_attr)
         heu, logit, emb = self.forward_relation(x.unsqueeze(0), rel.unsqueeze(0), 0.0, want == "logit", want == "emb")
         src, dst = pyg.edge_index[0], pyg.edge_index[1]

@@ -813,7 +813,7 @@ int daco_rcpsp_track(void *stream, int B, int n, int A, const int64_t *routes, c
  *   x [B][n][5] f32 node features (duration / max duration, requirements / capacities); feats must be 5 (DACO_E_BADARG)
  *   relation [B][n][n] uint8: 0 = no edge, 1 = precedence edge (attribute [1,0]), 2 = unrelated pair (attribute [0,1]),
  *     3 = the sink's self-loop (attribute [0,0]); edge (i, j) at slot i*n + j; a value above 3 is read as 0
- *   params: daco_rcpsp_net_param_floats() floats, layout at the top of csrc/daco_rcpsp_net.hip (that of csrc/daco_gnn.h with 64
+ *   params: daco_rcpsp_net_param_floats() floats, layout at the top of csrc/daco_rcpsp_net.h (that of csrc/daco_gnn.h with 64
  *     floats for e_lin0.weight; BatchNorm folded to scale / shift from the running statistics -> eval mode only)
  *   heu out [B][n][n] f32: sigmoid(logit) + eps on edges, eps exactly elsewhere (Net.reshape's zero plus eps)
  *   logit out [B][n][n] or NULL: the head's pre-sigmoid output on edges, -INFINITY elsewhere
