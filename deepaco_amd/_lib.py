@@ -69,6 +69,9 @@ SIGNATURES = {
                                  _i, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "daco_sibling_backward": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _vp, _l, _f, _vp, _i, _vp, _vp,
                                    _vp, _vp, _vp]),
+    # (long statuses, as daco_rcpsp_net_forward)
+    "daco_sibling_objective": (_l, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
+    "daco_sibling_record": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
     "daco_tsp_knn_graph": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp]),
     "daco_tsp_knn_graph_csr": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "daco_heu_matrix": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp]),

@@ -30,9 +30,10 @@ SIB_KINDS = {"sop": 3, "pctsp": 4, "op": 5, "mkp": 6}
 
 def sibling_sample(kind, tau, eta, n_ants, alpha=1.0, beta=1.0, aux_vec=None, aux_mat=None, scalar0=0.0,
                    item_weights=None, mode="scan", start=None, noise=None, seed=0, it=0, ant_gid0=0,
-                   require_prob=False, Lmax=None):
+                   require_prob=False, Lmax=None, flags=None):
     """Fused solution construction for sop / pctsp / op / mkp, one instance batch B = leading dim of tau
     (or 1).  See include/deepaco_hip.h daco_sibling_sample for the meaning of aux_vec / aux_mat / scalar0.
+    flags: the caller's own sticky flag words [B] int32, OR-ed into (no fill launch per call), instead of fresh zeros.
     Returns (paths [B,rows,A], log_probs|None, rowsum|None, lens [B,A]|None, flags [B])."""
     _require_gpu(tau, eta, aux_vec, aux_mat, item_weights, start, noise)
     n = tau.shape[-1]
@@ -51,7 +52,8 @@ def sibling_sample(kind, tau, eta, n_ants, alpha=1.0, beta=1.0, aux_vec=None, au
         logp = torch.empty((B, rows - 1, n_ants), dtype=torch.float32, device=dev) if require_prob else None
         rowsum = torch.ones((B, rows - 1, n_ants), dtype=torch.float32, device=dev) if require_prob else None
         lens = torch.empty((B, n_ants), dtype=torch.int32, device=dev) if varlen else None
-        flags = torch.zeros((B,), dtype=torch.int32, device=dev)
+        if flags is None:
+            flags = torch.zeros((B,), dtype=torch.int32, device=dev)
         noise, steps = _noise_steps(noise, B, n_ants, n, "sibling_sample") if noise is not None else (None, 0)
         if start is not None:
             start = start.to(torch.int64).contiguous().view(B, n_ants)

@@ -289,6 +289,21 @@ def infer_rcpsp_batch(instances, n_ants, t_aco, heuristic=None, seed=0, sampler=
     return torch.stack(out), colony
 
 
+@torch.no_grad()
+def infer_sibling_batch(problem, data, n_ants, t_aco, heuristic=None, seed=0, **aco_kw):
+    """The test loops of the sibling problems (op/test.py, mkp/test.py and the notebooks of smtwtp, sop, pctsp, bpp: one colony
+    per instance, the record read at every checkpoint of t_aco) for B instances of one size at once.  problem: 'smtwtp', 'sop',
+    'pctsp', 'op', 'bpp' or 'mkp'; data: the tuple of batched tensors of that problem's engine.Batched* constructor (e.g.
+    (distances [B,n,n], prizes [B,n], max_len) for 'op'); heuristic [B,.,.] as that constructor takes it, or None for the
+    reference's default; aco_kw: anything else the constructor takes.  Returns (records [len(t_aco), B], colony)."""
+    colony = engine.BATCHED_SIBLINGS[problem](*data, n_ants=n_ants, heuristic=heuristic, seed=seed, **aco_kw)
+    out, done = [], 0
+    for t in t_aco:
+        out.append(colony.run(t - done).clone())
+        done = t
+    return torch.stack(out), colony
+
+
 def _rcpsp_loss(net, instances, n_ants, seed=0, it=0, noise=None, **acoparam):
     """The loss of rcpsp/train.ipynb's train_instance for B projects of equal n: one HIP training forward -> B colonies sampled
     and scheduled with log-probabilities (one launch) -> per project sum_a (cost - mean cost) sum_t logp / n_ants / n, averaged

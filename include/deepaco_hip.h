@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129) */
 
 /* error codes */
 #define DACO_OK 0
@@ -335,6 +335,59 @@ int daco_sibling_sample(void *stream, int kind, int B, int n, int A,
                         uint64_t seed, uint64_t iter, uint32_t ant_gid0, int Lmax,
                         int64_t *paths, float *logp, float *rowsum, int32_t *lens, int32_t *flags,
                         void *workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_sibling_objective -- objective, elitist key and deposit amount of every ant, for the six sibling problems
+ *   (gen_path_costs / gen_sol_obj and the amount update_pheronome adds, of smtwtp/ sop/ pctsp/ op/ mkp/ bpp/aco.py)
+ * paths [B][rows][A] int64 as the constructions write them; lens [B][A] int32 or NULL (every ant uses all rows).  Per
+ * (instance, ant): obj [B][A] f32 (obj64 [B][A] f64 instead for DACO_SIB_BPP), key [B][A] f32 whose FIRST MINIMUM is the
+ * elitist ant (daco_pheromone_update's `costs`), weight [B][A] f32 (its `weights`).
+ * The arithmetic is part of the contract: every sum starts at +0.0f (+0.0 for BPP) and is sequential; a multiply and the add
+ * that takes it are rounded separately (no fused multiply-add); only an ant's own rows k < lens count.  A node id outside the
+ * instance reads as node 0.
+ *   DACO_SIB_SMTWTP smtwtp/aco.py:84-111   n = jobs, rows = n + 1 (the nodes daco_tsp_sample(fixed_start = 0) wrote; row 0 is
+ *                   the dummy); vec0 = processing_time, vec1 = due_time, vec2 = weights, [B][n] each.  For k = 1..n, j = node - 1:
+ *                   t += vec0[j]; late = (t - vec1[j] < 0) ? 0 : t - vec1[j]; c += vec2[j] * late.
+ *                   obj = key = c, weight = 1 / (c + 1)
+ *   DACO_SIB_SOP    sop/aco.py             mat = distances [B][n][n]; obj = sum_k mat[u_k][u_{k+1}], k ascending: bit for bit
+ *                   daco_tour_costs(closed = 0).  key = obj, weight = 1 / obj
+ *   DACO_SIB_PCTSP  pctsp/aco.py:104-129   mat = distances, vec0 = penalties [B][n].  length = the open length over the ant's
+ *                   rows, k ascending; penalty = sum of vec0[v] over the nodes v not among the ant's rows, v ascending from +0.0f;
+ *                   obj = length + penalty, key = -obj (the reference's arg-MAX, pctsp/aco.py:74), weight = 1 / obj
+ *   DACO_SIB_OP     op/aco.py:141-147      vec0 = prizes [B][n], n counts the dummy (prize 0); obj = sum_k vec0[u_k], k ascending;
+ *                   key = -obj, weight = scale[b] * obj (scale = the colony's Q)
+ *   DACO_SIB_MKP    mkp/aco.py             vec0 = prize [B][n] with the dummy item; obj, key, weight as DACO_SIB_OP
+ *   DACO_SIB_BPP    bpp/aco.py:26-40,121-126  float64.  vec0 = demand [B][n] f32 (widened exactly), capacity = C.  With
+ *                   L = max_a lens[b][a] (the width of the reference's padded matrix; rows without lens), rows past an ant's
+ *                   own reading as node 0: for j = 1..L-1: sub += demand[node] if node != 0, else f += (sub / C) * (sub / C),
+ *                   sub = 0.  n_bins = L - trailing_zeros - n + 1 (trailing zeros of the padded row; 0 for a row of zeros, as
+ *                   count_last_zero has it); cost = -(f / n_bins).  obj64 = cost, key = (float)cost,
+ *                   weight = (float)(fit / A), or (float)fit when elitist != 0, with fit = -cost
+ * Unused pointers may be NULL.  One launch, one lane per ant, the instance's vectors (and PCTSP's per-lane set of visited nodes)
+ * in LDS: 48 KiB at n = DACO_MAX_NODES, DACO_E_TOOLARGE above that.
+ *
+ * daco_sibling_record -- the record step of the six run() loops on the device, per instance: i = first minimum of key (ties:
+ * the lowest ant), and where that ant's objective beats the record under the problem's rule the record and its solution
+ * best_sol [B][len - row0] = paths[b][row0..len-1][i] are replaced (an unchanged record leaves best_sol untouched).
+ *   rule = the kind.  SMTWTP, SOP: obj < record (start it at +inf);  PCTSP: obj < record (start 1e10; obj is the iteration's
+ *   MAXIMUM, sic);  OP, MKP: obj > record (start 0);  BPP: -obj64 > best_obj64 (start 0; best_obj64 holds the fitness).
+ *   row0: 1 for SMTWTP (the dummy row is dropped), else 0.  best_idx [B] (optional): i.
+ *   mmas_max [B] (optional) is written for every instance from the record AFTER this step:  SOP (1 / record) * mmas_n (two
+ *   roundings, as daco_track_best);  PCTSP mmas_n / record (pass n - 1);  OP (record * mmas_n) * mmas_scale[b] (pass the number
+ *   of real nodes and Q);  the other rules leave it alone (SMTWTP's bound is 1, MKP's 20: the caller's constants).
+ * Both refuse bad input before any launch (DACO_E_BADARG, DACO_E_TOOLARGE for n > DACO_MAX_NODES, daco_last_error()).  The
+ * status is the usual DACO_OK / DACO_E_* value typed `long`, for the reason given at daco_rcpsp_net_forward; the refusals are
+ * held by tests/test_sibling_objective_spec.py.
+ */
+#define DACO_SIB_SMTWTP 7
+#define DACO_SIB_BPP 8
+long daco_sibling_objective(void *stream, int kind, int B, int n, int rows, int A, const int64_t *paths,
+                            const int32_t *lens, const float *vec0, const float *vec1, const float *vec2,
+                           const float *mat, long mat_bstride, double capacity, int elitist, const float *scale,
+                           float *obj, double *obj64, float *key, float *weight);
+long daco_sibling_record(void *stream, int rule, int B, int len, int A, const float *key, const float *obj,
+                         const double *obj64, const int64_t *paths, int row0, float *best_obj, double *best_obj64,
+                        int64_t *best_sol, int32_t *best_idx, float *mmas_max, float mmas_n, const float *mmas_scale);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_sibling_backward -- daco_sample_backward for the fused sibling constructions: the gradient of
