@@ -18,6 +18,21 @@
 // Across solutions: B x A independent wavefronts (10^5 at BASELINE's config 4), fetched from a queue.
 // State (linked routes, cumulated loads / reversal distances, route loads and penalties) lives in LDS, ~5 KB per
 // solution at n = 100; the float64 matrix (82 KB per instance, shared by the instance's ants) is gathered from L2.
+//
+// SWAP* (template flag SS, entry daco_hgs_local_search_ss; specification: oracle/hgs_ls.c with use_swap_star = 1).  What a user
+// gets who mends the reference's ctypes structure: Params takes the coordinates over (Params.cpp:40-54), updateRouteData keeps
+// every route's circle sector and barycentre angle (LocalSearch.cpp:652-707), every loop of LocalSearch::run ends with the
+// SWAP* phase over the route pairs whose sectors overlap (LocalSearch.cpp:77-99), swapStar() itself (:486-573) with
+// preprocessInsertions (:594-615) and getCheapestInsertSimultRemoval (:575-592), and the routes leave in the order of their
+// barycentre angles (:756-778).  Exact: the sector arithmetic (integers; the clients' polar angles come in as an array the host
+// made with libm's atan2), the three-best insertion memory with its tie rule (`>=`: an equal cost goes behind the kept one), the
+// choice of the move (first strict minimum in the order of the reference's loops), every cost as the reference's left-to-right
+// sum.  Not exact: the barycentre angle is the device library's atan2; it is only compared with other barycentre angles, so the
+// export order can differ from the reference where two routes' angles lie within that function's error of each other.
+// Mapping: one lane per client of one route, a wave-uniform loop over the other route.  The insertion memory is recomputed by
+// every swapStar call (it depends on the target route's content and the client alone: the reference's tables only cache it)
+// and lives in the wave's LDS for the duration of the call: [n] entries instead of the reference's [R][nc + 1].
+// The SS = false instantiations are compiled from the same statements as before the flag existed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -171,6 +186,8 @@ struct HgsParams {
   uint32_t *queue;                   // work counter (zeroed by the launcher)
   uint16_t *scratch;                 // per resident wavefront: shuffled neighbour lists, 2 * g * nc entries
   size_t scratch_stride;
+  const double *xy;                  // SS: [B][n][2] coordinates (node 0 the depot)
+  const int32_t *polar;              // SS: [B][n] Client::polarAngle (Params.cpp:42-47), made on the host
 };
 
 // LDS of one wavefront
@@ -183,10 +200,33 @@ struct HgsLds {
   double *rLoad, *rPen, *rRev;             // [Rmax]
   uint8_t *e2;                             // [n]  move of a node towards the empty route (valid while no move is applied)
   int32_t *rWhen, *rCnt;                   // [Rmax]
+  // SS only (hgs_ss_bytes, carved behind the rest)
+  double *tbC, *dRem;                      // [3][n] bestCost of a client's three best insertions into the other route, [n] deltaRemoval
+  double *rBary;                           // [Rmax] polarAngleBarycenter
+  int32_t *rSecS, *rSecE, *rWhenSS;        // [Rmax] sector.start / .end, whenLastTestedSWAPStar
+  uint16_t *tbL;                           // [3][n] bestLocation (HGS_NOLOC: NULL)
+  uint16_t *lst;                           // [n] the clients of the two routes of a swapStar call, in route order
+  uint16_t *ordR, *hF, *hL;                // [Rmax] orderRoutes; first / last client of the routes in export order
 };
 __host__ __device__ inline size_t hgs_lds_bytes(int n, int Rmax) {
   const size_t N = (size_t)n + 2 * Rmax;
   return a16(2 * N) * 4 + a16(8 * N) * 3 + a16(4 * (size_t)n) * 2 + a16(8 * (size_t)Rmax) * 3 + a16(4 * (size_t)Rmax) * 2 + a16((size_t)n);
+}
+__host__ __device__ inline size_t hgs_ss_bytes(int n, int Rmax) {
+  return a16(8 * (size_t)n) * 4 + a16(8 * (size_t)Rmax) + a16(4 * (size_t)Rmax) * 3 + a16(2 * (size_t)n) * 4 + a16(2 * (size_t)Rmax) * 3;
+}
+__device__ inline void hgs_carve_ss(HgsLds &l, unsigned char *p, int n, int Rmax) {
+  l.tbC = (double *)p; p += a16(8 * (size_t)n) * 3;
+  l.dRem = (double *)p; p += a16(8 * (size_t)n);
+  l.rBary = (double *)p; p += a16(8 * (size_t)Rmax);
+  l.rSecS = (int32_t *)p; p += a16(4 * (size_t)Rmax);
+  l.rSecE = (int32_t *)p; p += a16(4 * (size_t)Rmax);
+  l.rWhenSS = (int32_t *)p; p += a16(4 * (size_t)Rmax);
+  l.tbL = (uint16_t *)p; p += a16(2 * (size_t)n) * 3;
+  l.lst = (uint16_t *)p; p += a16(2 * (size_t)n);
+  l.ordR = (uint16_t *)p; p += a16(2 * (size_t)Rmax);
+  l.hF = (uint16_t *)p; p += a16(2 * (size_t)Rmax);
+  l.hL = (uint16_t *)p;
 }
 __device__ inline HgsLds hgs_carve(unsigned char *p, int n, int Rmax) {
   const size_t N = (size_t)n + 2 * Rmax;
@@ -218,6 +258,7 @@ __device__ inline double rl_d(double v, int lane) {
 struct HgsCtx {
   HgsLds l;
   const double *tc, *tct, *dem;         // tct: the transposed matrix (tc itself when symmetric)
+  const double *xy; const int32_t *polar;   // SS: the instance's coordinates [n][2] and polar angles [n]
   int n, nc, R, lane;
   double cap, penCap;
   int nbMoves;
@@ -235,10 +276,17 @@ struct HgsCtx {
 // updateRouteData (LocalSearch.cpp:652-707) without the duration, barycentre and sector (unused without SWAP*: every
 // coordinate is zero, Params.cpp:49-54).  The chain of nodes is chased once, the matrix entries of its edges are gathered
 // by the lanes, the cumulated sums run in route order (one addition after the other, as the reference's loop).
+// SS: with the barycentre and the sector (CircleSector.h:14-58).  The sector grows client by client in route order (which of its
+// two ends moves depends on the sector so far): a wave-uniform chain over the values the lanes fetched, next to the sums.
+__device__ inline int hgs_posmod(int i) { return (i % 65536 + 65536) % 65536; }
+template <bool SS>
 __device__ inline void hgs_update_route(HgsCtx &c, int r) {
   const int lane = c.lane;
   int node = c.dep(r), place = 0;
   double load = 0., rev = 0.;
+  [[maybe_unused]] double bx = 0., by = 0.;
+  [[maybe_unused]] int secS = 0, secE = 0;
+  [[maybe_unused]] bool first = true;
   if (lane == 0) { c.l.pos[node] = 0; c.l.cumLoad[node] = 0.; c.l.cumRev[node] = 0.; }
   bool done = false;
   while (!done) {
@@ -251,12 +299,15 @@ __device__ inline void hgs_update_route(HgsCtx &c, int r) {
       done = c.isdep(node) || c.tick(1);
     }
     double dl = 0., dr = 0.;
+    [[maybe_unused]] double px = 0., py = 0.;
+    [[maybe_unused]] int pol = 0;
     if (lane < cnt) {
       const int cc = c.cour(mine), pc = c.cour(mprev);
       dl = c.dem[cc];
       const double fwd = c.TC(pc, cc);
       dr = c.TC(cc, pc) - fwd;
       c.l.dNext[mprev] = fwd;
+      if constexpr (SS) { px = c.xy[2 * cc]; py = c.xy[2 * cc + 1]; pol = c.polar[cc]; }
     }
     double myl = 0., myr = 0.;
     for (int k = 0; k < cnt; ++k) {
@@ -265,12 +316,31 @@ __device__ inline void hgs_update_route(HgsCtx &c, int r) {
       if (lane == k) { myl = load; myr = rev; }
     }
     if (lane < cnt) { c.l.pos[mine] = (uint16_t)(place + lane + 1); c.l.cumLoad[mine] = myl; c.l.cumRev[mine] = myr; }
+    if constexpr (SS) {
+      const int ncl = cnt - (c.isdep(node) ? 1 : 0);          // (the closing depot is the last node of the chain)
+      for (int k = 0; k < ncl; ++k) {
+        bx += rl_d(px, k); by += rl_d(py, k);
+        const int pk = __builtin_amdgcn_readlane(pol, k);
+        if (first) { secS = secE = pk; first = false; }
+        else if (!(hgs_posmod(pk - secS) <= hgs_posmod(secE - secS))) {
+          if (hgs_posmod(pk - secE) <= hgs_posmod(secS - pk)) secE = pk; else secS = pk;
+        }
+      }
+    }
     place += cnt;
   }
   if (lane == 0) {
     c.l.dNext[node] = c.TC(0, 0);                      // the closing depot's own successor is the route's first depot
     c.l.rLoad[r] = load; c.l.rPen[r] = c.pen(load); c.l.rRev[r] = rev;
     c.l.rCnt[r] = place - 1; c.l.rWhen[r] = c.nbMoves;
+  }
+  if constexpr (SS) {
+    const int nb = place - 1;
+    const double bary = nb <= 0 ? 1.e30 : atan2(by / (double)nb - c.xy[1], bx / (double)nb - c.xy[0]);
+    if (lane == 0) {
+      if (!first) { c.l.rSecS[r] = secS; c.l.rSecE[r] = secE; }
+      c.l.rBary[r] = bary;
+    }
   }
 }
 
@@ -466,6 +536,7 @@ __device__ inline void hgs_swap_node(const HgsCtx &c, int U, int V) {           
 }
 
 // apply move `mv` to (U, V) (wave-uniform): the pointer surgery of LocalSearch.cpp:134-484, then the route data
+template <bool SS>
 __device__ inline void hgs_apply(HgsCtx &c, int mv, int U, int V) {
   uint16_t *nx = c.l.next, *pv = c.l.prev, *rt = c.l.route;
   const int X = nx[U], Y = nx[V], rU = rt[U], rV = rt[V];
@@ -528,8 +599,149 @@ __device__ inline void hgs_apply(HgsCtx &c, int mv, int U, int V) {
       break;
   }
   c.nbMoves++;
-  hgs_update_route(c, rU);
-  if (!intra) hgs_update_route(c, rV);
+  hgs_update_route<SS>(c, rU);
+  if (!intra) hgs_update_route<SS>(c, rV);
+}
+
+// ---------------------------------------------------------------------------------------------- SWAP*
+constexpr int HGS_NOLOC = 0xffff;                  // bestLocation == NULL (node ids stay below: n + 2 Rmax <= 65535)
+struct HgsTop3 { double c0, c1, c2; int l0, l1, l2; };
+// ThreeBestInsert::compareAndAdd (LocalSearch.h:69-89): `>=` -- a cost equal to a kept one goes behind it
+__device__ inline void hgs_tb_add(HgsTop3 &t, double cost, int loc) {
+  if (cost >= t.c2) return;
+  else if (cost >= t.c1) { t.c2 = cost; t.l2 = loc; }
+  else if (cost >= t.c0) { t.c2 = t.c1; t.l2 = t.l1; t.c1 = cost; t.l1 = loc; }
+  else { t.c2 = t.c1; t.l2 = t.l1; t.c1 = t.c0; t.l1 = t.l0; t.c0 = cost; t.l0 = loc; }
+}
+__device__ inline HgsTop3 hgs_tb_load(const HgsCtx &c, int u) {
+  HgsTop3 t;
+  t.c0 = c.l.tbC[u]; t.c1 = c.l.tbC[c.n + u]; t.c2 = c.l.tbC[2 * c.n + u];
+  t.l0 = c.l.tbL[u]; t.l1 = c.l.tbL[c.n + u]; t.l2 = c.l.tbL[2 * c.n + u];
+  return t;
+}
+// preprocessInsertions(R1, R2) (LocalSearch.cpp:594-615): one lane per client u of R1 walks R2 in route order, so that every
+// lane's three-best memory is filled by the reference's own sequence of compareAndAdd calls.  l1 / l2: the routes' clients.
+__device__ inline void hgs_preprocess(HgsCtx &c, const uint16_t *l1, int n1, int r2, const uint16_t *l2, int n2) {
+  const int lane = c.lane, d2 = c.dep(r2), f = l2[0];
+  const double d0f = c.TC(0, f);
+  for (int i0 = 0; i0 < n1 && !c.fail; i0 += 64) {
+    const bool on = i0 + lane < n1;
+    const int u = l1[on ? i0 + lane : 0];                      // (idle lanes shadow the route's first client and store nothing)
+    const int up = c.cour(c.l.prev[u]), un = c.cour(c.l.next[u]);
+    const double rem = c.TC(up, un) - c.TC(up, u) - c.TC(u, un);
+    HgsTop3 t;
+    t.c0 = c.TC(0, u) + c.TT(f, u) - d0f; t.l0 = d2;
+    t.c1 = 1.e30; t.c2 = 1.e30; t.l1 = HGS_NOLOC; t.l2 = HGS_NOLOC;
+    for (int j = 0; j < n2; ++j) {
+      if (c.tick(3)) break;
+      const int V = l2[j], vn = j + 1 < n2 ? (int)l2[j + 1] : 0;
+      hgs_tb_add(t, c.TC(V, u) + c.TT(vn, u) - c.TC(V, vn), V);
+    }
+    if (on) {
+      c.l.dRem[u] = rem;
+      c.l.tbC[u] = t.c0; c.l.tbC[c.n + u] = t.c1; c.l.tbC[2 * c.n + u] = t.c2;
+      c.l.tbL[u] = (uint16_t)t.l0; c.l.tbL[c.n + u] = (uint16_t)t.l1; c.l.tbL[2 * c.n + u] = (uint16_t)t.l2;
+    }
+  }
+}
+// getCheapestInsertSimultRemoval(U, V) (LocalSearch.cpp:575-592): the cheapest place for U in V's route once V is gone; t is U's
+// memory towards that route, pvV = prev(V) (`bestPosition->next != V` is `bestPosition != prev(V)`), d the cost of V's own place
+__device__ inline double hgs_cheapest(const HgsTop3 &t, int V, int pvV, double d, int &pos) {
+  pos = t.l0;
+  double best = t.c0;
+  bool found = pos != V && pos != pvV;
+  if (!found && t.l1 != HGS_NOLOC) {
+    pos = t.l1; best = t.c1;
+    found = pos != V && pos != pvV;
+    if (!found && t.l2 != HGS_NOLOC) { pos = t.l2; best = t.c2; found = true; }
+  }
+  if (!found || d < best) { pos = pvV; best = d; }
+  return best;
+}
+// swapStar(rU, rV) (LocalSearch.cpp:486-573).  The candidates are the pairs (U, V) in U-major order, then the relocations of a U,
+// then those of a V, and the reference keeps the first strict minimum of that sequence: every lane keeps the minimum of its
+// candidates under the key (cost, position in the sequence), the wave reduces under the same key.  Lanes: the clients of rV in
+// the pair loop (a wave-uniform loop over rU), the clients of either route in the relocations.
+__device__ inline bool hgs_swap_star(HgsCtx &c, int rU, int rV) {
+  const int lane = c.lane, nU = c.l.rCnt[rU], nV = c.l.rCnt[rV];
+  uint16_t *lU = c.l.lst, *lV = c.l.lst + nU;
+  // the two routes' clients in route order, from the positions the route update left (an entry nobody writes stays the depot:
+  // every index below is then inside the instance whatever the state)
+  if (nU + nV > c.nc) { if (!c.fail) c.fail = 3; return false; }   // (route counts of a broken state: reported like a spent budget)
+  for (int k = lane; k < nU + nV; k += 64) lU[k] = 0;
+  for (int i = 1 + lane; i <= c.nc; i += 64) {
+    const int r = c.l.route[i], ps = (int)c.l.pos[i] - 1;
+    if (r == rU && ps >= 0 && ps < nU) lU[ps] = (uint16_t)i;
+    else if (r == rV && ps >= 0 && ps < nV) lV[ps] = (uint16_t)i;
+  }
+  hgs_preprocess(c, lU, nU, rV, lV, nV);
+  hgs_preprocess(c, lV, nV, rU, lU, nU);
+  if (c.fail) return false;
+  const double loadRU = c.l.rLoad[rU], loadRV = c.l.rLoad[rV], penRU = c.l.rPen[rU], penRV = c.l.rPen[rV];
+  double best = 1.e30;
+  uint64_t key = ~0ull;
+  int bU = -1, bV = -1, bPU = -1, bPV = -1;
+  for (int j0 = 0; j0 < nV && !c.fail; j0 += 64) {
+    const bool on = j0 + lane < nV;
+    const int j = on ? j0 + lane : 0, V = lV[j];
+    const int pvV = c.l.prev[V], vp = c.cour(pvV), vn = c.cour(c.l.next[V]);
+    const double demV = c.dem[V], remV = c.l.dRem[V], dVpVn = c.TC(vp, vn);
+    const HgsTop3 tV = hgs_tb_load(c, V);
+    for (int i = 0; i < nU; ++i) {
+      if (c.tick(3)) break;
+      const int U = lU[i];
+      const double demU = c.dem[U], remU = c.l.dRem[U];
+      const double dPU = c.pen(loadRU + demV - demU) - penRU;
+      const double dPV = c.pen(loadRV + demU - demV) - penRV;
+      if (on && dPU + remU + dPV + remV <= 0) {
+        const int pvU = c.l.prev[U], up = c.cour(pvU), un = c.cour(c.l.next[U]);
+        const HgsTop3 tU = hgs_tb_load(c, U);
+        int pU, pV;
+        const double extraV = hgs_cheapest(tU, V, pvV, c.TT(U, vp) + c.TC(U, vn) - dVpVn, pU);
+        const double extraU = hgs_cheapest(tV, U, pvU, c.TC(up, V) + c.TT(un, V) - c.TC(up, un), pV);
+        const double mc = dPU + remU + extraU + dPV + remV + extraV + 0. + 0.;
+        const uint64_t k = ((uint64_t)i << 16) | (uint64_t)j;
+        if (mc < best || (mc == best && k < key)) { best = mc; key = k; bU = U; bV = V; bPU = pU; bPV = pV; }
+      }
+    }
+  }
+  for (int i0 = 0; i0 < nU; i0 += 64) {                       // U alone moves to rV (LocalSearch.cpp:525-539)
+    if (i0 + lane < nU) {
+      const int i = i0 + lane, U = lU[i];
+      const double demU = c.dem[U];
+      const double mc = c.l.dRem[U] + c.l.tbC[U] + c.pen(loadRU - demU) - penRU + c.pen(loadRV + demU) - penRV + 0. + 0.;
+      const uint64_t k = (1ull << 40) | ((uint64_t)i << 16);
+      if (mc < best || (mc == best && k < key)) { best = mc; key = k; bU = U; bPU = c.l.tbL[U]; bV = -1; bPV = -1; }
+    }
+  }
+  for (int j0 = 0; j0 < nV; j0 += 64) {                       // V alone moves to rU (:541-555)
+    if (j0 + lane < nV) {
+      const int j = j0 + lane, V = lV[j];
+      const double demV = c.dem[V];
+      const double mc = c.l.tbC[V] + c.l.dRem[V] + c.pen(loadRU + demV) - penRU + c.pen(loadRV - demV) - penRV + 0. + 0.;
+      const uint64_t k = (2ull << 40) | ((uint64_t)j << 16);
+      if (mc < best || (mc == best && k < key)) { best = mc; key = k; bV = V; bPV = c.l.tbL[V]; bU = -1; bPU = -1; }
+    }
+  }
+  double gbest = best;
+  uint64_t gkey = key;
+  for (int o = 32; o; o >>= 1) {
+    const double ob = __shfl_xor(gbest, o);
+    const uint64_t ok = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(gkey >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)gkey, o);
+    if (ob < gbest || (ob == gbest && ok < gkey)) { gbest = ob; gkey = ok; }
+  }
+  if (c.fail || gkey == ~0ull || gbest > -HGS_EPS) return false;
+  const uint64_t who = __ballot(key == gkey);
+  if (!who) return false;
+  const int wl = __builtin_ctzll(who);
+  bU = __builtin_amdgcn_readlane(bU, wl); bV = __builtin_amdgcn_readlane(bV, wl);
+  bPU = __builtin_amdgcn_readlane(bPU, wl); bPV = __builtin_amdgcn_readlane(bPV, wl);
+  if (bPU != -1) hgs_insert_node(c, bU, bPU);
+  if (bPV != -1) hgs_insert_node(c, bV, bPV);
+  c.nbMoves++;
+  hgs_update_route<true>(c, rU);
+  hgs_update_route<true>(c, rV);
+  return true;
 }
 
 // LM (round 6, "latency mode"): a launch of FEW solutions -- the reference's own calling pattern hands the local search the 8
@@ -539,17 +751,18 @@ __device__ inline void hgs_apply(HgsCtx &c, int mv, int U, int V) {
 // wavefront that keeps the stage's float64 matrix (n^2 x 8 bytes: 82 KB at n = 101) and the demands in LDS next to its state, so
 // those trips are LDS gathers; an asymmetric matrix keeps its transpose in global memory (the two do not fit together).  The
 // arithmetic, the order of evaluation and every decision are the kernel's above: the routes are the same.
-template <int WAVES, int WPS, bool LM = false>
+template <int WAVES, int WPS, bool LM = false, bool SS = false>
 __global__ __launch_bounds__(WAVES * 64, WPS) void hgs_ls_kernel(const HgsParams p) {
   static_assert(!LM || WAVES == 1, "latency mode: one wavefront per workgroup");
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = p.n, nc = n - 1;
-  const size_t per_wave = hgs_lds_bytes(n, p.Rmax);
+  const size_t per_wave = hgs_lds_bytes(n, p.Rmax) + (SS ? hgs_ss_bytes(n, p.Rmax) : 0);
   double *mat_lds = reinterpret_cast<double *>(lds_raw + per_wave);          // LM: [n][n], then the demands [n]
   double *dem_lds = mat_lds + (size_t)n * n;
   HgsCtx c;
   c.l = hgs_carve(lds_raw + (size_t)wave * per_wave, n, p.Rmax);
+  if constexpr (SS) hgs_carve_ss(c.l, lds_raw + (size_t)wave * per_wave + hgs_lds_bytes(n, p.Rmax), n, p.Rmax);
   c.n = n; c.nc = nc; c.lane = lane; c.cap = p.cap;
   uint16_t *scratch = p.scratch + (size_t)(blockIdx.x * WAVES + wave) * p.scratch_stride;
   const int nitems = p.B * p.A;
@@ -572,6 +785,7 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void hgs_ls_kernel(const HgsParams
     const int b = item / p.A, a = item - b * p.A;
     int64_t *col = p.paths + (size_t)b * p.Lmax * p.A + a;
     c.dem = p.demand + (size_t)b * n;
+    if constexpr (SS) { c.xy = p.xy + (size_t)b * n * 2; c.polar = p.polar + (size_t)b * n; }
     if constexpr (LM) {
       for (int i = lane; i < n; i += 64) dem_lds[i] = c.dem[i];
       c.dem = dem_lds;
@@ -678,7 +892,7 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void hgs_ls_kernel(const HgsParams
       c.nbMoves = 0;
       c.budget = p.budget;
       if (!thrown) {
-        for (int r = 0; r < R; ++r) hgs_update_route(c, r);                    // loadIndividual (LocalSearch.cpp:709-754)
+        for (int r = 0; r < R; ++r) hgs_update_route<SS>(c, r);                  // loadIndividual (LocalSearch.cpp:709-754)
         // Individual.cpp:26-35,70: feasible within MY_EPSILON, or it throws
         double excess = 0.;
         for (int r = 0; r < R; ++r) { const double ld = c.l.rLoad[r]; if (ld > c.cap) excess += ld - c.cap; }
@@ -690,7 +904,14 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void hgs_ls_kernel(const HgsParams
       // LocalSearch.cpp:9-14: orderNodes is in the table; orderRoutes is shuffled (its draws count, its order is only used by
       // SWAP*); every client's neighbour list is shuffled with probability 1 / nbGranular
       uint32_t x = hdr->rng_state;
-      shuffle_minstd(R, x, [](int, int) {});
+      if constexpr (SS) {
+        for (int r = lane; r < R; r += 64) { c.l.ordR[r] = (uint16_t)r; c.l.rWhenSS[r] = -1; }
+        uint16_t *ord = c.l.ordR;
+        if (lane == 0) shuffle_minstd(R, x, [&](int pa, int pb) { const uint16_t t = ord[pa]; ord[pa] = ord[pb]; ord[pb] = t; });
+        else shuffle_minstd(R, x, [](int, int) {});
+      } else {
+        shuffle_minstd(R, x, [](int, int) {});
+      }
       {
         uint32_t so = 0;
         for (int i = 1; i <= nc; ++i) {
@@ -770,7 +991,7 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void hgs_ls_kernel(const HgsParams
               const int mv = __builtin_amdgcn_readlane(code, pl);
               int V = __builtin_amdgcn_readlane(myV, pl);
               if (mv & 16) V = c.l.prev[V];
-              hgs_apply(c, mv & 15, U, V);
+              hgs_apply<SS>(c, mv & 15, U, V);
               PF_ADD(pf_apply);
               searchCompleted = false;
               start = pl + 1;
@@ -799,9 +1020,26 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void hgs_ls_kernel(const HgsParams
                 e2stamp = c.nbMoves; e2er = er;
               }
               const int mv = c.l.e2[U];
-              if (mv) { hgs_apply(c, mv, U, c.dep(er)); searchCompleted = false; }
+              if (mv) { hgs_apply<SS>(c, mv, U, c.dep(er)); searchCompleted = false; }
             }
             PF_ADD(pf_other);
+          }
+        }
+        if constexpr (SS) {                                                   // LocalSearch.cpp:77-99: the SWAP* phase
+          for (int ia = 0; ia < R && !c.fail; ++ia) {
+            const int rU = c.l.ordR[ia];
+            const int lastSS = c.l.rWhenSS[rU];
+            if (lane == 0) c.l.rWhenSS[rU] = c.nbMoves;
+            for (int ib = 0; ib < R; ++ib) {
+              if (c.tick(3)) break;
+              const int rV = c.l.ordR[ib];
+              if (!(rU < rV) || c.l.rCnt[rU] <= 0 || c.l.rCnt[rV] <= 0) continue;
+              const int wu = c.l.rWhen[rU], wv = c.l.rWhen[rV];
+              if (!(loopID == 0 || (wu > wv ? wu : wv) > lastSS)) continue;
+              const int s1 = c.l.rSecS[rU], e1 = c.l.rSecE[rU], s2 = c.l.rSecS[rV], e2 = c.l.rSecE[rV];
+              if (!(hgs_posmod(s2 - s1) <= hgs_posmod(e1 - s1) || hgs_posmod(s1 - s2) <= hgs_posmod(e2 - s2))) continue;
+              if (hgs_swap_star(c, rU, rV)) searchCompleted = false;
+            }
           }
         }
       }
@@ -811,7 +1049,39 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void hgs_ls_kernel(const HgsParams
       // exportIndividual: every barycentre angle is atan2(0, 0) = 0 (1e30 for an empty route): routes in index order, the
       // empty ones dropped (Individual.cpp:85-102).  Between stages the next Params sees the non-empty routes, renumbered:
       // the links are rebuilt through the sequence in the wave's scratch-free way: renumber in place.
-      if (sgi + 1 < p.nstages) {
+      if constexpr (SS) {
+        // exportIndividual (LocalSearch.cpp:756-778): the routes in ascending (barycentre angle, index), the empty ones (1e30)
+        // dropped by exportCVRPLibFormat.  The solution is re-indexed in that order after EVERY stage: the next stage then sees
+        // what a fresh load of the exported routes would (orderRoutes, the first empty route, the fleet size), and the
+        // write-back below walks the routes in index order as it always did.
+        int Rn = 0;
+        for (int r0 = 0; r0 < R; r0 += 64) Rn += __popcll(__ballot(r0 + lane < R && c.l.rCnt[r0 + lane] > 0));
+        for (int r0 = 0; r0 < R; r0 += 64) {
+          const int r = r0 + lane;
+          if (r < R && c.l.rCnt[r] > 0) {
+            const double ang = c.l.rBary[r];
+            int rank = 0;
+            for (int q = 0; q < R; ++q) {
+              const double aq = c.l.rBary[q];
+              if (c.l.rCnt[q] > 0 && (aq < ang || (aq == ang && q < r))) ++rank;
+            }
+            c.l.hF[rank] = c.l.next[nc + 1 + r];
+            c.l.hL[rank] = c.l.prev[nc + 1 + R + r];
+          }
+        }
+        if (lane == 0) {
+          for (int k = 0; k < Rn; ++k) {
+            const int d0 = nc + 1 + k, d1 = nc + 1 + Rn + k, first = c.l.hF[k], lastn = c.l.hL[k];
+            c.l.next[d0] = (uint16_t)first; c.l.prev[first] = (uint16_t)d0;
+            c.l.next[lastn] = (uint16_t)d1; c.l.prev[d1] = (uint16_t)lastn;
+            c.l.prev[d0] = (uint16_t)d1; c.l.next[d1] = (uint16_t)d0;
+            c.l.route[d0] = c.l.route[d1] = (uint16_t)k;
+            int node = first, guard = 0;
+            while (node != d1 && ++guard < 70000) { c.l.route[node] = (uint16_t)k; node = c.l.next[node]; }
+          }
+        }
+        c.R = Rn;
+      } else if (sgi + 1 < p.nstages) {
         // new route index = rank among the non-empty ones; the depots move to their new ids (nc + 1 + r', nc + 1 + R' + r')
         int Rn = 0;
         for (int r = 0; r < R; ++r) {
@@ -905,8 +1175,8 @@ extern "C" int daco_hgs_prepare(void *stream, int B, int n, const double *matrix
 // 309 k, four (128 registers, 49 of them spilled) 283 k solutions/s at 16 instances, 374 k against 384 k at 256.
 constexpr int HGS_WPS = 3;
 
-static int hgs_grid(int n, int Rmax, int *waves_out, size_t *lds_out) {
-  const size_t per_wave = hgs_lds_bytes(n, Rmax);
+static int hgs_grid(int n, int Rmax, bool ss, int *waves_out, size_t *lds_out) {
+  const size_t per_wave = hgs_lds_bytes(n, Rmax) + (ss ? hgs_ss_bytes(n, Rmax) : 0);
   int waves = 4;
   while (waves > 1 && per_wave * waves > 64 * 1024) waves >>= 1;
   *waves_out = waves;
@@ -925,38 +1195,44 @@ static int hgs_grid(int n, int Rmax, int *waves_out, size_t *lds_out) {
   return cus * wg_per_cu;
 }
 
-extern "C" size_t daco_hgs_workspace_bytes(int B, int n, int A, int Lmax, int nb_granular) {
+static size_t hgs_workspace_bytes(int B, int n, int A, int Lmax, int nb_granular, bool ss) {
   if (B <= 0 || n < 2 || A <= 0 || Lmax < 3 || nb_granular < 1) return 0;
   int Rmax = Lmax - (n - 1); if (Rmax > n - 1) Rmax = n - 1; if (Rmax < 1) Rmax = 1;
   int waves; size_t lds;
-  const int grid = hgs_grid(n, Rmax, &waves, &lds);
+  const int grid = hgs_grid(n, Rmax, ss, &waves, &lds);
   const size_t stride = a16(2 * (size_t)2 * nb_granular * (n - 1)) / 2;
   return 256 + (size_t)grid * waves * stride * 2;
 }
+extern "C" size_t daco_hgs_workspace_bytes(int B, int n, int A, int Lmax, int nb_granular) { return hgs_workspace_bytes(B, n, A, Lmax, nb_granular, false); }
+extern "C" size_t daco_hgs_workspace_bytes_ss(int B, int n, int A, int Lmax, int nb_granular) { return hgs_workspace_bytes(B, n, A, Lmax, nb_granular, true); }
 
-extern "C" int daco_hgs_local_search(void *stream, int B, int n, int A, int Lmax, int nstages, const double *const *matrices,
-                                     const double *const *matrices_t, const long *bstrides, const void *const *tables, const int *counts, const double *demand,
-                                     double capacity, int nb_granular, int64_t *paths, int32_t *status, int32_t *stats,
-                                     void *workspace, size_t workspace_bytes) {
+// both entries: SS selects the SWAP* instantiations and the name the messages carry
+template <bool SS>
+static int hgs_local_search(void *stream, int B, int n, int A, int Lmax, int nstages, const double *const *matrices,
+                            const double *const *matrices_t, const long *bstrides, const void *const *tables, const int *counts, const double *demand,
+                            double capacity, int nb_granular, int64_t *paths, int32_t *status, int32_t *stats,
+                            void *workspace, size_t workspace_bytes, const double *xy, const int32_t *polar) {
+  const char *who = SS ? "daco_hgs_local_search_ss" : "daco_hgs_local_search";
   if (B <= 0 || n < 2 || A <= 0 || Lmax < 3 || nstages < 1 || nstages > HGS_MAX_STAGES || !matrices || !bstrides || !tables ||
       !counts || !demand || !paths || !workspace || nb_granular < 1 || nb_granular > 64) {
-    set_error("daco_hgs_local_search: bad argument (B=%d n=%d A=%d Lmax=%d stages=%d)", B, n, A, Lmax, nstages);
+    set_error("%s: bad argument (B=%d n=%d A=%d Lmax=%d stages=%d)", who, B, n, A, Lmax, nstages);
     return DACO_E_BADARG;
   }
-  if (n > 16000) { set_error("daco_hgs_local_search: n=%d is above 16000 (node ids are 16-bit with two depots per route)", n); return DACO_E_TOOLARGE; }
-  if (workspace_bytes < daco_hgs_workspace_bytes(B, n, A, Lmax, nb_granular)) {
-    set_error("daco_hgs_local_search: workspace of %zu bytes, %zu needed", workspace_bytes, daco_hgs_workspace_bytes(B, n, A, Lmax, nb_granular));
+  if (SS && (!xy || !polar)) { set_error("%s: null xy or polar (SWAP* needs the coordinates and the polar angles)", who); return DACO_E_BADARG; }
+  if (n > 16000) { set_error("%s: n=%d is above 16000 (node ids are 16-bit with two depots per route)", who, n); return DACO_E_TOOLARGE; }
+  if (workspace_bytes < hgs_workspace_bytes(B, n, A, Lmax, nb_granular, SS)) {
+    set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, hgs_workspace_bytes(B, n, A, Lmax, nb_granular, SS));
     return DACO_E_BADARG;
   }
   HgsParams p;
   p.B = B; p.n = n; p.A = A; p.Lmax = Lmax; p.g = nb_granular; p.nstages = nstages;
   int Rmax = Lmax - (n - 1); if (Rmax > n - 1) Rmax = n - 1; if (Rmax < 1) Rmax = 1;
   p.Rmax = Rmax;
-  // watchdog of one stage of one solution (links chased + evaluation rounds): far above any search, finite on a broken table
+  // watchdog of one stage of one solution (links chased + evaluation rounds + SWAP* steps): far above any search, finite on a broken table
   p.budget = 0x7fffffff;
-  if (n + 2 * Rmax > 65535) { set_error("daco_hgs_local_search: n + 2 routes = %d does not fit 16-bit node ids", n + 2 * Rmax); return DACO_E_TOOLARGE; }
+  if (n + 2 * Rmax > 65535) { set_error("%s: n + 2 routes = %d does not fit 16-bit node ids", who, n + 2 * Rmax); return DACO_E_TOOLARGE; }
   for (int s = 0; s < nstages; ++s) {
-    if (!matrices[s] || !tables[s] || counts[s] < 0) { set_error("daco_hgs_local_search: stage %d: null matrix / table or negative count", s); return DACO_E_BADARG; }
+    if (!matrices[s] || !tables[s] || counts[s] < 0) { set_error("%s: stage %d: null matrix / table or negative count", who, s); return DACO_E_BADARG; }
     p.st[s].tc = matrices[s]; p.st[s].tct = (matrices_t && matrices_t[s]) ? matrices_t[s] : matrices[s]; p.st[s].bstride = bstrides[s]; p.st[s].tables = (const unsigned char *)tables[s];
     p.st[s].table_bytes = HgsLayout(n, nb_granular).total; p.st[s].count = counts[s];
   }
@@ -964,39 +1240,57 @@ extern "C" int daco_hgs_local_search(void *stream, int B, int n, int A, int Lmax
   p.queue = (uint32_t *)workspace;
   p.scratch = (uint16_t *)((unsigned char *)workspace + 256);
   p.scratch_stride = a16(2 * (size_t)2 * nb_granular * (n - 1)) / 2;
+  p.xy = xy; p.polar = polar;
   int waves; size_t lds;
-  int grid = hgs_grid(n, Rmax, &waves, &lds);
-  if (lds > 160 * 1024) { set_error("daco_hgs_local_search: %zu bytes of LDS per solution (n=%d, up to %d routes)", lds, n, Rmax); return DACO_E_TOOLARGE; }
+  int grid = hgs_grid(n, Rmax, SS, &waves, &lds);
+  if (lds > 160 * 1024) { set_error("%s: %zu bytes of LDS per solution (n=%d, up to %d routes)", who, lds, n, Rmax); return DACO_E_TOOLARGE; }
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = zero_async(workspace, 256, st);
-  if (e != hipSuccess) { set_error("daco_hgs_local_search: clearing the queue: %s", hipGetErrorString(e)); return DACO_E_HIP; }
+  if (e != hipSuccess) { set_error("%s: clearing the queue: %s", who, hipGetErrorString(e)); return DACO_E_HIP; }
   // latency mode (hgs_ls_kernel<1, .., true>): no more solutions than a quarter of the CUs (each then has a CU's LDS to itself and
-  // nothing would have overlapped anyway) and the matrix fits.  DACO_HGS_LATENCY=0 / 1 forces (1: whenever it fits).
+  // nothing would have overlapped anyway) and the matrix fits (with SS: next to the SWAP* state; a call it does not fit takes
+  // the throughput form).  DACO_HGS_LATENCY=0 / 1 forces (1: whenever it fits).
   {
-    const size_t lm_lds = hgs_lds_bytes(n, Rmax) + ((size_t)n * n + n) * sizeof(double);
+    const size_t lm_lds = hgs_lds_bytes(n, Rmax) + (SS ? hgs_ss_bytes(n, Rmax) : 0) + ((size_t)n * n + n) * sizeof(double);
     const char *ev = getenv("DACO_HGS_LATENCY");
     const int force = ev ? atoi(ev) : -1;
     const long items = (long)B * A;
     if (lm_lds <= 160 * 1024 - 256 && force != 0 && (force == 1 || items <= 64)) {
-      e = hipFuncSetAttribute((const void *)hgs_ls_kernel<1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds);
-      if (e != hipSuccess) { set_error("daco_hgs_local_search: cannot reserve %zu bytes of LDS: %s", lm_lds, hipGetErrorString(e)); return DACO_E_HIP; }
+      e = hipFuncSetAttribute((const void *)hgs_ls_kernel<1, 1, true, SS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds);
+      if (e != hipSuccess) { set_error("%s: cannot reserve %zu bytes of LDS: %s", who, lm_lds, hipGetErrorString(e)); return DACO_E_HIP; }
       // (the scratch stride was sized for hgs_grid's wavefronts: one wavefront per workgroup here, never more workgroups than that)
       const long lm_grid = items < (long)grid * waves ? items : (long)grid * waves;
-      hipLaunchKernelGGL((hgs_ls_kernel<1, 1, true>), dim3((unsigned)lm_grid), dim3(64), lm_lds, st, p);
-      return launch_status("hgs_ls_kernel (latency mode)");
+      hipLaunchKernelGGL((hgs_ls_kernel<1, 1, true, SS>), dim3((unsigned)lm_grid), dim3(64), lm_lds, st, p);
+      return launch_status(SS ? "hgs_ls_kernel (SWAP*, latency mode)" : "hgs_ls_kernel (latency mode)");
     }
   }
 #define DACO_HGS_LAUNCH(W_, S_)                                                                                                   \
   do {                                                                                                                              \
     if (lds > 64 * 1024) {                                                                                                          \
-      e = hipFuncSetAttribute((const void *)hgs_ls_kernel<W_, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-      if (e != hipSuccess) { set_error("daco_hgs_local_search: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return DACO_E_HIP; } \
+      e = hipFuncSetAttribute((const void *)hgs_ls_kernel<W_, S_, false, SS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      if (e != hipSuccess) { set_error("%s: cannot reserve %zu bytes of LDS: %s", who, lds, hipGetErrorString(e)); return DACO_E_HIP; } \
     }                                                                                                                               \
-    hipLaunchKernelGGL((hgs_ls_kernel<W_, S_>), dim3(grid), dim3(W_ * 64), lds, st, p);                                             \
+    hipLaunchKernelGGL((hgs_ls_kernel<W_, S_, false, SS>), dim3(grid), dim3(W_ * 64), lds, st, p);                                  \
   } while (0)
   if (waves == 4) DACO_HGS_LAUNCH(4, HGS_WPS);
   else if (waves == 2) DACO_HGS_LAUNCH(2, HGS_WPS);
   else DACO_HGS_LAUNCH(1, HGS_WPS);
 #undef DACO_HGS_LAUNCH
-  return launch_status("hgs_ls_kernel");
+  return launch_status(SS ? "hgs_ls_kernel (SWAP*)" : "hgs_ls_kernel");
+}
+
+extern "C" int daco_hgs_local_search(void *stream, int B, int n, int A, int Lmax, int nstages, const double *const *matrices,
+                                     const double *const *matrices_t, const long *bstrides, const void *const *tables, const int *counts, const double *demand,
+                                     double capacity, int nb_granular, int64_t *paths, int32_t *status, int32_t *stats,
+                                     void *workspace, size_t workspace_bytes) {
+  return hgs_local_search<false>(stream, B, n, A, Lmax, nstages, matrices, matrices_t, bstrides, tables, counts, demand, capacity, nb_granular,
+                                 paths, status, stats, workspace, workspace_bytes, nullptr, nullptr);
+}
+
+extern "C" long daco_hgs_local_search_ss(void *stream, int B, int n, int A, int Lmax, int nstages, const double *const *matrices,
+                                        const double *const *matrices_t, const long *bstrides, const void *const *tables, const int *counts, const double *demand,
+                                        double capacity, int nb_granular, int64_t *paths, int32_t *status, int32_t *stats,
+                                        void *workspace, size_t workspace_bytes, const double *xy, const int32_t *polar) {
+  return hgs_local_search<true>(stream, B, n, A, Lmax, nstages, matrices, matrices_t, bstrides, tables, counts, demand, capacity, nb_granular,
+                                paths, status, stats, workspace, workspace_bytes, xy, polar);
 }

@@ -15,7 +15,8 @@ improves all selected ants in ONE launch of daco_hgs_local_search (csrc/daco_hgs
 ROUTE FOR ROUTE: moves 1-9 under the 20-nearest granular restriction, first improvement in the order libstdc++'s
 std::shuffle over std::minstd_rand fixes, penalised loads, float64 -- and no SWAP*, because the reference's ctypes structure
 (swapstar.py:62-74: 10 fields of AlgorithmParameters.h's 15) makes HGS read useSwapStar beyond it (tests/golden/
-gen_g11_hgs_ls.py asserts that on every solution).  Pinned on the reference's own outputs: fixtures g8 / g11
+gen_g11_hgs_ls.py asserts that on every solution).  `use_swap_star=True` (keyword-only, needs `positions`) runs the same
+search WITH SWAP*, as HGS's sources mean it and as a mended structure would run it (daco_hgs_local_search_ss).  Pinned on the reference's own outputs: fixtures g8 / g11
 (tests/test_gpu_09_cvrp_ls.py, tests/test_gpu_13_hgs_ls.py).  `local_search="best_improvement"` selects round 3's
 deterministic best-improvement kernel instead (daco_cvrp_local_search: moves 1-9 + SWAP*, hard capacity; cost-pinned only).
 """
@@ -60,7 +61,12 @@ class ACO(_CvrpACO):
 
     def __init__(self, distances, demand, n_ants=20, decay=0.9, alpha=1, beta=1, elitist=False, min_max=False,
                  pheromone=None, heuristic=None, min=None, device='cpu', adaptive=False, capacity=CAPACITY,
-                 swapstar=False, positions=None, inference=False, *, sampler='scan', seed=None, local_search='hgs'):
+                 swapstar=False, positions=None, inference=False, *, sampler='scan', seed=None, local_search='hgs',
+                 use_swap_star=False):
+        if use_swap_star and positions is None:
+            raise ValueError("ACO: use_swap_star=True needs positions")
+        if use_swap_star and local_search != 'hgs':
+            raise ValueError("ACO: use_swap_star=True belongs to local_search='hgs'")
         # demand keeps its dtype: float64 demands (cvrp_nls/utils.py:12-26) select the float64 load bookkeeping of the
         # sampler (cvrp_nls/aco.py:254-272 runs it in double; with demands k / capacity the last bit decides exact fits)
         super().__init__(distances.float(), demand, n_ants, decay, alpha, beta, elitist, min_max,
@@ -71,6 +77,10 @@ class ACO(_CvrpACO):
         assert positions is not None if swapstar else True                      # cvrp_nls/aco.py:73
         assert local_search in ('hgs', 'best_improvement')
         self.local_search = local_search
+        # use_swap_star: the route-exact search WITH SWAP*, as HGS's sources mean it (the reference's `swapstar=True` keeps
+        # meaning "run the local search", which the reference runs without SWAP*: see the module docstring)
+        self.use_swap_star = bool(use_swap_star)
+        self._polar = None
         self._heuristic_dist = None
         # the local search works on the caller's own numbers (the reference hands HGS distances_cpu / heuristic_dist in the
         # dtype they came in, float64 from cvrp_nls/utils.py): kept next to the float32 copies the sampler uses
@@ -148,8 +158,15 @@ class ACO(_CvrpACO):
         if self.local_search == 'hgs':
             limit = 100000 if self.inference else max(self.problem_size, 50)
             td, th = self._hgs_stage_tables()
-            engine.hgs_local_search_(work, [(td, limit), (th, disturb), (td, limit)], self._demand_src,
-                                     capacity=1000.001 * self.capacity, demand_scale=1000.0)
+            if self.use_swap_star:
+                if self._polar is None:                      # once per colony
+                    self._polar = engine.hgs_polar_angles(self.positions)
+                engine.hgs_local_search_(work, [(td, limit), (th, disturb), (td, limit)], self._demand_src,
+                                         capacity=1000.001 * self.capacity, demand_scale=1000.0, positions=self.positions,
+                                         use_swap_star=True, polar=self._polar)
+            else:
+                engine.hgs_local_search_(work, [(td, limit), (th, disturb), (td, limit)], self._demand_src,
+                                         capacity=1000.001 * self.capacity, demand_scale=1000.0)
         else:
             # best improvement to convergence / `disturb` moves on the perturbation matrix / to convergence
             dist = self.distances.detach().float().contiguous()

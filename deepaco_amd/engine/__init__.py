@@ -11,7 +11,7 @@ from .colonies import (BatchedCVRP, BatchedTSP, StreamedTSP, ant_sharded_cvrp, a
 from .common import MODES, RACE_NOISE, RACE_PHILOX, SCAN, SCAN_WAVE, _f32c, _stream, _workspace, stage_to_hip  # noqa: F401
 from .cvrp_ops import cvrp_sample, sample_backward  # noqa: F401
 from .local_search import (HgsTables, TspLocalSearch, TwoOptTables, cvrp_local_search_, heuristic_dist, hgs_local_search_,  # noqa: F401
-                           nls_, transposed_for_two_opt, two_opt_, two_opt_tables)
+                           hgs_polar_angles, nls_, transposed_for_two_opt, two_opt_, two_opt_tables)
 from .mkp_ops import (BatchedMKPVec, mkpv_backward, mkpv_check_flags, mkpv_sample, mkpv_update_, transformer_backward,  # noqa: F401
                       transformer_forward, transformer_forward_train)
 from .rcpsp_ops import (RCPSP_FLAG_ORDER, RCPSP_FLAG_RESOURCE, RCPSP_MAX_HORIZON, RCPSP_MAX_N, RCPSP_MAX_R, RCPSP_NET_MAX_N,  # noqa: F401

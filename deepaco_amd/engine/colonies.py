@@ -3,7 +3,7 @@ import torch
 
 from .common import _f32c, _raise_flags, _require_gpu, _rows
 from .cvrp_ops import cvrp_sample
-from .local_search import HgsTables, TspLocalSearch, heuristic_dist, hgs_local_search_
+from .local_search import HgsTables, TspLocalSearch, heuristic_dist, hgs_local_search_, hgs_polar_angles
 from .tsp_ops import head_table, resolve_sampler, sparse_tours16, sparse_workspace, tsp_sample, tsp_sample_sparse
 from .update import pheromone_update_, tour_costs, track_best_
 
@@ -329,14 +329,25 @@ class BatchedCVRP:
 
     def __init__(self, distances, demand, n_ants=20, decay=0.9, alpha=1, beta=1, elitist=False, min_max=False,
                  pheromone=None, heuristic=None, min=None, capacity=50, sampler="scan", seed=None, ant_gid0=0,
-                 local_search=None, ls_ants=8, inference=False):
+                 local_search=None, ls_ants=8, inference=False, positions=None, use_swap_star=False):
         """local_search="hgs": the colony iteration of cvrp_nls/aco.py:134-171 (swapstar=True) for every instance -- the `ls_ants`
         cheapest ants of each instance go through neural_swapstar (cvrp_nls/aco.py:143-146, 443-448; daco_hgs_local_search, the
         reference's routes) before best tracking and the deposit.  The local search reads `distances` and the heuristic in the
-        dtype they are passed in (float64 instance data as cvrp_nls/utils.py builds it) and the demands as demand / capacity."""
+        dtype they are passed in (float64 instance data as cvrp_nls/utils.py builds it) and the demands as demand / capacity.
+        use_swap_star=True (with positions [B,n,2], node 0 the depot): that local search with SWAP*, as HGS's sources mean it
+        (engine.hgs_local_search_); the nodes' polar angles are computed here, once."""
+        if use_swap_star and positions is None:
+            raise ValueError("BatchedCVRP: use_swap_star=True needs positions")
+        if use_swap_star and local_search != "hgs":
+            raise ValueError('BatchedCVRP: use_swap_star=True belongs to local_search="hgs"')
         _require_gpu(distances, demand)
         assert local_search in (None, "hgs")
         self.local_search, self.ls_ants, self.inference = local_search, int(ls_ants), inference
+        self.use_swap_star = bool(use_swap_star)
+        self._hgs_pos = self._hgs_polar = None
+        if self.use_swap_star:
+            self._hgs_pos = positions.detach().to(distances.device).double().contiguous()
+            self._hgs_polar = hgs_polar_angles(self._hgs_pos)
         self._ls_src = (distances.detach(), demand.detach())
         self._hgs = None
         self.distances = _f32c(distances)
@@ -389,7 +400,11 @@ class BatchedCVRP:
             gi = idx.unsqueeze(1).expand(self.B, paths.shape[1], k)
             work = paths.gather(2, gi).contiguous()
             limit = 100000 if self.inference else max(self.n, 50)
-            hgs_local_search_(work, [(td, limit), (th, 10), (td, limit)], dem_n)
+            if self.use_swap_star:
+                hgs_local_search_(work, [(td, limit), (th, 10), (td, limit)], dem_n, positions=self._hgs_pos, use_swap_star=True,
+                                  polar=self._hgs_polar)
+            else:
+                hgs_local_search_(work, [(td, limit), (th, 10), (td, limit)], dem_n)
             paths.scatter_(2, gi, work)
             costs.scatter_(1, idx, tour_costs(self.distances, work, closed=False))
             # the rewritten columns' used rows: up to and including the depot after their last client

@@ -154,13 +154,43 @@ class HgsTables:
         _lib.check(rc, "daco_hgs_prepare")
 
 
-def hgs_local_search_(paths, stages, demand, capacity=1000.001, demand_scale=1000.0, want_stats=False):
+HGS_PI = 3.14159265359          # Params.h:42 (the constant HGS divides by, not math.pi)
+
+
+def hgs_polar_angles(positions):
+    """Client::polarAngle of every node (Params.cpp:42-47): posmod((int)(32768. * atan2(y_i - y_0, x_i - x_0) / PI)) in
+    [0, 65536), node 0 being the depot.  positions [B,n,2] or [n,2] float64 on any device -> int32 of shape [B,n] / [n] on that
+    device.  The SWAP* search branches on these angles (the routes' circle sectors), so they are computed with libm's atan2, the
+    function HGS itself calls -- math.atan2, one call per node, not a vectorised arctan2 whose SIMD kernels need not round
+    like libm.  Once per colony."""
+    import math
+    pos = positions.detach().to("cpu", torch.float64)
+    flat = pos.reshape(-1, pos.shape[-2], 2).tolist()
+    out = []
+    for inst in flat:
+        x0, y0 = inst[0]
+        row = []
+        for x, y in inst:
+            v = int(32768. * math.atan2(y - y0, x - x0) / HGS_PI)           # (double -> int truncates, as the C++ conversion)
+            row.append(v % 65536)                                           # (CircleSector.h:14-19 positive_mod)
+        out.append(row)
+    return torch.tensor(out, dtype=torch.int32).reshape(pos.shape[:-1]).to(positions.device)
+
+
+def hgs_local_search_(paths, stages, demand, capacity=1000.001, demand_scale=1000.0, want_stats=False, positions=None,
+                      use_swap_star=False, polar=None):
     """The reference's CVRP local search on every column of `paths`, route for route (csrc/daco_hgs_ls.hip; cvrp_nls/aco.py:
     114-126 -> swapstar.py:324-346 -> HGS LocalSearch::run as the reference runs it: moves 1-9, granular, no SWAP*).
     paths [B,Lmax,A] or [Lmax,A] int64, rewritten in place in merge_subroutes' layout; stages: up to three
     (HgsTables, count) pairs run one after the other on each solution (neural_swapstar: (dist, limit), (heuristic_dist, 10),
     (dist, limit)); demand [B,n] or [n] as the colony holds it (scaled by demand_scale = 1000 as swapstar.py:335 does).
+    use_swap_star=True (needs positions [B,n,2] or [n,2] float64, node 0 the depot): HGS as its sources mean it -- every loop
+    ends with the SWAP* phase and the routes leave in the order of their barycentre angles (daco_hgs_local_search_ss); polar:
+    hgs_polar_angles(positions), if the caller keeps them (a colony computes them once).  False: the reference as run, and
+    positions are not read.
     Returns paths (and status [B,A], stats [B,A,4] = moves, loops, evaluation rounds, watchdog)."""
+    if use_swap_star and positions is None:
+        raise ValueError("hgs_local_search_: use_swap_star=True needs positions (SWAP* works on the routes' circle sectors)")
     _require_gpu(paths)
     assert paths.dtype == torch.int64 and 1 <= len(stages) <= 3
     p3 = paths if paths.dim() == 3 else paths.unsqueeze(0)
@@ -184,6 +214,29 @@ def hgs_local_search_(paths, stages, demand, capacity=1000.001, demand_scale=100
         if st[0].B == 1 and B > 1:
             raise ValueError("hgs_local_search_: one table set per instance is needed (B tables)")
     L = _lib.lib()
+    if use_swap_star:
+        xy = positions.to(dev).double()
+        if xy.dim() == 2:
+            xy = xy.unsqueeze(0).expand(B, n, 2)
+        xy = xy.contiguous()
+        if polar is None:
+            polar = hgs_polar_angles(positions)
+        pol = polar.to(dev).to(torch.int32)
+        if pol.dim() == 1:
+            pol = pol.unsqueeze(0).expand(B, n)
+        pol = pol.contiguous()
+        if tuple(xy.shape) != (B, n, 2) or tuple(pol.shape) != (B, n):
+            raise ValueError(f"hgs_local_search_: positions {tuple(xy.shape)} / polar {tuple(pol.shape)} for B={B}, n={n}")
+        with _on(dev):
+            wsb = L.daco_hgs_workspace_bytes_ss(B, n, A, Lmax, g)
+            ws = _workspace(dev, wsb, "hgs_ls")
+            status = torch.empty((B, A), dtype=torch.int32, device=dev)
+            stats = torch.empty((B, A, 4), dtype=torch.int32, device=dev) if want_stats else None
+            rc = L.daco_hgs_local_search_ss(_stream(dev), B, n, A, Lmax, S, mats, mats_t, strides, tabs, counts, dem.data_ptr(), float(capacity),
+                                            g, p3.data_ptr(), status.data_ptr(), _ptr(stats), ws.data_ptr(), ws.numel(), xy.data_ptr(),
+                                            pol.data_ptr())
+        _lib.check(rc, "daco_hgs_local_search_ss")
+        return (paths, status, stats) if want_stats else paths
     with _on(dev):
         wsb = L.daco_hgs_workspace_bytes(B, n, A, Lmax, g)
         ws = _workspace(dev, wsb, "hgs_ls")

@@ -198,6 +198,8 @@ def infer_cvrp_nls_batch(locations, demands, n_ants, t_aco, k_sparse, net=None, 
         x, ei, ea = cvrp_nls_graph_batch(demands, dist, k_sparse)
         heu = net.forward_batch(x, ei, ea)
         heuristic = net.reshape_batch(n1, ei, heu, eps=EPS)
+    if aco_kw.get("use_swap_star") and aco_kw.get("positions") is None:
+        aco_kw["positions"] = loc                                    # (SWAP* works on the locations the distances were made of)
     colony = engine.BatchedCVRP(dist, demands.double(), n_ants=n_ants, capacity=1.0, heuristic=heuristic, seed=seed,
                                 local_search="hgs", ls_ants=ls_ants, inference=True, **aco_kw)
     out, done = [], 0

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise) */
 
 /* error codes */
 #define DACO_OK 0
@@ -672,6 +672,40 @@ int daco_hgs_local_search(void *stream, int B, int n, int A, int Lmax, int nstag
                           const double *const *matrices_t, const long *bstrides, const void *const *tables, const int *counts, const double *demand,
                           double capacity, int nb_granular, int64_t *paths, int32_t *status, int32_t *stats,
                           void *workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_hgs_local_search_ss -- the same local search WITH SWAP*, as HGS's sources mean it (opt-in)
+ *   What a caller of the reference gets once swapstar.py's CAlgorithmParameters carries all 15 fields of
+ *   AlgorithmParameters.h:10-28 and useSwapStar = 1 arrives: on top of everything daco_hgs_local_search replaces,
+ *   Params.cpp:40-54 (coordinates and polar angles taken over), the circle sector and barycentre angle of
+ *   updateRouteData (LocalSearch.cpp:652-707, CircleSector.h:14-58), the SWAP* phase that ends every loop of
+ *   LocalSearch::run (LocalSearch.cpp:77-99), swapStar (:486-573) with preprocessInsertions (:594-615) and
+ *   getCheapestInsertSimultRemoval (:575-592), and the export in ascending barycentre angle (:756-778), which is also the
+ *   order in which the next stage of a multi-stage call numbers the routes.
+ *   Exact: the sector arithmetic (integers), the three-best insertion memory and its tie rule (an equal cost goes behind
+ *   the kept entry), the choice of the move (first strict minimum over the pairs in U-major order, then the relocations of
+ *   a U, then of a V; applied at <= -MY_EPSILON), every cost as the reference's left-to-right float64 sum
+ *   (specification: oracle/hgs_ls.c use_swap_star = 1; fixtures tests/golden/g11_* keys paths_ss1_*).
+ *   NOT exact, one quantity: a route's barycentre angle is the device library's double-precision atan2, not libm's.  It is
+ *   only ever compared with other routes' barycentre angles, so the export order can differ from the reference's only where
+ *   two routes' angles lie within that function's error (a few ulp) of each other.
+ *   Arguments as daco_hgs_local_search, then
+ *   xy      [B][n][2] f64 coordinates, node 0 the depot
+ *   polar   [B][n] int32 Client::polarAngle = posmod((int)(32768. * atan2(y_i - y_0, x_i - x_0) / 3.14159265359))
+ *           (Params.cpp:42-47), computed BY THE CALLER with libm's atan2 -- the search branches on these through the sector
+ *           tests, so they are an input and not recomputed on the device
+ *   workspace daco_hgs_workspace_bytes_ss(B, n, A, Lmax, nb_granular) bytes
+ *   stats[..][3] watchdog: 3 the budget ran out inside the SWAP* phase
+ *   Errors: DACO_E_BADARG for a null xy or polar (and whatever daco_hgs_local_search refuses), DACO_E_TOOLARGE for n above
+ *   16000 (16-bit node ids).  A call whose SWAP* state does not fit next to the matrix in the latency mode's LDS takes the
+ *   throughput form.  The status is the usual DACO_OK / DACO_E_* value typed `long`, for the reason given at
+ *   daco_rcpsp_net_forward; the refusals are held by tests/test_hgs_swap_star_refusals.py.
+ */
+size_t daco_hgs_workspace_bytes_ss(int B, int n, int A, int Lmax, int nb_granular);
+long daco_hgs_local_search_ss(void *stream, int B, int n, int A, int Lmax, int nstages, const double *const *matrices,
+                              const double *const *matrices_t, const long *bstrides, const void *const *tables, const int *counts, const double *demand,
+                              double capacity, int nb_granular, int64_t *paths, int32_t *status, int32_t *stats,
+                              void *workspace, size_t workspace_bytes, const double *xy, const int32_t *polar);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_tsp_knn_graph -- replaces gen_distance_matrix + gen_pyg_data for a batch of instances
