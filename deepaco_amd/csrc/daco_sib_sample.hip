@@ -39,6 +39,9 @@ extern "C" int daco_sibling_sample(void *stream, int kind, int B, int n, int A, 
   if (mode < 0 || mode > 2) { set_error("daco_sibling_sample: bad mode %d", mode); return DACO_E_BADARG; }
   if (mode == DACO_RACE_NOISE && (!noise || noise_steps <= 0)) { set_error("daco_sibling_sample: DACO_RACE_NOISE needs a noise tensor"); return DACO_E_BADARG; }
   const bool varlen = kind != DACO_SIB_SOP;
+  // SOP draws exactly n - 1 times and the kernel strides its instances' noise by that: fewer steps would be read past, more would
+  // shift every instance after the first
+  if (!varlen && mode == DACO_RACE_NOISE && noise_steps != n - 1) { set_error("daco_sibling_sample: SOP needs n - 1 = %d noise steps, got %d", n - 1, noise_steps); return DACO_E_BADARG; }
   if (varlen && (Lmax < 2 || !lens)) { set_error("daco_sibling_sample: variable-length kinds need Lmax >= 2 and lens"); return DACO_E_BADARG; }
   if ((kind == DACO_SIB_SOP || kind == DACO_SIB_OP) && (!aux_vec || !aux_mat)) { set_error("daco_sibling_sample: kind %d needs aux_vec and aux_mat", kind); return DACO_E_BADARG; }
   if (kind == DACO_SIB_PCTSP && !aux_vec) { set_error("daco_sibling_sample: PCTSP needs the prizes in aux_vec"); return DACO_E_BADARG; }

@@ -321,6 +321,7 @@ int daco_pick_move(void *stream, int B, int n, int A, const void *prob_workspace
  * n-1) and lens [B][A]; logp/rowsum [B][rows-1][A] optional; flags as daco_cvrp_sample.  aux_mat
  * is dense [B][n][n] (aux_mat_bstride between instances, 0 = shared).  Draws, modes, noise layout
  * ([B][noise_steps][A][n]) and Philox counters are those of daco_tsp_sample / daco_pick_move.
+ * DACO_SIB_SOP draws n - 1 times: its noise_steps must be n - 1 (DACO_E_BADARG otherwise).
  */
 #define DACO_SIB_SOP 3
 #define DACO_SIB_PCTSP 4

@@ -73,6 +73,12 @@ def neg_log2_1m(w):
     return float(lib().orc_neg_log2_1m(C.c_float(float(w))))
 
 
+def start_node(seed, it, gid, m):
+    """The start node ant `gid` draws for itself among m nodes (STREAM_START): m = n for TSP, n - 1 for MKP."""
+    return int(lib().orc_start_node(C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(it)), C.c_uint32(int(gid) & 0xFFFFFFFF),
+                                    int(m)))
+
+
 def prob_matrix(tau, eta, alpha=1.0, beta=1.0):
     tau, eta = _f32(tau), _f32(eta)
     n = tau.shape[0]

@@ -91,6 +91,14 @@ static inline void rng_block(uint64_t seed, uint64_t iter, uint32_t stream, uint
   philox4x32_10(out, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
+/* the start node an ant draws for itself: floor(m * u32 / 2^32), u32 = component 0 of the ant's STREAM_START block 0.
+ * m = n for TSP, n - 1 for MKP (the dummy is no start).  Exported for oracle/siblings.py. */
+int orc_start_node(uint64_t seed, uint64_t iter, uint32_t gid, int m) {
+  uint32_t r4[4];
+  rng_block(seed, iter, STREAM_START, gid, 0, r4);
+  return (int)(((uint64_t)r4[0] * (uint64_t)m) >> 32);
+}
+
 /* uniform in (0,1), exactly representable: (2m+1) * 2^-24 with m the top 23 bits */
 static inline float u01(uint32_t x) { return (float)(2u * (x >> 9) + 1u) * 0x1p-24f; }
 
@@ -275,14 +283,11 @@ static int tsp_sample(int mode, int n, int A, const float *P, const int64_t *sta
   float *p = (float *)malloc(sizeof(float) * n);
   unsigned char *vis = (unsigned char *)malloc(n);
   for (int a = 0; a < A; ++a) {
-    uint32_t gid = ant_gid0 + (uint32_t)a, r4[4];
+    uint32_t gid = ant_gid0 + (uint32_t)a;
     int prev;
     if (start) prev = (int)start[a];
     else if (fixed_start >= 0) prev = fixed_start;
-    else {
-      rng_block(seed, iter, STREAM_START, gid, 0, r4);
-      prev = (int)(((uint64_t)r4[0] * (uint64_t)n) >> 32);
-    }
+    else prev = orc_start_node(seed, iter, gid, n);
     memset(vis, 0, n);
     vis[prev] = 1;
     paths[a] = prev;
@@ -476,10 +481,10 @@ int orc_tsp_sample_scan_sparse(int n, int A, const float *P, const uint16_t *hea
   if (kh != 64 && kh != 128) return ORC_INFEASIBLE;
   unsigned char *vis = (unsigned char *)malloc(n), *is_head = (unsigned char *)malloc(n);
   for (int a = 0; a < A; ++a) {
-    uint32_t gid = ant_gid0 + (uint32_t)a, r4[4];
+    uint32_t gid = ant_gid0 + (uint32_t)a;
     int prev;
     if (fixed_start >= 0) prev = fixed_start;
-    else { rng_block(seed, iter, STREAM_START, gid, 0, r4); prev = (int)(((uint64_t)r4[0] * (uint64_t)n) >> 32); }
+    else prev = orc_start_node(seed, iter, gid, n);
     memset(vis, 0, n);
     vis[prev] = 1;
     paths[a] = prev;

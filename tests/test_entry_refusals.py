@@ -199,6 +199,9 @@ REFUSED = [
     ("daco_transformer_backward", BADARG, "bad argument", {}),
     ("daco_transformer_backward", TOOLARGE, "tokens exceed", dict(_TF_B, n=100000)),
     ("daco_transformer_backward", WORKSPACE, "workspace 16 <", dict(_TF_B, param_floats="layout", saved_floats=1 << 40, workspace_bytes=16)),
+    # (the test ids carry the row's index: new rows go at the end)
+    ("daco_sibling_sample", BADARG, "SOP needs n - 1 = 99 noise steps, got 100", dict(_SIB, mode=_lib.RACE_NOISE, noise=P, noise_steps=100)),
+    ("daco_sibling_sample", BADARG, "SOP needs n - 1 = 99 noise steps, got 98", dict(_SIB, mode=_lib.RACE_NOISE, noise=P, noise_steps=98)),
 ]
 
 

@@ -19,11 +19,11 @@ import torch
 
 from oracle import grad as ograd
 from conftest import load_golden
+from sibling_sample_cases import rowsum_bound, rule_exercised
 
 pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 3e-4, 3e-6
-U = 2.0 ** -24                       # unit roundoff of float32
 EPS = float(ograd.EPS)
 KINDS = ("sop", "pctsp", "op", "mkp")
 
@@ -158,43 +158,6 @@ def weights(rows, A, zero_steps=False, zero_ants=False):
 
 
 # ------------------------------------------------------------------------------------------ the checks
-def rule_exercised(kind, paths, aux):
-    """sop: some draw had an unvisited candidate gated by a pending predecessor; pctsp: an ant went home with nodes left;
-    op / mkp: a candidate was closed by the sticky rule (unvisited, not open) before the route ended."""
-    rows, A = paths.shape
-    n = aux["open"].shape[-1]
-    live = ~np.isnan(aux["S"])
-    for a in range(A):
-        seen = np.zeros(n, bool)
-        seen[paths[0, a]] = kind != "pctsp"
-        for t in range(1, rows):
-            if not live[t - 1, a]:
-                break
-            o, j = aux["open"][t - 1, a], int(paths[t, a])
-            if kind == "sop" and (~o & ~seen).any():
-                return True
-            if kind == "pctsp" and j == 0 and (~seen[1:]).any():
-                return True
-            if kind in ("op", "mkp") and j != n - 1 and (~o[:n - 1] & ~seen[:n - 1]).any():
-                return True
-            seen[j] = True
-    return False
-
-
-def rowsum_bound(N, alpha, beta):
-    """Relative bound on |S_float32 - S_exact| for a float32 sum of at most N non-negative terms in any order,
-    each term fl(fl(tau^alpha) * fl(eta^beta)):
-        (N - 1) u  for the additions (u = 2^-24; the terms are non-negative, so relative errors add and never amplify),
-      + r u        for each term: one rounding of the product, one more per squared factor (x * x), and 32 u per powf
-                   (16 ulp = 16 * 2^-23: the bound of the OpenCL full profile for pow, which the ROCm device library the
-                   kernels' powf comes from is written to; HIP's own table of measured errors gives 1 ulp),
-    times 1.01 for the second-order terms."""
-    r = 1
-    for e in (alpha, beta):
-        r += 0 if e == 1 else (1 if e == 2 else 32)
-    return 1.01 * (N - 1 + r) * U
-
-
 def verify(kind, tau, eta, alpha, beta, paths, lens, G, got, problem, rowsum=None, label="", forced=False):
     """Everything that is asserted on one [n, n] gradient `got` (numpy).  The closed form's side first (d.), so that a case
     that proves nothing fails rather than passes."""
