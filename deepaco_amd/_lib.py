@@ -78,6 +78,10 @@ SIGNATURES = {
     "daco_tsp_knn_graph": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp]),
     "daco_tsp_knn_graph_csr": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "daco_heu_matrix": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp]),
+    # (long statuses, as daco_rcpsp_net_forward)
+    "daco_sparsify": (_l, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _vp]),
+    "daco_sparse_head": (_l, [_vp, _i, _i, _i, _vp, _l, _vp]),
+    "daco_head_stats": (_l, [_vp, _i, _i, _vp, _l, _i, C.c_double, C.c_double, _vp]),
     "daco_two_opt": (_i, [_vp, _i, _i, _i, _vp, _vp, _l, _vp, _l, _vp]),
     "daco_two_opt_tables_bytes": (_sz, [_i, _i]),
     "daco_two_opt_prepare": (_i, [_vp, _i, _i, _vp, _l, _vp, _sz]),

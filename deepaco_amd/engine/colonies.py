@@ -4,7 +4,7 @@ import torch
 from .common import _f32c, _raise_flags, _require_gpu, _rows
 from .cvrp_ops import cvrp_sample
 from .local_search import HgsTables, TspLocalSearch, heuristic_dist, hgs_local_search_, hgs_polar_angles
-from .tsp_ops import head_table, resolve_sampler, sparse_tours16, sparse_workspace, tsp_sample, tsp_sample_sparse
+from .tsp_ops import head_table, resolve_sampler, sparse_tours16, sparse_workspace, sparsify_heuristic, tsp_sample, tsp_sample_sparse
 from .update import pheromone_update_, tour_costs, track_best_
 
 
@@ -67,6 +67,8 @@ class BatchedTSP:
     Semantics per instance are those of tsp/aco.py ACO.run (AS / elitist / MMAS); best-so-far
     tracking is done on the device, so an iteration never synchronises with the host."""
 
+    setup_path = None      # sparsify / head table / 'auto' test: None = the set-up kernels where they apply, 'hip' | 'torch' (sparsify_heuristic)
+
     def __init__(self, distances, n_ants=20, decay=0.9, alpha=1, beta=1, elitist=False, min_max=False,
                  pheromone=None, heuristic=None, min=None, sampler="auto", seed=None, ant_gid0=0,
                  fixed_start=-1, local_search=None, inference=False, norm_passes=1):
@@ -123,10 +125,7 @@ class BatchedTSP:
     @torch.no_grad()
     def sparsify(self, k_sparse):
         """tsp/aco.py:52-67 for a batch: 1/dist on each node's k nearest edges, 1e-10 elsewhere."""
-        _, idx = torch.topk(self.distances, k=k_sparse, dim=2, largest=False)
-        sparse = torch.full_like(self.distances, 1e10)
-        sparse.scatter_(2, idx, torch.gather(self.distances, 2, idx))
-        self.heuristic = 1 / sparse
+        self.heuristic = sparsify_heuristic(self.distances, k_sparse, path=self.setup_path)
         self.head_k = min(int(k_sparse), 127)
         self._head = None
 
@@ -134,13 +133,13 @@ class BatchedTSP:
         """(kernel family this colony's next step runs, head size): see resolve_sampler."""
         if getattr(self, "_auto", None) is None:
             self._auto = {}
-        return resolve_sampler(self.sampler, self.n, self.head_k, self.heuristic, self._auto)
+        return resolve_sampler(self.sampler, self.n, self.head_k, self.heuristic, self._auto, path=self.setup_path)
 
     def _head_table(self, k=None):
         """(heuristic object it was built from, [B,n,64] head ids) for sampler='scan_sparse'."""
         if self._head is None or self._head[0] is not self.heuristic or (k is not None and self._head[2] != k):
             k = k if k is not None else (self.head_k if self.head_k is not None else max(1, min(127, self.n // 10)))
-            self._head = (self.heuristic, head_table(self.heuristic, k, self.B, getattr(self, "_auto", None)), k)
+            self._head = (self.heuristic, head_table(self.heuristic, k, self.B, getattr(self, "_auto", None), path=self.setup_path), k)
         return self._head[1]
 
     @torch.no_grad()

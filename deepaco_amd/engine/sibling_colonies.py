@@ -11,7 +11,7 @@ from .colonies import _mmas_bounds
 from .common import _bstride, _f32c, _on, _ptr, _raise_flags, _require_gpu, _stream
 from .cvrp_ops import cvrp_sample
 from .sibling_ops import SIB_KINDS, sibling_sample
-from .tsp_ops import tsp_sample
+from .tsp_ops import sparsify_heuristic, tsp_sample
 from .update import pheromone_update_
 
 # the kinds of daco_sibling_objective / the rules of daco_sibling_record (include/deepaco_hip.h)
@@ -280,6 +280,7 @@ class BatchedOP(_BatchedSibling):
     Record: alltime_best_obj [B], alltime_best_sol [B, 2(n+1)+1] (padded with the dummy)."""
 
     kind = "op"
+    setup_path = None      # sparsify: None = daco_sparsify where it applies, 'hip' | 'torch' (sparsify_heuristic)
 
     def __init__(self, distances, prizes, max_len, n_ants=20, decay=0.9, alpha=1, beta=1, elitist=False, min_max=False,
                  pheromone=None, heuristic=None, min=None, k_sparse=None, sampler="scan", seed=None, ant_gid0=0):
@@ -311,10 +312,7 @@ class BatchedOP(_BatchedSibling):
 
     @torch.no_grad()
     def sparsify(self, k_sparse):
-        _, idx = torch.topk(self.distances, k=k_sparse, dim=2, largest=False)
-        sparse = torch.full_like(self.distances, 1e10)
-        sparse.scatter_(2, idx, torch.gather(self.distances, 2, idx))
-        self.heuristic = self.prizes.unsqueeze(1) / sparse
+        self.heuristic = sparsify_heuristic(self.distances, k_sparse, numer=self.prizes, path=self.setup_path)
 
     def _mmas(self):
         return self.n, self.Q

@@ -1,4 +1,5 @@
 """TSP construction: the dense and race samplers, the head-row samplers with their head tables, the k-nn graph."""
+import numpy as np
 import torch
 
 from .. import _lib
@@ -61,18 +62,77 @@ def tsp_sample(tau, eta, n_ants, alpha=1.0, beta=1.0, mode="scan", norm_passes=1
     return paths, logp, rowsum, flags
 
 
-def sparse_head(weights, k, top=None):
+SETUP_MAX_N = 1024          # sizes the set-up kernels cover (csrc/daco_colony_setup.hip: a row in one wavefront's registers)
+
+
+def _setup_path(path, n, *tensors):
+    """'hip' | 'torch' for a set-up call on n-node rows: path=None takes the kernels of csrc/daco_colony_setup.hip for float32
+    device tensors with n <= 1024 and the torch expression otherwise (CPU tensors, larger n, other dtypes); an explicit
+    'hip' outside that range raises DacoError."""
+    ok = 2 <= n <= SETUP_MAX_N and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in tensors)
+    if path is None:
+        return "hip" if ok else "torch"
+    if path not in ("hip", "torch"):
+        raise ValueError(f"path must be None, 'hip' or 'torch' (got {path!r})")
+    if path == "hip" and not ok:
+        raise _lib.DacoError(f"path='hip' takes float32 tensors on a HIP device with 2 <= n <= {SETUP_MAX_N} (n = {n})")
+    return path
+
+
+def sparsify_heuristic(dist, k, numer=None, path=None):
+    """ACO.sparsify (tsp/aco.py:52-67; op/aco.py with the prizes as `numer`): dist [n,n] or [B,n,n] -> numer_j / dist on each
+    row's k smallest entries, numer_j / 1e10 elsewhere (numer [n] or [B,n]; None = 1).
+    path 'hip' (the default on a device, n <= 1024; _setup_path): one launch of daco_sparsify, ties at the k-th distance to the
+    smaller column id; 'torch': the reference's topk / scatter_ / divide, whose choice among equal distances is torch.topk's.
+    On rows without such a tie the two are equal bit for bit."""
+    n = dist.shape[-1]
+    if _setup_path(path, n, dist, numer) == "torch":
+        _, idx = torch.topk(dist, k=k, dim=-1, largest=False)
+        sparse = torch.full_like(dist, 1e10)
+        sparse.scatter_(-1, idx, torch.gather(dist, -1, idx))
+        return (1 if numer is None else numer.unsqueeze(-2)) / sparse
+    d = dist.detach()
+    B = d.shape[0] if d.dim() == 3 else 1
+    d = d if d.is_contiguous() else d.contiguous()
+    nbs = 0
+    if numer is not None:
+        numer = numer.detach().contiguous()
+        assert numer.shape[-1] == n and (numer.dim() == 1 or tuple(numer.shape) == (B, n))
+        nbs = n if numer.dim() == 2 else 0
+    dev = d.device
+    with _on(dev):
+        out = torch.empty_like(d)
+        rc = _lib.lib().daco_sparsify(_stream(dev), B, n, int(k), d.data_ptr(), n * n, _ptr(numer), nbs, out.data_ptr())
+    _lib.check(rc, "daco_sparsify")
+    return out
+
+
+def sparse_head(weights, k, top=None, path=None, batch=None):
     """Head table of scan_sparse for `weights` [B,n,n] or [n,n] (the colony passes its heuristic): per row the k (<= 127)
     largest entries, ids ascending (ties at the k-th value: the smaller id) -- [B,n,S] int16 holding uint16 ids with S = 64
     slots for k <= 63, else 128; the unused slots 0, the last slot = k (include/deepaco_hip.h daco_tsp_sample_sparse;
     oracle.sparse_head_ids is the same rule).
-    top: the rows' largest values in descending order, at least k of them ([.., m >= k], e.g. what auto_head_k computed for the
-    same matrix): the one torch.topk this function needs is then skipped."""
+    path 'hip' (the default for n <= 1024; _setup_path): one launch of daco_sparse_head; a [n,n] matrix with batch=B is read once
+    and its table written B times.  'torch': the expression below -- the same ids on every input.
+    top (torch path only): the rows' largest values in descending order, at least k of them ([.., m >= k], e.g. what auto_head_k
+    computed for the same matrix): the one torch.topk this function needs is then skipped."""
     _require_gpu(weights)
-    w = weights if weights.dim() == 3 else weights.unsqueeze(0)
-    B, n, _ = w.shape
+    n = weights.shape[-1]
     assert 1 <= k <= 127 and k <= n
     slots = 64 if k <= 63 else 128
+    if _setup_path(path, n, weights) == "hip":
+        w, wbs = _bstride(weights.detach(), n)
+        B = w.shape[0] if w.dim() == 3 else (batch or 1)
+        dev = w.device
+        with _on(dev):
+            ids = torch.empty((B, n, slots), dtype=torch.int16, device=dev)
+            rc = _lib.lib().daco_sparse_head(_stream(dev), B, n, int(k), w.data_ptr(), wbs, ids.data_ptr())
+        _lib.check(rc, "daco_sparse_head")
+        return ids
+    w = weights if weights.dim() == 3 else weights.unsqueeze(0)
+    if w.shape[0] == 1 and batch:
+        w = w.expand(batch, n, n)
+    B = w.shape[0]
     # the k largest by (value descending, id ascending), without sorting the rows (ADVICE r4): everything above the k-th value,
     # and of the entries equal to it the smallest ids.  The chosen ids ascending = the chosen columns in column order: their
     # running count is the slot (the others go to a spare slot that is cut off).
@@ -96,17 +156,23 @@ def sparse_head(weights, k, top=None):
 SPARSE_MIN_N, SPARSE_MAX_N = 129, 1024        # sizes daco_tsp_sample_sparse / _race_head cover
 
 
-def auto_head_k(heuristic, mass=0.98, want_top=False):
+def auto_head_k(heuristic, mass=0.98, want_top=False, path=None):
     """Head size for sampler='auto' on a heuristic nobody sparsified by hand: 63 or 127 if that many largest entries hold at
     least `mass` of (nearly) every row (the learned heuristic is k-sparse by construction: tsp/net.py:94-102 scatters k values per row
     into zeros, + 1e-10), else None.  One reduction and one host read per heuristic object.
     mass = 0.98: a step that has to leave the head re-reads the whole row for its ants (each such step stops four
     ants for a row walk); with a fifth of the mass in the tail (plain 1/d at n = 200: 0.85 in the best 127) the head rows lose.
-    want_top: also return the rows' 127 largest values (descending), which sparse_head takes instead of its own torch.topk."""
+    want_top: also return the rows' 127 largest values (descending), which sparse_head takes instead of its own torch.topk.
+    path 'hip' (the default on a device; _setup_path): the rows are judged by daco_head_stats -- row sums in float64, the host reads
+    three counters -- and there are no sorted values to hand on: want_top returns (k, None).  'torch' (and CPU tensors): the
+    float32 expression below; a row within float32 rounding of a threshold can be classed differently by the two."""
     h = heuristic.detach()
     n = h.shape[-1]
     if not (SPARSE_MIN_N <= n <= SPARSE_MAX_N):
         return (None, None) if want_top else None
+    if _setup_path(path, n, h) == "hip":
+        k = _auto_head_k_hip(h, n, mass)
+        return (k, None) if want_top else k
     h = h.to(torch.float32)
     top = torch.topk(h, min(127, n - 1), dim=-1).values
     tot = h.sum(dim=-1)
@@ -118,23 +184,48 @@ def auto_head_k(heuristic, mass=0.98, want_top=False):
     # n = 500, <= 62 below n = 410) lets a launch of few ants -- one instance, the reference's own call pattern, tsp/test.ipynb:66-68 --
     # keep its head rows in LDS; taken when it holds practically ALL of the mass (1 - 1e-4: the network's output has
     # exactly the graph's k live entries per row, so k = 50 -> a head of 51), since whatever it left out would be walked as tail
-    lanes = min(16, (160 * 1024 - 128 - 4 * 528 - 4 * 514 * 2 - 32) // (n * 24))
-    k_lds = min(62, 4 * lanes - 1, top.shape[-1])
+    k_lds = _lds_head_k(n, top.shape[-1])
     ok_lds = ((top[..., :k_lds].sum(dim=-1) / tot) >= 1.0 - 1e-4).float().mean() if k_lds >= 8 else torch.zeros((), device=h.device)
     ok63, ok127, ok_lds = (float(x) for x in torch.stack((ok63, ok127, ok_lds)).tolist())          # (one host read)
     k = k_lds if ok_lds >= 0.95 else (63 if ok63 >= 0.95 else (127 if ok127 >= 0.95 else None))
     return (k, top if k else None) if want_top else k
 
 
+def _lds_head_k(n, most):
+    """auto_head_k's LDS-resident head size for n nodes (at most `most` entries): n x ceil((k + 1) / 4) lanes x 24 bytes next to
+    four ants in a CU's LDS."""
+    lanes = min(16, (160 * 1024 - 128 - 4 * 528 - 4 * 514 * 2 - 32) // (n * 24))
+    return min(62, 4 * lanes - 1, most)
+
+
+def _auto_head_k_hip(h, n, mass):
+    """auto_head_k's rule with the rows judged on the device (daco_head_stats): one launch, one read of three counters."""
+    h, wbs = _bstride(h, n)
+    B = h.shape[0] if h.dim() == 3 else 1
+    k_lds = _lds_head_k(n, min(127, n - 1))
+    dev = h.device
+    with _on(dev):
+        counts = torch.empty(3, dtype=torch.int32, device=dev)
+        rc = _lib.lib().daco_head_stats(_stream(dev), B, n, h.data_ptr(), wbs, k_lds if k_lds >= 8 else 0, float(mass), 1.0 - 1e-4,
+                                        counts.data_ptr())
+    _lib.check(rc, "daco_head_stats")
+    rows = np.float32(B * n)
+    ok63, ok127, ok_lds = (float(np.float32(c) / rows) for c in counts.tolist())                   # (one host read; torch's f32 mean)
+    if k_lds < 8:
+        ok_lds = 0.0
+    return k_lds if ok_lds >= 0.95 else (63 if ok63 >= 0.95 else (127 if ok127 >= 0.95 else None))
+
+
 _warned_sparse_range = False
 
 
-def resolve_sampler(sampler, n, head_k, heuristic, cache):
+def resolve_sampler(sampler, n, head_k, heuristic, cache, path=None):
     """('scan' | 'scan_wave' | 'race' | 'scan_sparse', head size) for a colony of n nodes.
     'auto': head / tail rows (scan_sparse: the same categorical as 'scan', 384 / 768 bytes per step instead of a row) whenever
     they apply -- after sparsify(k), or when auto_head_k finds the heuristic concentrated -- and 129 <= n <= 1024; else the dense
     scan.  An explicit 'scan_sparse' outside that range falls back to 'scan' with one warning.
-    cache: a dict of the colony (the concentration test is repeated only when the heuristic object changes)."""
+    cache: a dict of the colony (the concentration test is repeated only when the heuristic object changes).
+    path: auto_head_k's."""
     global _warned_sparse_range
     in_range = SPARSE_MIN_N <= n <= SPARSE_MAX_N
     if sampler == "scan_sparse" and not in_range:
@@ -152,9 +243,11 @@ def resolve_sampler(sampler, n, head_k, heuristic, cache):
         return "scan_sparse", head_k
     hit = cache.get("auto_head")
     if hit is None or hit[0] is not heuristic:
-        k, top = auto_head_k(heuristic, want_top=True)
+        k, top = auto_head_k(heuristic, want_top=True, path=path)
         hit = cache["auto_head"] = (heuristic, k)
-        cache["auto_top"] = (heuristic, top)            # (taken -- and dropped -- by the colony's next head table)
+        cache.pop("auto_top", None)
+        if top is not None:                             # (the torch path's sorted values: taken -- and dropped -- by the colony's next head table)
+            cache["auto_top"] = (heuristic, top)
     return ("scan_sparse", hit[1]) if hit[1] else ("scan", None)
 
 
@@ -165,12 +258,16 @@ def take_auto_top(cache, heuristic):
     return hit[1] if hit is not None and hit[0] is heuristic else None
 
 
-def head_table(heuristic, k, B, cache=None):
+def head_table(heuristic, k, B, cache=None, path=None):
     """sparse_head(.., k) of a colony's heuristic object ([n,n] shared, or [B,n,n]) for its B instances; cache: the colony's
-    resolve_sampler cache, whose sorted top values for this object are taken (take_auto_top)."""
+    resolve_sampler cache, whose sorted top values for this object are taken (take_auto_top: the torch path uses them).
+    path: sparse_head's; on 'hip' a shared [n,n] heuristic is read once for the B tables."""
     h = heuristic.detach()
+    top = take_auto_top(cache, heuristic)
+    if _setup_path(path, h.shape[-1], h) == "hip":
+        return sparse_head(h, k, path="hip", batch=B)
     h = h if h.dim() == 3 else h.unsqueeze(0).expand(B, *h.shape)
-    return sparse_head(_f32c(h), k, top=take_auto_top(cache, heuristic))
+    return sparse_head(_f32c(h), k, top=top, path="torch")
 
 
 def sparse_workspace(device, B, n, n_ants, unit_exponents=True):

@@ -394,6 +394,8 @@ class OP(_Base):
     """op/aco.py:5-224: orienteering -- maximise collected prize on a route from the depot whose
     length stays within max_len; a dummy end node n absorbs finished ants."""
 
+    setup_path = None      # sparsify: None = daco_sparsify where it applies, 'hip' | 'torch' (engine.sparsify_heuristic)
+
     def __init__(self, distances, prizes, max_len, n_ants=20, decay=0.9, alpha=1, beta=1, elitist=False,
                  min_max=False, pheromone=None, heuristic=None, min=None, device='cpu', k_sparse=None, *,
                  sampler='scan', seed=None):
@@ -420,10 +422,7 @@ class OP(_Base):
 
     @torch.no_grad()
     def sparsify(self, k_sparse):
-        _, idx = torch.topk(self.distances, k=k_sparse, dim=1, largest=False)
-        sparse = torch.full_like(self.distances, 1e10)
-        sparse.scatter_(1, idx, torch.gather(self.distances, 1, idx))
-        self.heuristic = self.prizes.unsqueeze(0) / sparse
+        self.heuristic = engine.sparsify_heuristic(self.distances, k_sparse, numer=self.prizes, path=self.setup_path)
 
     def sample(self):
         sols, log_probs = self.gen_sol(require_prob=True)

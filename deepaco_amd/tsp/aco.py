@@ -34,6 +34,7 @@ except ImportError:  # imported as a bare module from this directory, like the r
 class ACO():
 
     NORM_PASSES = 1      # Categorical(dist) normalises once (tsp/aco.py:174)
+    setup_path = None    # sparsify / head table / 'auto' test: None = the set-up kernels where they apply, 'hip' | 'torch' (engine.sparsify_heuristic)
     FIXED_START = -1     # random start node per ant (tsp/aco.py:141)
 
     def __init__(self,
@@ -95,23 +96,21 @@ class ACO():
     def sparsify(self, k_sparse):
         '''Heuristic = 1/dist on each node's k nearest neighbours, 1e-10 elsewhere
         (vanilla-ACO baseline).'''
-        _, topk_indices = torch.topk(self.distances, k=k_sparse, dim=1, largest=False)
-        sparse_distances = torch.full_like(self.distances, 1e10)
-        sparse_distances.scatter_(1, topk_indices, torch.gather(self.distances, 1, topk_indices))
-        self.heuristic = 1 / sparse_distances
+        self.heuristic = engine.sparsify_heuristic(self.distances, k_sparse, path=self.setup_path)
         self._head_k = min(int(k_sparse), 127)              # sampler='scan_sparse': the head of a row = these k entries
 
     def resolved_sampler(self):
         """(sampler the next construction runs, head size): engine.resolve_sampler."""
         cache = self.__dict__.setdefault("_auto", {})
-        return engine.resolve_sampler(self.sampler, self.problem_size, self.__dict__.get("_head_k"), self.heuristic, cache)
+        return engine.resolve_sampler(self.sampler, self.problem_size, self.__dict__.get("_head_k"), self.heuristic, cache,
+                                      path=self.setup_path)
 
     def _head_table(self, k=None):
         """[1, n, 64 | 128] head ids for sampler='scan_sparse' (engine.sparse_head), once per heuristic object."""
         hit = self.__dict__.get("_head")
         if hit is None or hit[0] is not self.heuristic or (k is not None and hit[2] != k):
             k = k or self.__dict__.get("_head_k") or max(1, min(127, self.problem_size // 10))
-            hit = (self.heuristic, engine.head_table(self.heuristic, k, 1, self.__dict__.get("_auto")), k)
+            hit = (self.heuristic, engine.head_table(self.heuristic, k, 1, self.__dict__.get("_auto"), path=self.setup_path), k)
             self._head = hit
         return hit[1]
 
@@ -146,6 +145,7 @@ class ACO():
                                     alpha=self.alpha, beta=self.beta, elitist=self.elitist, min_max=self.min_max, heuristic=eta,
                                     min=self.min if self.min_max else None, sampler=sampler, seed=self.seed,
                                     fixed_start=self.FIXED_START, norm_passes=self.NORM_PASSES)
+            col.setup_path = self.setup_path
             if sampler == "scan_sparse":                    # (head_k stays unset otherwise: 'race' after sparsify(k) runs the dense race kernel here)
                 col.head_k = hk
                 col._head = (eta, self._head_table(hk), hk)     # (this object's table: built once, from the sorted top values if 'auto' left them)

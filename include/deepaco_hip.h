@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats) */
 
 /* error codes */
 #define DACO_OK 0
@@ -732,6 +732,42 @@ int daco_tsp_knn_graph_csr(void *stream, int B, int n, int k, const float *coord
  */
 int daco_heu_matrix(void *stream, int B, int n, int E, const int64_t *edge_index, const float *heu, float fill, float add,
                     float *out, int32_t *bad);
+
+/* ---------------------------------------------------------------------------------------------
+ * The colony's set-up: daco_sparsify, daco_sparse_head, daco_head_stats (csrc/daco_colony_setup.hip)
+ *   ACO.sparsify tsp/aco.py:52-67 (and op/aco.py's, with the prizes as numerator); the head table of the head-row samplers
+ *   and the concentration test of sampler='auto' (engine.sparse_head / engine.auto_head_k), which were torch.topk / cumsum /
+ *   scatter_ on the device.  One wavefront per matrix row, the row in registers: 2 <= n <= 1024 (DACO_E_TOOLARGE above).
+ *   The k-th value of a row comes from a threshold search on the floats' order-preserving integer image; THE TIE RULE of all
+ *   three: values compare as floats with -0.0 == +0.0, and of the entries equal to the k-th value the smaller column ids are
+ *   taken.  NaN inputs are outside the contract (an unspecified selection; nothing faults).  No host synchronisation.
+ *   The statuses are the usual DACO_OK / DACO_E_* values typed `long`, for the reason given at daco_rcpsp_net_forward; the
+ *   refusals are held by tests/test_colony_setup_refusals.py.
+ *
+ * daco_sparsify: dist [B][n][n] f32 (dist_bstride between instances).  Per row the k entries smallest by (value ascending,
+ *   column ascending) are selected; out [B][n][n] (dense) = num_j / dist[b][i][j] on the selected columns and num_j / 1e10f on
+ *   the others, with IEEE-correct f32 division (bit-equal to torch's `1 / sparse`), the dist value with its own sign of zero.
+ *   num_j = 1 if numer is NULL (TSP), else numer[b * numer_bstride + j] (OP's prizes; numer_bstride = 0: one vector for the batch).
+ *   Errors: DACO_E_BADARG for k < 1, k > n, n < 2, B < 1, a null dist / out or a negative stride.
+ */
+long daco_sparsify(void *stream, int B, int n, int k, const float *dist, long dist_bstride, const float *numer,
+                  long numer_bstride, float *out);
+/* daco_sparse_head: the head table daco_tsp_sample_sparse takes (head_id above).  weights [B][n][n] f32 (w_bstride between
+ *   instances); per row the k (1 .. 127, <= n) entries largest by (value descending, column ascending), their column ids in
+ *   ascending order in slots 0 .. k-1 of ids [B][n][S] uint16, S = 64 for k <= 63, else 128; the other slots 0, slot S-1 = k.
+ *   Every slot is written by this call.  w_bstride = 0: one matrix for the batch -- each row is read once and its table
+ *   written for all B instances.  Errors: DACO_E_BADARG for k outside 1 .. min(127, n) or a null pointer.
+ */
+long daco_sparse_head(void *stream, int B, int n, int k, const float *weights, long w_bstride, uint16_t *ids);
+/* daco_head_stats: how many rows of weights are concentrated in their K largest entries, for K = 63, 127 and k_lds.
+ *   Per row, in float64: tot = the sum of the row, S_K = the sum of its K largest values (= the values above the K-th largest
+ *   + the remaining places times that value; K above n counts as n); the row passes K if S_K / tot >= mass (mass_lds for
+ *   K = k_lds); a NaN ratio fails.  counts [3] int32 = the passing rows for K = 63, 127, k_lds (integer atomics: the same
+ *   on every run); k_lds < 1: not asked, counts[2] = 0.  The rows are those of B matrices, or of the one matrix if w_bstride = 0
+ *   (n rows).  The call clears counts itself (a kernel, not a memset node).  Errors: DACO_E_BADARG for a null pointer.
+ */
+long daco_head_stats(void *stream, int B, int n, const float *weights, long w_bstride, int k_lds, double mass,
+                    double mass_lds, int32_t *counts);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_mkpv_sample -- fused solution construction of the vector-pheromone knapsack colony (one launch)
