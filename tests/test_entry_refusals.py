@@ -202,6 +202,7 @@ REFUSED = [
     # (the test ids carry the row's index: new rows go at the end)
     ("daco_sibling_sample", BADARG, "SOP needs n - 1 = 99 noise steps, got 100", dict(_SIB, mode=_lib.RACE_NOISE, noise=P, noise_steps=100)),
     ("daco_sibling_sample", BADARG, "SOP needs n - 1 = 99 noise steps, got 98", dict(_SIB, mode=_lib.RACE_NOISE, noise=P, noise_steps=98)),
+    ("daco_pheromone_update", TOOLARGE, "n=4097 exceeds DACO_MAX_NODES", dict(_UPD, n=4097, len=4097)),   # (4096 runs: test_gpu_32)
 ]
 
 
