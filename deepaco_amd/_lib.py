@@ -53,6 +53,9 @@ SIGNATURES = {
                               _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp, C.c_double, _vp, _vp]),
     "daco_sample_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp,
                                   C.c_double]),
+    # (long statuses, as daco_rcpsp_net_forward)
+    "daco_tsp_edge_logp": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _l, _vp, _f, _f, _vp, _vp, _vp]),
+    "daco_tsp_edge_backward": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _l, _vp, _f, _f, _vp, _vp, _vp, _vp]),
     "daco_gnn_param_floats": (_sz, [_i]),
     "daco_gnn_workspace_bytes": (_sz, [_i, _i]),
     "daco_gnn_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),

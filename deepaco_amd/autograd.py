@@ -55,6 +55,45 @@ class TspBatchSampleFn(torch.autograd.Function):
         return (grad,) + (None,) * 10
 
 
+class TspEdgeSampleFn(torch.autograd.Function):
+    """TspBatchSampleFn on the k-sparse graph's edge list, for a fresh colony (pheromone = ones):
+    (heu [B, E = n k], edge_index [B, 2, E] in engine.tsp_knn_graph's layout) -> (paths [B,n,A], log_probs [B,n-1,A], flags [B]);
+    the gradient flows to heu itself.  Forward: the dense eta the samplers read (engine.heu_matrix, fill = add = eps), the tours
+    -- on head rows (sparse_head + tsp_sample_sparse) for 129 <= n <= 1024 and k <= 127, else the dense scan without
+    log-probabilities, which draws what TspBatchSampleFn draws for the same seed, iteration and start -- and one
+    daco_tsp_edge_logp launch.  Backward: one daco_tsp_edge_backward launch; no [B, n, n] gradient exists on this path."""
+
+    @staticmethod
+    def forward(ctx, heu, edge_index, n, k, n_ants, beta, eps, fixed_start, seed, it, iter_dev=None):
+        h = heu.detach().float().contiguous()
+        B = h.shape[0]
+        # (refused before anything is launched: a CPU tensor, an irregular edge_index, sizes the edge kernels do not take)
+        engine.tsp_ops._edge_destinations("TspEdgeSampleFn", edge_index, h, n, k, None)
+        eta = engine.heu_matrix(n, edge_index, h, fill=eps, add=eps)
+        tau = torch.ones((n, n), dtype=torch.float32, device=h.device)
+        if engine.SPARSE_MIN_N <= n <= engine.SPARSE_MAX_N and k <= 127:
+            head = engine.sparse_head(eta, k, path="hip")                  # (on the device: no host read, capturable)
+            paths, flags, _, _ = engine.tsp_sample_sparse(tau, eta, n_ants, head, 1.0, beta, fixed_start=fixed_start, seed=seed, it=it,
+                                                          batch=B, iter_dev=iter_dev)
+        else:
+            paths, _, _, flags = engine.tsp_sample(tau, eta, n_ants, 1.0, beta, mode="scan", norm_passes=1, fixed_start=fixed_start,
+                                                   seed=seed, it=it, require_prob=False, batch=B, iter_dev=iter_dev)
+        logp, rowsum = engine.tsp_edge_logp(h, edge_index, n, k, paths, beta=beta, eps=eps)
+        ctx.save_for_backward(h, paths, rowsum)
+        ctx.edge_index = edge_index          # (the object itself: the graph arrays that ride on it are not part of a saved copy)
+        ctx.meta = (n, k, beta, eps)
+        ctx.mark_non_differentiable(paths, flags)
+        return paths, logp, flags
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _gp, glogp, _gf):
+        h, paths, rowsum = ctx.saved_tensors
+        edge_index, (n, k, beta, eps) = ctx.edge_index, ctx.meta
+        grad = engine.tsp_edge_backward(h, edge_index, n, k, paths, rowsum, glogp.contiguous(), beta=beta, eps=eps)
+        return (grad,) + (None,) * 10
+
+
 class CvrpSampleFn(torch.autograd.Function):
     """(heuristic [n,n]) -> (paths [Lmax,A], log_probs [Lmax-1,A], lens [A], flags [1])."""
 

@@ -3,7 +3,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .common import MODES, RACE_NOISE, _bstride, _f32c, _on, _ptr, _require_gpu, _stream, _workspace
+from .common import MODES, RACE_NOISE, _bstride, _f32c, _grad_out, _on, _ptr, _require_gpu, _stream, _workspace
 
 
 def tsp_sample(tau, eta, n_ants, alpha=1.0, beta=1.0, mode="scan", norm_passes=1, start=None,
@@ -403,3 +403,78 @@ def heu_matrix(n, edge_index, heu, fill=0.0, add=0.0, check=False):
     if check and int(bad.item()):
         raise IndexError(f"heu_matrix: {int(bad.item())} edge(s) with a node id outside [0, {n})")
     return out
+
+
+def _edge_destinations(who, edge_index, heu, n, k, pheromone, *others):
+    """What tsp_edge_logp / tsp_edge_backward refuse, and the destination array they hand to the library:
+    -> (edge_dst pointer | None, stride, edge_dst32 pointer | None, the tensor kept alive).  The int32 array of a valid `_daco_csr`
+    (engine.tsp_knn_graph's: half the bytes, regular by construction) is taken where the tensor carries one; any other edge_index
+    must be in the regular layout -- edge j k + t leaves node j -- which costs one comparison and one host read per tensor object,
+    cached on it like `_daco_ids_ok`."""
+    dense = "engine.sample_backward (the dense path) takes such input"
+    if pheromone is not None:
+        raise _lib.DacoError(f"{who}: the edge-list path replays a fresh colony (pheromone = ones), pheromone must be None; {dense}")
+    for t in (heu, edge_index) + others:
+        if not t.is_cuda:
+            raise _lib.DacoError(f"{who}: runs on a HIP device only (got a CPU tensor), there is no CPU fallback; {dense}")
+    B, E = heu.shape
+    n, k = int(n), int(k)
+    if k < 1 or E != n * k or tuple(edge_index.shape) != (B, 2, E) or edge_index.dtype != torch.int64:
+        raise _lib.DacoError(f"{who}: heu [B, n k] and an int64 edge_index [B, 2, n k] expected (n = {n}, k = {k}, heu {tuple(heu.shape)}, "
+                             f"edge_index {tuple(edge_index.shape)}); {dense}")
+    csr = getattr(edge_index, "_daco_csr", None)
+    if (csr is not None and csr[2] == n and csr[3] == k and csr[4] == edge_index._version and csr[1].numel() == B * E
+            and csr[1].device == heu.device):
+        return None, 0, csr[1].data_ptr(), csr[1]
+    if getattr(edge_index, "_daco_regular", None) != (n, k, edge_index._version):
+        rows = torch.arange(n, device=edge_index.device).repeat_interleave(k)
+        if not bool((edge_index[:, 0] == rows).all()):                   # (one host read)
+            raise _lib.DacoError(f"{who}: edge_index is not in the regular layout (edge j k + t leaves node j, as engine.tsp_knn_graph "
+                                 f"writes it); {dense}")
+        edge_index._daco_regular = (n, k, edge_index._version)
+    ei = edge_index.contiguous()
+    return ei.data_ptr() + E * 8, 2 * E, None, ei
+
+
+def tsp_edge_logp(heu, edge_index, n, k, paths, beta=1.0, eps=1e-10, pheromone=None):
+    """Log-probabilities of given tours on the k-sparse graph's edge list (daco_tsp_edge_logp): heu [B, n k] f32 (the network's
+    output; eta = heu + eps on the graph, eps off it), edge_index [B, 2, n k] in tsp_knn_graph's layout, paths [B, n, A] int64
+    -> (log_probs [B, n-1, A], rowsum [B, n-1, A]) -- what tsp_sample(require_prob=True) returns for heu_matrix(n, edge_index,
+    heu, fill=eps, add=eps) under a pheromone of ones, reading k edges per step instead of a row.  1 <= k <= 128, k < n <= 4096."""
+    who = "tsp_edge_logp"
+    d64, dbs, d32, keep = _edge_destinations(who, edge_index, heu, n, k, pheromone, paths)
+    B, E = heu.shape
+    heu = _f32c(heu.detach())
+    paths = paths.contiguous()
+    A = paths.shape[2]
+    assert tuple(paths.shape) == (B, n, A) and paths.dtype == torch.int64
+    dev = heu.device
+    with _on(dev):
+        logp = torch.empty((B, n - 1, A), dtype=torch.float32, device=dev)
+        rowsum = torch.empty((B, n - 1, A), dtype=torch.float32, device=dev)
+        rc = _lib.lib().daco_tsp_edge_logp(_stream(dev), B, int(n), int(k), A, heu.data_ptr(), d64, dbs, d32, float(eps), float(beta),
+                                           paths.data_ptr(), logp.data_ptr(), rowsum.data_ptr())
+    _lib.check(rc, "daco_tsp_edge_logp")
+    return logp, rowsum
+
+
+def tsp_edge_backward(heu, edge_index, n, k, paths, rowsum, grad_logp, beta=1.0, eps=1e-10, pheromone=None, out=None):
+    """Gradient of sum(grad_logp * log_probs) w.r.t. heu -> [B, n k] (daco_tsp_edge_backward): sample_backward followed by
+    reshape's gather, without the [B, n, n] gradient in between.  rowsum: tsp_edge_logp's; out: a contiguous float32 [B, n k]
+    tensor to accumulate into (default: fresh zeros)."""
+    who = "tsp_edge_backward"
+    d64, dbs, d32, keep = _edge_destinations(who, edge_index, heu, n, k, pheromone, paths, rowsum, grad_logp)
+    B, E = heu.shape
+    heu = _f32c(heu.detach())
+    paths = paths.contiguous()
+    A = paths.shape[2]
+    assert tuple(paths.shape) == (B, n, A) and paths.dtype == torch.int64
+    assert tuple(rowsum.shape) == (B, n - 1, A) and tuple(grad_logp.shape) == (B, n - 1, A)
+    rowsum, grad_logp = _f32c(rowsum), _f32c(grad_logp)
+    dev = heu.device
+    with _on(dev):
+        grad = _grad_out(out, (B, E), who, dev)
+        rc = _lib.lib().daco_tsp_edge_backward(_stream(dev), B, int(n), int(k), A, heu.data_ptr(), d64, dbs, d32, float(eps), float(beta),
+                                               paths.data_ptr(), rowsum.data_ptr(), grad_logp.data_ptr(), grad.data_ptr())
+    _lib.check(rc, "daco_tsp_edge_backward")
+    return grad

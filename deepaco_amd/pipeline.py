@@ -48,21 +48,38 @@ def infer_tsp_batch(coords, n_ants, t_aco, k_sparse, net=None, node_feature="coo
 W_2OPT = 0.95      # tsp_nls/train.py:13: weight of the locally-searched costs in the REINFORCE signal
 
 
-def _tsp_nls_loss(net, coords, n_ants, k_sparse, seed, it, iter_dev, local_search):
+GRAD_PATHS = ("dense", "edges")
+
+
+def _check_grad_path(grad_path):
+    if grad_path not in GRAD_PATHS:
+        raise ValueError(f"grad_path must be one of {GRAD_PATHS} (got {grad_path!r})")
+
+
+def _tsp_nls_loss(net, coords, n_ants, k_sparse, seed, it, iter_dev, local_search, grad_path="dense"):
     """The forward half of tsp_nls/train.py:15-44 for B instances: graphs -> Net (training mode) -> heuristic matrices ->
     B colonies sampled with log-probabilities -> NLS / 2-opt costs -> REINFORCE loss with the mixed baseline.
     iter_dev: optional int64 device scalar added to `it` inside the sampler (a captured step advances it).
+    grad_path: 'dense' -- the heuristic matrix under autograd, TspBatchSampleFn, a [B, n, n] gradient of which reshape's backward
+    gathers n k entries; 'edges' -- TspEdgeSampleFn: log-probabilities and gradient on the graph's edge list (for 129 <= n <= 1024
+    the tours come from the head-row sampler: the same distribution, other draws).
     Returns (loss, mean sampled cost, mean locally-searched cost)."""
-    from .autograd import TspBatchSampleFn
+    from .autograd import TspBatchSampleFn, TspEdgeSampleFn
+    _check_grad_path(grad_path)
     B, n, _ = coords.shape
     dev = coords.device
     dist, ei, ea = engine.tsp_knn_graph(coords, k_sparse)
     x = torch.zeros((B, n, 1), device=dev)
     x[:, 0] = 1.0                                                     # tsp_nls/utils.py:38-44: one-hot of the start node
     heu = net.forward_batch_train(x, ei, ea, k_sparse=k_sparse)
-    heu_mat = net.reshape_batch(n, ei, heu) + EPS
-    tau = torch.ones((B, n, n), device=dev)
-    paths, log_probs, flags = TspBatchSampleFn.apply(heu_mat, tau, n_ants, 1.0, 1.0, "scan", 2, 0, seed, it, iter_dev)
+    if grad_path == "edges":
+        paths, log_probs, flags = TspEdgeSampleFn.apply(heu, ei, n, int(k_sparse), n_ants, 1.0, EPS, 0, seed, it, iter_dev)
+        # (the matrix the guided perturbation of the NLS reads; 2-opt alone needs none)
+        heu_mat = engine.heu_matrix(n, ei, heu.detach(), fill=EPS, add=EPS) if local_search == "nls" else None
+    else:
+        heu_mat = net.reshape_batch(n, ei, heu) + EPS
+        tau = torch.ones((B, n, n), device=dev)
+        paths, log_probs, flags = TspBatchSampleFn.apply(heu_mat, tau, n_ants, 1.0, 1.0, "scan", 2, 0, seed, it, iter_dev)
     with torch.no_grad():
         costs = engine.tour_costs(dist, paths)                        # [B, A]
         tours = paths.permute(0, 2, 1).to(torch.int16).contiguous()
@@ -81,20 +98,57 @@ def _tsp_nls_loss(net, coords, n_ants, k_sparse, seed, it, iter_dev, local_searc
     return loss, costs.mean(), costs_ls.mean()
 
 
-def train_tsp_nls_batch(net, optimizer, coords, n_ants, k_sparse, seed=0, it=0, max_norm=3.0, local_search="nls"):
+def train_tsp_nls_batch(net, optimizer, coords, n_ants, k_sparse, seed=0, it=0, max_norm=3.0, local_search="nls", grad_path="dense"):
     """One optimisation step of tsp_nls/train.py:15-44 (`train_instance`) for a batch of B instances, on the device end
     to end: kNN graphs (one launch) -> Net in training mode (HIP kernels, per-graph BatchNorm statistics) -> heuristic
     matrices -> B colonies sampled with log-probabilities (one launch) -> NLS / 2-opt costs -> REINFORCE loss with the
     mixed baseline -> backward (sampler backward + GNN backward kernels) -> gradient clipping -> optimizer step.
     coords [B,n,2].  Returns (loss, mean sampled cost, mean locally-searched cost) as tensors.
-    (After net.flatten_parameters() the clipping runs over the flat block: the same norm in one launch.)"""
+    (After net.flatten_parameters() the clipping runs over the flat block: the same norm in one launch.)
+    grad_path: 'dense' (the default) or 'edges' -- see _tsp_nls_loss."""
     net.train()
-    loss, c, c_ls = _tsp_nls_loss(net, coords, n_ants, k_sparse, seed, it, None, local_search)
+    loss, c, c_ls = _tsp_nls_loss(net, coords, n_ants, k_sparse, seed, it, None, local_search, grad_path)
     optimizer.zero_grad()
     loss.backward()
     torch.nn.utils.clip_grad_norm_(parameters=net.train_parameters(), max_norm=max_norm, norm_type=2)
     optimizer.step()
     return loss.detach(), c, c_ls
+
+
+def _tsp_loss(net, coords, n_ants, k_sparse, seed, it, grad_path="dense"):
+    """The loss of tsp/train.ipynb:32-46 for B instances: kNN graphs -> Net in training mode on the coordinates -> heuristic + EPS
+    -> B fresh colonies sampled from random starts with log-probabilities (Categorical normalises once) ->
+    sum_a (cost_a - mean cost) * sum_t logp[t, a] / n_ants per instance, averaged over the batch.  -> (loss, mean cost)"""
+    from .autograd import TspBatchSampleFn, TspEdgeSampleFn
+    _check_grad_path(grad_path)
+    B, n, _ = coords.shape
+    dist, ei, ea = engine.tsp_knn_graph(coords, k_sparse)
+    heu = net.forward_batch_train(coords, ei, ea, k_sparse=k_sparse)
+    if grad_path == "edges":
+        paths, log_probs, flags = TspEdgeSampleFn.apply(heu, ei, n, int(k_sparse), n_ants, 1.0, EPS, -1, seed, it, None)
+    else:
+        heu_mat = net.reshape_batch(n, ei, heu) + EPS
+        tau = torch.ones((B, n, n), device=coords.device)
+        paths, log_probs, flags = TspBatchSampleFn.apply(heu_mat, tau, n_ants, 1.0, 1.0, "scan", 1, -1, seed, it, None)
+    with torch.no_grad():
+        costs = engine.tour_costs(dist, paths)                        # [B, A]
+        adv = costs - costs.mean(dim=1, keepdim=True)
+    loss = torch.sum(adv.unsqueeze(1) * log_probs) / n_ants / B
+    return loss, costs.mean()
+
+
+def train_tsp_batch(net, optimizer, coords, n_ants, k_sparse, seed=0, it=0, grad_path="dense"):
+    """One optimisation step of tsp/train.ipynb:32-49 (`train_instance`) for a batch of B instances, on the device end to end:
+    kNN graphs -> Net in training mode (node features: the coordinates) -> B fresh colonies from random starts, sampled with
+    log-probabilities (one launch) -> REINFORCE loss with the mean cost as baseline, averaged over the instances -> backward
+    -> optimizer step (the notebook clips nothing).  coords [B,n,2]; net: a Net(feats=2).
+    grad_path: 'dense' (the default) or 'edges' -- see _tsp_nls_loss.  Returns (loss, mean sampled cost) as tensors."""
+    net.train()
+    loss, c = _tsp_loss(net, coords, n_ants, k_sparse, seed, it, grad_path)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    return loss.detach(), c
 
 
 class TspNlsTrainer:
@@ -111,10 +165,12 @@ class TspNlsTrainer:
     step() returns (loss, mean sampled cost, mean locally-searched cost) as device scalars that the next step overwrites."""
 
     def __init__(self, net, B, n, n_ants, k_sparse, lr=3e-4, seed=0, max_norm=3.0, local_search="nls", graph=True,
-                 optimizer=None, device=None):
+                 optimizer=None, device=None, grad_path="dense"):
         dev = torch.device(device) if device is not None else next(net.parameters()).device
         if dev.type != "cuda":
             raise _lib.DacoError("TspNlsTrainer runs on a HIP device only")
+        _check_grad_path(grad_path)
+        self.grad_path = grad_path       # ('edges': the head table is built on the device, so the capture holds no host read)
         self.net, self.B, self.n, self.n_ants, self.k = net, int(B), int(n), int(n_ants), int(k_sparse)
         self.seed, self.max_norm, self.local_search, self.use_graph = int(seed), float(max_norm), local_search, bool(graph)
         self.block = net.flatten_parameters()
@@ -130,7 +186,8 @@ class TspNlsTrainer:
 
     def _body(self):
         self.net.train()
-        loss, c, c_ls = _tsp_nls_loss(self.net, self.coords, self.n_ants, self.k, self.seed, 0, self.it_dev, self.local_search)
+        loss, c, c_ls = _tsp_nls_loss(self.net, self.coords, self.n_ants, self.k, self.seed, 0, self.it_dev, self.local_search,
+                                      self.grad_path)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         torch.nn.utils.clip_grad_norm_([self.block], max_norm=self.max_norm, norm_type=2)

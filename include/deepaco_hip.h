@@ -422,6 +422,36 @@ int daco_sample_backward(void *stream, int B, int n, int A, int rows,
                          float capacity, float *grad_eta, const double *demand64, double capacity64);
 
 /* ---------------------------------------------------------------------------------------------
+ * daco_tsp_edge_logp / daco_tsp_edge_backward -- the log-probabilities of given TSP tours and their gradient on the k-sparse
+ *   graph's EDGE LIST (the training step of tsp/train.ipynb:32-49 and tsp_nls/train.py:15-44 without the [B][n][n] gradient
+ *   that daco_sample_backward fills and Net.reshape's backward gathers n k entries of).  The pheromone is ones (every training
+ *   step of the reference builds a fresh ACO).
+ *   heu [B][E = n k] f32: the network's output; edge j k + t leaves node j (the regular layout daco_tsp_knn_graph writes).
+ *   The edges' destinations: exactly one of edge_dst (int64, graph-local ids, [B] rows of E ids edge_dst_bstride elements apart:
+ *   row 1 of an edge_index [B][2][E] with stride 2 E) and edge_dst32 (int32 [B][E], ids of the block-diagonal batch graph
+ *   b n + local, as daco_tsp_knn_graph_csr's dst32 -- half the bytes).  A destination outside [0, n) is an edge that is never open.
+ *   Model: eta_e = heu_e + eps on the graph, eps off it.  At step t from node i: p_e = eta_e^beta over the row's edges whose
+ *   destination is unvisited, S = sum p_e + eps^beta (n - t - live neighbours), p_j = the chosen edge's p or eps^beta for a move
+ *   off the graph.
+ *   daco_tsp_edge_logp:     logp [B][n-1][A] = log clamp(p_j / S, 2^-23, 1 - 2^-23) (the dense kernels' clamp), rowsum [B][n-1][A] = S.
+ *   daco_tsp_edge_backward: grad_heu[b][e] += sum over draws (t, a) made from e's row with e live of
+ *                           grad_logp[t][a] beta ([e chosen] / eta_e - p_e / (eta_e rowsum[t][a])), nothing for a clamped draw;
+ *                           eta = 0 as daco_sample_backward treats it.  The [k = j] term of an off-graph move has no edge and is
+ *                           dropped.  grad_heu [B][E] must be zeroed (or hold a gradient to accumulate into).  f32 hardware
+ *                           atomics: summation order across ants is not fixed, the result is reproducible to rounding.
+ *   Limits: 1 <= k <= 128 (DACO_E_TOOLARGE above), k < n (DACO_E_BADARG), 2 <= n <= DACO_MAX_NODES (DACO_E_TOOLARGE above); every
+ *   refusal comes before any HIP call and its daco_last_error() names the dense path, which has none of these limits.  The status is
+ *   the usual DACO_OK / DACO_E_* value typed `long`, for the reason given at daco_rcpsp_net_forward.  Added under DACO_VERSION 129:
+ *   new entry points only.
+ */
+long daco_tsp_edge_logp(void *stream, int B, int n, int k, int A, const float *heu, const int64_t *edge_dst,
+                        long edge_dst_bstride, const int32_t *edge_dst32, float eps, float beta, const int64_t *paths,
+                        float *logp, float *rowsum);
+long daco_tsp_edge_backward(void *stream, int B, int n, int k, int A, const float *heu, const int64_t *edge_dst,
+                            long edge_dst_bstride, const int32_t *edge_dst32, float eps, float beta, const int64_t *paths,
+                            const float *rowsum, const float *grad_logp, float *grad_heu);
+
+/* ---------------------------------------------------------------------------------------------
  * daco_tour_costs -- replaces ACO.gen_path_costs
  *   closed = 1: sum_k dist[u_k][u_{k-1}] over the closed tour     (tsp/aco.py:121-132),
  *               added in the order k = 1..len-1 and the closing edge dist[u_0][u_{len-1}] last
