@@ -80,6 +80,7 @@ SIGNATURES = {
     "daco_sibling_record": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
     "daco_tsp_knn_graph": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp]),
     "daco_tsp_knn_graph_csr": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "daco_cvrp_knn_graph": (_l, [_vp, _i, _i, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp]),   # (a long status too)
     "daco_heu_matrix": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp]),
     # (long statuses, as daco_rcpsp_net_forward)
     "daco_sparsify": (_l, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _vp]),

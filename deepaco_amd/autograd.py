@@ -117,6 +117,32 @@ class CvrpSampleFn(torch.autograd.Function):
         return (grad[0],) + (None,) * 10
 
 
+class CvrpBatchSampleFn(torch.autograd.Function):
+    """B colonies at once: (heuristic [B,n,n], pheromone [B,n,n] or [n,n], demand [B,n] or [n]) -> (paths [B,Lmax,A], log_probs
+    [B,Lmax-1,A], lens [B,A], flags [B]), Lmax = 2 n + 1 as the sampler allots it (nothing is trimmed: that would need the
+    longest route on the host); one sampler launch forward, one daco_sample_backward launch for the whole batch backward.
+    Instance b draws what a single colony with ant_gid0 + b * n_ants as its first ant id draws."""
+
+    @staticmethod
+    def forward(ctx, heuristic, pheromone, demand, capacity, n_ants, alpha, beta, mode, noise, seed, it, ant_gid0=0):
+        eta = heuristic.detach().contiguous()
+        B = eta.shape[0]
+        paths, logp, rowsum, lens, flags = engine.cvrp_sample(
+            pheromone, eta, demand, capacity, n_ants, alpha, beta, mode=mode, noise=noise, seed=seed, it=it, ant_gid0=ant_gid0,
+            require_prob=True, batch=B)
+        ctx.save_for_backward(pheromone, eta, paths, rowsum, lens, demand)
+        ctx.misc = (alpha, beta, capacity)
+        ctx.mark_non_differentiable(paths, lens, flags)
+        return paths, logp, lens, flags
+
+    @staticmethod
+    def backward(ctx, _gp, glogp, _gl, _gf):
+        tau, eta, paths, rowsum, lens, demand = ctx.saved_tensors
+        a, b, cap = ctx.misc
+        grad = engine.sample_backward(tau, eta, a, b, paths, rowsum, glogp.contiguous(), lens=lens, demand=demand, capacity=cap)
+        return (grad,) + (None,) * 11
+
+
 class SiblingSampleFn(torch.autograd.Function):
     """Fused sop / pctsp / op / mkp construction whose log-probabilities carry gradient to the heuristic
     (daco_sibling_sample forward, daco_sibling_backward = route replay with the problem's own feasibility rules)."""

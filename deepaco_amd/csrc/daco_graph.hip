@@ -66,6 +66,117 @@ knn_graph_kernel(int B, int n, int k, const float *coords, float diag, float *di
   }
 }
 
+// ---- the CVRP graph of cvrp_nls/utils.py:34-59 (gen_pyg_data) for B instances of n1 = n + 1 nodes (node 0 = the depot), from the
+// distance matrix the caller holds (float64 in cvrp_nls, float32 instantiated too): one wavefront per customer row i = 1 .. n
+// takes the k smallest of dist[i][1:] (the row in registers, lane l owns customer columns l, l + 64, ...; k rounds of a wave
+// arg-min in the matrix's own precision, ascending, ties -> smaller column; the diagonal's 1e-10 makes the customer its own
+// first neighbour, as torch.topk does in the reference: the self loop is kept).  Per instance E = n (k + 2) edges in the
+// reference's order -- (i-1) k + r the k-NN part, n k + (i-1) depot -> i, n k + n + (i-1) i -> depot, both depot blocks with
+// dist[i][0] -- as int64 graph-local ids and float32 attributes, and the whole batch as one merged int32 graph with its CSR by
+// source: the depot has n out-edges and customer i has k + 1, so
+//   rowptr[b n1] = b E,  rowptr[b n1 + i] = b E + n + (i-1)(k+1),  rowptr[B n1] = B E
+//   perm[b E + (i-1)] = b E + n k + (i-1)                         (the depot's row: its edges in original order)
+//   perm[b E + n + (i-1)(k+1) + r] = b E + (i-1) k + r, r < k;   ... + k] = b E + n k + n + (i-1)
+// which is the stable argsort by source of the merged edge list (what Net's _csr_graph derives with a sort and a host read).
+template <typename T> struct CvrpKey { T key; int idx; };
+
+template <typename T, int CTRL, int ROW_MASK>
+__device__ inline void cvrp_arg_step(T &k, int &i) {
+  T ok;
+  if constexpr (sizeof(T) == 4) {
+    ok = dpp_f<CTRL, ROW_MASK, false>(k, k);
+  } else {
+    const long long bits = __double_as_longlong(k);
+    const int lo = (int)(bits & 0xffffffffLL), hi = (int)(bits >> 32);
+    const int olo = dpp_i<CTRL, ROW_MASK, false>(lo, lo), ohi = dpp_i<CTRL, ROW_MASK, false>(hi, hi);
+    ok = __longlong_as_double(((long long)ohi << 32) | (long long)(unsigned)olo);
+  }
+  const int oi = dpp_i<CTRL, ROW_MASK, false>(i, i);
+  if (ok < k || (ok == k && oi < i)) { k = ok; i = oi; }
+}
+// (key, idx) arg-min over the wave along wave_arg's network, in T
+template <typename T>
+__device__ inline CvrpKey<T> cvrp_wave_argmin(T k, int i) {
+  cvrp_arg_step<T, DPP_ROW_SHR(1), 0xF>(k, i);
+  cvrp_arg_step<T, DPP_ROW_SHR(2), 0xF>(k, i);
+  cvrp_arg_step<T, DPP_ROW_SHR(4), 0xF>(k, i);
+  cvrp_arg_step<T, DPP_ROW_SHR(8), 0xF>(k, i);
+  cvrp_arg_step<T, DPP_ROW_BCAST15, 0xA>(k, i);
+  cvrp_arg_step<T, DPP_ROW_BCAST31, 0xC>(k, i);
+  CvrpKey<T> w;
+  w.idx = readlane_i(i, 63);
+  if constexpr (sizeof(T) == 4) {
+    w.key = readlane_f(k, 63);
+  } else {
+    const long long bits = __double_as_longlong(k);
+    const int lo = readlane_i((int)(bits & 0xffffffffLL), 63), hi = readlane_i((int)(bits >> 32), 63);
+    w.key = __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+  }
+  return w;
+}
+
+template <typename T, int CPL>   // customer columns per lane
+__global__ void __launch_bounds__(256)
+cvrp_knn_graph_kernel(int B, int n, int k, const T *dist, long dist_bs, int64_t *edge_index, float *edge_attr, int32_t *src32,
+                      int32_t *dst32, int32_t *rowptr, int32_t *perm) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long row = (long)blockIdx.x * 4 + wave;          // b*n + (i-1)
+  if (row >= (long)B * n) return;
+  const int b = (int)(row / n), c0 = (int)(row % n), i = c0 + 1;
+  const int n1 = n + 1, E = n * (k + 2);
+  const T *drow = dist + (size_t)b * dist_bs + (size_t)i * n1;
+  const T inf = (T)__builtin_inff();
+  T dv[CPL];
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) {
+    const int c = lane + 64 * q;                          // customer column c is node c + 1
+    dv[q] = c < n ? drow[1 + c] : inf;
+  }
+  int64_t *esrc = edge_index + (size_t)b * 2 * E, *edst = esrc + E;
+  float *attr = edge_attr + (size_t)b * E;
+  const int eb = b * E, nb = b * n1;                      // (B E and B n1 fit 32 bits: checked on the host)
+  if (lane == 0) {
+    const float d0 = (float)drow[0];
+    const int e1 = n * k + c0, e2 = e1 + n;
+    esrc[e1] = 0; edst[e1] = i; attr[e1] = d0;
+    esrc[e2] = i; edst[e2] = 0; attr[e2] = d0;
+    src32[eb + e1] = nb; dst32[eb + e1] = nb + i;
+    src32[eb + e2] = nb + i; dst32[eb + e2] = nb;
+    perm[eb + c0] = eb + e1;
+    perm[eb + n + c0 * (k + 1) + k] = eb + e2;
+    rowptr[nb + i] = eb + n + c0 * (k + 1);
+    if (c0 == 0) rowptr[nb] = eb;
+    if (row == (long)B * n - 1) rowptr[nb + n1] = eb + E;
+  }
+  // round r's winner is kept by lane r % 64; every 64 rounds (and at the end) the lanes store their edges side by side
+  T rkey = (T)0;
+  int ridx = 0;
+  for (int r = 0; r < k; ++r) {
+    T bk = inf;
+    int bj = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q)
+      if (dv[q] < bk) { bk = dv[q]; bj = lane + 64 * q; }
+    const CvrpKey<T> w = cvrp_wave_argmin<T>(bk, bj);
+#pragma unroll
+    for (int q = 0; q < CPL; ++q)
+      if (lane + 64 * q == w.idx) dv[q] = inf;            // taken
+    if (lane == (r & 63)) { rkey = w.key; ridx = w.idx < n ? w.idx : n - 1; }   // (a row of NaN / inf has no winner: the id stays a node's)
+    if ((r & 63) == 63 || r == k - 1) {
+      const int r0 = r & ~63;
+      if (lane <= r - r0) {
+        const int e = c0 * k + r0 + lane;
+        esrc[e] = i;
+        edst[e] = ridx + 1;
+        attr[e] = (float)rkey;
+        src32[eb + e] = nb + i;
+        dst32[eb + e] = nb + ridx + 1;
+        perm[eb + n + c0 * (k + 1) + r0 + lane] = eb + e;
+      }
+    }
+  }
+}
+
 // ---- Net.reshape for a batch (tsp/net.py:94-102) with the "+ eps" of its callers (tsp/train.ipynb:35, tsp_nls/test.py:28):
 // out[b] = fill everywhere, heu[b][e] + add at [src_e][dst_e].  Two launches on one stream: the fill, then one thread per edge.
 __global__ void __launch_bounds__(256)
@@ -121,6 +232,47 @@ extern "C" int daco_tsp_knn_graph_csr(void *stream, int B, int n, int k, const f
                                       int64_t *edge_src, int64_t *edge_dst, float *edge_attr, int32_t *src32, int32_t *dst32) {
   if (!src32 || !dst32) { set_error("daco_tsp_knn_graph_csr: src32 / dst32 missing"); return DACO_E_BADARG; }
   return knn_graph_launch("daco_tsp_knn_graph_csr", stream, B, n, k, coords, diag, dist, edge_src, edge_dst, edge_attr, src32, dst32);
+}
+
+template <typename T>
+static void cvrp_knn_graph_dispatch(hipStream_t s, int B, int n, int k, const T *dist, long dist_bs, int64_t *edge_index,
+                                    float *edge_attr, int32_t *src32, int32_t *dst32, int32_t *rowptr, int32_t *perm) {
+  const dim3 grid((unsigned)(((long)B * n + 3) / 4)), block(256);
+  const int cpl = (n + 63) / 64;
+#define DACO_CVRP_KNN(C) hipLaunchKernelGGL((cvrp_knn_graph_kernel<T, C>), grid, block, 0, s, B, n, k, dist, dist_bs, edge_index, \
+                                            edge_attr, src32, dst32, rowptr, perm)
+  if (cpl <= 2) DACO_CVRP_KNN(2);
+  else if (cpl <= 4) DACO_CVRP_KNN(4);
+  else if (cpl <= 8) DACO_CVRP_KNN(8);
+  else if (cpl <= 16) DACO_CVRP_KNN(16);
+  else if (cpl <= 32) DACO_CVRP_KNN(32);
+  else DACO_CVRP_KNN(64);
+#undef DACO_CVRP_KNN
+}
+
+extern "C" long daco_cvrp_knn_graph(void *stream, int B, int n1, int k, const void *dist, int dist_f64, long dist_bstride,
+                                    int64_t *edge_index, float *edge_attr, int32_t *src32, int32_t *dst32, int32_t *rowptr,
+                                    int32_t *perm) {
+  const int n = n1 - 1;                                   // customers
+  if (B <= 0 || n1 < 2 || k < 1 || k > n || (dist_f64 != 0 && dist_f64 != 1) || dist_bstride < (long)n1 * n1) {
+    set_error("daco_cvrp_knn_graph: bad argument (B=%d n1=%d k=%d dist_f64=%d dist_bstride=%ld; 1 <= k <= n1 - 1, n1 >= 2, "
+              "dist_bstride >= n1 * n1)", B, n1, k, dist_f64, dist_bstride);
+    return DACO_E_BADARG;
+  }
+  if (!dist || !edge_index || !edge_attr || !src32 || !dst32 || !rowptr || !perm) {
+    set_error("daco_cvrp_knn_graph: bad argument (null pointer)");
+    return DACO_E_BADARG;
+  }
+  if (n1 > DACO_MAX_NODES) { set_error("daco_cvrp_knn_graph: n1=%d exceeds DACO_MAX_NODES", n1); return DACO_E_TOOLARGE; }
+  const long E = (long)n * (k + 2);
+  if ((long)B * E > 0x7fffffffL || (long)B * n1 + 1 > 0x7fffffffL) {
+    set_error("daco_cvrp_knn_graph: B * E = %ld edge ids / B * n1 = %ld node ids do not fit 32 bits", (long)B * E, (long)B * n1);
+    return DACO_E_TOOLARGE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (dist_f64) cvrp_knn_graph_dispatch<double>(s, B, n, k, (const double *)dist, dist_bstride, edge_index, edge_attr, src32, dst32, rowptr, perm);
+  else cvrp_knn_graph_dispatch<float>(s, B, n, k, (const float *)dist, dist_bstride, edge_index, edge_attr, src32, dst32, rowptr, perm);
+  return launch_status("cvrp_knn_graph_kernel");
 }
 
 extern "C" int daco_heu_matrix(void *stream, int B, int n, int E, const int64_t *edge_index, const float *heu, float fill, float add,

@@ -10,6 +10,40 @@ def _demand_rows(demand, B):
     return _rows(demand, B), (_rows(demand, B, torch.float64) if demand.dtype == torch.float64 else None)
 
 
+def cvrp_knn_graph(distances, demands, k_sparse):
+    """Batched gen_pyg_data of cvrp_nls/utils.py:34-59 in one launch: distances [B,n1,n1] float64 or float32 (node 0 = the depot,
+    1e-10 on the diagonal: every customer's first neighbour is itself), demands [B,n1] -> (x [B,n1,1] f32, edge_index
+    [B,2,E] int64 with ids local to each graph, edge_attr [B,E,1] f32), E = (n1 - 1)(k + 2), in the reference's edge order --
+    what pipeline.cvrp_nls_graph_batch(path="torch") builds with topk and three cats, ties in a row going to the smaller column.
+    The same launch writes the batch as one block-diagonal int32 graph with its CSR by source; it rides on the returned
+    edge_index as `_daco_cvrp_csr` = (src32, dst32, rowptr, perm, n1, k, edge_index._version), and Net.forward_batch /
+    forward_batch_train use it instead of deriving it (a sort and a host read) while that tensor object is not written to."""
+    _require_gpu(distances, demands)
+    if distances.dim() != 3 or distances.shape[1] != distances.shape[2] or tuple(demands.shape) != tuple(distances.shape[:2]):
+        raise _lib.DacoError(f"cvrp_knn_graph: distances [B,n1,n1] and demands [B,n1] expected, got {tuple(distances.shape)} and "
+                             f"{tuple(demands.shape)}")
+    if distances.dtype not in (torch.float32, torch.float64):
+        distances = distances.float()
+    dist = distances.contiguous()
+    B, n1, _ = dist.shape
+    k = int(k_sparse)
+    E = (n1 - 1) * (k + 2)
+    dev = dist.device
+    with _on(dev):
+        # (k out of range, n1 < 2: the shapes below are never allocated -- the library refuses first)
+        ok = n1 >= 2 and 1 <= k <= n1 - 1
+        ei = torch.empty((B, 2, E if ok else 0), dtype=torch.int64, device=dev)
+        ea = torch.empty((B, E if ok else 0, 1), dtype=torch.float32, device=dev)
+        i32 = torch.empty((3 * B * E + B * n1 + 1) if ok else 1, dtype=torch.int32, device=dev)     # (one allocation for the four)
+        src32, dst32, perm, rowptr = i32[:B * E], i32[B * E:2 * B * E], i32[2 * B * E:3 * B * E], i32[3 * B * E:3 * B * E + B * n1 + 1]
+        rc = _lib.lib().daco_cvrp_knn_graph(_stream(dev), B, n1, k, dist.data_ptr(), int(dist.dtype == torch.float64), n1 * n1,
+                                            ei.data_ptr(), ea.data_ptr(), src32.data_ptr(), dst32.data_ptr(), rowptr.data_ptr(),
+                                            perm.data_ptr())
+    _lib.check(rc, "daco_cvrp_knn_graph")
+    ei._daco_cvrp_csr = (src32, dst32, rowptr, perm, n1, k, ei._version)
+    return demands.unsqueeze(2).float(), ei, ea
+
+
 def cvrp_sample(tau, eta, demand, capacity, n_ants, alpha=1.0, beta=1.0, mode="scan", noise=None, seed=0,
                 it=0, ant_gid0=0, require_prob=False, Lmax=None, batch=None, dist=None, want_table=False,
                 iter_dev=None, events=None, ant_gid_bstride=0, flags=None):

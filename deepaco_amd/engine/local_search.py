@@ -133,16 +133,21 @@ def cvrp_local_search_(dist, demand, capacity, paths, max_moves, want_stats=Fals
 class HgsTables:
     """What HGS's Params derives from a matrix (Params.cpp:77-103, LocalSearch.cpp:9): per instance the largest entry, the
     correlated vertices (nb_granular nearest, symmetric) and the shuffled node order -- daco_hgs_prepare's output, built once
-    per matrix and shared by every ant (and iteration, for the distance matrix)."""
+    per matrix and shared by every ant (and iteration, for the distance matrix).
+    symmetric: None -- the matrix is compared with its transpose on the device (one host read); True / False -- the caller's
+    word instead, without the comparison: True keeps no transposed copy, False builds it (always right, for a symmetric matrix
+    too; a training step that makes tables of a fresh heuristic every step says so and reads nothing)."""
 
-    def __init__(self, matrix, nb_granular=20):
+    def __init__(self, matrix, nb_granular=20, symmetric=None):
         _require_gpu(matrix)
         m = matrix if matrix.dim() == 3 else matrix.unsqueeze(0)
         self.matrix = m if (m.dtype == torch.float64 and m.is_contiguous()) else m.contiguous().double()
         self.B, self.n = self.matrix.shape[0], self.matrix.shape[-1]
         # the transposed copy the search reads "column" entries from (None for a symmetric matrix: one device comparison)
         mt = self.matrix.transpose(-1, -2)
-        self.matrix_t = None if bool(torch.equal(self.matrix, mt)) else mt.contiguous()
+        if symmetric is None:
+            symmetric = bool(torch.equal(self.matrix, mt))
+        self.matrix_t = None if symmetric else mt.contiguous()
         self.nb_granular = int(nb_granular)
         L = _lib.lib()
         self.table_bytes = L.daco_hgs_table_bytes(self.n, self.nb_granular)

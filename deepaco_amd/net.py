@@ -171,7 +171,16 @@ def _merge_graphs(x, edge_index, edge_attr, k_sparse=None):
         merged = GraphData(x=x.reshape(B * n, feats), edge_index=None, edge_attr=edge_attr.reshape(B * E, 1))
         merged._daco_graph = (csr[0], csr[1], _regular_rowptr(B * n, k_sparse, x.device), None)
         return merged
-    off = (torch.arange(B, device=x.device, dtype=edge_index.dtype) * n).view(B, 1, 1)
+    # engine.cvrp_knn_graph's edge_index (the depot blocks last: not sorted by source) carries the merged graph WITH its
+    # row pointer and by-source permutation, (src32, dst32, rowptr, perm, n1, k, version): taken as they are while the tensor is
+    # untouched -- what _csr_graph would derive from the merged edge list with a sortedness test (a host read) and a stable sort
+    ccsr = getattr(edge_index, "_daco_cvrp_csr", None) if k_sparse is None else None
+    if (ccsr is not None and ccsr[4] == n and E == (n - 1) * (ccsr[5] + 2) and ccsr[6] == edge_index._version
+            and ccsr[0].numel() == B * E and ccsr[2].numel() == B * n + 1 and ccsr[0].device == x.device):
+        merged = GraphData(x=x.reshape(B * n, feats), edge_index=None, edge_attr=edge_attr.reshape(B * E, 1))
+        merged._daco_graph = (ccsr[0], ccsr[1], ccsr[2], ccsr[3])
+        return merged
+    off =(torch.arange(B, device=x.device, dtype=edge_index.dtype) * n).view(B, 1, 1)
     ei = (edge_index + off).permute(1, 0, 2).reshape(2, B * E)
     merged = GraphData(x=x.reshape(B * n, feats), edge_index=ei, edge_attr=edge_attr.reshape(B * E, 1))
     if k_sparse is not None:
@@ -533,7 +542,9 @@ class Net(nn.Module):
             # the tensor like `_daco_csr`
             if getattr(edge_index, "_daco_ids_ok", None) != (n_nodes, edge_index._version):
                 csr = getattr(edge_index, "_daco_csr", None)
-                if not (csr is not None and csr[2] == n_nodes and csr[4] == edge_index._version):
+                ccsr = getattr(edge_index, "_daco_cvrp_csr", None)            # (engine.cvrp_knn_graph's: in range by construction too)
+                if not (csr is not None and csr[2] == n_nodes and csr[4] == edge_index._version) and \
+                        not (ccsr is not None and ccsr[4] == n_nodes and ccsr[6] == edge_index._version):
                     lo, hi = (int(v) for v in torch.stack(torch.aminmax(edge_index)).tolist())
                     if lo < 0 or hi >= n_nodes:
                         raise IndexError(f"Net.reshape_batch: edge_index holds node ids in [{lo}, {hi}], outside [0, {n_nodes})")

@@ -220,11 +220,30 @@ class TspNlsTrainer:
         return self._out
 
 
+GRAPH_PATHS = ("torch", "hip")
+
+
+def _cvrp_distances(locations):
+    """(locations as float64, float64 distances [B,n1,n1] with 1e-10 on the diagonal): cvrp_nls/utils.py:28-32 for a batch."""
+    loc = locations.double()
+    dist = torch.norm(loc[:, :, None] - loc[:, None], dim=3, p=2)
+    ar = torch.arange(loc.shape[1], device=loc.device)
+    dist[:, ar, ar] = 1e-10
+    return loc, dist
+
+
 @torch.no_grad()
-def cvrp_nls_graph_batch(demands, distances, k_sparse):
+def cvrp_nls_graph_batch(demands, distances, k_sparse, path="torch"):
     """cvrp_nls/utils.py:34-60 (gen_pyg_data) for B instances at once: every customer's k nearest customers (customer order,
     nearest first), then depot -> customer and customer -> depot; node feature = demand.  demands [B,n+1], distances
-    [B,n+1,n+1] -> (x [B,n+1,1] f32, edge_index [B,2,E] int64 with ids local to each graph, edge_attr [B,E,1] f32)."""
+    [B,n+1,n+1] -> (x [B,n+1,1] f32, edge_index [B,2,E] int64 with ids local to each graph, edge_attr [B,E,1] f32).
+    path: 'torch' (the default) -- topk, repeat_interleave and three cats, the comparator; 'hip' -- engine.cvrp_knn_graph,
+    one launch that writes the same arrays (ties in a row: the smaller column, where topk promises nothing) and leaves the
+    batch's merged int32 CSR on the edge_index for Net.forward_batch / forward_batch_train."""
+    if path not in GRAPH_PATHS:
+        raise ValueError(f"path must be one of {GRAPH_PATHS} (got {path!r})")
+    if path == "hip":
+        return engine.cvrp_knn_graph(distances, demands, k_sparse)
     B, n1 = demands.shape
     dev = demands.device
     near_d, near_i = torch.topk(distances[:, 1:, 1:], k=k_sparse, dim=2, largest=False)
@@ -239,20 +258,18 @@ def cvrp_nls_graph_batch(demands, distances, k_sparse):
 
 
 @torch.no_grad()
-def infer_cvrp_nls_batch(locations, demands, n_ants, t_aco, k_sparse, net=None, seed=0, ls_ants=8, **aco_kw):
+def infer_cvrp_nls_batch(locations, demands, n_ants, t_aco, k_sparse, net=None, seed=0, ls_ants=8, graph_path="torch", **aco_kw):
     """The batched counterpart of cvrp_nls/test.py:40-60 (`infer_instance`): locations [B,n+1,2] (node 0 = depot) and
     demands [B,n+1] normalised to capacity 1, float64 as cvrp_nls/utils.py:12-26 builds them -> distances -> sparse graph ->
     heuristic (the network in eval mode, + 1e-10; None: 1 / distance) -> B colonies whose `ls_ants` cheapest ants go through the
     reference's local search every iteration (engine.BatchedCVRP(local_search="hgs", inference=True)).
+    graph_path: 'torch' (the default) or 'hip' -- see cvrp_nls_graph_batch.
     Returns (best costs [len(t_aco), B], colony); colony.shortest_path holds the best route sequences."""
     B, n1, _ = locations.shape
-    loc = locations.double()
-    dist = torch.norm(loc[:, :, None] - loc[:, None], dim=3, p=2)
-    ar = torch.arange(n1, device=loc.device)
-    dist[:, ar, ar] = 1e-10                                                                         # cvrp_nls/utils.py:28-32
+    loc, dist = _cvrp_distances(locations)
     heuristic = None
     if net is not None:
-        x, ei, ea = cvrp_nls_graph_batch(demands, dist, k_sparse)
+        x, ei, ea = cvrp_nls_graph_batch(demands, dist, k_sparse, path=graph_path)
         heu = net.forward_batch(x, ei, ea)
         heuristic = net.reshape_batch(n1, ei, heu, eps=EPS)
     if aco_kw.get("use_swap_star") and aco_kw.get("positions") is None:
@@ -265,6 +282,74 @@ def infer_cvrp_nls_batch(locations, demands, n_ants, t_aco, k_sparse, net=None, 
         done = t
         out.append(colony.lowest_cost.clone())
     return torch.stack(out), colony
+
+
+CVRP_NLS_EPS = 1e-5      # cvrp_nls/train.py:11 (`EPS`, added to the reshaped heuristic in training; inference adds 1e-10)
+CVRP_NLS_K = 5           # cvrp_nls/train.py's generate_traindata never passes k_sparse: gen_pyg_data's default (utils.py:34) is what it trains on
+HGS_DISTURB = 10         # cvrp_nls/aco.py:443-448 neural_swapstar: loops on the heuristic-derived matrix
+
+
+def _cvrp_nls_loss(net, locations, demands, n_ants, k_sparse=CVRP_NLS_K, seed=0, it=0, eps=CVRP_NLS_EPS, use_swap_star=False,
+                   ant_gid0=0):
+    """The forward half of cvrp_nls/train.py:14-51 for B instances: float64 distances -> sparse graphs (engine.cvrp_knn_graph) ->
+    Net in training mode -> heuristic matrices + eps -> B colonies sampled with log-probabilities (pheromone ones, capacity 1,
+    alpha = beta = 1, float64 loads) -> raw costs -> the three stages of neural_swapstar on a clone of every ant's routes ->
+    searched costs -> per instance sum_a (cost_a - mean) * sum_t logp[t, a] / n_ants, averaged over the instances.
+    Private: the body of train_cvrp_nls_batch with what the tests need.  ant_gid0: the id of the first ant (instance b of a
+    batch draws what a single instance with ant_gid0 = b * n_ants draws).  The log-probability rows stay at the sampler's
+    2 n1 rows; the reference's loop ends with the instance's longest ant (aco.py:205-232), and the rows past it -- padding
+    draws of log(1 - eps) -- are masked on the device instead of trimmed, which would need that length on the host.
+    -> (loss, costs_raw [B,A], costs [B,A], dict(paths, routes, log_probs, lens, flags, heu_mat, edge_index))"""
+    from .autograd import CvrpBatchSampleFn
+    B, n1, _ = locations.shape
+    loc, dist = _cvrp_distances(locations)
+    dem = demands.double()
+    x, ei, ea = engine.cvrp_knn_graph(dist, dem, k_sparse)
+    heu = net.forward_batch_train(x, ei, ea)
+    heu_mat = net.reshape_batch(n1, ei, heu) + eps
+    tau = torch.ones((n1, n1), dtype=torch.float32, device=dist.device)
+    paths, log_probs, lens, flags = CvrpBatchSampleFn.apply(heu_mat, tau, dem, 1.0, n_ants, 1.0, 1.0, "scan", None, seed, it, ant_gid0)
+    with torch.no_grad():
+        dist32 = dist.float()
+        costs_raw = engine.tour_costs(dist32, paths, closed=False)
+        routes = paths.clone()                        # (the sampled routes stay as drawn: the backward pass replays them)
+        limit = max(n1, 50)                           # cvrp_nls/aco.py:123, not inference
+        td = engine.HgsTables(dist, symmetric=True)   # (norms of a - b and of b - a: the same bits)
+        th = engine.HgsTables(engine.heuristic_dist(heu_mat.detach()), symmetric=False)
+        ss = dict(positions=loc, use_swap_star=True) if use_swap_star else {}
+        engine.hgs_local_search_(routes, [(td, limit), (th, HGS_DISTURB), (td, limit)], dem, capacity=1000.001, demand_scale=1000.0, **ss)
+        costs = engine.tour_costs(dist32, routes, closed=False)
+        adv = costs - costs.mean(dim=1, keepdim=True)
+        rows = torch.arange(log_probs.shape[1], device=dist.device).view(1, -1, 1)
+        live = rows < (lens.max(dim=1).values.view(B, 1, 1) - 1)
+    loss = ((adv * (log_probs * live).sum(dim=1)).sum(dim=1) / n_ants).mean()
+    return loss, costs_raw, costs, dict(paths=paths, routes=routes, log_probs=log_probs, lens=lens, flags=flags, heu_mat=heu_mat,
+                                        edge_index=ei)
+
+
+def train_cvrp_nls_batch(net, optimizer, locations, demands, n_ants, k_sparse=CVRP_NLS_K, seed=0, it=0, eps=CVRP_NLS_EPS, max_norm=3.0,
+                         use_swap_star=False):
+    """One optimisation step of cvrp_nls/train.py:14-55 (`train_instance`) for a batch of B instances, on the device end to end:
+    sparse graphs with their merged CSR (one launch) -> Net in training mode (HIP kernels, per-graph BatchNorm statistics) ->
+    heuristic matrices + eps -> B colonies sampled with log-probabilities (one launch) -> the reference's local search on
+    every ant of every instance (one launch, limit max(n + 1, 50) as the class has it outside inference) -> REINFORCE loss
+    with the mean searched cost as baseline, averaged over the instances -> backward (one daco_sample_backward launch, the
+    GNN backward kernels) -> clip_grad_norm_(max_norm=3.0) -> optimizer.step().
+    locations [B,n+1,2] (node 0 = the depot) and demands [B,n+1] normalised to capacity 1, float64 as cvrp_nls/utils.py:12-26
+    builds them.  eps = 1e-5 is train.py:11's EPS; k_sparse = 5 is gen_pyg_data's default, which is what the reference trains on
+    (its generate_traindata never passes k_sparse; the test harness uses max(n // 5, 4)).
+    The step reads nothing on the host: the graph's CSR comes out of the graph kernel, the local search's tables are told
+    whether their matrix is symmetric, and the samplers' flag words stay on the device, unread.
+    use_swap_star=True runs the search WITH SWAP* (engine.hgs_local_search_) on the locations as positions, as
+    infer_cvrp_nls_batch does; its polar angles are a host computation (libm's atan2 per node) once per batch.
+    Returns (loss, mean raw cost, mean searched cost) as device tensors."""
+    net.train()
+    loss, c_raw, c_ls, _ = _cvrp_nls_loss(net, locations, demands, n_ants, k_sparse, seed, it, eps, use_swap_star)
+    optimizer.zero_grad()
+    loss.backward()
+    torch.nn.utils.clip_grad_norm_(parameters=net.train_parameters(), max_norm=max_norm, norm_type=2)
+    optimizer.step()
+    return loss.detach(), c_raw.mean(), c_ls.mean()
 
 
 @torch.no_grad()

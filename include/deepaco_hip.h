@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats, and daco_cvrp_knn_graph) */
 
 /* error codes */
 #define DACO_OK 0
@@ -752,6 +752,27 @@ int daco_tsp_knn_graph(void *stream, int B, int n, int k, const float *coords, f
  * would otherwise derive from edge_src / edge_dst with a handful of elementwise launches per forward. */
 int daco_tsp_knn_graph_csr(void *stream, int B, int n, int k, const float *coords, float diag, float *dist,
                            int64_t *edge_src, int64_t *edge_dst, float *edge_attr, int32_t *src32, int32_t *dst32);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_cvrp_knn_graph -- replaces gen_pyg_data of cvrp_nls/utils.py:34-59 for a batch of instances, with the merged CSR
+ * B instances of n1 = n + 1 nodes, node 0 the depot.  dist [B][n1][n1] (dist_bstride elements between instances) is the matrix
+ * the caller holds: float64 if dist_f64 = 1 (cvrp_nls keeps its instance data in double), float32 if 0; the selection compares
+ * its values in their own precision.  Per customer i = 1 .. n the k smallest entries of dist[i][1:] (ascending, ties -> the
+ * smaller column; the diagonal's 1e-10 makes every customer its own first neighbour, as torch.topk does in the reference --
+ * the self loop is kept), then depot -> i and i -> depot for every customer.  Per instance E = n (k + 2) edges:
+ *   edge_index [B][2][E] int64 graph-local ids, edge_attr [B][E] f32 (the matrix entry rounded as .float() rounds it):
+ *              edge (i-1) k + r = (i, r-th nearest), n k + (i-1) = (0, i), n k + n + (i-1) = (i, 0), both with dist[i][0]
+ *   src32 / dst32 [B E] int32   the batch as ONE block-diagonal graph (ids b n1 + id), in the same edge order
+ *   rowptr [B n1 + 1], perm [B E] int32   its CSR by source: perm is the stable argsort by source of the merged edge list (sorted
+ *              position -> edge), written in closed form -- the depot has n out-edges, customer i has k + 1:
+ *              rowptr[b n1] = b E, rowptr[b n1 + i] = b E + n + (i-1)(k+1); perm[b E + (i-1)] = b E + n k + (i-1),
+ *              perm[b E + n + (i-1)(k+1) + r] = b E + (i-1) k + r (r < k), and + k: b E + n k + n + (i-1)
+ * Limits: 1 <= k <= n, 2 <= n1 (DACO_E_BADARG), n1 <= DACO_MAX_NODES, B E and B n1 + 1 within int32 (DACO_E_TOOLARGE); every
+ * pointer is required.  Refusals come before any HIP call.  The status is the usual DACO_OK / DACO_E_* value typed `long`,
+ * for the reason given at daco_rcpsp_net_forward; the refusals are held by tests/test_cvrp_graph_refusals.py.
+ */
+long daco_cvrp_knn_graph(void *stream, int B, int n1, int k, const void *dist, int dist_f64, long dist_bstride,
+                         int64_t *edge_index, float *edge_attr, int32_t *src32, int32_t *dst32, int32_t *rowptr, int32_t *perm);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_heu_matrix -- replaces Net.reshape for a batch, with the "+ eps" its callers add
