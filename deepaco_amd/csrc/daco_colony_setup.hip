@@ -12,6 +12,8 @@
 // column ids that still fit": with this layout column order is (chunk, lane), so the rank of a column among the selected ones is
 // the popcounts of the earlier chunks' ballots plus the bits below the lane in its own chunk's ballot.
 // NaN inputs are outside the contract (some k columns come out, nothing is written out of bounds).
+// A fourth kernel, head_eta_kernel (daco_head_eta), serves the uniform-tail mode of the head-row path: also one wavefront per
+// row, but it walks the row (no selection) and tests that eta is one number outside the head.
 #include "daco_host.h"
 
 namespace daco {
@@ -145,6 +147,62 @@ sparse_head_kernel(int B, int n, int k, int slots, const float *w, long w_bstrid
   }
 }
 
+// ---- daco_head_eta: what the uniform-tail mode of the head-row path needs of eta, once per head table (daco_head_rows.h).
+// head_eta[row][m] = eta[row][id_m] for the table's live slots (m < count, id < n), +0 for the others; and the test the mode
+// rests on, over all B n rows: every entry outside the head has ONE bit pattern c, a finite number with the sign bit clear
+// (-0.0 in the tail is refused: it is not bit-equal to +0.0), and every live head entry is >= c (a NaN fails).
+// verdict[0] |= 1 for a row that fails on its own; verdict[1] = max of ~(tail pattern), verdict[2] = max of the tail pattern over
+// the rows (patterns with a clear sign bit order as unsigned): the caller accepts when verdict[0] == 0 and ~verdict[1] ==
+// verdict[2], and c is that pattern.  (No row has a tail: ~0 != 0, refused.)
+__global__ void __launch_bounds__(256)
+head_eta_kernel(int B, int n, int slots, const float *eta, long eta_bs, const uint16_t *ids, float *head_eta, uint32_t *verdict) {
+  __shared__ uint32_t bm[4][32];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= (long)B * n) return;
+  const int b = (int)(row / n), r = (int)(row - (long)b * n);
+  const float *er = eta + (size_t)b * eta_bs + (size_t)r * n;
+  const uint16_t *id = ids + (size_t)row * slots;
+  const int cnt = id[slots - 1] < slots - 1 ? id[slots - 1] : slots - 1;
+  if (lane < 32) bm[wave][lane] = 0u;
+  __builtin_amdgcn_wave_barrier();
+  float eh[2];
+  bool live[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int m = lane + 64 * j;
+    const int k = m < slots ? (int)id[m] : n;
+    live[j] = m < cnt && k < n;
+    eh[j] = live[j] ? er[k] : 0.0f;
+    if (live[j]) atomicOr(&bm[wave][k >> 5], 1u << (k & 31));
+    if (m < slots) head_eta[(size_t)row * slots + m] = eh[j];
+  }
+  __builtin_amdgcn_wave_barrier();
+  uint32_t lo = 0xFFFFFFFFu, hi = 0u;                       // the tail's bit patterns: smallest and largest
+  for (int k = lane; k < n; k += 64) {
+    if ((bm[wave][k >> 5] >> (k & 31)) & 1u) continue;
+    const uint32_t u = __float_as_uint(er[k]);
+    lo = u < lo ? u : lo;
+    hi = u > hi ? u : hi;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint32_t l2 = (uint32_t)__shfl_xor((int)lo, o, 64), h2 = (uint32_t)__shfl_xor((int)hi, o, 64);
+    lo = l2 < lo ? l2 : lo;
+    hi = h2 > hi ? h2 : hi;
+  }
+  const bool tail = lo <= hi;                               // (a row that is all head: nothing to say about c)
+  const float c = __uint_as_float(lo);
+  bool bad = tail && (lo != hi || lo >= 0x7f800000u);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) bad = bad || (tail && live[j] && !(eh[j] >= c));
+  const bool any_bad = __ballot(bad) != 0;
+  if (lane == 0) {
+    if (any_bad) atomicOr(verdict + 0, 1u);
+    if (tail) { atomicMax(verdict + 1, ~lo); atomicMax(verdict + 2, hi); }
+  }
+}
+
 // the wave's total of a double, the same in every lane (a fixed butterfly: deterministic)
 __device__ inline double cs_wave_sum(double x) {
 #pragma unroll
@@ -265,4 +323,18 @@ extern "C" long daco_head_stats(void *stream, int B, int n, const float *weights
   DACO_CS_DISPATCH(n, DACO_CS_STATS);
 #undef DACO_CS_STATS
   return launch_status("head_stats_kernel");
+}
+
+extern "C" long daco_head_eta(void *stream, int B, int n, const float *eta, long eta_bstride, const uint16_t *head_id, int head_slots,
+                              float *head_eta, uint32_t *verdict) {
+  if (B <= 0 || n < 2 || !eta || !head_id || !head_eta || !verdict || eta_bstride < 0 || (head_slots != 64 && head_slots != 128)) {
+    set_error("daco_head_eta: bad argument (B=%d n=%d head_slots=%d)", B, n, head_slots);
+    return DACO_E_BADARG;
+  }
+  if (const int rc = cs_check_size("daco_head_eta", B, n)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (const int rc = launch_status(zero_async(verdict, 3 * sizeof(uint32_t), s), "daco_head_eta (clearing the verdict)")) return rc;
+  hipLaunchKernelGGL(head_eta_kernel, dim3((unsigned)(((long)B * n + 3) / 4)), dim3(256), 0, s, B, n, head_slots, eta, eta_bstride, head_id,
+                     head_eta, verdict);
+  return launch_status("head_eta_kernel");
 }

@@ -201,6 +201,36 @@ __device__ __forceinline__ void emit_rows_of_wave(int n, int b, int i0, int Rv, 
   }
 }
 
+// The same in the uniform-tail mode (HEADS = 3; daco_head_rows.h emit_head_row_ut): what a row needs from global memory -- two
+// ids and two head values of eta per lane -- does not depend on tau, so a wavefront fetches it for its first UT_PRE rows at kernel
+// entry (R <= 16: all of them; three registers per row through the chains) and the emission phase has no memory round trip
+// left: no row of eta, no gather, no dense row P.  Rows past UT_PRE (R = 32: n <= 180) are fetched when their turn comes.
+constexpr int UT_PRE = 4;
+__device__ __forceinline__ void ut_prefetch_rows(HeadUt (&pre)[UT_PRE], int n, int b, int i0, int Rv, const HeadEmit &he, int lane, int wave) {
+#pragma unroll
+  for (int j = 0; j < UT_PRE; ++j) {
+    const int rr = wave + 4 * j;
+    const size_t slot0 = ((size_t)b * n + i0 + (rr < Rv ? rr : 0)) * (16 * he.spl);     // (a row past the slab: the slab's first row, not used)
+    head_ut_fetch(pre[j], n, he.heta + slot0, he.hid + slot0, he.spl, lane);
+  }
+}
+template <int CH>
+__device__ __forceinline__ void emit_rows_of_wave_ut(const HeadUt (&pre)[UT_PRE], int n, int ch, int b, int i0, int Rv, const float *rows,
+                                                     const HeadEmit &he, uint32_t *bm, int lane, int wave) {
+#pragma unroll
+  for (int j = 0; j < UT_PRE; ++j) {
+    const int rr = wave + 4 * j;
+    if (rr < Rv)
+      emit_head_row_ut<CH>(n, ch, rows + rr * n, he.tail_c, pre[j], bm, he.hrow + ((size_t)b * n + i0 + rr) * sp_head_row_bytes(he.spl), he.spl, he.dead, lane);
+  }
+  for (int rr = wave + 4 * UT_PRE; rr < Rv; rr += 4) {
+    const size_t row = (size_t)b * n + i0 + rr;
+    HeadUt h;
+    head_ut_fetch(h, n, he.heta + row * (16 * he.spl), he.hid + row * (16 * he.spl), he.spl, lane);
+    emit_head_row_ut<CH>(n, ch, rows + rr * n, he.tail_c, h, bm, he.hrow + row * sp_head_row_bytes(he.spl), he.spl, he.dead, lane);
+  }
+}
+
 // SYM: symmetric deposit, two lanes per row (prev / next side).  !SYM: directed deposit, one lane
 // per row adds at next_a(i) (0xFFFF = ant a does not leave node i); the hub row is skipped (it
 // belongs to deposit_hub_kernel).  LDS: rows[R][n] | stage[2][R][DEP_CHUNK] | wts[2][DEP_CHUNK].
@@ -208,6 +238,7 @@ __device__ __forceinline__ void emit_rows_of_wave(int n, int b, int i0, int Rv, 
 // one wavefront per row then forms the NEXT iteration's head row of sampler "scan_sparse" (HEADS = 1) or of the race on head rows
 // (HEADS = 2) from them and the row of eta (daco_head_rows.h emit_head_row: the very code of sparse_prepass_kernel), so that
 // iteration neither launches the pre-pass nor reads tau again.
+// HEADS = 3: the scan draw's head rows in the uniform-tail mode (above): tau is all the emission reads, and it reads it from LDS.
 // GT (symmetric only): the table in the grouped layout [B][ceil(A/8)][n][8] (daco_tsp_sample_heads(nbr_grouped = 1)): the
 // entries of a workgroup's R rows and eight ants are one run of R x 32 bytes.
 template <bool SYM, int HEADS, bool GT = false>
@@ -229,6 +260,8 @@ deposit_rows_kernel(int n, int A, int R, int hub, float *tau, const uint32_t *nb
   const uint32_t *tab = GT ? nbr + (size_t)b * ((A + 7) >> 3) * n * 8 + (size_t)i0 * 8     // group g, row r, ant a8 at ((g n) + r) 8 + a8
                            : nbr + ((size_t)b * n + i0) * A;        // rows i0.. of this instance's [n][A] table
   const float *cs = costs + (size_t)b * A, *wt = weights ? weights + (size_t)b * A : nullptr;
+  HeadUt ut_pre[HEADS == 3 ? UT_PRE : 1];
+  if constexpr (SYM && HEADS == 3) ut_prefetch_rows(ut_pre, n, b, i0, Rv, he, threadIdx.x & 63, threadIdx.x >> 6);
   // chunk loader: consecutive threads on consecutive ants of one row (256-byte segments).  Wave 0 runs
   // the chains, so after the first chunk only waves 1..3 fetch: a chain never waits for a prefetch.
   // (Round 6, last session: a loader thread's entries of a chunk are all in flight before the first is waited for.  The loop used
@@ -364,6 +397,10 @@ deposit_rows_kernel(int n, int A, int R, int hub, float *tau, const uint32_t *nb
     // (16-byte row vectors: the LDS rows are aligned whenever n % 4 == 0; eta's rows when its base and stride are -- he.ch < 0 says no)
     const bool vec4 = he.ch > 0;
     const int ch = vec4 ? he.ch : -he.ch;
+    if constexpr (HEADS == 3) {                             // (the entry point sends only aligned rows here: n % 4 == 0)
+      if (ch <= 2) emit_rows_of_wave_ut<2>(ut_pre, n, ch, b, i0, Rv, rows, he, head_bm[wave], lane, wave);
+      else emit_rows_of_wave_ut<4>(ut_pre, n, ch, b, i0, Rv, rows, he, head_bm[wave], lane, wave);
+    } else
     if (ch <= 2) { if (vec4) emit_rows_of_wave<HEADS == 2, 2, true>(n, b, i0, Rv, rows, he, head_bm[wave], lane, wave);
                    else emit_rows_of_wave<HEADS == 2, 2, false>(n, b, i0, Rv, rows, he, head_bm[wave], lane, wave); }
     else { if (vec4) emit_rows_of_wave<HEADS == 2, 4, true>(n, b, i0, Rv, rows, he, head_bm[wave], lane, wave);
@@ -601,7 +638,8 @@ static int pheromone_update_impl(void *stream, int B, int n, int len, int A, flo
                                                     nbr, costs, weights, decay, elitist ? best : nullptr, clamp_min, clamp_max, floor_val, he)
 #define DACO_DEPOSIT_SYM(H) do { if (grouped) DACO_DEPOSIT_SYM_G(H, true); else DACO_DEPOSIT_SYM_G(H, false); } while (0)
   const bool grouped = nbr_in != nullptr && he.nbr_grouped != 0;        // (a table rebuilt here from `paths` is [n][A])
-  if (!he.eta) DACO_DEPOSIT_SYM(0);
+  if (he.heta) DACO_DEPOSIT_SYM(3);
+  else if (!he.eta) DACO_DEPOSIT_SYM(0);
   else if (!he.race) DACO_DEPOSIT_SYM(1);
   else DACO_DEPOSIT_SYM(2);
 #undef DACO_DEPOSIT_SYM
@@ -637,6 +675,27 @@ extern "C" int daco_pheromone_update_heads(void *stream, int B, int n, int A, fl
   he.dead = ws.ld;
   const bool vec4 = rows_vec4(n, tau, (long)n * n, eta, eta_bstride);
   he.ch = vec4 ? ws.ld / 256 : -(ws.ld / 256);
+  return pheromone_update_impl(stream, B, n, n, A, tau, paths, costs, decay, elitist, 1, clamp_min, clamp_max, floor_val, nbr_in, weights, 0,
+                               workspace, workspace_bytes, he);
+}
+
+// the same call in the uniform-tail mode (daco_head_rows.h): head_eta / tail_c from daco_head_eta, whose verdict the caller read
+extern "C" long daco_pheromone_update_heads_ut(void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,
+                                              float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,
+                                              const uint32_t *nbr_in, const float *weights, void *workspace, size_t workspace_bytes,
+                                              const uint16_t *head_id, int head_slots, int nbr_grouped, void *sparse_workspace,
+                                              size_t sparse_workspace_bytes, const float *head_eta, float tail_c) {
+  if (!head_eta || !head_id || !sparse_workspace || !(tail_c >= 0.0f)) { set_error("daco_pheromone_update_heads_ut: bad argument"); return DACO_E_BADARG; }
+  if (head_slots != 64 && head_slots != 128) { set_error("daco_pheromone_update_heads_ut: head_slots = %d (64 or 128)", head_slots); return DACO_E_BADARG; }
+  if (n <= 128 || n > 1024) { set_error("daco_pheromone_update_heads_ut: n=%d outside 129..1024 (the sizes daco_tsp_sample_heads serves)", n); return DACO_E_TOOLARGE; }
+  if ((n & 3) != 0 || ((uintptr_t)tau & 15) != 0) { set_error("daco_pheromone_update_heads_ut: the uniform-tail mode needs n %% 4 == 0 and 16-byte-aligned rows of tau (n=%d)", n); return DACO_E_BADARG; }
+  const size_t need = daco_tsp_sparse_workspace_bytes(B, n, A);
+  if (sparse_workspace_bytes < need) { set_error("daco_pheromone_update_heads_ut: sparse workspace %zu < %zu bytes", sparse_workspace_bytes, need); return DACO_E_WORKSPACE; }
+  const HeadWs ws = HeadWs::carve(sparse_workspace, B, n, A);
+  HeadEmit he;
+  he.hid = head_id; he.hrow = ws.hrow; he.heta = head_eta; he.tail_c = tail_c;      // (eta and P stay null: neither is touched)
+  he.spl = head_slots / 16; he.nbr_grouped = nbr_grouped ? 1 : 0;
+  he.dead = ws.ld; he.ch = ws.ld / 256;
   return pheromone_update_impl(stream, B, n, n, A, tau, paths, costs, decay, elitist, 1, clamp_min, clamp_max, floor_val, nbr_in, weights, 0,
                                workspace, workspace_bytes, he);
 }

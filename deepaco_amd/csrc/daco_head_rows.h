@@ -153,6 +153,74 @@ __device__ __forceinline__ void emit_head_row(int n, int ch, const float *tr, co
   emit_head_row_pre<RACE, CH, VEC4>(n, ch, tr, h, bm, hl, pr, spl, dead, lane);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// UNIFORM TAIL (scan draw, unit exponents, n % 4 == 0, aligned rows of tau): eta is one number c outside the head of every row
+// (daco_head_eta checked that, bit for bit, and that no live head entry is below c), so a head row needs neither the row of eta
+// nor a gather from it: the head's own eta values come from the table head_eta [B][n][16 spl] the set-up wrote once, the tail
+// total is the 64-lane scan of tau * c.  Same multiplication, same order of the additions: the head rows are the bytes
+// emit_head_row_pre writes.  No dense row P is stored: the rare ways of the scan walk the row of tau itself (SpRowUT,
+// daco_scan_sparse.hip).
+// What a row needs from global memory: its two ids per lane and the head's eta values at them.  Independent of tau, so the
+// update fetches them before its chains.
+struct HeadUt {
+  float eh[2];
+  uint32_t idp;      // the ids of slots lane and lane + 64, two u16 (n: not a slot)
+  int cnt;
+};
+__device__ __forceinline__ void head_ut_fetch(HeadUt &h, int n, const float *heta, const uint16_t *ids, int spl, int lane) {
+  const int kh = 16 * spl;
+  h.cnt = ids[kh - 1] < kh - 1 ? ids[kh - 1] : kh - 1;
+  uint32_t idp = 0;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int m = lane + 64 * j;
+    idp |= (uint32_t)(m < kh ? (int)ids[m] : n) << (16 * j);
+    h.eh[j] = m < kh ? heta[m] : 0.0f;
+  }
+  h.idp = idp;
+}
+template <int CH>
+__device__ __forceinline__ void emit_head_row_ut(int n, int ch, const float *tr, float c, const HeadUt &h, uint32_t *bm, char *hl,
+                                                 int spl, int dead, int lane) {
+  const int kh = 16 * spl, ls = sp_lane_bytes(spl);
+  const int cnt = h.cnt;
+  const float4 c4 = make_float4(c, c, c, c);
+  if (lane < 32) bm[lane] = 0u;
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < 2; ++j) { const int m = lane + 64 * j, id = (int)((h.idp >> (16 * j)) & 0xFFFFu); if (m < cnt && id < n) atomicOr(&bm[id >> 5], 1u << (id & 31)); }
+  __builtin_amdgcn_wave_barrier();
+  float part = 0.0f;
+#pragma unroll
+  for (int q = 0; q < CH; ++q) {
+    if (q < ch) {
+      const int k0 = (q * 64 + lane) * 4;
+      float4 t;
+      sp_load4<true>(tr, n, k0, t);
+      const float4 v = sp_mul4_masked(t, c4, n, k0);
+      const uint32_t w = bm[(k0 >> 5) & 31] >> (k0 & 31);
+      part = part + ((w & 1u) ? 0.0f : v.x);
+      part = part + ((w & 2u) ? 0.0f : v.y);
+      part = part + ((w & 4u) ? 0.0f : v.z);
+      part = part + ((w & 8u) ? 0.0f : v.w);
+    }
+  }
+  const float T = readlane_f(wave_scan_add(part), 63);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int m = lane + 64 * j;
+    if (m < kh) {
+      const int id = (int)((h.idp >> (16 * j)) & 0xFFFFu);
+      const bool live = m < cnt && id < n;
+      const float pid = live ? tr[id] * h.eh[j] : 0.0f;
+      char *hs = hl + (m / spl) * ls;
+      *reinterpret_cast<float *>(hs + (m % spl) * 4) = m == kh - 1 ? T : pid;
+      *reinterpret_cast<uint16_t *>(hs + spl * 4 + (m % spl) * 2) = (uint16_t)(live && m != kh - 1 ? id : dead);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
 // what the update needs to emit head rows (null eta: no emission)
 struct HeadEmit {
   const float *eta = nullptr;      // [B][n][n] or one shared [n][n] (eta_bs = 0)
@@ -162,6 +230,8 @@ struct HeadEmit {
   float *P = nullptr;              // [B][n][256 ch]: the dense rows the scan's rare ways walk
   int spl = 4, ch = 2, dead = 512, race = 0;
   int nbr_grouped = 0;             // the update's table arrives as [B][ceil(A/8)][n][8] (written by daco_tsp_sample_heads(nbr_grouped = 1))
+  const float *heta = nullptr;     // uniform tail: [B][n][16 spl] eta at the head's live ids (daco_head_eta); then eta and P are not touched
+  float tail_c = 0.0f;             // uniform tail: eta outside the head
 };
 
 }  // namespace daco

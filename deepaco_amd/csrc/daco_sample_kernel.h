@@ -54,11 +54,13 @@ struct SampleParams {
   const uint16_t *hid = nullptr;     // the caller's head table [B][n][slots] (the pre-pass reads it; the scan reads the head rows)
   unsigned long long *stats = nullptr;   // [3] dense steps, tail walks, rejections (tests) or null
   uint16_t *tours16 = nullptr;       // scan_sparse at n > 512: [B][A][ld] the tours as they are built (32 bytes per ant every 16 steps)
-  // the rows the rare ways of scan_sparse walk: tau^alpha * eta^beta formed from the caller's tensors (no dense copy since round 6)
+  // scan_sparse: the caller's matrices (unit exponents: powers are applied before the launch).  Read only in the uniform-tail mode,
+  // whose rare ways walk the row of tau times tail_c (and the rows of tau and eta after a rejected tail walk); every other launch
+  // walks the dense rows P above and ignores these.
   const float *tau = nullptr, *eta = nullptr;
   long tau_bs = 0, eta_bs = 0;
-  float alpha = 1.0f, beta = 1.0f;
-  int row_vec = 0;                   // rows can be read as aligned 16-byte vectors (n % 4 == 0, aligned bases and strides)
+  float tail_c = 0.0f;               // uniform-tail mode: eta outside the head (daco_head_eta)
+  float alpha = 1.0f, beta = 1.0f;   // PROB_RCPSP: the exponents of its pheromone and heuristic (the head-row kernels take unit exponents)
   int nbr_grouped = 0;               // scan_sparse: nbr as [B][ceil(A/8)][n][8] (eight ants' entries of a node together) instead of [B][n][A]
   int lh_kl = 0, lh_kmax = 0;        // scan_sparse, LDS-heads variant: lane records per row kept in LDS, the caller's bound of live slots per row
   RcpspDev rc;                       // PROB_RCPSP (daco_rcpsp.hip): the project, the evaluation rule, the decoder's outputs

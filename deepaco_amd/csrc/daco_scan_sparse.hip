@@ -44,10 +44,11 @@ __device__ inline uint64_t sp_row_first(uint64_t m) { return m & ~((m | 0x800080
 // ---------------------------------------------------------------------------------------------------------------
 // the pre-pass of one iteration, one wavefront per row: the HEAD ROW the scan reads each step (daco_head_rows.h emit_head_row:
 // 16 lanes x ls bytes, lane s = {values of slots 4s..4s+3 (f32), their node ids (u16)}; the last slot = the tail total), from one
-// read of the rows of tau and eta.  Round 6: the dense fused row P = tau^alpha * eta^beta is no longer written (65 MB per
-// iteration at the headline shape for the 1.4 % of the steps that walked it): the rare ways form tau * eta from the two rows
-// themselves (sp_prob4: the same product), and an iteration whose pheromone update emitted the head rows
+// read of the rows of tau and eta, and next to it the dense row P = tau * eta (unit exponents: others are applied to the two
+// matrices first) that the rare ways of the scan walk.  An iteration whose pheromone update emitted the head rows
 // (daco_pheromone_update_heads) does not run this kernel at all.
+// sparse_prepass_ut_kernel: the same head rows in the uniform-tail mode (daco_head_rows.h emit_head_row_ut), from the row of
+// tau and the head's eta values alone: no row of eta is read and no P is written.
 template <bool RACE, bool VEC4, int CH>
 __global__ void __launch_bounds__(256)
 sparse_prepass_kernel(int B, int n, int ch, const float *tau, long tau_bs, const float *eta, long eta_bs,
@@ -61,25 +62,87 @@ sparse_prepass_kernel(int B, int n, int ch, const float *tau, long tau_bs, const
   emit_head_row<RACE, CH, VEC4>(n, ch, tr, er, hid + row * (16 * spl), bm[wave], hrow + row * sp_head_row_bytes(spl), P + row * (256 * ch), spl, dead, lane);
 }
 
+template <int CH>
+__global__ void __launch_bounds__(256)
+sparse_prepass_ut_kernel(int B, int n, int ch, const float *tau, long tau_bs, const float *heta, float tail_c, const uint16_t *hid,
+                         char *hrow, int spl, int dead) {
+  __shared__ uint32_t bm[4][32];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= (long)B * n) return;
+  const int b = (int)(row / n), r = (int)(row - (long)b * n);
+  HeadUt h;
+  head_ut_fetch(h, n, heta + row * (16 * spl), hid + row * (16 * spl), spl, lane);
+  emit_head_row_ut<CH>(n, ch, tau + b * tau_bs + (long)r * n, tail_c, h, bm[wave], hrow + row * sp_head_row_bytes(spl), spl, dead, lane);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // one wave-cooperative draw over a whole row for ONE ant (the rare ways).  TAIL = false: the dense masked draw of the
 // 64-lane scan specification with uniform `ur` (oracle draw_scan, lanes = 64).  TAIL = true: the walk over the row's
 // non-head entries, visited or not, with the threshold `ur` given (oracle draw_scan_sparse, "past the head").
 // Returns the node, -1 if no candidate can be drawn (dense: infeasible; tail: a tail without mass).
-// (the row itself: the padded dense row of P the pre-pass / the update wrote next to the head row)
+// The row itself, three sources:
+//   SpRowSrc  the padded dense row of P = tau * eta the pre-pass / the update wrote next to the head row (zeros past n);
+//   SpRowUT   uniform-tail mode: the row of tau times c, the one value eta has outside the head (daco_head_eta) -- no P exists.
+//             Exact for the tail walk (the head's columns are masked by the bitmap) and for the dense draw of a step whose head has
+//             no live mass (every head candidate is visited or has tau * eta_head == 0, and 0 <= c <= eta_head with monotone
+//             rounding gives tau * c == 0 as well; tests/test_uniform_tail_lemma.py);
+//   SpRowTE   uniform-tail mode, the draw after a rejected tail walk: open head candidates count there, so the true product of the
+//             rows of tau and eta (the product P holds).
+// SpRowUT / SpRowTE (n % 4 == 0, aligned rows) read through a buffer descriptor of the row's n floats: a vector past the row
+// comes back as zeros from the bounds check, and 0 * c = 0 * 0 = +0 is what P holds there.  (The clamped load and masked
+// product of daco_head_rows.h -- sp_load4 / sp_mul4_masked, the same values -- take a 64-bit address and four compares per
+// vector: in the split-tour kernel, which has 64 registers, the walk then spilled 52 bytes per lane into scratch memory.  The
+// descriptor is four scalar registers built from the row index, which is uniform here.)
+typedef uint32_t sp_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t sp_u32x2 __attribute__((ext_vector_type(2)));
 struct SpRowSrc { const float *p; };
-__device__ __forceinline__ float4 sp_row4(const SpRowSrc &r, int k0) { return *reinterpret_cast<const float4 *>(r.p + k0); }
+struct SpRowUT { __amdgpu_buffer_rsrc_t t; float c; };
+struct SpRowTE { __amdgpu_buffer_rsrc_t t, e; };
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t sp_row_rsrc(const float *row, int n) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)row, 0, (int)((uint32_t)n * 4u), 0x00020000);
+}
+// candidates (c * 64 + lane) * 4 .. + 3 of the row.  lo = sp_lane_off(row, lane): the lane's place in a chunk -- for the
+// descriptor reads its byte offset lane * 16, made opaque so that `lo + c * 1024` stays an addition and c * 1024 becomes the
+// instruction's immediate offset, which the bounds check includes (as a disjoint OR it took a register per chunk).
+__device__ __forceinline__ int sp_lane_off(const SpRowSrc &, int lane) { return lane; }
+template <class Src> __device__ __forceinline__ int sp_lane_off(const Src &, int lane) {
+  int lo = lane * 16;
+  asm volatile("" : "+v"(lo));
+  return lo;
+}
+__device__ __forceinline__ float4 sp_row4(const SpRowSrc &r, int c, int lo) { return *reinterpret_cast<const float4 *>(r.p + (c * 64 + lo) * 4); }
+__device__ __forceinline__ float4 sp_row4(const SpRowUT &r, int c, int lo) {
+  const sp_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(r.t, lo + c * 1024, 0, 0);
+  return make_float4(__uint_as_float(t.x) * r.c, __uint_as_float(t.y) * r.c, __uint_as_float(t.z) * r.c, __uint_as_float(t.w) * r.c);
+}
+__device__ __forceinline__ float4 sp_row4(const SpRowTE &r, int c, int lo) {
+  const sp_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(r.t, lo + c * 1024, 0, 0), e = __builtin_amdgcn_raw_buffer_load_b128(r.e, lo + c * 1024, 0, 0);
+  return make_float4(__uint_as_float(t.x) * __uint_as_float(e.x), __uint_as_float(t.y) * __uint_as_float(e.y),
+                     __uint_as_float(t.z) * __uint_as_float(e.z), __uint_as_float(t.w) * __uint_as_float(e.w));
+}
 
-template <int CHD, bool TAIL>
-__device__ __forceinline__ int sparse_row_walk(const SpRowSrc &rowp, const uint8_t *flg, const uint32_t *bm, int lane, float ur) {
+typedef const __attribute__((address_space(4))) SampleParams *sp_args_t;      // (the kernel's arguments as the segment holds them)
+template <bool UT>
+__device__ __forceinline__ auto sp_row_of(const float *base, sp_args_t pa, int b, int row, int ld, int n) {
+  if constexpr (UT) asm volatile("" : "+s"(pa));          // (read here, each time: the compiler cannot move the loads in front of the tour)
+  if constexpr (UT) return SpRowUT{sp_row_rsrc(pa->tau + (size_t)b * pa->tau_bs + (size_t)row * n, n), pa->tail_c};
+  else return SpRowSrc{base + (size_t)row * ld};
+}
+
+template <int CHD, bool TAIL, class Src>
+__device__ __forceinline__ int sparse_row_walk(const Src &rowp, const uint8_t *flg, const uint32_t *bm, int lane, float ur) {
   constexpr int NJ = CHD * 4;
   float run[16];
   float acc = 0.0f;
   uint32_t pos = 0;                                      // slots with a positive term (a term can be absorbed by the running sum)
+  const int lo = sp_lane_off(rowp, lane);
 #pragma unroll
   for (int c = 0; c < CHD; ++c) {
     const int k0 = (c * 64 + lane) * 4;
-    const float4 rv = sp_row4(rowp, k0);
+    // (two rows: one chunk's vectors in flight at a time -- this draw is the rarest way and must not set the kernel's registers)
+    if constexpr (std::is_same<Src, SpRowTE>::value) __builtin_amdgcn_sched_barrier(0);
+    const float4 rv = sp_row4(rowp, c, lo);
     float f[4];
     if constexpr (TAIL) {
       const uint32_t w = bm[(k0 >> 5) & 31] >> (k0 & 31);
@@ -145,8 +208,6 @@ __device__ __forceinline__ int sparse_row_walk(const SpRowSrc &rowp, const uint8
 // and broadcasts the product, the chosen slot is a three-deep select on the running sums, the WINNING lane of each ant stores the
 // flag byte and the tour entry, and the row reads the tour entry back as the next row index (one LDS read instead of a
 // four-stage DPP OR network).  All of that leaves the arithmetic (summation order, thresholds, rounding cases) as the oracle has it.
-typedef uint32_t sp_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t sp_u32x2 __attribute__((ext_vector_type(2)));
 __device__ inline float sp_at_least_denorm(float x) {     // max(x, denorm_min) for x that is not a signalling NaN
   float y;
   asm("v_max_f32 %0, 1, %1" : "=v"(y) : "v"(x));
@@ -183,9 +244,12 @@ static_assert(SP_ST_DEAD >= 16 * SP_EW * 2 + 4 * 512 * 2, "ST: early parts and t
 // (ST's epilogue reads `p` again from the start of the kernel-argument segment: `p` must stay the kernel's FIRST explicit
 // argument, and every launch passes exactly this struct -- sample_sparse_impl is the only launch site.)
 static_assert(std::is_trivially_copyable<SampleParams>::value, "SampleParams is read back from the kernel-argument segment as plain bytes");
-template <int CHD, bool RACE, int SPL, bool LH = false, bool ST = false>
+// UT (scan draw only): the uniform-tail mode.  No dense rows P exist; the rare ways walk the row of tau (SpRowUT / SpRowTE above).
+// Only the code behind the rare-way branch differs: the step itself is the same instructions.
+template <int CHD, bool RACE, int SPL, bool LH = false, bool ST = false, bool UT = false>
 __global__ void __launch_bounds__(256, LH ? 1 : (ST ? 8 : (CHD == 2 ? (RACE ? 4 : 6) : 5)))
 scan_sparse_kernel(const SampleParams p) {
+  static_assert(!UT || !RACE, "the uniform-tail mode: scan draw");
   static_assert(!LH || (CHD == 2 && !RACE && SPL == 4), "the LDS-heads variant: n <= 512, scan draw, 64-slot heads");
   static_assert(!ST || (CHD == 2 && !RACE && SPL == 4 && !LH), "the split-tour variant: n <= 512, scan draw, 64-slot heads, not LH");
   constexpr int APW = 4, APB = LH ? 4 : 16;
@@ -229,10 +293,13 @@ scan_sparse_kernel(const SampleParams p) {
   const bool active = a0 < A && (!LH || wave == 0);
   const int a = a0 + q < A ? a0 + q : A - 1;             // spare groups build ant A-1 again (not written)
   const uint32_t gid = p.ant_gid0 + (uint32_t)(b * (p.gid_bstride ? p.gid_bstride : A) + a);
-  const float *Pb = p.P + (size_t)b * n * p.ld;
+  // the rows the rare ways walk: P, or in the uniform-tail mode the rows of tau, whose base, stride and factor c are read from
+  // the kernel-argument segment when a rare way runs (not three scalars carried through the tour: the split-tour kernel's
+  // scalars spill into vector lanes, and the walk then spills vectors)
+  const float *Pb = UT ? nullptr : p.P + (size_t)b * n * p.ld;
   const char *hrb = (const char *)p.hval + (size_t)b * n * ROWB;
   const __amdgpu_buffer_rsrc_t hres = __builtin_amdgcn_make_buffer_rsrc((void *)hrb, 0, (int)((uint32_t)n * ROWB), 0x00020000);
-#define SP_ROW_OF(pv) SpRowSrc{Pb + (size_t)(pv) * p.ld}
+#define SP_ROW_OF(pv) sp_row_of<UT>(Pb, (sp_args_t)__builtin_amdgcn_kernarg_segment_ptr(), b, pv, p.ld, n)
   uint32_t sls = (uint32_t)s * LS;
   asm volatile("" : "+v"(sls));                          // (kept in a register: the loop adds it to the row offset)
   uint8_t *fl = flag_mem + (wave * APW + q) * FLP;
@@ -408,14 +475,14 @@ scan_sparse_kernel(const SampleParams p) {
             const int pv = readlane_i(prev, gl);
             const uint32_t gidg = (uint32_t)readlane_i((int)gid, gl);
             const uint8_t *flg = flag_mem + (wave * APW + g) * FLP;
-            const SpRowSrc rowp = SP_ROW_OF(pv);
+            const auto rowp = SP_ROW_OF(pv);
             n_dense += a0 + g < A ? 1ull : 0ull;
             float dk = __builtin_inff();
             int di = 0x7fffffff;
 #pragma unroll
             for (int c = 0; c < CHD; ++c) {
               const int k0 = (c * 64 + lane) * 4;
-              const float4 pvv = sp_row4(rowp, k0);
+              const float4 pvv = sp_row4(rowp, c, sp_lane_off(rowp, lane));
               const uint32_t ff = *reinterpret_cast<const uint32_t *>(flg + k0);
               const u32x4 r4 = rng_block(p.seed, iter_now, STREAM_RACE, gidg, ((uint32_t)t << 12) | (uint32_t)(c * 64 + lane));
               const float pp[4] = {pvv.x, pvv.y, pvv.z, pvv.w};
@@ -501,7 +568,7 @@ scan_sparse_kernel(const SampleParams p) {
               const float ug = readlane_f(ucur, gl), rg = readlane_f(r, gl);     // (ucur: already rotated, lane 0 holds this step's)
               const uint32_t gidg = (uint32_t)readlane_i((int)gid, gl);
               const uint8_t *flg = flag_mem + (wave * APW + g) * FLP;
-              const SpRowSrc rowp = SP_ROW_OF(pv);
+              const auto rowp = SP_ROW_OF(pv);
               int choice_g = -1;
               const unsigned long long real = a0 + g < A ? 1ull : 0ull;      // (a spare group repeats ant A-1: not counted)
               if (!(Hg > 0.0f)) {                               // no live head candidate: the dense masked draw with this uniform
@@ -542,7 +609,15 @@ scan_sparse_kernel(const SampleParams p) {
                   n_rej += real;
                   n_dense += real;
                   const u32x4 rb = rng_block(p.seed, iter_now, STREAM_SPARSE_RETRY, gidg, (uint32_t)t << 8);
-                  choice_g = sparse_row_walk<CHD, false>(rowp, flg, nullptr, lane, u01(rb.x));
+                  if constexpr (UT) {
+                    // (eta is read from the kernel-argument segment here: not a pair of registers carried through the tour)
+                    sp_args_t pr_ = (sp_args_t)__builtin_amdgcn_kernarg_segment_ptr();
+                    asm volatile("" : "+s"(pr_));
+                    const SpRowTE rowe{rowp.t, sp_row_rsrc(pr_->eta + (size_t)b * pr_->eta_bs + (size_t)pv * n, n)};
+                    choice_g = sparse_row_walk<CHD, false>(rowe, flg, nullptr, lane, u01(rb.x));
+                  } else {
+                    choice_g = sparse_row_walk<CHD, false>(rowp, flg, nullptr, lane, u01(rb.x));
+                  }
                 }
               }
               if (choice_g < 0) { infeasible = true; choice_g = 0; }
@@ -578,7 +653,6 @@ scan_sparse_kernel(const SampleParams p) {
   // ST: what follows reads the kernel's arguments again from the argument segment (the one SampleParams at its start) through
   // a pointer the compiler cannot trace back: two dozen scalars that the loop does not use then do not live through it -- they
   // were spilled into lanes of a second vector register, which the rare ways of the step had to make room for in scratch memory
-  typedef const __attribute__((address_space(4))) SampleParams *sp_args_t;
   sp_args_t pe = (sp_args_t)__builtin_amdgcn_kernarg_segment_ptr();
   if constexpr (ST) asm volatile("" : "+s"(pe));
 #define SP_E(x) (ST ? pe->x : p.x)
@@ -824,9 +898,16 @@ static bool sparse_many_workgroups(long workgroups) {
 }
 
 struct SparseVariant { const void *fn; size_t lds; };
-static SparseVariant sparse_variant(int ld, bool race, int spl, bool many) {
+static SparseVariant sparse_variant(int ld, bool race, int spl, bool many, bool ut = false) {
 #define DACO_SPARSE_LDS(C) ((C) == 2 ? 16 * ((C) * 256 + 16) + 16 * ((C) * 256 + 2) * 2 : 2 * 8 * (C) * 256 * 2)
 #define DACO_SPARSE_V(C, R, S) SparseVariant{reinterpret_cast<const void *>(&scan_sparse_kernel<C, R, S>), (size_t)DACO_SPARSE_LDS(C)}
+#define DACO_SPARSE_U(C, S) SparseVariant{reinterpret_cast<const void *>(&scan_sparse_kernel<C, false, S, false, false, true>), (size_t)DACO_SPARSE_LDS(C)}
+  if (ut) {                                              // the uniform-tail mode: the same variants of the scan draw, same LDS
+    if (ld <= 512 && spl == 4 && many) return SparseVariant{reinterpret_cast<const void *>(&scan_sparse_kernel<2, false, 4, false, true, true>), (size_t)SP_ST_LDS};
+    if (ld <= 512) return spl == 4 ? DACO_SPARSE_U(2, 4) : DACO_SPARSE_U(2, 8);
+    return spl == 4 ? DACO_SPARSE_U(4, 4) : DACO_SPARSE_U(4, 8);
+  }
+#undef DACO_SPARSE_U
   if (ld <= 512 && !race && spl == 4 && many) return SparseVariant{reinterpret_cast<const void *>(&scan_sparse_kernel<2, false, 4, false, true>), (size_t)SP_ST_LDS};
   if (ld <= 512) return race ? (spl == 4 ? DACO_SPARSE_V(2, true, 4) : DACO_SPARSE_V(2, true, 8)) : (spl == 4 ? DACO_SPARSE_V(2, false, 4) : DACO_SPARSE_V(2, false, 8));
   return race ? (spl == 4 ? DACO_SPARSE_V(4, true, 4) : DACO_SPARSE_V(4, true, 8)) : (spl == 4 ? DACO_SPARSE_V(4, false, 4) : DACO_SPARSE_V(4, false, 8));
@@ -849,7 +930,7 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
                                       int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
                                       uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
                                       long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
-                                      size_t workspace_bytes, void *ev_begin, void *ev_end) {
+                                      size_t workspace_bytes, void *ev_begin, void *ev_end, const float *head_eta = nullptr, float tail_c = 0.0f) {
   if (B <= 0 || A <= 0 || !tau || !eta || !head_id || !workspace || (!paths && !nbr)) {
     set_error("%s: bad argument (B=%d n=%d A=%d)", what, B, n, A);
     return DACO_E_BADARG;
@@ -884,7 +965,16 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
     alpha = beta = 1.0f;
   }
   const bool vec4 = rows_vec4(n, tau, tau_bstride, eta, eta_bstride);
-  if (!heads_ready) {
+  const bool ut = head_eta != nullptr;                  // the uniform-tail mode (daco_tsp_sample_heads_ut)
+  if (ut && (race || !vec4 || alpha != 1.0f || beta != 1.0f || !(tail_c >= 0.0f))) {
+    set_error("%s: the uniform-tail mode serves the scan draw with alpha = beta = 1, n %% 4 == 0, 16-byte-aligned rows of tau and eta and tail_c >= 0 (n=%d)", what, n);
+    return DACO_E_BADARG;
+  }
+  if (ut && !heads_ready) {
+    const dim3 pg((unsigned)(((long)B * n + 3) / 4));
+    if (ld <= 512) hipLaunchKernelGGL((sparse_prepass_ut_kernel<2>), pg, dim3(256), 0, s, B, n, ld / 256, tau, tau_bstride, head_eta, tail_c, head_id, ws.hrow, spl, ld);
+    else hipLaunchKernelGGL((sparse_prepass_ut_kernel<4>), pg, dim3(256), 0, s, B, n, ld / 256, tau, tau_bstride, head_eta, tail_c, head_id, ws.hrow, spl, ld);
+  } else if (!heads_ready) {
     const dim3 pg((unsigned)(((long)B * n + 3) / 4));
 #define DACO_PREPASS_C(R, V, C) hipLaunchKernelGGL((sparse_prepass_kernel<R, V, C>), pg, dim3(256), 0, s, B, n, ld / 256, tau, tau_bstride, eta, eta_bstride, \
                                                    head_id, ws.P, ws.hrow, spl, ld)
@@ -897,7 +987,7 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   if (const int rc = launch_status("sparse_prepass_kernel")) return rc;
   SampleParams sp = sample_params(B, n, A, ld, ld / 256, ws.P, nullptr, nullptr, seed, iter, ant_gid0, paths, nullptr, nullptr, flags);
   sp.start = start; sp.fixed_start = fixed_start;
-  sp.tau = tau; sp.tau_bs = tau_bstride; sp.eta = eta; sp.eta_bs = eta_bstride; sp.alpha = alpha; sp.beta = beta; sp.row_vec = vec4 ? 1 : 0;
+  sp.tau = tau; sp.tau_bs = tau_bstride; sp.eta = eta; sp.eta_bs = eta_bstride; sp.tail_c = tail_c;
   sp.iter_dev = iter_offset; sp.gid_bstride = ant_gid_bstride;
   sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr; sp.nbr_grouped = nbr_grouped ? 1 : 0;
   sp.hval = (const float *)ws.hrow; sp.hid = head_id; sp.stats = stats; sp.tours16 = ws.tours16;
@@ -917,11 +1007,13 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   if (lh) {
     // (more than 64 KB of dynamic LDS has to be asked for; per call: the attribute belongs to the current device's copy of the
     // kernel and a process may drive several devices)
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_sparse_kernel<2, false, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    const void *lh_fn = ut ? reinterpret_cast<const void *>(&scan_sparse_kernel<2, false, 4, true, false, true>) : reinterpret_cast<const void *>(&scan_sparse_kernel<2, false, 4, true>);
+    if (hipFuncSetAttribute(lh_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024 - 128) != hipSuccess) { set_error("%s: hipFuncSetAttribute(dynamic LDS) failed", what); return DACO_E_HIP; }
-    hipLaunchKernelGGL((scan_sparse_kernel<2, false, 4, true>), grid, dim3(256), lh_lds, s, sp);
+    if (ut) hipLaunchKernelGGL((scan_sparse_kernel<2, false, 4, true, false, true>), grid, dim3(256), lh_lds, s, sp);
+    else hipLaunchKernelGGL((scan_sparse_kernel<2, false, 4, true>), grid, dim3(256), lh_lds, s, sp);
   } else {
-    const SparseVariant v = sparse_variant(ld, race, spl, sparse_many_workgroups((long)B * bpi));
+    const SparseVariant v = sparse_variant(ld, race, spl, sparse_many_workgroups((long)B * bpi), ut);
     void *args[] = {&sp};                               // (the one argument: the split-tour variant's epilogue reads it back from offset 0 of the segment)
     if (hipLaunchKernel(v.fn, grid, dim3(256), args, v.lds, s) != hipSuccess) { set_error("%s: scan_sparse_kernel launch failed", what); return DACO_E_HIP; }
   }
@@ -955,4 +1047,15 @@ extern "C" int daco_tsp_sample_heads(void *stream, int race, int heads_ready, in
                                      long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
                                      size_t workspace_bytes, void *ev_begin, void *ev_end) {
   return sample_sparse_impl(race != 0, heads_ready != 0, head_live_max, nbr_grouped, "daco_tsp_sample_heads", DACO_SPARSE_ARGS);
+}
+// daco_tsp_sample_heads for the scan draw in the uniform-tail mode: head_eta / tail_c from daco_head_eta, whose verdict the caller read
+extern "C" long daco_tsp_sample_heads_ut(void *stream, int heads_ready, int head_live_max, int nbr_grouped, int B, int n, int A, const float *tau, long tau_bstride, const float *eta,
+                                        long eta_bstride, const uint16_t *head_id, int head_slots, const int64_t *start,
+                                        int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
+                                        uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
+                                        long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
+                                        size_t workspace_bytes, void *ev_begin, void *ev_end, const float *head_eta, float tail_c) {
+  if (!head_eta) { set_error("daco_tsp_sample_heads_ut: bad argument (head_eta)"); return DACO_E_BADARG; }
+  const float alpha = 1.0f, beta = 1.0f;
+  return sample_sparse_impl(false, heads_ready != 0, head_live_max, nbr_grouped, "daco_tsp_sample_heads_ut", DACO_SPARSE_ARGS, head_eta, tail_c);
 }

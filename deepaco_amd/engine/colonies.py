@@ -4,7 +4,7 @@ import torch
 from .common import _f32c, _raise_flags, _require_gpu, _rows
 from .cvrp_ops import cvrp_sample
 from .local_search import HgsTables, TspLocalSearch, heuristic_dist, hgs_local_search_, hgs_polar_angles
-from .tsp_ops import head_table, resolve_sampler, sparse_tours16, sparse_workspace, sparsify_heuristic, tsp_sample, tsp_sample_sparse
+from .tsp_ops import head_eta_table, head_table, resolve_sampler, sparse_tours16, sparse_workspace, sparsify_heuristic, tsp_sample, tsp_sample_sparse
 from .update import pheromone_update_, tour_costs, track_best_
 
 
@@ -109,6 +109,12 @@ class BatchedTSP:
         self._heads_for = None
         self._flags = torch.zeros((self.B,), dtype=torch.int32, device=dev)      # sticky: bit 0 a draw without a candidate, bit 2 see daco_tsp_sample_heads
         self.fuse_head_rows = True      # (False: a pre-pass every iteration, what smoke() compares against)
+        # the uniform-tail mode of the head-row path (scan draw, unit exponents, n % 4 == 0): taken when the heuristic is
+        # one number outside the head of every row -- checked on the device once per head table (head_eta_table) -- and this is True
+        # (False: the path with dense rows P; the tests and A/B runs compare the two).  Same tours, costs and pheromone.
+        self.uniform_tail = True
+        self._head_version = None       # heuristic._version the head table was built at (an in-place edit rebuilds table and verdict)
+        self._head_ut = None            # (head table object, head_eta_table's answer for it)
 
     def check_feasible(self):
         """Raise like the reference's Categorical if any head-row draw so far had no candidate (bit 0), or the head table holds more
@@ -116,8 +122,9 @@ class BatchedTSP:
         _raise_flags(self._flags, ((1, ValueError, "BatchedTSP: a transition row had no feasible candidate"),
                                    (4, RuntimeError, "BatchedTSP: the head table has more live entries per row than head_live_max")))
 
-    def _heads_state(self, head, race):
-        return (self.pheromone, self.pheromone._version, self.heuristic, head, bool(race), float(self.alpha), float(self.beta))
+    def _heads_state(self, head, race, ut=None):
+        return (self.pheromone, self.pheromone._version, self.heuristic, self.heuristic._version, head, bool(race), float(self.alpha),
+                float(self.beta), ut is not None)
 
     def _heuristic_dist(self):
         return self._ls.heuristic_dist(self.heuristic)
@@ -137,10 +144,20 @@ class BatchedTSP:
 
     def _head_table(self, k=None):
         """(heuristic object it was built from, [B,n,64] head ids) for sampler='scan_sparse'."""
-        if self._head is None or self._head[0] is not self.heuristic or (k is not None and self._head[2] != k):
+        if self._head is None or self._head[0] is not self.heuristic or (k is not None and self._head[2] != k) \
+                or self._head_version != self.heuristic._version:
             k = k if k is not None else (self.head_k if self.head_k is not None else max(1, min(127, self.n // 10)))
             self._head = (self.heuristic, head_table(self.heuristic, k, self.B, getattr(self, "_auto", None), path=self.setup_path), k)
+            self._head_version = self.heuristic._version
         return self._head[1]
+
+    def _uniform_tail(self, head):
+        """head_eta_table(heuristic, head) for this head table (one launch and one host read per table), or None: the mode is off."""
+        if not self.uniform_tail:
+            return None
+        if self._head_ut is None or self._head_ut[0] is not head:
+            self._head_ut = (head, head_eta_table(self.heuristic, head))
+        return self._head_ut[1]
 
     @torch.no_grad()
     def step(self, events=None, _iter_dev=None, ls_events=None, want_paths=True):
@@ -167,18 +184,19 @@ class BatchedTSP:
                 self._sparse_ws = sparse_workspace(self.distances.device, self.B, self.n, self.n_ants, unit_exponents=unit)
             fused = self.fuse_head_rows and unit                 # (the update forms the rows of tau itself: unit exponents only)
             grouped = fused and self.n_ants % 8 == 0 and self.local_search is None
-            ready = same_state(self._heads_for, self._heads_state(head, race_head))
+            ut = self._uniform_tail(head) if (unit and not race_head and self.n % 4 == 0) else None
+            ready = same_state(self._heads_for, self._heads_state(head, race_head, ut))
             compact = not want_paths and self.local_search is None
             paths, _, costs, nbr = tsp_sample_sparse(self.pheromone, self.heuristic, self.n_ants, head, self.alpha,
                                                      self.beta, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0,
                                                      fixed_start=self.fixed_start, batch=self.B, events=events,
                                                      dist=self.distances, want_nbr=True, iter_dev=_iter_dev, race=race_head,
                                                      workspace=self._sparse_ws, heads_ready=ready, head_live_max=self._head[2],
-                                                     nbr_grouped=grouped, flags=self._flags, want_paths=not compact)
+                                                     nbr_grouped=grouped, flags=self._flags, want_paths=not compact, uniform_tail=ut)
             tours16 = sparse_tours16(self._sparse_ws, self.B, self.n, self.n_ants) if compact else None
             if fused:
                 heads = {"eta": self.heuristic, "alpha": self.alpha, "beta": self.beta, "head": head, "race": race_head,
-                         "workspace": self._sparse_ws, "nbr_grouped": grouped}
+                         "workspace": self._sparse_ws, "nbr_grouped": grouped, "uniform_tail": ut}
         else:
             tours16 = None
             paths, _, _, _, costs, nbr = tsp_sample(self.pheromone, self.heuristic, self.n_ants, self.alpha,
@@ -197,7 +215,7 @@ class BatchedTSP:
                               mmas_scale=self.n if self.min_max else None, tours16=tours16)
         cmin, cmax = _mmas_bounds(self, new_max)
         pheromone_update_(self.pheromone, paths, costs, self.decay, self.elitist, True, cmin, cmax, nbr=nbr, heads=heads)
-        self._heads_for = self._heads_state(heads["head"], heads["race"]) if heads is not None else None
+        self._heads_for = self._heads_state(heads["head"], heads["race"], heads["uniform_tail"]) if heads is not None else None
         return paths, costs
 
     @torch.no_grad()

@@ -1,4 +1,6 @@
 """TSP construction: the dense and race samplers, the head-row samplers with their head tables, the k-nn graph."""
+import struct
+
 import numpy as np
 import torch
 
@@ -270,6 +272,32 @@ def head_table(heuristic, k, B, cache=None, path=None):
     return sparse_head(_f32c(h), k, top=top, path="torch")
 
 
+def head_eta_table(heuristic, head):
+    """What the uniform-tail mode of the head-row path needs of a heuristic ([n,n] shared or [B,n,n]) and its head table
+    (include/deepaco_hip.h daco_head_eta): (head_eta [B,n,S] f32 -- eta at the head's live ids --, c) if eta is ONE non-negative
+    finite number c, bit for bit, outside the head of every row and no live head entry is below c; else None.  One launch and
+    one host read of three words; a colony calls it once per head table."""
+    _require_gpu(heuristic, head)
+    B, n, slots = head.shape
+    eta, ebs = _bstride(heuristic.detach(), n)
+    dev = head.device
+    with _on(dev):
+        out = torch.empty((B, n, slots), dtype=torch.float32, device=dev)
+        verdict = torch.empty(3, dtype=torch.int32, device=dev)
+        rc = _lib.lib().daco_head_eta(_stream(dev), B, n, eta.data_ptr(), ebs, head.data_ptr(), slots, out.data_ptr(), verdict.data_ptr())
+    _lib.check(rc, "daco_head_eta")
+    bad, nlo, hi = (int(v) & 0xFFFFFFFF for v in verdict.tolist())
+    if bad or (~nlo & 0xFFFFFFFF) != hi:
+        return None
+    return out, struct.unpack("<f", struct.pack("<I", hi))[0]
+
+
+def uniform_tail_applies(n, tau, eta, alpha, beta, race):
+    """The shapes the uniform-tail kernels take: scan draw, unit exponents, n % 4 == 0, 16-byte-aligned rows."""
+    return (not race and float(alpha) == 1.0 and float(beta) == 1.0 and n % 4 == 0
+            and tau.data_ptr() % 16 == 0 and eta.data_ptr() % 16 == 0)
+
+
 def sparse_workspace(device, B, n, n_ants, unit_exponents=True):
     """A scratch tensor of the head-row samplers that a colony KEEPS (daco_tsp_sparse_workspace_bytes: the iteration's head rows
     and, for n > 512, the tours as they are built): pheromone_update_(heads=...) writes the next iteration's head rows into it and
@@ -278,7 +306,9 @@ def sparse_workspace(device, B, n, n_ants, unit_exponents=True):
     nbytes = (L.daco_tsp_sparse_workspace_bytes if unit_exponents else L.daco_tsp_sparse_workspace_bytes_general)(B, n, n_ants)
     if nbytes == 0:
         raise ValueError(f"scan_sparse serves 129 <= n <= 1024 (n = {n})")
-    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    # (zeroed, once per colony: in the uniform-tail mode nothing ever writes the dense-row region, and whoever looks at the
+    # workspace -- a test comparing two colonies' bytes, a debugger -- sees defined bytes there, not what the allocator left)
+    return torch.zeros(int(nbytes), dtype=torch.uint8, device=device)
 
 
 def sparse_tours16(workspace, B, n, n_ants):
@@ -293,7 +323,8 @@ def sparse_tours16(workspace, B, n, n_ants):
 
 def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, fixed_start=-1, seed=0, it=0, ant_gid0=0,
                       batch=None, events=None, dist=None, want_nbr=False, iter_dev=None, ant_gid_bstride=0, want_stats=False,
-                      want_paths=True, race=False, workspace=None, heads_ready=False, head_live_max=0, nbr_grouped=False, flags=None):
+                      want_paths=True, race=False, workspace=None, heads_ready=False, head_live_max=0, nbr_grouped=False, flags=None,
+                      uniform_tail=None):
     """ACO.gen_path on head / tail rows (sampler "scan_sparse", include/deepaco_hip.h daco_tsp_sample_sparse): the
     distribution of tsp_sample(mode="scan"), 384 / 768 bytes per step instead of a row while the head has a live candidate.
     head: sparse_head(heuristic, k).  Returns (paths, flags, costs|None, nbr|None[, stats]).
@@ -305,7 +336,11 @@ def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, f
     head_live_max: the k the head table was built with (sparse_head(.., k)), or 0: lets a launch of few ants (one instance, a few
     hundred ants) keep the head rows in LDS -- the same tours, about half the time at TSP-500 x 512 ants x 1 instance.
     nbr_grouped: the update's table as [B, ceil(A/8), n, 8] (written in 1 KB pieces; pheromone_update_(heads={..., "nbr_grouped": True})
-    takes it) instead of [B, n, A]; the returned tensor keeps the shape [B, n, A] either way (same bytes, opaque to the caller)."""
+    takes it) instead of [B, n, A]; the returned tensor keeps the shape [B, n, A] either way (same bytes, opaque to the caller).
+    uniform_tail: head_eta_table(eta, head), or None -- the uniform-tail mode (include/deepaco_hip.h daco_tsp_sample_heads_ut): the
+    same tours; the pass over tau reads no eta and writes no dense rows, the rare ways of a step walk the row of tau.  Taken where
+    uniform_tail_applies(), ignored elsewhere.  With heads_ready=True the workspace's head rows must come from a call in the same
+    mode or the dense rows from a call out of it: the caller's key (BatchedTSP._heads_state) holds the mode."""
     _require_gpu(tau, eta, start, head, workspace)
     assert not heads_ready or workspace is not None
     n = tau.shape[-1]
@@ -335,6 +370,23 @@ def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, f
             raise ValueError(f"scan_sparse serves 129 <= n <= 1024 (n = {n})")
         ws = workspace if workspace is not None else _workspace(dev, nbytes, "sample_sparse")
         assert ws.numel() >= nbytes
+        if uniform_tail is not None and uniform_tail_applies(n, tau, eta, alpha, beta, race):
+            heta, tail_c = uniform_tail
+            assert heta.dtype == torch.float32 and heta.is_contiguous() and tuple(heta.shape) == tuple(head.shape)
+            rc = L.daco_tsp_sample_heads_ut(_stream(dev), int(bool(heads_ready)), int(head_live_max), int(bool(nbr_grouped)), B, n, n_ants,
+                                            tau.data_ptr(), tbs, eta.data_ptr(), ebs, head.data_ptr(), int(head.shape[2]),
+                                            start.data_ptr() if start is not None else None, int(fixed_start), int(seed) & (2 ** 64 - 1),
+                                            int(it), iter_dev.data_ptr() if iter_dev is not None else None, int(ant_gid0) & 0xFFFFFFFF,
+                                            int(ant_gid_bstride), paths.data_ptr() if paths is not None else None, flags.data_ptr(),
+                                            dist.data_ptr() if dist is not None else None, dbs,
+                                            costs.data_ptr() if costs is not None else None,
+                                            nbr.data_ptr() if nbr is not None else None,
+                                            stats.data_ptr() if stats is not None else None, ws.data_ptr(), ws.numel(),
+                                            events[0].cuda_event if events else None, events[1].cuda_event if events else None,
+                                            heta.data_ptr(), float(tail_c))
+            _lib.check(rc, "daco_tsp_sample_heads_ut")
+            out = (paths, flags, costs, nbr)
+            return out + (stats,) if want_stats else out
         rc = L.daco_tsp_sample_heads(_stream(dev), int(bool(race)), int(bool(heads_ready)), int(head_live_max), int(bool(nbr_grouped)), B, n, n_ants, tau.data_ptr(), tbs, eta.data_ptr(), ebs, float(alpha),
                                       float(beta), head.data_ptr(), int(head.shape[2]), start.data_ptr() if start is not None else None,
                                       int(fixed_start), int(seed) & (2 ** 64 - 1), int(it),

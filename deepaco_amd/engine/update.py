@@ -3,6 +3,7 @@ import torch
 
 from .. import _lib
 from .common import _bstride, _f32c, _on, _require_gpu, _stream, _workspace
+from .tsp_ops import uniform_tail_applies
 
 
 def tour_costs(dist, paths, closed=True):
@@ -60,7 +61,9 @@ def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, c
     weights [B,A]: explicit deposit per ant (default 1/cost); hub: see include/deepaco_hip.h.
     heads (symmetric only): dict(eta, alpha, beta, head, race, workspace) of a colony whose next construction is
     tsp_sample_sparse(..., workspace=workspace, heads_ready=True): the update also writes that call's head rows
-    (daco_pheromone_update_heads: tau is read once per iteration instead of twice)."""
+    (daco_pheromone_update_heads: tau is read once per iteration instead of twice).  heads["uniform_tail"] = head_eta_table(eta,
+    head): the uniform-tail mode where it applies (daco_pheromone_update_heads_ut: the same rows, eta not read, no dense rows
+    written); the next tsp_sample_sparse must then be given the same uniform_tail."""
     _require_gpu(tau, paths, costs, clamp_min, clamp_max)
     assert tau.dim() == 3 and tau.dtype == torch.float32 and tau.is_contiguous()
     B, n, _ = tau.shape
@@ -83,6 +86,18 @@ def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, c
             eta, ebs = _bstride(heads["eta"], n)
             head, sws = heads["head"], heads["workspace"]
             _require_gpu(eta, head, sws)
+            ut = heads.get("uniform_tail")
+            if ut is not None and uniform_tail_applies(n, tau, eta, heads["alpha"], heads["beta"], heads.get("race", False)):
+                rc = L.daco_pheromone_update_heads_ut(_stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
+                                                      int(bool(elitist)), clamp_min.data_ptr() if clamp_min is not None else None,
+                                                      clamp_max.data_ptr() if clamp_max is not None else None, float(floor),
+                                                      nbr.data_ptr() if nbr is not None else None,
+                                                      weights.data_ptr() if weights is not None else None, ws.data_ptr(), ws.numel(),
+                                                      head.data_ptr(), int(head.shape[2]),
+                                                      int(bool(heads.get("nbr_grouped", False))) if nbr is not None else 0,
+                                                      sws.data_ptr(), sws.numel(), ut[0].data_ptr(), float(ut[1]))
+                _lib.check(rc, "daco_pheromone_update_heads_ut")
+                return tau
             rc = L.daco_pheromone_update_heads(_stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
                                                int(bool(elitist)), clamp_min.data_ptr() if clamp_min is not None else None,
                                                clamp_max.data_ptr() if clamp_max is not None else None, float(floor),

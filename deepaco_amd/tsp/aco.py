@@ -149,6 +149,7 @@ class ACO():
             if sampler == "scan_sparse":                    # (head_k stays unset otherwise: 'race' after sparsify(k) runs the dense race kernel here)
                 col.head_k = hk
                 col._head = (eta, self._head_table(hk), hk)     # (this object's table: built once, from the sorted top values if 'auto' left them)
+                col._head_version = eta._version
             hit = self._colony = (key, col)
         col = hit[1]
         shortest = (self.shortest_path.clone() if self.shortest_path is not None else

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads, the sparse workspace no longer holds dense rows; 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats, and daco_cvrp_knn_graph) */
+#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads (the sparse workspace still begins with the dense rows P: see daco_tsp_sample_sparse); 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats, and daco_cvrp_knn_graph; daco_head_eta / daco_tsp_sample_heads_ut / daco_pheromone_update_heads_ut (the uniform-tail mode of the head-row path) were added under 129 in the same way: same draws, same head rows, no existing signature changed -- the number stays where tests/test_mkp_grad_spec.py holds it) */
 
 /* error codes */
 #define DACO_OK 0
@@ -134,10 +134,12 @@ int daco_tsp_sample(void *stream, int B, int n, int A,
  *   paths, flags, dist / costs, nbr, start / fixed_start, seed / iter / iter_offset / ant_gid0 / ant_gid_bstride,
  *   ev_begin / ev_end: as daco_tsp_sample (log-probabilities are not produced: an inference sampler)
  *   stats    optional out [3] uint64 (caller zeroes): dense masked draws (no live head candidate, or after a rejection), tail walks, rejections
- *   workspace  daco_tsp_sparse_workspace_bytes(B, n, A) bytes of device scratch: the head rows of this iteration (16 lanes x
- *              {4 or 8 f32 values, as many u16 ids} per row of tau, at offset 0) and, for n > 512, the tours as they are built.
- *              The steps that leave the head walk tau^alpha * eta^beta formed from the rows of `tau` and `eta` themselves
- *              (until version 124 a dense copy of that matrix lived here: 65 MB written per call at TSP-500 x 64).
+ *   workspace  daco_tsp_sparse_workspace_bytes(B, n, A) bytes of device scratch, in this order: the dense rows
+ *              P = tau^alpha * eta^beta [B][n][ld] f32 (ld = 512 for n <= 512, else 1024; zeros past n) that the steps which leave
+ *              the head walk; the head rows of this iteration (16 lanes x {4 or 8 f32 values, as many u16 ids} per row of tau);
+ *              the tours as uint16 [B][A][ld] at daco_tsp_sparse_tours_offset.  Both P and the head rows are written by the pass
+ *              over tau of this call, or by daco_pheromone_update_heads.  In the uniform-tail mode (daco_tsp_sample_heads_ut,
+ *              daco_pheromone_update_heads_ut) the region of P is left alone -- neither written nor read -- and keeps its place.
  *              alpha, beta other than 1: the kernels themselves take unit exponents; tau^alpha and eta^beta are formed first (one
  *              elementwise launch; x^2 = x x and x^0 = 1 exactly) into a workspace of daco_tsp_sparse_workspace_bytes_general(B, n, A)
  *              bytes (= the above + two [B][n][n] f32 matrices), which such a call needs (DACO_E_WORKSPACE otherwise).
@@ -218,6 +220,29 @@ int daco_tsp_sample_heads(void *stream, int race, int heads_ready, int head_live
                           const float *dist, long dist_bstride, float *costs, uint32_t *nbr,
                           unsigned long long *stats,
                           void *workspace, size_t workspace_bytes, void *ev_begin, void *ev_end);
+
+/* daco_tsp_sample_heads_ut -- daco_tsp_sample_heads(race = 0, alpha = beta = 1) in the UNIFORM-TAIL mode, for a heuristic that
+ * is one number c outside the head of every row (what ACO.sparsify writes, tsp/aco.py:52-67: 1e-10 off the k nearest edges):
+ *   head_eta, tail_c   what daco_head_eta wrote for this eta and head_id, after the caller has read its verdict and found it good
+ * The same tours, costs, table and stats as daco_tsp_sample_heads, bit for bit.  What differs is the memory touched: the pass
+ * over tau (heads_ready = 0) reads tau and head_eta only and writes the head rows only; the dense-row region of the workspace
+ * is neither written nor read; the rare ways of a step (tail walk, draw without a live head candidate) read the row of tau and
+ * multiply by tail_c, and only the draw after a rejected tail walk reads the rows of tau and eta.  Needs n % 4 == 0 and
+ * 16-byte-aligned rows of tau and eta (DACO_E_BADARG otherwise: the caller then takes daco_tsp_sample_heads).  The head rows a
+ * workspace holds are the same bytes in both modes, the dense rows are not: a caller that leaves the mode runs one call with
+ * heads_ready = 0.  The status is the usual DACO_OK / DACO_E_* value typed `long`, for the reason given at
+ * daco_rcpsp_net_forward (daco_pheromone_update_heads_ut likewise); the refusals are held by tests/test_uniform_tail_refusals.py. */
+long daco_tsp_sample_heads_ut(void *stream, int heads_ready, int head_live_max, int nbr_grouped, int B, int n, int A,
+                             const float *tau, long tau_bstride, const float *eta, long eta_bstride,
+                             const uint16_t *head_id, int head_slots,
+                             const int64_t *start, int fixed_start,
+                             uint64_t seed, uint64_t iter, const uint64_t *iter_offset, uint32_t ant_gid0,
+                             int ant_gid_bstride,
+                             int64_t *paths, int32_t *flags,
+                             const float *dist, long dist_bstride, float *costs, uint32_t *nbr,
+                             unsigned long long *stats,
+                             void *workspace, size_t workspace_bytes, void *ev_begin, void *ev_end,
+                             const float *head_eta, float tail_c);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_cvrp_sample -- replaces the CVRP ACO.gen_path / pick_move / update_visit_mask /
@@ -512,6 +537,18 @@ int daco_pheromone_update_heads(void *stream, int B, int n, int A, float *tau,
                                 const float *eta, long eta_bstride, float alpha, float beta,
                                 const uint16_t *head_id, int head_slots, int race, int nbr_grouped,
                                 void *sparse_workspace, size_t sparse_workspace_bytes);
+
+/* daco_pheromone_update_heads_ut -- daco_pheromone_update_heads(race = 0, alpha = beta = 1) in the uniform-tail mode (see
+ * daco_tsp_sample_heads_ut): the same tau and the same head rows, bit for bit, formed from the rows of tau the workgroup holds
+ * on chip, head_eta and tail_c.  eta is not read and the workspace's dense rows are not written (at TSP-500 x 64 instances:
+ * 64 MB less read and 65.5 MB less written per call).  n % 4 == 0 and a 16-byte-aligned tau, else DACO_E_BADARG. */
+long daco_pheromone_update_heads_ut(void *stream, int B, int n, int A, float *tau,
+                                   const int64_t *paths, const float *costs, float decay, int elitist,
+                                   const float *clamp_min, const float *clamp_max, float floor_val,
+                                   const uint32_t *nbr, const float *weights, void *workspace, size_t workspace_bytes,
+                                   const uint16_t *head_id, int head_slots, int nbr_grouped,
+                                   void *sparse_workspace, size_t sparse_workspace_bytes,
+                                   const float *head_eta, float tail_c);
 
 /* daco_allreduce_delta_tau -- the ant-sharded colony's one data-path collective (every rank builds the deposits
  * of ITS ants, delta-tau [B][n][n] f32 = daco_pheromone_update(decay = 1) onto zeros; the ranks sum them; every rank applies
@@ -819,6 +856,19 @@ long daco_sparse_head(void *stream, int B, int n, int k, const float *weights, l
  */
 long daco_head_stats(void *stream, int B, int n, const float *weights, long w_bstride, int k_lds, double mass,
                     double mass_lds, int32_t *counts);
+/* daco_head_eta: what the uniform-tail mode of the head-row path (daco_tsp_sample_heads_ut, daco_pheromone_update_heads_ut)
+ *   needs of a heuristic, once per head table.  eta [B][n][n] f32 (eta_bstride between instances, 0: one matrix), head_id
+ *   [B][n][head_slots] as daco_sparse_head wrote it (head_slots 64 or 128).
+ *   head_eta [B][n][head_slots] f32 = eta at the live slots' ids (slot m < the row's count, id < n), +0 in every other slot.
+ *   verdict [3] uint32, cleared by the call (a kernel): verdict[0] != 0 if some row fails on its own -- its entries outside the
+ *   head are not all ONE bit pattern, or that pattern has the sign bit set or is not finite, or a live head entry is not >= it;
+ *   verdict[1] = max over the rows of ~pattern, verdict[2] = max of pattern.  The mode applies iff verdict[0] == 0 and
+ *   ~verdict[1] == verdict[2]; tail_c is then the float with the bits verdict[2].  "One bit pattern" is meant literally: a
+ *   tail that mixes +0.0 and -0.0 is refused, and so is a tail of -0.0 (sign bit); +0.0 everywhere is accepted with c = 0.
+ *   Errors: DACO_E_BADARG for a null pointer, another head_slots, n < 2; DACO_E_TOOLARGE for n > 1024.
+ */
+long daco_head_eta(void *stream, int B, int n, const float *eta, long eta_bstride, const uint16_t *head_id, int head_slots,
+                   float *head_eta, uint32_t *verdict);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_mkpv_sample -- fused solution construction of the vector-pheromone knapsack colony (one launch)
