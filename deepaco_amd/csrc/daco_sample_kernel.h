@@ -62,6 +62,7 @@ struct SampleParams {
   float tail_c = 0.0f;               // uniform-tail mode: eta outside the head (daco_head_eta)
   float alpha = 1.0f, beta = 1.0f;   // PROB_RCPSP: the exponents of its pheromone and heuristic (the head-row kernels take unit exponents)
   int nbr_grouped = 0;               // scan_sparse: nbr as [B][ceil(A/8)][n][8] (eight ants' entries of a node together) instead of [B][n][A]
+  int dist_symmetric = 0;            // scan_sparse, n <= 512: the caller states that dist is bitwise symmetric (tour lengths gather from one triangle)
   int lh_kl = 0, lh_kmax = 0;        // scan_sparse, LDS-heads variant: lane records per row kept in LDS, the caller's bound of live slots per row
   RcpspDev rc;                       // PROB_RCPSP (daco_rcpsp.hip): the project, the evaluation rule, the decoder's outputs
 };

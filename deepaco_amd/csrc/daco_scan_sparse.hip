@@ -712,6 +712,13 @@ scan_sparse_kernel(const SampleParams p) {
       // of the wave's four ants are gathered with every lane active and staged in the (dead) flag array.
       __syncthreads();
       const float *dist_b = SP_E(dist) + (size_t)b * SP_E(dist_bs);
+      // dist_symmetric (the caller's statement: dist[u][v] and dist[v][u] are the same bits): the edge is read from the upper
+      // triangle, dist[min(u, v)][max(u, v)] -- the same values from half the lines.  The eight instances whose workgroups share
+      // an XCD gather from 8 MB of dist through a 4 MB L2; half of that fits (profiles/epilogue_one_pass_ab.txt).
+      const bool tri = SP_E(dist_symmetric) != 0;
+      // (Measured and not kept, same file: the int64 path stores of a pass's steps issued between its gathers and their wait --
+      // buffer stores switched off by offset, the wait vmcnt(1).  0.5543-0.5575 against 0.5568-0.5613 ms per iteration alone, 2-3 us
+      // in the medians with overlapping ranges on top of the triangle: gathers that miss the L2 share the HBM side with the stores.)
       // (LH: the flag array is four ants' worth; the head table is dead by now and holds the staging rows and the inverse table)
       // (ST: 32 edges of each ant per pass, staged behind the early parts; the sum takes them in the same order)
       constexpr int DSW = ST ? 32 : 64;
@@ -727,7 +734,13 @@ scan_sparse_kernel(const SampleParams p) {
 #pragma unroll
           for (int r4 = 0; r4 < APW; r4 += 64 / DSW) {
             const int kr = wave * APW + r4 + lane / DSW;
-            dstage[wave][r4 + lane / DSW][lane & (DSW - 1)] = t < n ? dist_b[(uint32_t)SP_TOUR(kr, t) * (uint32_t)n + SP_TOUR(kr, t - 1)] : 0.0f;
+            float dv = 0.0f;
+            if (t < n) {
+              const uint32_t eu = SP_TOUR(kr, t), ev = SP_TOUR(kr, t - 1);
+              const bool sw = tri && ev < eu;
+              dv = dist_b[(sw ? ev : eu) * (uint32_t)n + (sw ? eu : ev)];
+            }
+            dstage[wave][r4 + lane / DSW][lane & (DSW - 1)] = dv;
           }
           __builtin_amdgcn_wave_barrier();
           if (s == 0) {
@@ -741,7 +754,9 @@ scan_sparse_kernel(const SampleParams p) {
         }
         if (s == 0 && a0 + q < A) {
           const int km = wave * APW + q;
-          cost = cost + dist_b[(uint32_t)SP_TOUR(km, 0) * (uint32_t)n + SP_TOUR(km, n - 1)];
+          const uint32_t eu = SP_TOUR(km, 0), ev = SP_TOUR(km, n - 1);
+          const bool sw = tri && ev < eu;
+          cost = cost + dist_b[(sw ? ev : eu) * (uint32_t)n + (sw ? eu : ev)];
           SP_E(costs)[(size_t)b * A + a0 + q] = cost;
         }
       }
@@ -931,7 +946,7 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
                                       uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
                                       long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
                                       size_t workspace_bytes, void *ev_begin, void *ev_end, const float *head_eta = nullptr, float tail_c = 0.0f) {
-  if (B <= 0 || A <= 0 || !tau || !eta || !head_id || !workspace || (!paths && !nbr)) {
+  if (B <= 0 || A <= 0 || !tau || !eta || !head_id || !workspace || (!paths && !nbr && !costs)) {
     set_error("%s: bad argument (B=%d n=%d A=%d)", what, B, n, A);
     return DACO_E_BADARG;
   }
@@ -989,7 +1004,7 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   sp.start = start; sp.fixed_start = fixed_start;
   sp.tau = tau; sp.tau_bs = tau_bstride; sp.eta = eta; sp.eta_bs = eta_bstride; sp.tail_c = tail_c;
   sp.iter_dev = iter_offset; sp.gid_bstride = ant_gid_bstride;
-  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr; sp.nbr_grouped = nbr_grouped ? 1 : 0;
+  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr; sp.nbr_grouped = nbr_grouped & 1; sp.dist_symmetric = (nbr_grouped >> 1) & 1;
   sp.hval = (const float *)ws.hrow; sp.hid = head_id; sp.stats = stats; sp.tours16 = ws.tours16;
   if (const int rc = record_event(ev_begin, s, "ev_begin")) return rc;
   // few ants (no more workgroups of four than the chip has CUs) and a head table that fits a CU's LDS: the LDS-heads variant

@@ -4,7 +4,7 @@ import torch
 from .common import _f32c, _raise_flags, _require_gpu, _rows
 from .cvrp_ops import cvrp_sample
 from .local_search import HgsTables, TspLocalSearch, heuristic_dist, hgs_local_search_, hgs_polar_angles
-from .tsp_ops import head_eta_table, head_table, resolve_sampler, sparse_tours16, sparse_workspace, sparsify_heuristic, tsp_sample, tsp_sample_sparse
+from .tsp_ops import dist_is_symmetric, head_eta_table, head_table, resolve_sampler, sparse_tours16, sparse_workspace, sparsify_heuristic, tsp_sample, tsp_sample_sparse
 from .update import pheromone_update_, tour_costs, track_best_
 
 
@@ -115,6 +115,7 @@ class BatchedTSP:
         self.uniform_tail = True
         self._head_version = None       # heuristic._version the head table was built at (an in-place edit rebuilds table and verdict)
         self._head_ut = None            # (head table object, head_eta_table's answer for it)
+        self._dist_sym = None           # (distances._version, dist_is_symmetric's answer): the tour lengths may gather from one triangle
 
     def check_feasible(self):
         """Raise like the reference's Categorical if any head-row draw so far had no candidate (bit 0), or the head table holds more
@@ -159,6 +160,12 @@ class BatchedTSP:
             self._head_ut = (head, head_eta_table(self.heuristic, head))
         return self._head_ut[1]
 
+    def _dist_symmetric(self):
+        """dist_is_symmetric(distances), asked once (one device comparison and one host read; again after an in-place edit)."""
+        if self._dist_sym is None or self._dist_sym[0] != self.distances._version:
+            self._dist_sym = (self.distances._version, dist_is_symmetric(self.distances))
+        return self._dist_sym[1]
+
     @torch.no_grad()
     def step(self, events=None, _iter_dev=None, ls_events=None, want_paths=True):
         # want_paths=False (head-row samplers without local search; what run() passes): the iteration keeps its tours to itself, as
@@ -192,7 +199,8 @@ class BatchedTSP:
                                                      fixed_start=self.fixed_start, batch=self.B, events=events,
                                                      dist=self.distances, want_nbr=True, iter_dev=_iter_dev, race=race_head,
                                                      workspace=self._sparse_ws, heads_ready=ready, head_live_max=self._head[2],
-                                                     nbr_grouped=grouped, flags=self._flags, want_paths=not compact, uniform_tail=ut)
+                                                     nbr_grouped=grouped, flags=self._flags, want_paths=not compact, uniform_tail=ut,
+                                                     dist_symmetric=self._dist_symmetric())
             tours16 = sparse_tours16(self._sparse_ws, self.B, self.n, self.n_ants) if compact else None
             if fused:
                 heads = {"eta": self.heuristic, "alpha": self.alpha, "beta": self.beta, "head": head, "race": race_head,

@@ -292,6 +292,14 @@ def head_eta_table(heuristic, head):
     return out, struct.unpack("<f", struct.pack("<I", hi))[0]
 
 
+def dist_is_symmetric(dist):
+    """True if `dist` ([n,n] or [B,n,n] float32 on the device) equals its transpose bit for bit -- the verdict behind
+    tsp_sample_sparse(dist_symmetric=True).  Formed on the device; one host read.  A colony asks once per distance matrix."""
+    _require_gpu(dist)
+    bits = dist.detach().view(torch.int32)
+    return bool(torch.equal(bits, bits.transpose(-1, -2)))
+
+
 def uniform_tail_applies(n, tau, eta, alpha, beta, race):
     """The shapes the uniform-tail kernels take: scan draw, unit exponents, n % 4 == 0, 16-byte-aligned rows."""
     return (not race and float(alpha) == 1.0 and float(beta) == 1.0 and n % 4 == 0
@@ -324,7 +332,7 @@ def sparse_tours16(workspace, B, n, n_ants):
 def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, fixed_start=-1, seed=0, it=0, ant_gid0=0,
                       batch=None, events=None, dist=None, want_nbr=False, iter_dev=None, ant_gid_bstride=0, want_stats=False,
                       want_paths=True, race=False, workspace=None, heads_ready=False, head_live_max=0, nbr_grouped=False, flags=None,
-                      uniform_tail=None):
+                      uniform_tail=None, dist_symmetric=False):
     """ACO.gen_path on head / tail rows (sampler "scan_sparse", include/deepaco_hip.h daco_tsp_sample_sparse): the
     distribution of tsp_sample(mode="scan"), 384 / 768 bytes per step instead of a row while the head has a live candidate.
     head: sparse_head(heuristic, k).  Returns (paths, flags, costs|None, nbr|None[, stats]).
@@ -340,7 +348,10 @@ def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, f
     uniform_tail: head_eta_table(eta, head), or None -- the uniform-tail mode (include/deepaco_hip.h daco_tsp_sample_heads_ut): the
     same tours; the pass over tau reads no eta and writes no dense rows, the rare ways of a step walk the row of tau.  Taken where
     uniform_tail_applies(), ignored elsewhere.  With heads_ready=True the workspace's head rows must come from a call in the same
-    mode or the dense rows from a call out of it: the caller's key (BatchedTSP._heads_state) holds the mode."""
+    mode or the dense rows from a call out of it: the caller's key (BatchedTSP._heads_state) holds the mode.
+    dist_symmetric: the caller's statement that every instance of `dist` is bitwise symmetric (dist_is_symmetric(dist), checked
+    once per matrix): at n <= 512 the fused tour lengths then read each edge from the upper triangle -- the same costs from half
+    the cache lines (include/deepaco_hip.h daco_tsp_sample_heads, nbr_grouped + 2).  Never set it for a matrix that is not."""
     _require_gpu(tau, eta, start, head, workspace)
     assert not heads_ready or workspace is not None
     n = tau.shape[-1]
@@ -370,10 +381,11 @@ def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, f
             raise ValueError(f"scan_sparse serves 129 <= n <= 1024 (n = {n})")
         ws = workspace if workspace is not None else _workspace(dev, nbytes, "sample_sparse")
         assert ws.numel() >= nbytes
+        table_bits = int(bool(nbr_grouped)) | (2 if dist_symmetric and dist is not None else 0)     # (the library's nbr_grouped argument)
         if uniform_tail is not None and uniform_tail_applies(n, tau, eta, alpha, beta, race):
             heta, tail_c = uniform_tail
             assert heta.dtype == torch.float32 and heta.is_contiguous() and tuple(heta.shape) == tuple(head.shape)
-            rc = L.daco_tsp_sample_heads_ut(_stream(dev), int(bool(heads_ready)), int(head_live_max), int(bool(nbr_grouped)), B, n, n_ants,
+            rc = L.daco_tsp_sample_heads_ut(_stream(dev), int(bool(heads_ready)), int(head_live_max), table_bits, B, n, n_ants,
                                             tau.data_ptr(), tbs, eta.data_ptr(), ebs, head.data_ptr(), int(head.shape[2]),
                                             start.data_ptr() if start is not None else None, int(fixed_start), int(seed) & (2 ** 64 - 1),
                                             int(it), iter_dev.data_ptr() if iter_dev is not None else None, int(ant_gid0) & 0xFFFFFFFF,
@@ -387,7 +399,7 @@ def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, f
             _lib.check(rc, "daco_tsp_sample_heads_ut")
             out = (paths, flags, costs, nbr)
             return out + (stats,) if want_stats else out
-        rc = L.daco_tsp_sample_heads(_stream(dev), int(bool(race)), int(bool(heads_ready)), int(head_live_max), int(bool(nbr_grouped)), B, n, n_ants, tau.data_ptr(), tbs, eta.data_ptr(), ebs, float(alpha),
+        rc = L.daco_tsp_sample_heads(_stream(dev), int(bool(race)), int(bool(heads_ready)), int(head_live_max), table_bits, B, n, n_ants, tau.data_ptr(), tbs, eta.data_ptr(), ebs, float(alpha),
                                       float(beta), head.data_ptr(), int(head.shape[2]), start.data_ptr() if start is not None else None,
                                       int(fixed_start), int(seed) & (2 ** 64 - 1), int(it),
                                       iter_dev.data_ptr() if iter_dev is not None else None, int(ant_gid0) & 0xFFFFFFFF,

@@ -148,7 +148,7 @@ size_t daco_tsp_sparse_workspace_bytes(int B, int n, int A);
 size_t daco_tsp_sparse_workspace_bytes_general(int B, int n, int A);
 /* daco_tsp_sparse_tours_offset -- where the workspace keeps the tours in their compact form: uint16 [B][A][ld], ld = 512 (n <= 512) or
  * 1024, entry t of ant a = the node visited at step t (entries >= n: undefined).  Valid after a call of daco_tsp_sample_sparse /
- * _race_head / _heads with n > 512 (the tours are built there), and for n <= 512 after a call with paths = NULL (nbr given): the
+ * _race_head / _heads with n > 512 (the tours are built there), and for n <= 512 after a call with paths = NULL (nbr or costs given): the
  * colony loop of ACO.run (tsp/aco.py:75-92) keeps `paths` to itself -- costs, best tour and deposit are all it takes from them -- so
  * its iteration asks for no int64 [B][n][A] tensor (131 MB per iteration at TSP-500 x 512 x 64) and hands these rows to
  * daco_track_best_tours16. */
@@ -209,7 +209,12 @@ int daco_tsp_sample_race_head(void *stream, int B, int n, int A,
  *                bit 2 of flags[b].
  *   nbr_grouped  0: nbr as [B][n][A] (what daco_pheromone_update takes); 1: nbr as [B][ceil(A/8)][n][8] -- the eight ants' entries
  *                of a node together, so that the sampler writes the table in 1 KB pieces instead of 32-byte runs and the update
- *                reads it in runs of R x 32 bytes (daco_pheromone_update_heads(nbr_grouped = 1) takes this form). */
+ *                reads it in runs of R x 32 bytes (daco_pheromone_update_heads(nbr_grouped = 1) takes this form).
+ *                + 2 (bit 1, either layout): the caller states that every instance of `dist` is bitwise symmetric --
+ *                dist[u][v] and dist[v][u] hold the same bits, which it has checked once for this matrix.  At n <= 512 the fused
+ *                tour lengths then read each edge from the upper triangle, dist[min(u, v)][max(u, v)]: the same costs bit for bit
+ *                from half the cache lines.  Without the bit (or on a matrix that is not symmetric, where it must not be set)
+ *                every edge is read as dist[u_k][u_{k-1}].  daco_tsp_sample_heads_ut takes the same two bits. */
 int daco_tsp_sample_heads(void *stream, int race, int heads_ready, int head_live_max, int nbr_grouped, int B, int n, int A,
                           const float *tau, long tau_bstride, const float *eta, long eta_bstride,
                           float alpha, float beta, const uint16_t *head_id, int head_slots,
