@@ -8,6 +8,7 @@
 
 #include "daco_host.h"
 #include "daco_rcpsp.h"
+#include "daco_tour_epilogue.h"
 
 namespace daco {
 
@@ -605,57 +606,17 @@ tsp_sample_kernel(const SampleParams p) {
     }
   }
   if constexpr (EPI) {
-    // ---- the workgroup's (up to) 4 tours leave LDS together (see tsp_scan32_kernel): paths in 32-byte runs per step
-    // row, tour lengths from 64-edge gathers summed in step order by one lane, the neighbour table through an
-    // inverse-permutation table in LDS.  Per-step stores / gathers with one active lane cost more than the row stream.
+    // ---- the workgroup's (up to) 4 tours leave LDS together (daco_tour_epilogue.h): one ant per wavefront, 32-byte runs,
+    // the inverse table behind the tours and a staging row per wavefront behind that
     __syncthreads();
     const int abase = (w - b * bpi) * 4;
     const int nant = A - abase < 4 ? A - abase : 4;
-    const int k4 = threadIdx.x & 3;
-    {
-      int64_t *pb = p.paths + (size_t)b * n * A + abase;
-      if (k4 < nant)
-        for (int tt = threadIdx.x >> 2; tt < n; tt += 64) pb[(size_t)tt * A + k4] = (int64_t)epi_lds[(size_t)k4 * TL + tt];
-    }
-    if (p.costs && !dup) {
-      const float *dist_e = p.dist + (size_t)b * p.dist_bs;
-      float *stage = reinterpret_cast<float *>(epi_lds + (size_t)8 * TL) + wave * 64;
-      float cost_e = 0.0f;
-      for (int base = 1; base < n; base += 64) {
-        const int tt = base + lane;
-        stage[lane] = tt < n ? dist_e[(unsigned)tour[tt] * (unsigned)n + (unsigned)tour[tt - 1]] : 0.0f;   // d[u_t][u_{t-1}], tsp/aco.py:127
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-#pragma unroll
-          for (int q4 = 0; q4 < 16; ++q4) {
-            const float4 v = *reinterpret_cast<const float4 *>(stage + 4 * q4);     // (slots past the tour's end hold +0.0f)
-            cost_e = cost_e + v.x; cost_e = cost_e + v.y; cost_e = cost_e + v.z; cost_e = cost_e + v.w;
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
-      if (lane == 0) {
-        cost_e = cost_e + dist_e[(unsigned)tour[0] * (unsigned)n + (unsigned)tour[n - 1]];    // closing edge d[u_0][u_{n-1}] last
-        p.costs[(size_t)b * A + a] = cost_e;
-      }
-    }
-    if (p.nbr) {
-      uint16_t *inv = epi_lds + (size_t)4 * TL;
-      for (int e = threadIdx.x; e < 4 * TL; e += 256) inv[e] = 0;
-      __syncthreads();
-      if (k4 < nant)
-        for (int tt = threadIdx.x >> 2; tt < n; tt += 64) inv[(size_t)k4 * TL + epi_lds[(size_t)k4 * TL + tt]] = (uint16_t)tt;
-      __syncthreads();
-      uint32_t *nb = p.nbr + (size_t)b * n * A + abase;
-      if (k4 < nant) {
-        const uint16_t *tk = epi_lds + (size_t)k4 * TL;
-        for (int node = threadIdx.x >> 2; node < n; node += 64) {
-          const int tt = inv[(size_t)k4 * TL + node];
-          const uint32_t pv = tk[tt == 0 ? n - 1 : tt - 1], nx = tk[tt == n - 1 ? 0 : tt + 1];
-          nb[(size_t)node * A + k4] = pv | (nx << 16);
-        }
-      }
-    }
+    const TourRows<uint16_t> tours{epi_lds, TL};
+    epi_paths<4>(tours, p.paths + (size_t)b * n * A + abase, n, A, nant);
+    if (p.costs && !dup)
+      epi_tour_costs<64, 1>(tours, wave, nant, n, p.dist + (size_t)b * p.dist_bs, false,
+                            reinterpret_cast<float *>(epi_lds + (size_t)8 * TL) + wave * 64, p.costs + (size_t)b * A + abase);
+    if (p.nbr) epi_nbr_table<4>(tours, 0, epi_lds + (size_t)4 * TL, TL, nant, n, p.nbr + (size_t)b * n * A + abase, (size_t)A);
   }
 }
 

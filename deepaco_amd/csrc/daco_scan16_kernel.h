@@ -24,6 +24,7 @@
 // bit-exact against the CPU restatement of that specification (which honours DACO_SCAN_LAYOUT like the library).
 #include <type_traits>
 #include "daco_sample_kernel.h"
+#include "daco_tour_epilogue.h"
 
 namespace daco {
 
@@ -317,18 +318,54 @@ scan16_kernel(const SampleParams p, const int TL /* entries per tour buffer */) 
   }
   if (feasible != ~0ull && p.flags && lane == 0) atomicOr(p.flags + b, 1);
 
-  // ------------------------------------------------------------------ epilogue: the workgroup's 16 tours leave LDS
+  // ------------------------------------------------------------------ epilogue: the workgroup's APB tours leave LDS
   __syncthreads();
   const int nant = A - abase < APB ? A - abase : APB;     // ants of this workgroup (the last one may hold fewer)
-  const int k16 = threadIdx.x & (APB - 1);               // this thread's ant in the epilogue: APB lanes = one run per row
-  constexpr int TSTEP = 256 / APB;
-  {
-    // paths[b][t][abase + k]: 16 lanes = one 128-byte run per step row; CVRP pads a finished route with the depot
-    int64_t *pb = p.paths + (size_t)b * rows * A + abase;
+  // (the flags are dead: their array holds the edge staging of the costs, 256 B per ant, and then the inverse table)
+  float (*dstage)[APW][64] = reinterpret_cast<float (*)[APW][64]>(&open_flags[0][0]);
+  static_assert(sizeof(open_flags) >= sizeof(float) * 4 * APW * 64, "edge staging inside the flag array");
+  uint16_t (*inv)[FL] = reinterpret_cast<uint16_t (*)[FL]>(open_flags);
+  if constexpr (!CVRP) {
+    // TSP: the stages of daco_tour_epilogue.h, APB lanes = one run per row (128-byte runs of paths for sixteen ants)
+    const TourRows<tour_t> tours{tour_s, TL};
+    epi_paths<APB>(tours, p.paths + (size_t)b * n * A + abase, n, A, nant);
+    if (p.costs && active) {
+      // (the cost stage in this kernel's own text, on the shared chunk sum and edge address: through epi_tour_costs <4, 6, true> took
+      // 78 VGPRs for the parent's 71, occupancy 6 for 7, in the step loop's re-read block: profiles/tour_epilogue_once.txt part B)
+      const float *dist_b = p.dist + (size_t)b * p.dist_bs;
+      float cost = 0.0f;
+      for (int base = 1; base < n; base += 64) {
+        const int t = base + lane;
+#pragma unroll
+        for (int r4 = 0; r4 < APW; ++r4) {
+          const tour_t *tr = tour_s + (size_t)(wave * APW + r4) * TL;
+          float dv = 0.0f;
+          if (t < n) dv = dist_b[epi_edge(tr[t], tr[t - 1], n, false)];
+          dstage[wave][r4][lane] = dv;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (s == 0) cost = epi_chunk_sum<64>(cost, dstage[wave][q]);
+        __builtin_amdgcn_wave_barrier();
+      }
+      if (s == 0 && a0 + q < A) {
+        cost = cost + dist_b[epi_edge(tour[0], tour[n - 1], n, false)];
+        p.costs[(size_t)b * A + a0 + q] = cost;
+      }
+    }
+    if (p.nbr) {
+      __syncthreads();
+      epi_nbr_table<APB>(tours, 0, &inv[0][0], FL, nant, n, p.nbr + (size_t)b * n * A + abase, (size_t)A);
+    }
+  } else {
+    // CVRP: routes of len_s[k] entries -- paths padded with the depot, route lengths without a closing edge, a successor-only
+    // table and the depot's successors as a bitmap per ant
+    const int k16 = threadIdx.x & (APB - 1);               // this thread's ant in the epilogue: APB lanes = one run per row
+    constexpr int TSTEP = 256 / APB;
     if (k16 < nant) {
-      const int lk = CVRP ? len_s[k16] : n;
+      int64_t *pb = p.paths + (size_t)b * rows * A + abase;
+      const int lk = len_s[k16];
       for (int t = threadIdx.x / APB; t < rows; t += TSTEP) pb[(size_t)t * A + k16] = t < lk ? (int64_t)tour_s[(size_t)k16 * TL + t] : 0;
-      if constexpr (CVRP && LOGP) {
+      if constexpr (LOGP) {
         // the reference steps every ant until the slowest one is done: a done ant keeps drawing the depot
         // (probability 1), so its log-prob column is padded with log(1-eps)
         float *lp = p.logp + (size_t)b * (rows - 1) * A + abase;
@@ -336,89 +373,54 @@ scan16_kernel(const SampleParams p, const int TL /* entries per tour buffer */) 
         for (int t = threadIdx.x / APB; t < rows; t += TSTEP) if (t >= lk && t >= 1) lp[(size_t)(t - 1) * A + k16] = lp1;
       }
     }
-  }
-  if constexpr (CVRP) {
     if (threadIdx.x < nant) {
       const int a_ = abase + threadIdx.x;
       if (p.lens) p.lens[(size_t)b * A + a_] = len_s[threadIdx.x];
       if (p.tab_lens) p.tab_lens[(size_t)b * A + a_] = len_s[threadIdx.x];
     }
     if (active && s == 0 && a0 + q < A && !finished && p.flags) atomicOr(p.flags + b, 2);
-  }
-  if (p.costs) {
-    // route / tour lengths: f32 sum in step order (TSP: d[u_t][u_{t-1}], tsp/aco.py:127, closing edge last; CVRP:
-    // d[u_{t-1}][u_t], cvrp/aco.py:135).  64 edges of each of the wave's four ants are gathered with every lane active
-    // and staged in LDS; lane 0 of each row adds its ant's 64 values one after the other.
-    const float *dist_b = p.dist + (size_t)b * p.dist_bs;
-    float (*dstage)[APW][64] = reinterpret_cast<float (*)[APW][64]>(&open_flags[0][0]);   // (the flags are dead; 256 B per ant)
-    static_assert(sizeof(open_flags) >= sizeof(float) * 4 * APW * 64, "edge staging inside the flag array");
-    if (active) {
-      int lmax = n;
-      if constexpr (CVRP) {
-        lmax = 0;
+    if (p.costs && active) {
+      // route lengths: f32 sum in step order of d[u_{t-1}][u_t] (cvrp/aco.py:135).  64 edges of each of the wave's ants are
+      // gathered with every lane active and staged in LDS; lane 0 of each row adds its ant's 64 values one after the other.
+      const float *dist_b = p.dist + (size_t)b * p.dist_bs;
+      int lmax = 0;
 #pragma unroll
-        for (int r4 = 0; r4 < APW; ++r4) lmax = max(lmax, len_s[wave * APW + r4]);
-      }
-      const int myl = CVRP ? len_s[wave * APW + q] : n;
+      for (int r4 = 0; r4 < APW; ++r4) lmax = max(lmax, len_s[wave * APW + r4]);
+      const int myl = len_s[wave * APW + q];
       float cost = 0.0f;
-      const float *mine_d = dstage[wave][q];
       for (int base = 1; base < lmax; base += 64) {
         const int t = base + lane;
 #pragma unroll
         for (int r4 = 0; r4 < APW; ++r4) {
           const tour_t *tr = tour_s + (size_t)(wave * APW + r4) * TL;
-          const int lr = CVRP ? len_s[wave * APW + r4] : n;
-          float dv = 0.0f;
-          if (t < lr) dv = CVRP ? dist_b[(uint32_t)tr[t - 1] * (uint32_t)n + tr[t]] : dist_b[(uint32_t)tr[t] * (uint32_t)n + tr[t - 1]];
-          dstage[wave][r4][lane] = dv;
+          dstage[wave][r4][lane] = t < len_s[wave * APW + r4] ? dist_b[(uint32_t)tr[t - 1] * (uint32_t)n + tr[t]] : 0.0f;
         }
         __builtin_amdgcn_wave_barrier();
-        if (s == 0 && base < myl) {
-#pragma unroll
-          for (int v4 = 0; v4 < 16; ++v4) {
-            const float4 v = *(const float4 *)(mine_d + 4 * v4);   // (slots past the route's end hold +0.0f)
-            cost = cost + v.x; cost = cost + v.y; cost = cost + v.z; cost = cost + v.w;
-          }
-        }
+        if (s == 0 && base < myl) cost = epi_chunk_sum<64>(cost, dstage[wave][q]);   // (slots past the route's end hold +0.0f)
         __builtin_amdgcn_wave_barrier();
       }
-      if (s == 0 && a0 + q < A) {
-        if constexpr (!CVRP) cost = cost + dist_b[(uint32_t)tour[0] * (uint32_t)n + tour[n - 1]];
-        p.costs[(size_t)b * A + a0 + q] = cost;
-      }
+      if (s == 0 && a0 + q < A) p.costs[(size_t)b * A + a0 + q] = cost;
     }
-  }
-  if (p.nbr) {
-    // the update's table: invert the tours in LDS (the flag array is free now), then 16 lanes write one 64-byte run per
-    // node row.  TSP: nbr[node][ant] = prev | next << 16.  CVRP: successor << 16 (customers are visited once; row 0 is
-    // never read -- the depot's successors are a SET, kept as a bitmap per ant).
-    __syncthreads();
-    uint16_t (*inv)[FL] = reinterpret_cast<uint16_t (*)[FL]>(open_flags);
-    for (int e = threadIdx.x; e < APB * FL / 8; e += 256) ((uint4 *)&inv[0][0])[e] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    if (k16 < nant) {
-      const int lk = CVRP ? len_s[k16] : n;
+    if (p.nbr) {
+      // the update's table: invert the routes in LDS, then APB lanes write one run per node row: successor << 16 (customers are
+      // visited once; row 0 is never read -- the depot's successors are a SET, kept as a bitmap per ant)
+      __syncthreads();
+      for (int e = threadIdx.x; e < APB * FL / 8; e += 256) ((uint4 *)&inv[0][0])[e] = make_uint4(0, 0, 0, 0);
+      __syncthreads();
       const tour_t *tk = tour_s + (size_t)k16 * TL;
-      for (int t = threadIdx.x / APB; t < lk; t += TSTEP) {
-        const int v = tk[t];
-        if (!CVRP || v != 0) inv[k16][v] = (uint16_t)t;
-        if constexpr (CVRP) { if (t >= 1 && tk[t - 1] == 0 && v != 0) atomicOr(&hub_s[k16][v >> 5], 1u << (v & 31)); }
-      }
-    }
-    __syncthreads();
-    uint32_t *nb = p.nbr + (size_t)b * n * A + abase;
-    if (k16 < nant) {
-      const tour_t *tk = tour_s + (size_t)k16 * TL;
-      for (int node = threadIdx.x / APB; node < n; node += TSTEP) {
-        const int t = inv[k16][node];
-        if constexpr (CVRP) {
-          if (node != 0) nb[(size_t)node * A + k16] = (uint32_t)tk[t + 1] << 16;
-        } else {
-          const uint32_t pv = tk[t == 0 ? n - 1 : t - 1], nx = tk[t == n - 1 ? 0 : t + 1];
-          nb[(size_t)node * A + k16] = pv | (nx << 16);
+      if (k16 < nant) {
+        const int lk = len_s[k16];
+        for (int t = threadIdx.x / APB; t < lk; t += TSTEP) {
+          const int v = tk[t];
+          if (v != 0) inv[k16][v] = (uint16_t)t;
+          if (t >= 1 && tk[t - 1] == 0 && v != 0) atomicOr(&hub_s[k16][v >> 5], 1u << (v & 31));
         }
       }
-      if constexpr (CVRP) {
+      __syncthreads();
+      if (k16 < nant) {
+        uint32_t *nb = p.nbr + (size_t)b * n * A + abase;
+        for (int node = threadIdx.x / APB; node < n; node += TSTEP)
+          if (node != 0) nb[(size_t)node * A + k16] = (uint32_t)tk[inv[k16][node] + 1] << 16;
         const int W32 = (n + 31) >> 5;
         uint32_t *hub_a = p.hubmask + ((size_t)b * A + abase + k16) * W32;
         for (int i = threadIdx.x / APB; i < W32; i += TSTEP) hub_a[i] = hub_s[k16][i];

@@ -17,9 +17,10 @@
 // level 2 a compare tree on the winning lane's running sums; the winning lane stores the choice and the ant's lanes read it back.
 // The rare ways (tail walk, dense draw) are wave-cooperative: the 64 lanes serve one ant at a time (candidate
 // k = (c * 64 + lane) * 4 + v, the 64-lane scan).  Tours (u16) and visited flags (bytes, node order) live in LDS; paths / tour
-// lengths / the update's table leave the workgroup in the epilogue of the scan16 family (16 ants = one 128-byte run per row).
+// lengths / the update's table leave the workgroup through the stages of daco_tour_epilogue.h (16 ants = one 128-byte run per row).
 #include "daco_sample_kernel.h"
 #include "daco_head_rows.h"
+#include "daco_tour_epilogue.h"
 
 namespace daco {
 
@@ -233,7 +234,7 @@ __device__ inline float sp_at_least_denorm(float x) {     // max(x, denorm_min) 
 // no workgroup barrier, nothing else added to the loop: the offset is folded into the ant's window pointer at that boundary, so a
 // step's instructions are those of the kernel above).  20 KB per workgroup and 64 registers: eight workgroups per CU, one round.
 // The epilogue copies the early parts back (L2 lines the workgroup wrote itself) into the dead flag array and reads a tour
-// through a two-piece accessor; cost staging and the inverse table share what is left of that array (SP_TOUR, DSW, NI below).
+// through a two-piece accessor; cost staging and the inverse table share what is left of that array (TourSplit, DSW, NI below).
 constexpr int SP_W = 352;                                // ST: window entries per ant
 constexpr int SP_EW = 160;                               // ST: early entries per ant at most (n <= 512: TE <= 160)
 constexpr int SP_ST_DEAD = 16 * (512 + 16) + 4 * 128 + 256;   // ST: flags, bitmaps and spare bytes in front of the window (dead after the loop)
@@ -656,12 +657,15 @@ scan_sparse_kernel(const SampleParams p) {
   sp_args_t pe = (sp_args_t)__builtin_amdgcn_kernarg_segment_ptr();
   if constexpr (ST) asm volatile("" : "+s"(pe));
 #define SP_E(x) (ST ? pe->x : p.x)
+  // (ST <2, false, 4, false, true, true> through the shared stages: 64 VGPRs, no scratch, the step block's instructions; scalar spill
+  // lanes 63 -> 65, the reloads in the rare-way block and none in the step: profiles/tour_epilogue_once.txt part B)
   if (infeasible && SP_E(flags) && lane == 0) atomicOr(SP_E(flags) + b, 1);
   if (SP_E(stats) && lane == 0 && (n_dense | n_tail | n_rej)) {
     atomicAdd(SP_E(stats) + 0, n_dense); atomicAdd(SP_E(stats) + 1, n_tail); atomicAdd(SP_E(stats) + 2, n_rej);
   }
 
   // ------------------------------------------------------------------ epilogue: the workgroup's 16 tours leave
+  // (the stages are those of daco_tour_epilogue.h; the places in dead LDS, the compact rows and the order are this kernel's)
   const int nant = A - abase < APB ? A - abase : APB;
   if constexpr (!TG) {
     uint16_t (*tour_s)[FLT] = reinterpret_cast<uint16_t (*)[FLT]>(tour_mem);
@@ -669,7 +673,9 @@ scan_sparse_kernel(const SampleParams p) {
     // ST: entry t of tour k is early_s[k][t] (t < TE) or late_s[k][t - TE]
     uint16_t (*early_s)[SP_EW] = reinterpret_cast<uint16_t (*)[SP_EW]>(sparse_dyn);
     uint16_t (*late_s)[SP_W] = reinterpret_cast<uint16_t (*)[SP_W]>(tour_mem);
-#define SP_TOUR(k, t) (ST ? ((t) < TE ? early_s[k][t] : late_s[k][(t) - TE]) : tour_s[k][t])
+    std::conditional_t<ST, TourSplit<SP_EW, SP_W>, TourRows<uint16_t>> tours;
+    if constexpr (ST) tours = {&early_s[0][0], &late_s[0][0], TE};
+    else tours = {&tour_s[0][0], FLT};
     if constexpr (ST) {
       if (TE > 0) {
         // the early parts come back from this workgroup's rows of tours16 (its own stores: visible after the barrier, as in the
@@ -682,12 +688,7 @@ scan_sparse_kernel(const SampleParams p) {
         __syncthreads();
       }
     }
-    const int k16 = threadIdx.x & (APB - 1);
-    constexpr int TSTEP = 256 / APB;
-    if (SP_E(paths) && k16 < nant) {
-      int64_t *pb = SP_E(paths) + (size_t)b * n * A + abase;
-      for (int t = threadIdx.x / APB; t < n; t += TSTEP) pb[(size_t)t * A + k16] = (int64_t)SP_TOUR(k16, t);
-    }
+    if (SP_E(paths)) epi_paths<APB>(tours, SP_E(paths) + (size_t)b * n * A + abase, n, A, nant);
     if constexpr (ST) {
       if (!SP_E(paths) && SP_E(tours16)) {
         // compact tours: the early parts are at their place already, the windows follow them (entries TE .. TE + SP_W - 1)
@@ -708,95 +709,48 @@ scan_sparse_kernel(const SampleParams p) {
       }
     }
     if (SP_E(costs)) {
-      // tour lengths (tsp/aco.py:121-132): sum_k d[u_k][u_{k-1}], then the closing edge -- f32, that order.  64 edges of each
-      // of the wave's four ants are gathered with every lane active and staged in the (dead) flag array.
+      // 64 edges of each of the wave's four ants per pass, staged in the (dead) flag array.
       __syncthreads();
-      const float *dist_b = SP_E(dist) + (size_t)b * SP_E(dist_bs);
       // dist_symmetric (the caller's statement: dist[u][v] and dist[v][u] are the same bits): the edge is read from the upper
-      // triangle, dist[min(u, v)][max(u, v)] -- the same values from half the lines.  The eight instances whose workgroups share
-      // an XCD gather from 8 MB of dist through a 4 MB L2; half of that fits (profiles/epilogue_one_pass_ab.txt).
-      const bool tri = SP_E(dist_symmetric) != 0;
+      // triangle (epi_edge).  The eight instances whose workgroups share an XCD gather from 8 MB of dist through a 4 MB L2;
+      // half of that fits (profiles/epilogue_one_pass_ab.txt).
       // (Measured and not kept, same file: the int64 path stores of a pass's steps issued between its gathers and their wait --
       // buffer stores switched off by offset, the wait vmcnt(1).  0.5543-0.5575 against 0.5568-0.5613 ms per iteration alone, 2-3 us
       // in the medians with overlapping ranges on top of the triangle: gathers that miss the L2 share the HBM side with the stores.)
       // (LH: the flag array is four ants' worth; the head table is dead by now and holds the staging rows and the inverse table)
       // (ST: 32 edges of each ant per pass, staged behind the early parts; the sum takes them in the same order)
+      // (Round 6, last session, measured and not kept: four chunks' gathers in flight together -- sixteen loads per lane -- made
+      // the headline launch SLOWER, 0.522 -> 0.532 ms on one box: the phase is bound by the L2's line rate, as DESIGN 9.1 says,
+      // and deeper bursts only disturb the loops of the workgroups still building tours.)
       constexpr int DSW = ST ? 32 : 64;
       float (*dstage)[APW][DSW] = reinterpret_cast<float (*)[APW][DSW]>(LH ? lh_tab : ST ? sparse_dyn + APB * SP_EW * 2 : flag_mem);
-      if (active) {
-        float cost = 0.0f;
-        const float *mine_d = dstage[wave][q];
-        // (Round 6, last session, measured and not kept: four chunks' gathers in flight together -- sixteen loads per lane -- made
-        // the headline launch SLOWER, 0.522 -> 0.532 ms on one box: the phase is bound by the L2's line rate, as DESIGN 9.1 says,
-        // and deeper bursts only disturb the loops of the workgroups still building tours.)
-        for (int base = 1; base < n; base += DSW) {
-          const int t = base + (lane & (DSW - 1));
-#pragma unroll
-          for (int r4 = 0; r4 < APW; r4 += 64 / DSW) {
-            const int kr = wave * APW + r4 + lane / DSW;
-            float dv = 0.0f;
-            if (t < n) {
-              const uint32_t eu = SP_TOUR(kr, t), ev = SP_TOUR(kr, t - 1);
-              const bool sw = tri && ev < eu;
-              dv = dist_b[(sw ? ev : eu) * (uint32_t)n + (sw ? eu : ev)];
-            }
-            dstage[wave][r4 + lane / DSW][lane & (DSW - 1)] = dv;
-          }
-          __builtin_amdgcn_wave_barrier();
-          if (s == 0) {
-#pragma unroll
-            for (int v4 = 0; v4 < DSW / 4; ++v4) {
-              const float4 v = *(const float4 *)(mine_d + 4 * v4);
-              cost = cost + v.x; cost = cost + v.y; cost = cost + v.z; cost = cost + v.w;
-            }
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-        if (s == 0 && a0 + q < A) {
-          const int km = wave * APW + q;
-          const uint32_t eu = SP_TOUR(km, 0), ev = SP_TOUR(km, n - 1);
-          const bool sw = tri && ev < eu;
-          cost = cost + dist_b[(sw ? ev : eu) * (uint32_t)n + (sw ? eu : ev)];
-          SP_E(costs)[(size_t)b * A + a0 + q] = cost;
-        }
-      }
+      if (active)
+        epi_tour_costs<DSW, APW>(tours, wave * APW, nant, n, SP_E(dist) + (size_t)b * SP_E(dist_bs), SP_E(dist_symmetric) != 0,
+                                 &dstage[wave][0][0], SP_E(costs) + (size_t)b * A + abase);
     }
     if (SP_E(nbr)) {
       // the update's table through an inverse-permutation table in the (dead) flag array, eight ants at a time (ST: four, behind
       // the early parts)
       constexpr int NI = ST ? 4 : 8;
-      uint16_t (*inv)[FL] = reinterpret_cast<uint16_t (*)[FL]>(LH ? lh_tab + 4096 : ST ? sparse_dyn + APB * SP_EW * 2 : flag_mem);
+      uint16_t *inv = reinterpret_cast<uint16_t *>(LH ? lh_tab + 4096 : ST ? sparse_dyn + APB * SP_EW * 2 : flag_mem);   // [NI][FL]
       static_assert(LH || ST || APB * FLP >= 8 * FL * (int)sizeof(uint16_t), "inverse table of eight ants inside the flag array");
-      const int k8 = threadIdx.x & (NI - 1);
       for (int half = 0; half < 16 / NI; ++half) {
         const int nh = nant - half * NI < NI ? nant - half * NI : NI;
         __syncthreads();
         if (nh <= 0) break;
-        for (int e = threadIdx.x; e < NI * FL / 8; e += 256) ((uint4 *)&inv[0][0])[e] = make_uint4(0, 0, 0, 0);
-        __syncthreads();
-        const int kt = half * NI + (k8 < nh ? k8 : 0);
-        if (k8 < nh)
-          for (int t = threadIdx.x / NI; t < n; t += 256 / NI) inv[k8][SP_TOUR(kt, t)] = (uint16_t)t;
-        __syncthreads();
         // classic layout [B][n][A]: one 32-byte run per node; grouped (nbr_grouped: [B][ceil(A/8)][n][8]): the eight ants' entries
         // of consecutive nodes are consecutive -- the 256 threads of a pass write 1 KB in one piece
         const int a8 = abase + half * NI;
         uint32_t *nb = SP_E(nbr_grouped) ? SP_E(nbr) + (((size_t)b * ((A + 7) >> 3) + (a8 >> 3)) * n) * 8 + (a8 & 7) : SP_E(nbr) + (size_t)b * n * A + a8;
-        const size_t nstride = SP_E(nbr_grouped) ? 8 : (size_t)A;
-        if (k8 < nh)
-          for (int node = threadIdx.x / NI; node < n; node += 256 / NI) {
-            const int t = inv[k8][node];
-            const int tp = t == 0 ? n - 1 : t - 1, tn = t == n - 1 ? 0 : t + 1;
-            const uint32_t pv = SP_TOUR(kt, tp), nx = SP_TOUR(kt, tn);
-            nb[(size_t)node * nstride + k8] = pv | (nx << 16);
-          }
+        epi_nbr_table<NI>(tours, half * NI, inv, FL, nh, n, nb, SP_E(nbr_grouped) ? 8 : (size_t)A);
       }
     }
-#undef SP_TOUR
 #undef SP_E
   } else {
     // TG: eight tours at a time, global -> LDS (this workgroup wrote them: its stores are visible after the barrier's release /
-    // acquire), into the block the loop no longer needs: [8][FL] tours | [8][FL] inverse table (cost staging before it is built)
+    // acquire), into the block the loop no longer needs: [8][FL] tours | [8][FL] inverse table (cost staging before it is built).
+    // (Costs and table in this copy's own text, on the shared chunk sum and edge address: with either on its shared stage function
+    // tools/ablate_epilogue.py 24 2 2048 1000 ran 0.8-1.3 % slower in every output subset, profiles/tour_epilogue_once.txt part E.)
     uint16_t (*tl)[FL] = reinterpret_cast<uint16_t (*)[FL]>(sparse_dyn);
     uint16_t (*inv)[FL] = reinterpret_cast<uint16_t (*)[FL]>(sparse_dyn + 8 * FL * 2);
     const int k8 = threadIdx.x & 7;
@@ -811,16 +765,12 @@ scan_sparse_kernel(const SampleParams p) {
           if (e / V < nh) reinterpret_cast<uint4 *>(&tl[0][0])[e] = src[e];
       }
       __syncthreads();
-      if (p.paths && k8 < nh) {
-        int64_t *pb = p.paths + (size_t)b * n * A + abase + half * 8;
-        for (int t = threadIdx.x >> 3; t < n; t += 32) pb[(size_t)t * A + k8] = (int64_t)tl[k8][t];
-      }
+      if (p.paths) epi_paths<8>(TourRows<uint16_t>{&tl[0][0], FL}, p.paths + (size_t)b * n * A + abase + half * 8, n, A, nh);
       if (p.costs) {
-        // tour lengths (tsp/aco.py:121-132): sum_k d[u_k][u_{k-1}], then the closing edge -- f32, that order.  64 edges of
-        // each of the wave's two ants are gathered with every lane active and staged in LDS.
+        // 64 edges of each of the wave's two ants per pass, staged where the inverse table is built afterwards; lanes 0 and 32 add
         const float *dist_b = p.dist + (size_t)b * p.dist_bs;
         float (*dstage)[2][64] = reinterpret_cast<float (*)[2][64]>(&inv[0][0]);
-        const int hh = lane >> 5;                             // lanes 0 and 32 sum the wave's two ants
+        const int hh = lane >> 5;
         const int mine = wave * 2 + hh;
         float cost = 0.0f;
         for (int base = 1; base < n; base += 64) {
@@ -828,22 +778,15 @@ scan_sparse_kernel(const SampleParams p) {
 #pragma unroll
           for (int r2 = 0; r2 < 2; ++r2) {
             const uint16_t *tr = tl[wave * 2 + r2];
-            dstage[wave][r2][lane] = t < n && wave * 2 + r2 < nh ? dist_b[(uint32_t)tr[t] * (uint32_t)n + tr[t - 1]] : 0.0f;
+            dstage[wave][r2][lane] = t < n && wave * 2 + r2 < nh ? dist_b[epi_edge(tr[t], tr[t - 1], n, false)] : 0.0f;
           }
           __builtin_amdgcn_wave_barrier();
-          if ((lane & 31) == 0) {
-            const float *md = dstage[wave][hh];
-#pragma unroll
-            for (int v4 = 0; v4 < 16; ++v4) {
-              const float4 v = *(const float4 *)(md + 4 * v4);
-              cost = cost + v.x; cost = cost + v.y; cost = cost + v.z; cost = cost + v.w;
-            }
-          }
+          if ((lane & 31) == 0) cost = epi_chunk_sum<64>(cost, dstage[wave][hh]);
           __builtin_amdgcn_wave_barrier();
         }
         if ((lane & 31) == 0 && mine < nh) {
           const uint16_t *tm = tl[mine];
-          cost = cost + dist_b[(uint32_t)tm[0] * (uint32_t)n + tm[n - 1]];
+          cost = cost + dist_b[epi_edge(tm[0], tm[n - 1], n, false)];
           p.costs[(size_t)b * A + abase + half * 8 + mine] = cost;
         }
       }
@@ -855,8 +798,6 @@ scan_sparse_kernel(const SampleParams p) {
         if (k8 < nh)
           for (int t = threadIdx.x >> 3; t < n; t += 32) inv[k8][tk[t]] = (uint16_t)t;
         __syncthreads();
-        // classic layout [B][n][A]: one 32-byte run per node; grouped (nbr_grouped: [B][ceil(A/8)][n][8]): the eight ants' entries
-        // of consecutive nodes are consecutive -- the 256 threads of a pass write 1 KB in one piece
         const int a8 = abase + half * 8;
         uint32_t *nb = p.nbr_grouped ? p.nbr + (((size_t)b * ((A + 7) >> 3) + (a8 >> 3)) * n) * 8 + (a8 & 7) : p.nbr + (size_t)b * n * A + a8;
         const size_t nstride = p.nbr_grouped ? 8 : (size_t)A;

@@ -16,6 +16,7 @@
 // Draw semantics are the 32-lane variant of the scan specification; the GPU
 // tests hold it bit-exact against the CPU restatement of that specification.
 #include "daco_sample_kernel.h"
+#include "daco_tour_epilogue.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -266,19 +267,16 @@ tsp_scan32_kernel(const SampleParams p) {
 
   // ------------------------------------------------------------------ epilogue: the workgroup's 8 tours leave LDS
   __syncthreads();
+  // (daco_tour_epilogue.h: 8 lanes = one 64-byte run of paths per step row and one 32-byte run of the table per node row)
   const int nant = A - abase < 8 ? A - abase : 8;        // ants of this workgroup (the last one may hold fewer)
-  {
-    // paths[b][t][abase + k]: 8 lanes = one 64-byte run per step row
-    int64_t *pb = p.paths + (size_t)b * n * A + abase;
-    const int k = threadIdx.x & 7;
-    if (k < nant && p.paths)
-      for (int t = threadIdx.x >> 3; t < n; t += 32) pb[(size_t)t * A + k] = (int64_t)tour_s[k][t];
-  }
+  const TourRows<uint16_t> tours{&tour_s[0][0], FL};
+  if (p.paths) epi_paths<8>(tours, p.paths + (size_t)b * n * A + abase, n, A, nant);
   if (p.costs) {
-    // tour lengths (tsp/aco.py:121-132): sum_k d[u_k][u_{k-1}], k = 1..n-1, then the closing edge -- f32, that order.
-    // 64 edges of each of the wave's two ants are gathered with every lane active and staged in LDS; lanes 0 and 32
-    // add their ant's 64 values one after the other.
+    // tour lengths: epi_tour_costs' passes (64 edges of each of the wave's two ants, lanes 0 and 32 add), with this kernel's own
+    // order of the gathers
     const float *dist_b = p.dist + (size_t)b * p.dist_bs;
+    // (the wave's two rows as pointers, not through the accessor: one register less in every instantiation, and <4, true> sits
+    // at the 72 that seven waves per SIMD allow)
     const uint16_t *t0 = tour_s[wave * 2], *t1 = tour_s[wave * 2 + 1];
     const float *mine = dstage[wave][up];
     float cost = 0.0f;
@@ -292,25 +290,19 @@ tsp_scan32_kernel(const SampleParams p) {
         const int t = 1 + c * 64 + lane;
         d0[c] = 0.0f; d1[c] = 0.0f;
         if (t < n) {
-          d0[c] = dist_b[(uint32_t)t0[t] * (uint32_t)n + t0[t - 1]];
-          d1[c] = dist_b[(uint32_t)t1[t] * (uint32_t)n + t1[t - 1]];
+          d0[c] = dist_b[epi_edge(t0[t], t0[t - 1], n, false)];
+          d1[c] = dist_b[epi_edge(t1[t], t1[t - 1], n, false)];
         }
       }
       const uint16_t *tm = up ? t1 : t0;
-      const float closing = dist_b[(uint32_t)tm[0] * (uint32_t)n + tm[n - 1]];
+      const float closing = dist_b[epi_edge(tm[0], tm[n - 1], n, false)];
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         if (1 + c * 64 < n) {                               // uniform
           dstage[wave][0][lane] = d0[c];
           dstage[wave][1][lane] = d1[c];
           __builtin_amdgcn_wave_barrier();
-          if (lead) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-              const float4 v = *(const float4 *)(mine + 4 * q);      // (slots past the tour's end hold +0.0f)
-              cost = cost + v.x; cost = cost + v.y; cost = cost + v.z; cost = cost + v.w;
-            }
-          }
+          if (lead) cost = epi_chunk_sum<64>(cost, mine);
           __builtin_amdgcn_wave_barrier();
         }
       }
@@ -321,23 +313,8 @@ tsp_scan32_kernel(const SampleParams p) {
     }
   }
   if (p.nbr) {
-    // neighbour table nbr[b][node][ant] = prev | next << 16 (what the pheromone update consumes): invert the tours in
-    // LDS (the flag array is free now), then 8 lanes write one 32-byte run per node row
-    __syncthreads();                                     // every wave is done with its flags
-    uint16_t (*inv)[FL] = reinterpret_cast<uint16_t (*)[FL]>(open_flags);
-    for (int e = threadIdx.x; e < 8 * FL / 8; e += 256) ((uint4 *)&inv[0][0])[e] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    const int k = threadIdx.x & 7;
-    if (k < nant)                                         // (the other slots hold no tour: their entries are not nodes)
-      for (int t = threadIdx.x >> 3; t < n; t += 32) inv[k][tour_s[k][t]] = (uint16_t)t;
-    __syncthreads();
-    uint32_t *nb = p.nbr + (size_t)b * n * A + abase;
-    if (k < nant)
-      for (int node = threadIdx.x >> 3; node < n; node += 32) {
-        const int t = inv[k][node];
-        const uint32_t pv = tour_s[k][t == 0 ? n - 1 : t - 1], nx = tour_s[k][t == n - 1 ? 0 : t + 1];
-        nb[(size_t)node * A + k] = pv | (nx << 16);
-      }
+    __syncthreads();                                     // every wave is done with its flags: the array holds the inverse table now
+    epi_nbr_table<8>(tours, 0, reinterpret_cast<uint16_t *>(&open_flags[0][0]), FL, nant, n, p.nbr + (size_t)b * n * A + abase, (size_t)A);
   }
 }
 
