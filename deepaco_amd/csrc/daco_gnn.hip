@@ -26,22 +26,7 @@ constexpr int U = 32;                       // units
 
 constexpr int GNN_SPLIT_MIN_EDGES = 200000;   // above this a layer is two launches (edge | node), below it one
 
-// The two-wide versions of the activations of daco_gnn.h: the same arithmetic on v_pk_* instructions.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ inline f32x2 sigmoid2(f32x2 x) {
-  f32x2 nx;
-  nx.x = fminf(-x.x, 87.0f); nx.y = fminf(-x.y, 87.0f);
-  const f32x2 hi = {L2E_HI, L2E_HI}, lw = {L2E_LO, L2E_LO}, ln2 = {LN2F, LN2F}, one = {1.0f, 1.0f};
-  const f32x2 t = nx * hi;
-  const f32x2 lo = __builtin_elementwise_fma(nx, lw, __builtin_elementwise_fma(nx, hi, -t));
-  f32x2 e;
-  e.x = __builtin_amdgcn_exp2f(t.x); e.y = __builtin_amdgcn_exp2f(t.y);
-  const f32x2 d = one + __builtin_elementwise_fma(e, lo * ln2, e);
-  f32x2 r;
-  r.x = __builtin_amdgcn_rcpf(d.x); r.y = __builtin_amdgcn_rcpf(d.y);
-  return r;
-}
-__device__ inline f32x2 silu2(f32x2 x) { return x * sigmoid2(x); }
+typedef float f32x2 __attribute__((ext_vector_type(2)));   // two elements side by side: v_pk_* instructions
 
 // x = silu(v_lin0(x)); X1234(0) = layer-0 node linears.  8 nodes per 256-thread workgroup.
 __global__ void __launch_bounds__(256)
@@ -162,7 +147,9 @@ __device__ inline void edge_update(int E, int wg, const int *src, const int *dst
 // The neighbour ids of a node are fetched 32 at a time by its lanes (one coalesced load), so the
 // feature gathers X[dst] depend on a lane exchange, not on a second trip to memory, and the
 // compiler can keep several of them in flight.
-__device__ inline void node_update(int n, int wg, int feats, int layer, const int *dst, const int *rowptr, const int *perm,
+// (__forceinline__: the inliner prices this function within five units of its threshold, and a call left in gnn_layer_kernel /
+// gnn_node_kernel costs them 32 / 36 registers)
+__device__ __forceinline__ void node_update(int n, int wg, int feats, int layer, const int *dst, const int *rowptr, const int *perm,
                                    const float *params, const float *sv, const float *tv, const float *x0, const float *X,
                                    const float *w0, float *x1out, float *Xnext, float (*xs)[U]) {
   const int il = threadIdx.x >> 5, o = threadIdx.x & 31;
@@ -257,207 +244,19 @@ gnn_node_kernel(int n, int feats, int layer, const int *dst, const int *rowptr, 
 }
 
 // ---------------- fused layer for src-sorted edge lists (perm == nullptr; the reference's k-NN graphs are built that way,
-// tsp/utils.py:16-27): a wave owns NPW consecutive nodes AND their out-edges, so the old edge state is read once -- it feeds
-// the edge update (w') and, through gate = sigmoid(w0), the node aggregation -- instead of once per half.  Per 32-edge tile:
-// the MFMA tile GEMM and the edge-major epilogue of edge_update, plus gate * x2[dst] written channel-major into a second
-// wave-private LDS tile; lane = channel then adds the tile's edges in edge order, cutting at the nodes' CSR boundaries
-// (wave-uniform scalars).  The wave finishes its nodes itself: x' and the next layer's four node linears.
-// Sum order of the aggregation: the node's edges in list order (a fixed order; the split kernels add four interleaved
-// partial sums -- both are within the fixtures' tolerance of the reference's scatter-mean).
-constexpr int FUSED_MAX_NPW = 16;
-__global__ void __launch_bounds__(256, 3)
-gnn_fused_layer_kernel(int n, int E, int feats, int layer, int npw, const int *src, const int *dst, const int *rowptr,
-                       const float *params, const float *x0, const float *X, const float *w0, float *x1out, float *Xnext,
-                       float *w1out) {
-  __shared__ __attribute__((aligned(16))) float tile_s[4][32][36];
-  __shared__ __attribute__((aligned(16))) float prod_s[4][32][36];            // [channel][edge of the tile]
-  __shared__ float agg_s[4][FUSED_MAX_NPW][U];
-  __shared__ __attribute__((aligned(16))) float we_s[32][36];                 // We, re-read per tile (16 registers less)
-  const float *lp = params + off_layer(feats, layer);
-  const float *We = lp + 32 * 128 + 128, *be = We + 32 * 32;
-  const float *sv = be + 32, *tv = sv + 32, *se = tv + 32, *te = se + 32;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  *reinterpret_cast<float4 *>(&we_s[threadIdx.x >> 3][(threadIdx.x & 7) * 4]) = *reinterpret_cast<const float4 *>(We + threadIdx.x * 4);
-  __syncthreads();                                                            // the only workgroup barrier
-  // Workgroups are dealt round-robin to the 8 XCDs, each with its own 4 MiB L2.  All workgroups are resident at once, so
-  // with the natural numbering every XCD would gather node rows of every graph (64 x TSP-500: 16 MB).  Renumbered, XCD x
-  // owns one contiguous eighth of the nodes -- its gathers stay inside a few graphs' rows (2 MB).
-  const int per_xcd = (int)gridDim.x >> 3;                                    // the grid is a multiple of 8
-  const int block = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-  const int i0 = (block * 4 + wave) * npw;
-  if (i0 >= n) return;
-  const int cnt = min(npw, n - i0);
-  // the wave's CSR boundaries live in lanes 0..cnt of one register (read back with v_readlane: the walk below must not
-  // touch memory, a vector load there would drain the prefetch queue)
-  const int rp = rowptr[i0 + min(lane, cnt)];
-  auto row_at = [&](int j) { return __builtin_amdgcn_readlane(rp, j); };
-  const int ebeg = row_at(0), eend = row_at(cnt);
-  float (*tile)[36] = tile_s[wave], (*prod)[36] = prod_s[wave];
-  const int o = lane & 31, h = lane >> 5, c0 = (lane & 7) * 4;
-#pragma unroll
-  for (int j = 0; j < FUSED_MAX_NPW; ++j) agg_s[wave][j][o] = 0.0f;           // nodes without out-edges aggregate 0
-  const float bias_h = be[o];                       // the accumulator starts from the bias (lane = output channel)
-  const float4 sc = *reinterpret_cast<const float4 *>(se + c0), sh = *reinterpret_cast<const float4 *>(te + c0);
-  // walk state of the aggregation: node i0 + cur collects edges up to seg_end
-  int cur = 0, seg_end = row_at(1);
-  while (cur < cnt && seg_end <= ebeg) { ++cur; seg_end = cur < cnt ? row_at(cur + 1) : 0x7fffffff; }
-  float run = 0.0f;
-  // Every load of the loop is unconditional (edge ids clamped to the wave's last edge; the stores and the products are
-  // masked instead), so one iteration's twelve gathers and the next tile's rows are all in flight together: eight lanes per
-  // edge (4 channels each), eight edges per pass, four passes per tile.
-  const int g8 = lane >> 3, elast = eend - 1;
-  float4 res[4];
-  int sn[4], dn[4];
-  if (ebeg < eend) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int e = min(ebeg + q * 8 + g8, elast);
-      res[q] = *reinterpret_cast<const float4 *>(w0 + (size_t)e * U + c0);
-      sn[q] = src[e]; dn[q] = dst[e];
-    }
-  }
-  for (int e0 = ebeg; e0 < eend; e0 += 32) {
-    float4 a3[4], a4[4], x2[4], old[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      old[q] = res[q];
-      *reinterpret_cast<float4 *>(&tile[q * 8 + g8][c0]) = old[q];
-    }
-    __builtin_amdgcn_wave_barrier();
-    // (values the compiler would otherwise keep across iterations -- a 16-register accumulator seed, the We operands --
-    // and then spill are made to look loop-variant)
-    f32x16 acc;
-    float seed = bias_h;
-    int opaque = 0;
-    asm volatile("" : "+v"(seed), "+s"(opaque));
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = seed;
-    {
-      float a[16], bw[16];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 t = *reinterpret_cast<const float4 *>(&tile[o][h * 16 + q * 4]);
-        a[q * 4 + 0] = t.x; a[q * 4 + 1] = t.y; a[q * 4 + 2] = t.z; a[q * 4 + 3] = t.w;
-        const float4 u = *reinterpret_cast<const float4 *>(&we_s[o][h * 16 + q * 4 + opaque * 4]);
-        bw[q * 4 + 0] = u.x; bw[q * 4 + 1] = u.y; bw[q * 4 + 2] = u.z; bw[q * 4 + 3] = u.w;
-      }
-#pragma unroll
-      for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bw[kk], acc, 0, 0, 0);
-    }
-    // The gates sigmoid(w0) need nothing but the old rows: they are computed here, between the sixteen dependent MFMAs
-    // (64 cycles each, during which the wave would otherwise issue nothing) -- half of the tile's activation work.
-    f32x2 gate[4][2];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x2 w01 = {old[q].x, old[q].y}, w23 = {old[q].z, old[q].w};
-      gate[q][0] = sigmoid2(w01);
-      gate[q][1] = sigmoid2(w23);
-      asm volatile("" : "+v"(gate[q][0]), "+v"(gate[q][1]));                   // computed here, not sunk to their use
-    }
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // one MFMA ...
-      __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);                     // ... then ten VALU instructions of the gates
-    }
-    __builtin_amdgcn_sched_barrier(0);                                        // (nothing else moves into the chain)
-    // behind the matrix work: this tile's twelve gathers, then the next tile's rows and node ids
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      a3[q] = *reinterpret_cast<const float4 *>(X + (size_t)sn[q] * 128 + 64 + c0);
-      a4[q] = *reinterpret_cast<const float4 *>(X + (size_t)dn[q] * 128 + 96 + c0);
-      x2[q] = *reinterpret_cast<const float4 *>(X + (size_t)dn[q] * 128 + 32 + c0);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int e = min(e0 + 32 + q * 8 + g8, elast);
-      res[q] = *reinterpret_cast<const float4 *>(w0 + (size_t)e * U + c0);
-      sn[q] = src[e]; dn[q] = dst[e];
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tile[drow(r, lane)][o] = acc[r];
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int el = q * 8 + g8, e = e0 + el;
-      const bool live = e < eend;
-      const float4 g = *reinterpret_cast<const float4 *>(&tile[el][c0]);
-      const f32x2 y01 = {fmaf(g.x + a3[q].x + a4[q].x, sc.x, sh.x), fmaf(g.y + a3[q].y + a4[q].y, sc.y, sh.y)};
-      const f32x2 y23 = {fmaf(g.z + a3[q].z + a4[q].z, sc.z, sh.z), fmaf(g.w + a3[q].w + a4[q].w, sc.w, sh.w)};
-      const f32x2 s01 = silu2(y01), s23 = silu2(y23);
-      const f32x2 g01 = gate[q][0], g23 = gate[q][1];
-      if (live) {
-        float4 out;
-        out.x = old[q].x + s01.x; out.y = old[q].y + s01.y; out.z = old[q].z + s23.x; out.w = old[q].w + s23.y;
-        *reinterpret_cast<float4 *>(w1out + (size_t)e * U + c0) = out;
-      }
-      prod[c0 + 0][el] = live ? g01.x * x2[q].x : 0.0f;
-      prod[c0 + 1][el] = live ? g01.y * x2[q].y : 0.0f;
-      prod[c0 + 2][el] = live ? g23.x * x2[q].z : 0.0f;
-      prod[c0 + 3][el] = live ? g23.y * x2[q].w : 0.0f;
-    }
-    __builtin_amdgcn_wave_barrier();
-    // lane = channel: the tile's 32 products in edge order, cut at the CSR boundaries
-#pragma unroll 1
-    for (int j = 0; j < 8; ++j) {
-      const float4 v4 = *reinterpret_cast<const float4 *>(&prod[o][j * 4]);
-      const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        run += v[k];
-        const int enext = e0 + j * 4 + k + 1;
-        if (enext == seg_end) {
-          agg_s[wave][cur][o] = run;
-          run = 0.0f;
-          do { ++cur; seg_end = cur < cnt ? row_at(cur + 1) : 0x7fffffff; } while (cur < cnt && seg_end <= enext);
-        }
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-  // the wave's nodes, four at a time: x' = x0 + silu(bn_v(x1 + mean)), then the next layer's node linears (lane -> outputs
-  // lane and lane + 64; the weights are read once per group of four nodes)
-  const float *WT = params + off_layer(feats, layer + 1), *bv = WT + 32 * 128;
-  for (int j0 = 0; j0 < cnt; j0 += 4) {
-    float xn[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      xn[j] = 0.0f;
-      if (j0 + j < cnt) {
-        const int i = i0 + j0 + j;
-        const int deg = row_at(j0 + j + 1) - row_at(j0 + j);
-        const float agg = agg_s[wave][j0 + j][o] / (float)max(deg, 1);
-        const float y = fmaf(X[(size_t)i * 128 + o] + agg, sv[o], tv[o]);
-        xn[j] = x0[(size_t)i * U + o] + silu(y);
-        if (h == 0) x1out[(size_t)i * U + o] = xn[j];
-      }
-    }
-    if (layer == 11) continue;
-    float y0[4], y1[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { y0[j] = bv[lane]; y1[j] = bv[64 + lane]; }
-    for (int c = 0; c < U; ++c) {
-      const float wa = WT[c * 128 + lane], wb = WT[c * 128 + 64 + lane];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float xc = __shfl(xn[j], c, 64);
-        y0[j] = fmaf(xc, wa, y0[j]);
-        y1[j] = fmaf(xc, wb, y1[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j0 + j < cnt) {
-        Xnext[(size_t)(i0 + j0 + j) * 128 + lane] = y0[j];
-        Xnext[(size_t)(i0 + j0 + j) * 128 + 64 + lane] = y1[j];
-      }
-  }
-}
-
-// ---------------- fused layer, second version (round 4).  Same ownership and arithmetic structure as gnn_fused_layer_kernel;
-// what changed is what the counters of round 3 pointed at (154-168 registers -> 3 waves per SIMD, VALU 0.47 of the time, a
-// third of it 64-bit address arithmetic and quarter-rate transcendentals):
+// tsp/utils.py:16-27): a wave owns NPW <= 16 consecutive nodes AND their out-edges, so the old edge state is read once -- it
+// feeds the edge update (w') and, through gate = sigmoid(w0), the node aggregation -- instead of once per half.  Per 32-edge
+// tile: the MFMA tile GEMM and the edge-major epilogue of edge_update, plus gate * x2[dst] written channel-major back into the
+// wave-private LDS tile and added to the nodes' aggregates.  The wave finishes its nodes itself: x' and the next layer's four
+// node linears.
+// Workgroups are dealt round-robin to the 8 XCDs, each with its own 4 MiB L2.  All workgroups are resident at once, so with the
+// natural numbering every XCD would gather node rows of every graph (64 x TSP-500: 16 MB).  Renumbered (the grid is a multiple
+// of 8), XCD x owns one contiguous eighth of the nodes -- its gathers stay inside a few graphs' rows (2 MB).
+// Sum order of the aggregation: the wave's tiles in edge order, eight K-steps per tile, step kk adding the edges kk, 8 + kk,
+// 16 + kk, 24 + kk of the tile that leave the node (one 16x16x4 MFMA) -- a fixed order for a given nodes-per-wave; the split
+// kernels add four interleaved partial sums: both are within the fixtures' tolerance of the reference's scatter-mean.
+// What the counters of an earlier form of this kernel pointed at (154-168 registers -> 3 waves per SIMD, VALU 0.47 of the time,
+// a third of it 64-bit address arithmetic and quarter-rate transcendentals) is built in:
 //   * four waves per SIMD: <= 128 registers and <= 40 KB of LDS per workgroup.  The products gate * x2[dst] go back into the
 //     MFMA tile (all four result rows of a lane are read first), the gate is not kept across the MFMA chain, the MFMA
 //     operands are fetched from LDS in two K-halves;
@@ -469,8 +268,8 @@ gnn_fused_layer_kernel(int n, int E, int feats, int layer, int npw, const int *s
 //     sigmoid(y) = r (1 + e^-w0) -- 3 instead of 4 quarter-rate instructions per element (arguments clamped to e^44 so the
 //     product stays finite; sigmoid(-44) = 8e-20 is zero at the network's 1e-5 tolerance either way);
 //   * the accumulator starts from zero (inline constant) and the bias is folded into the BatchNorm shift; every address is
-//     a uniform base plus a 32-bit byte offset (host guarantees E * 128 < 4 GB).
-// Round 5, after an ablation of this kernel (profiles/r05_gnn_layer_ablation.txt: memory alone and compute alone ~85 us each,
+//     a uniform base plus a 32-bit byte offset (the host sends larger graphs to the split kernels: fits_u32_offsets).
+// After an ablation of this kernel (profiles/r05_gnn_layer_ablation.txt: memory alone and compute alone ~85 us each,
 // together 114; no single part is the bound) -- 120 -> 113 us per launch in alternating profiler runs:
 //   * the aggregate is S x P on the matrix unit (S[node][edge] = 1 where the edge leaves the node), accumulated over the
 //     wave's tiles in two 16x16x4 blocks: the products are read back once, nothing is cut by scalar compares and branches;
@@ -479,13 +278,13 @@ gnn_fused_layer_kernel(int n, int E, int feats, int layer, int npw, const int *s
 //   * e^-x without the residual term of exp_neg (see one_plus_exp_neg2).
 // NOTE: a register spilled INSIDE the tile loop is reloaded behind `s_waitcnt vmcnt(0)`, i.e. behind the next tile's row
 // prefetch (loads return in order) -- that serialises the loop (measured: +5 us with two such reloads).  Check the .s.
-constexpr int F2_MAX_NPW = 16;
+constexpr int F2_MAX_NPW = 16;                            // nodes per wave: rows of agg_s / x3_s, four bits of `sl`, one 16-row S block
 __device__ inline f32x2 one_plus_exp_neg2(f32x2 x) {       // 1 + e^-x, x clamped at -44
   // -min(-x, 44) = max(x, -44): one v_max with a literal each (fminf would add a second instruction that quiets NaNs)
   f32x2 m;
   asm("v_max_f32 %0, 0xc2300000, %1" : "=v"(m.x) : "v"(x.x));
   asm("v_max_f32 %0, 0xc2300000, %1" : "=v"(m.y) : "v"(x.y));
-  // 2^(-x log2 e) on the rounded product alone (no residual term, unlike exp_neg above): the argument's rounding moves
+  // 2^(-x log2 e) on the rounded product alone (no residual term, unlike exp_neg of daco_gnn.h): the argument's rounding moves
   // sigmoid(x) by at most s (1 - s) |x| 2^-24 <= 1.4e-8 and silu(x) by at most 2.7e-8 -- below half an ulp of either wherever
   // they are not themselves below 1e-7 -- and takes four of ten instructions off each of the 2 * 32 * E evaluations of a layer
   const f32x2 nl2e = {-L2E_HI, -L2E_HI}, one = {1.0f, 1.0f};
@@ -500,12 +299,57 @@ __device__ inline f32x2 silu2_fast(f32x2 x) {             // x sigmoid(x) on the
   r.x = __builtin_amdgcn_rcpf(d.x); r.y = __builtin_amdgcn_rcpf(d.y);
   return x * r;
 }
+
+// ---------------- the head on a tile: heu = sigmoid(W3 silu(W2 silu(W1 w + b1) + b2) + b3) for the 32 edge rows e0 .. e0 + 31
+// in the wave's LDS tile `t` (rows from `eend` on are not stored), two chained tile GEMMs with an LDS transpose between them
+// and the 32 -> 1 row sum.  `hp`: the head's parameters (params + off_head).  The caller has put a wave barrier behind the
+// writes of the rows.  Rows of an MFMA tile do not interact, so an edge's bits do not depend on where its tile starts.
+__device__ inline void head_tile(float (*t)[36], const float *hp, int e0, int eend, float *heu) {
+  const float *W1 = hp, *b1 = W1 + 1024, *W2 = b1 + 32, *b2 = W2 + 1024, *W3 = b2 + 32, *b3 = W3 + 32;
+  const int lane = threadIdx.x & 63, o = lane & 31;
+  __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0): the rows are in the tile
+  f32x16 acc = tile_gemm(&t[o][0], W1, lane);
+  __builtin_amdgcn_wave_barrier();
+  {
+    const float bo = b1[o];
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      const f32x2 v = {acc[r] + bo, acc[r + 1] + bo};
+      const f32x2 a = silu2_fast(v);
+      t[drow(r, lane)][o] = a.x; t[drow(r + 1, lane)][o] = a.y;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0): LDS writes of this wave landed
+  acc = tile_gemm(&t[o][0], W2, lane);
+  __builtin_amdgcn_wave_barrier();
+  {
+    const float bo = b2[o], wo = W3[o];
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      const f32x2 v = {acc[r] + bo, acc[r + 1] + bo};
+      const f32x2 a = silu2_fast(v);
+      t[drow(r, lane)][o] = a.x * wo; t[drow(r + 1, lane)][o] = a.y * wo;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  // final 32 -> 1: row sums of the tile, one edge per lane (lanes 0..31), fixed channel order
+  if (lane < 32) {
+    float s = 0.0f;
+#pragma unroll
+    for (int c = 0; c < U; ++c) s = s + t[lane][c];
+    const int e = e0 + lane;
+    if (e < eend) heu[e] = sigmoidf(s + b3[0]);
+  }
+}
+
 // INIT (layer 0 only): the old edge state is not read but made on the fly, w0 = silu(e_lin0(edge_attr)) (tsp/net.py:31) --
 // 4 bytes per edge instead of 128, and no separate launch that writes E * 128 bytes first.
 // HEAD (round 6): the LAST layer with the output head in it (tsp/net.py:59-66 on top of :27-45).  The head only takes the edge
 // state, and layer 12's node state feeds nothing, so this variant runs the edge update of a tile, keeps the new rows in the
-// wavefront's LDS tile and sends them through the head's two 32x32 linears and the 32 -> 1 row sum right there (the tile code
-// of gnn_head_kernel, the same MFMA order per row: the same bits): it writes heu[E] -- 4 bytes per edge -- and neither the edge
+// wavefront's LDS tile and sends them through the head's two 32x32 linears and the 32 -> 1 row sum right there (head_tile, as
+// gnn_head_kernel does: the same bits): it writes heu[E] -- 4 bytes per edge -- and neither the edge
 // state (128 bytes per edge written here and read again by the head launch) nor the node state; no x2 gathers, no aggregate, no
 // node phase.  Used when the caller does not ask for the embedding.
 #ifndef DACO_GNN_F2_OCC
@@ -531,11 +375,12 @@ gnn_fused2_layer_kernel(int n, int E, int feats, int layer, int npw, const int *
   __shared__ __attribute__((aligned(16))) float init_s[INIT ? 2 : 1][INIT ? 32 : 4];
   if (INIT && threadIdx.x < 64) init_s[threadIdx.x >> 5][threadIdx.x & 31] = params[32 * feats + 32 + threadIdx.x];
   __syncthreads();                                                            // the only workgroup barrier
-  const int per_xcd = (int)gridDim.x >> 3;                                    // XCD x owns one contiguous eighth of the nodes
+  const int per_xcd = (int)gridDim.x >> 3;                                    // XCD x owns one contiguous eighth of the nodes (header)
   const int block = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
   const int i0 = (block * 4 + wave) * npw;
   if (i0 >= n) return;
   const int cnt = min(npw, n - i0);
+  // the wave's CSR boundaries live in lanes 0..cnt of one register, read back with v_readlane
   const int rp = rowptr[i0 + min(lane, cnt)];
   auto row_at = [&](int j) { return __builtin_amdgcn_readlane(rp, j); };
   const int ebeg = row_at(0), eend = row_at(cnt);
@@ -702,43 +547,7 @@ gnn_fused2_layer_kernel(int n, int E, int feats, int layer, int npw, const int *
     }
     __builtin_amdgcn_wave_barrier();
     if constexpr (HEAD) {
-      // the head on this tile: heu = sigmoid(W3 silu(W2 silu(W1 w + b1) + b2) + b3)
-      const float *hp = params + off_head(feats);
-      const float *W1 = hp, *b1 = W1 + 1024, *W2 = b1 + 32, *b2 = W2 + 1024, *W3 = b2 + 32, *b3 = W3 + 32;
-      __builtin_amdgcn_s_waitcnt(0xc07f);                                      // lgkmcnt(0): the rows are in the tile
-      f32x16 hacc = tile_gemm(&tile[o][0], W1, lane);
-      __builtin_amdgcn_wave_barrier();
-      {
-        const float bo = b1[o];
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 v = {hacc[r] + bo, hacc[r + 1] + bo};
-          const f32x2 a = silu2_fast(v);
-          tile[drow(r, lane)][o] = a.x; tile[drow(r + 1, lane)][o] = a.y;
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      hacc = tile_gemm(&tile[o][0], W2, lane);
-      __builtin_amdgcn_wave_barrier();
-      {
-        const float bo = b2[o], wo = W3[o];
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 v = {hacc[r] + bo, hacc[r + 1] + bo};
-          const f32x2 a = silu2_fast(v);
-          tile[drow(r, lane)][o] = a.x * wo; tile[drow(r + 1, lane)][o] = a.y * wo;
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      if (lane < 32) {                                                         // 32 -> 1: row sums, fixed channel order
-        float sum = 0.0f;
-#pragma unroll
-        for (int c = 0; c < U; ++c) sum = sum + tile[lane][c];
-        const int e = e0 + lane;
-        if (e < eend) heu[e] = sigmoidf(sum + b3[0]);
-      }
+      head_tile(tile, params + off_head(feats), e0, eend, heu);
       __builtin_amdgcn_wave_barrier();
       continue;
     }
@@ -772,8 +581,8 @@ gnn_fused2_layer_kernel(int n, int E, int feats, int layer, int npw, const int *
   // nothing hides a load's latency here but the wavefront's own other loads: (1) x' = x0 + silu(bn_v(x1 + mean)) for ALL of
   // the wave's nodes with their rows in flight together (lane = channel, half-wave h takes the nodes 2t + h; x' replaces the
   // aggregate in LDS); (2) the next layer's node linears for eight nodes at a time, the weights sixteen loads per batch and
-  // x' read back from LDS as broadcasts -- the same fma order per output as the first version's four-at-a-time loop, which
-  // waited for memory once per node and once per input channel (15 us of a layer's 109).
+  // x' read back from LDS as broadcasts -- one output's fmas in channel order.  (A loop over four nodes at a time
+  // waited for memory once per node and once per input channel: 15 us of a layer's 109.)
   const float *WT = params + off_layer(feats, layer + 1), *bv = WT + 32 * 128;
   {
     constexpr int T = F2_MAX_NPW / 2;
@@ -838,16 +647,13 @@ gnn_fused2_layer_kernel(int n, int E, int feats, int layer, int npw, const int *
   }
 }
 
-// head: heu = sigmoid(W3 silu(W2 silu(W1 w + b1) + b2) + b3), three chained tile GEMMs
+// head as its own launch: a 32-edge tile of the stored edge state per wave through head_tile
 __global__ void __launch_bounds__(256)
 gnn_head_kernel(int E, int feats, const float *params, const float *w, float *heu) {
   __shared__ __attribute__((aligned(16))) float tile[4][32][36];   // 36: keeps float4 rows 16-B aligned
-  const float *hp = params + off_head(feats);
-  const float *W1 = hp, *b1 = W1 + 1024, *W2 = b1 + 32, *b2 = W2 + 1024, *W3 = b2 + 32, *b3 = W3 + 32;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int e0 = (blockIdx.x * 4 + wave) * 32;
   if (e0 >= E) return;
-  const int o = lane & 31;
   float (*t)[36] = tile[wave];
   {                                                       // the 32 x 32 input tile: coalesced 1 KiB runs into LDS
     const int c0 = (lane & 7) * 4;
@@ -858,42 +664,52 @@ gnn_head_kernel(int E, int feats, const float *params, const float *w, float *he
     }
   }
   __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  f32x16 acc = tile_gemm(&t[o][0], W1, lane);
-  __builtin_amdgcn_wave_barrier();
-  {
-    const float bo = b1[o];
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const f32x2 v = {acc[r] + bo, acc[r + 1] + bo};
-      const f32x2 a = silu2_fast(v);
-      t[drow(r, lane)][o] = a.x; t[drow(r + 1, lane)][o] = a.y;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0): LDS writes of this wave landed
-  acc = tile_gemm(&t[o][0], W2, lane);
-  __builtin_amdgcn_wave_barrier();
-  {
-    const float bo = b2[o], wo = W3[o];
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const f32x2 v = {acc[r] + bo, acc[r + 1] + bo};
-      const f32x2 a = silu2_fast(v);
-      t[drow(r, lane)][o] = a.x * wo; t[drow(r + 1, lane)][o] = a.y * wo;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  // final 32 -> 1: row sums of the tile, one edge per lane (lanes 0..31), fixed channel order
-  if (lane < 32) {
-    float s = 0.0f;
-#pragma unroll
-    for (int c = 0; c < U; ++c) s = s + t[lane][c];
-    const int e = e0 + lane;
-    if (e < E) heu[e] = sigmoidf(s + b3[0]);
-  }
+  head_tile(t, params + off_head(feats), e0, E, heu);
 }
+
+// ---------------- host side
+// workspace: node state x [n][32] | node linears X [n][128] | edge state w [E][32], two of each (a layer reads one, writes the other)
+struct GnnWs {
+  float *x[2], *X[2], *w[2];
+  static size_t bytes(int n, int E) {
+    return 2 * align256((size_t)n * 32 * 4) + 2 * align256((size_t)n * 128 * 4) + 2 * align256((size_t)E * 32 * 4);
+  }
+  static GnnWs carve(void *base, int n, int E) {
+    GnnWs ws;
+    char *p = (char *)base;
+    for (int k = 0; k < 2; ++k) { ws.x[k] = (float *)p; p += align256((size_t)n * 32 * 4); }
+    for (int k = 0; k < 2; ++k) { ws.X[k] = (float *)p; p += align256((size_t)n * 128 * 4); }
+    for (int k = 0; k < 2; ++k) { ws.w[k] = (float *)p; p += align256((size_t)E * 32 * 4); }
+    return ws;
+  }
+};
+
+// The fused kernel addresses with 32-bit byte offsets: an edge row is 128 bytes, a row of node linears 512.  A graph past
+// either limit takes the split edge | node kernels, which index with size_t.
+constexpr bool fits_u32_offsets(long n, long E) { return E * 128 < (1L << 32) && n * 512 < (1L << 32); }
+static_assert(fits_u32_offsets(1, (1L << 25) - 1) && !fits_u32_offsets(1, 1L << 25), "edge rows: E * 128 < 2^32");
+static_assert(fits_u32_offsets((1L << 23) - 1, 1) && !fits_u32_offsets(1L << 23, 1), "node rows: n * 512 < 2^32");
+
+// nodes per wave of the fused kernel: the launch should fill the device's wave slots (4 per SIMD at its register budget) a
+// whole number of times -- 1.3 rounds of workgroups cost as much as 2 -- with 4 to 16 nodes per wave
+static int fused_nodes_per_wave(int n) {
+  static int slots = 0;
+  if (!slots) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    slots = cus * 4 * 4;
+  }
+  const int rounds = (n + F2_MAX_NPW * slots - 1) / (F2_MAX_NPW * slots);
+  const int npw = (n + rounds * slots - 1) / (rounds * slots);
+  return npw < 4 ? 4 : npw;
+}
+
+// how the twelve layers of a forward are launched
+enum class GnnRoute {
+  Single,   // one launch per layer, edge and node workgroups side by side (small graphs are launch-bound)
+  Fused,    // gnn_fused2_layer_kernel: src-sorted edge list within 32-bit offsets
+  Split,    // the node and the edge half as two launches: everything else
+};
 
 }  // namespace daco
 
@@ -901,10 +717,7 @@ using namespace daco;
 
 extern "C" size_t daco_gnn_param_floats(int feats) { return off_head(feats) + HEAD_FLOATS; }
 
-extern "C" size_t daco_gnn_workspace_bytes(int n, int E) {
-  if (n <= 0 || E <= 0) return 0;
-  return 2 * align256((size_t)n * 32 * 4) + 2 * align256((size_t)n * 128 * 4) + 2 * align256((size_t)E * 32 * 4);
-}
+extern "C" size_t daco_gnn_workspace_bytes(int n, int E) { return n <= 0 || E <= 0 ? 0 : GnnWs::bytes(n, E); }
 
 extern "C" int daco_gnn_forward(void *stream, int n, int E, int feats, const float *x, const int32_t *src,
                                 const int32_t *dst, const int32_t *rowptr, const int32_t *perm,
@@ -914,74 +727,56 @@ extern "C" int daco_gnn_forward(void *stream, int n, int E, int feats, const flo
     set_error("daco_gnn_forward: bad argument (n=%d E=%d feats=%d)", n, E, feats);
     return DACO_E_BADARG;
   }
-  const size_t need = daco_gnn_workspace_bytes(n, E);
+  const size_t need = GnnWs::bytes(n, E);
   if (workspace_bytes < need) { set_error("daco_gnn_forward: workspace %zu < %zu", workspace_bytes, need); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
-  char *p = (char *)workspace;
-  float *xb[2], *Xb[2], *wb[2];
-  for (int k = 0; k < 2; ++k) { xb[k] = (float *)p; p += align256((size_t)n * 32 * 4); }
-  for (int k = 0; k < 2; ++k) { Xb[k] = (float *)p; p += align256((size_t)n * 128 * 4); }
-  for (int k = 0; k < 2; ++k) { wb[k] = (float *)p; p += align256((size_t)E * 32 * 4); }
-  const int node_blocks = (n + 7) / 8, edge_blocks = (E + 127) / 128;
-  hipLaunchKernelGGL(gnn_node_init_kernel, dim3(node_blocks), dim3(256), 0, s, n, feats, x, params, xb[0], Xb[0]);
-  int cur = 0;
-  // tuning / test knobs, read per call: the edge count from which a layer leaves the single-launch kernel, and the fused
-  // kernel's nodes per wave (0: the split edge | node kernels)
-  const int split_min = getenv("DACO_GNN_SPLIT_MIN_EDGES") ? atoi(getenv("DACO_GNN_SPLIT_MIN_EDGES")) : GNN_SPLIT_MIN_EDGES;
-  const int fused_npw = getenv("DACO_GNN_FUSED_NPW") ? atoi(getenv("DACO_GNN_FUSED_NPW")) : -1;
-  // second version of the fused kernel unless the edge array outgrows 32-bit byte offsets (DACO_GNN_FUSED_V=1: the first)
-  const int fused_v = (getenv("DACO_GNN_FUSED_V") && atoi(getenv("DACO_GNN_FUSED_V")) == 1) || (size_t)E * 128 >= ((size_t)1 << 32) || (size_t)n * 512 >= ((size_t)1 << 32) ? 1 : 2;
-  // nodes per wave of the fused kernel: the launch should fill the device's wave slots (3 per SIMD at its register
-  // budget) a whole number of times -- 1.3 rounds of workgroups cost as much as 2 -- with at most 16 nodes per wave
-  int npw = fused_npw;
-  if (npw < 0) {
-    static int slots = 0;
-    if (!slots) {
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-      slots = cus * 4;
-    }
-    const int slots_v = slots * (fused_v == 2 ? 4 : 3);                 // wave slots: 4 (second version) / 3 waves per SIMD
-    const int rounds = (n + FUSED_MAX_NPW * slots_v - 1) / (FUSED_MAX_NPW * slots_v);
-    npw = (n + rounds * slots_v - 1) / (rounds * slots_v);
-    if (npw < 4) npw = 4;
+  GnnWs ws = GnnWs::carve(workspace, n, E);
+  // tuning / test knobs, read per call: the edge count from which a layer leaves the single-launch kernel, the fused kernel's
+  // nodes per wave (0: the split edge | node kernels; default: fills the device), 0 for the output head as its own launch
+  int split_min = GNN_SPLIT_MIN_EDGES, npw_knob = -1;
+  bool head_knob = true;
+  if (const char *ev = getenv("DACO_GNN_SPLIT_MIN_EDGES")) split_min = atoi(ev);
+  if (const char *ev = getenv("DACO_GNN_FUSED_NPW")) npw_knob = atoi(ev);
+  if (const char *ev = getenv("DACO_GNN_HEAD_FUSED")) head_knob = atoi(ev) != 0;
+  const GnnRoute route = E < split_min ? GnnRoute::Single : !perm && npw_knob != 0 && fits_u32_offsets(n, E) ? GnnRoute::Fused : GnnRoute::Split;
+  // the output head inside the last layer's launch: the fused kernel has that variant, and it stores no last edge state
+  const bool head_fused = route == GnnRoute::Fused && !emb && head_knob;
+  int npw = 0, fused_blocks = 0;
+  if (route == GnnRoute::Fused) {
+    npw = npw_knob < 0 ? fused_nodes_per_wave(n) : npw_knob;
+    if (npw > F2_MAX_NPW) npw = F2_MAX_NPW;
+    fused_blocks = ((n + 4 * npw - 1) / (4 * npw) + 7) / 8 * 8;           // four waves per workgroup; a multiple of 8 (XCD renumbering)
   }
-  if (npw > FUSED_MAX_NPW) npw = FUSED_MAX_NPW;
   const int nt_rows = 1;                                                // non-temporal edge rows (measured 1.81 -> 1.72 ms per forward)
-  const bool fused2 = E >= split_min && !perm && fused_npw != 0 && fused_v == 2;
-  // (the second fused kernel makes layer 0's edge state itself; every other path reads it from the init launch)
-  if (!fused2) hipLaunchKernelGGL(gnn_edge_init_kernel, dim3((unsigned)(((long)E * 8 + 255) / 256)), dim3(256), 0, s, E, feats, edge_attr, params, wb[0]);
-  // the output head inside the last layer's launch (no embedding asked for; DACO_GNN_HEAD_FUSED=0: the separate head launch)
-  const bool head_fused = fused2 && !emb && !(getenv("DACO_GNN_HEAD_FUSED") && atoi(getenv("DACO_GNN_HEAD_FUSED")) == 0);
-  int wcur = 0;
-  for (int l = 0; l < 12; ++l) {
-    float *wout = (l == 11 && emb) ? emb : wb[wcur ^ 1];
-    if (fused2) {
-      const dim3 grid((unsigned)(((n + 4 * npw - 1) / (4 * npw) + 7) / 8 * 8));
-      if (l == 0) hipLaunchKernelGGL((gnn_fused2_layer_kernel<true, false>), grid, dim3(256), 0, s, n, E, feats, l, npw, src, dst, rowptr, params, xb[cur],
-                                     Xb[cur], wb[wcur], xb[cur ^ 1], Xb[cur ^ 1], wout, edge_attr, nt_rows, nullptr);
-      else if (l == 11 && head_fused) hipLaunchKernelGGL((gnn_fused2_layer_kernel<false, true>), grid, dim3(256), 0, s, n, E, feats, l, npw, src, dst, rowptr,
-                                                         params, xb[cur], Xb[cur], wb[wcur], xb[cur ^ 1], Xb[cur ^ 1], wout, edge_attr, nt_rows, heu);
-      else hipLaunchKernelGGL((gnn_fused2_layer_kernel<false, false>), grid, dim3(256), 0, s, n, E, feats, l, npw, src, dst, rowptr, params, xb[cur],
-                              Xb[cur], wb[wcur], xb[cur ^ 1], Xb[cur ^ 1], wout, edge_attr, nt_rows, nullptr);
-    } else if (E >= split_min && !perm && fused_npw != 0) {
-      hipLaunchKernelGGL(gnn_fused_layer_kernel, dim3((unsigned)(((n + 4 * npw - 1) / (4 * npw) + 7) / 8 * 8)), dim3(256), 0, s, n, E, feats, l,
-                         npw, src, dst, rowptr, params, xb[cur], Xb[cur], wb[wcur], xb[cur ^ 1], Xb[cur ^ 1], wout);
-    } else if (E < split_min) {
-      hipLaunchKernelGGL(gnn_layer_kernel, dim3(edge_blocks + node_blocks), dim3(256), 0, s, n, E, feats, l, edge_blocks, src,
-                         dst, rowptr, perm, params, xb[cur], Xb[cur], wb[wcur], xb[cur ^ 1], Xb[cur ^ 1], wout);
-    } else {
-      hipLaunchKernelGGL(gnn_node_kernel, dim3(node_blocks), dim3(256), 0, s, n, feats, l, dst, rowptr, perm, params, xb[cur],
-                         Xb[cur], wb[wcur], xb[cur ^ 1], Xb[cur ^ 1]);
-      hipLaunchKernelGGL(gnn_edge_kernel, dim3(edge_blocks), dim3(256), 0, s, E, feats, l, src, dst, params, Xb[cur], wb[wcur],
-                         wout);
+  const int node_blocks = (n + 7) / 8, edge_blocks = (E + 127) / 128;
+  hipLaunchKernelGGL(gnn_node_init_kernel, dim3(node_blocks), dim3(256), 0, s, n, feats, x, params, ws.x[0], ws.X[0]);
+  // (the fused kernel makes layer 0's edge state itself; the other routes read it from the init launch)
+  if (route != GnnRoute::Fused) hipLaunchKernelGGL(gnn_edge_init_kernel, dim3((unsigned)(((long)E * 8 + 255) / 256)), dim3(256), 0, s, E, feats, edge_attr, params, ws.w[0]);
+  int cur = 0;                                                          // the buffers a layer reads; it writes the others
+  for (int l = 0; l < 12; ++l, cur ^= 1) {
+    const int nxt = cur ^ 1;
+    if (l == 11 && emb) ws.w[nxt] = emb;                                // the last edge state is the embedding the caller asked for
+    switch (route) {
+      case GnnRoute::Single:
+        hipLaunchKernelGGL(gnn_layer_kernel, dim3(edge_blocks + node_blocks), dim3(256), 0, s, n, E, feats, l, edge_blocks, src, dst, rowptr, perm,
+                           params, ws.x[cur], ws.X[cur], ws.w[cur], ws.x[nxt], ws.X[nxt], ws.w[nxt]);
+        break;
+      case GnnRoute::Fused: {
+        const bool head = l == 11 && head_fused;
+        auto *kernel = l == 0 ? gnn_fused2_layer_kernel<true, false> : head ? gnn_fused2_layer_kernel<false, true> : gnn_fused2_layer_kernel<false, false>;
+        hipLaunchKernelGGL(kernel, dim3(fused_blocks), dim3(256), 0, s, n, E, feats, l, npw, src, dst, rowptr, params, ws.x[cur], ws.X[cur], ws.w[cur],
+                           ws.x[nxt], ws.X[nxt], ws.w[nxt], edge_attr, nt_rows, head ? heu : nullptr);
+        break;
+      }
+      case GnnRoute::Split:
+        hipLaunchKernelGGL(gnn_node_kernel, dim3(node_blocks), dim3(256), 0, s, n, feats, l, dst, rowptr, perm, params, ws.x[cur], ws.X[cur], ws.w[cur],
+                           ws.x[nxt], ws.X[nxt]);
+        hipLaunchKernelGGL(gnn_edge_kernel, dim3(edge_blocks), dim3(256), 0, s, E, feats, l, src, dst, params, ws.X[cur], ws.w[cur], ws.w[nxt]);
+        break;
     }
-    if (l == 11 && emb) { wb[wcur ^ 1] = emb; wcur ^= 1; }
-    else wcur ^= 1;
-    cur ^= 1;
   }
   // (a head that walks several tiles per wave with the next rows in flight, W1 / W2 in LDS, was measured: 139 us against
   // this kernel's 131 at 64 x TSP-500 -- not kept)
-  if (!head_fused) hipLaunchKernelGGL(gnn_head_kernel, dim3(edge_blocks), dim3(256), 0, s, E, feats, params, wb[wcur], heu);
+  if (!head_fused) hipLaunchKernelGGL(gnn_head_kernel, dim3(edge_blocks), dim3(256), 0, s, E, feats, params, ws.w[cur], heu);
   return launch_status("gnn kernels");
 }

@@ -160,7 +160,6 @@ def test_two_opt_candidate_entry_points_validate_arguments():
 # knobs that no test or tool sets, each with the reason it is read all the same
 KNOBS_WITHOUT_A_USER = {
     "DACO_LIB_PATH": "selects the build: how two builds of the library are compared in one checkout",
-    "DACO_GNN_FUSED_V": "the first fused GNN layer is still chosen from the size of the edge arrays; no test reaches it at any size",
 }
 
 

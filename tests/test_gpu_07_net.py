@@ -564,6 +564,20 @@ def test_fused_layer_kernel_vs_oracle_on_ragged_sorted_graph(npw, monkeypatch):
     with torch.no_grad():
         heu_split = net(pyg)
     torch.testing.assert_close(heu, heu_split, rtol=1e-5, atol=2e-6)
+    _, emb_split = net.forward_hip(pyg, return_embedding=True)
+    # back on the fused route, the three ways the last layer and the head can be launched: the head inside the last layer's
+    # launch (`heu` above), the head as its own launch over the stored edge state, and the same with the edge state written
+    # to the caller's embedding.  One head_tile serves both head forms and rows of an MFMA tile do not interact, so where an
+    # edge sits in its tile (the fused launch cuts tiles at the waves' first edges, the head launch at multiples of 32) cannot
+    # show: the same bits.  The embedding against the split route's guards the buffer rotation of the layer loop.
+    monkeypatch.setenv("DACO_GNN_FUSED_NPW", str(npw))
+    monkeypatch.setenv("DACO_GNN_HEAD_FUSED", "0")
+    with torch.no_grad():
+        assert torch.equal(net(pyg), heu)
+    monkeypatch.delenv("DACO_GNN_HEAD_FUSED")
+    heu_emb, emb = net.forward_hip(pyg, return_embedding=True)
+    assert torch.equal(heu_emb.view(-1), heu.view(-1))
+    torch.testing.assert_close(emb, emb_split, rtol=1e-5, atol=2e-6)
 
 
 def test_fused_layer_kernel_at_bench_size_equals_per_graph(monkeypatch):
