@@ -43,6 +43,13 @@ SIGNATURES = {
                                       _vp, _l, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _f]),
     "daco_pheromone_update_heads_ut": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _f, _vp, _vp, _vp, _sz,
                                             _vp, _i, _i, _vp, _sz, _vp, _f]),
+    # (the updates that also keep the colony's record: the arguments of the call without `_record`, then tours16, tours_ld, lowest, shortest)
+    "daco_pheromone_update_record": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp,
+                                          _sz, _vp, _i, _vp, _vp]),
+    "daco_pheromone_update_heads_record": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _f, _vp, _vp, _vp, _sz,
+                                                _vp, _l, _f, _f, _vp, _i, _i, _i, _vp, _sz, _vp, _i, _vp, _vp]),
+    "daco_pheromone_update_heads_ut_record": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _f, _vp, _vp, _vp, _sz,
+                                                   _vp, _i, _i, _vp, _sz, _vp, _f, _vp, _i, _vp, _vp]),
     "daco_head_eta": (_l, [_vp, _i, _i, _vp, _l, _vp, _i, _vp, _vp]),
     "daco_allreduce_delta_tau": (_i, [_vp, _vp, _vp, _sz]),
     "daco_tour_costs": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _i, _vp]),

@@ -262,6 +262,30 @@ deposit_rows_kernel(int n, int A, int R, int hub, float *tau, const uint32_t *nb
   const float *cs = costs + (size_t)b * A, *wt = weights ? weights + (size_t)b * A : nullptr;
   HeadUt ut_pre[HEADS == 3 ? UT_PRE : 1];
   if constexpr (SYM && HEADS == 3) ut_prefetch_rows(ut_pre, n, b, i0, Rv, he, threadIdx.x & 63, threadIdx.x >> 6);
+  // The colony's record (he.rec_lowest; symmetric only): what track_best_kernel does, for an update that uses none of it (no
+  // elitist ant, no clamps), by the workgroup of the instance's LAST slab -- the one whose own work is shortest (n = 500, R = 16:
+  // four rows of sixteen).  Each of its wavefronts finds the first minimum of all A costs for itself (the minimum, ties to the
+  // lowest index: what track_best_kernel's three stages of the same comparison arrive at), so no LDS and no barrier are added;
+  // the costs and the record are asked for here, in front of the first chunk and the rows.
+  // (As compiled for <true, 3, true>: the four loads of a pass are issued together behind the head-row prefetch, and the compare
+  // waits for them with vmcnt(0) BEFORE the first chunk's and the rows' loads are issued -- at A = 512 two L2 round trips that this
+  // one workgroup of an instance's 32 does not overlap with its own loads.  Holding the first passes' values in registers across
+  // the chunk loader would overlap them and costs eight registers in every instantiation, two of which (HEADS = 1, 2) are at 128
+  // with scratch already; the launch's median moved 86.4 -> 86.5 us with the wait where it is, so it stays.)
+  const bool rec = SYM && he.rec_lowest != nullptr && i0 + R >= n;
+  float rec_k = __builtin_inff(), rec_low = 0.0f;
+  int rec_i = 0x7fffffff;
+  if (rec) {
+    rec_low = he.rec_lowest[b];
+    for (int a0 = threadIdx.x & 63; a0 < A; a0 += 256) {
+      float c[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) c[u] = a0 + 64 * u < A ? cs[a0 + 64 * u] : __builtin_inff();
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (c[u] < rec_k) { rec_k = c[u]; rec_i = a0 + 64 * u; }
+    }
+  }
   // chunk loader: consecutive threads on consecutive ants of one row (256-byte segments).  Wave 0 runs
   // the chains, so after the first chunk only waves 1..3 fetch: a chain never waits for a prefetch.
   // (Round 6, last session: a loader thread's entries of a chunk are all in flight before the first is waited for.  The loop used
@@ -327,7 +351,21 @@ deposit_rows_kernel(int n, int A, int R, int hub, float *tau, const uint32_t *nb
     for (int i = threadIdx.x; i < cnt; i += blockDim.x)
       if (SYM || i < hub_lo || i >= hub_hi) rows[i] = g[i] * decay;
   }
-  __syncthreads();
+  int rec_take = -1;
+  if (rec) {
+    const KeyIdx rm = wave_arg<false>(rec_k, rec_i);
+    rec_k = rm.key;
+    if (rec_k < rec_low) rec_take = rm.idx;               // `if best_cost < self.lowest_cost` (a minimum below the record has an index)
+  }
+  __syncthreads();                                         // (every wavefront has read the old record: thread 0 may replace it)
+  if (rec_take >= 0) {
+    if (threadIdx.x == 0) he.rec_lowest[b] = rec_k;
+    if (he.rec_shortest) {
+      int64_t *sp = he.rec_shortest + (size_t)b * n;
+      if (he.rec_tours16) { for (int k = threadIdx.x; k < n; k += 256) sp[k] = (int64_t)he.rec_tours16[((size_t)b * A + rec_take) * he.rec_ld + k]; }
+      else for (int k = threadIdx.x; k < n; k += 256) sp[k] = he.rec_paths[((size_t)b * n + k) * A + rec_take];
+    }
+  }
   const int r = SYM ? threadIdx.x >> 1 : threadIdx.x;
   const int sh = SYM ? (threadIdx.x & 1) << 4 : 16;                // prev side: low half-word, next side: high
   const bool chain = r < Rv && (SYM || i0 + r != hub);
@@ -593,6 +631,10 @@ static int pheromone_update_impl(void *stream, int B, int n, int len, int A, flo
   if (hub >= n) { set_error("daco_pheromone_update: hub %d >= n %d", hub, n); return DACO_E_BADARG; }
   if (!symmetric && len < 2) { set_error("daco_pheromone_update: directed deposit needs len >= 2"); return DACO_E_BADARG; }
   if (!symmetric && nbr_in && hub != 0) { set_error("daco_pheromone_update: a directed next_table implies hub = 0"); return DACO_E_BADARG; }
+  if (he.rec_lowest && (!symmetric || elitist || clamp_max || (he.rec_shortest && !he.rec_paths && !he.rec_tours16) || (he.rec_tours16 && he.rec_ld < n))) {
+    set_error("daco_pheromone_update: the record is kept by a symmetric update that does not use it (no elitist ant, no clamps), with a tour from paths or tours16 rows of ld >= n");
+    return DACO_E_BADARG;
+  }
   const size_t need = daco_pheromone_update_workspace_bytes(B, n, len, A);
   if (workspace_bytes < need) { set_error("daco_pheromone_update: workspace %zu < %zu", workspace_bytes, need); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
@@ -656,11 +698,16 @@ extern "C" int daco_pheromone_update(void *stream, int B, int n, int len, int A,
                                weights, hub, workspace, workspace_bytes, HeadEmit{});
 }
 
-extern "C" int daco_pheromone_update_heads(void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,
-                                           float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,
-                                           const uint32_t *nbr_in, const float *weights, void *workspace, size_t workspace_bytes,
-                                           const float *eta, long eta_bstride, float alpha, float beta, const uint16_t *head_id,
-                                           int head_slots, int race, int nbr_grouped, void *sparse_workspace, size_t sparse_workspace_bytes) {
+#define DACO_UPDATE_HEADS_PARAMS void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,                       \
+                                 float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,                 \
+                                 const uint32_t *nbr_in, const float *weights, void *workspace, size_t workspace_bytes,                     \
+                                 const float *eta, long eta_bstride, float alpha, float beta, const uint16_t *head_id,                      \
+                                 int head_slots, int race, int nbr_grouped, void *sparse_workspace, size_t sparse_workspace_bytes
+#define DACO_UPDATE_HEADS_ARGS stream, B, n, A, tau, paths, costs, decay, elitist, clamp_min, clamp_max, floor_val, nbr_in, weights, workspace, \
+                               workspace_bytes, eta, eta_bstride, alpha, beta, head_id, head_slots, race, nbr_grouped, sparse_workspace,    \
+                               sparse_workspace_bytes
+// (he: empty, or the record block of the *_record form)
+static int update_heads_impl(HeadEmit he, DACO_UPDATE_HEADS_PARAMS) {
   if (!eta || !head_id || !sparse_workspace) { set_error("daco_pheromone_update_heads: bad argument"); return DACO_E_BADARG; }
   if (head_slots != 64 && head_slots != 128) { set_error("daco_pheromone_update_heads: head_slots = %d (64 or 128)", head_slots); return DACO_E_BADARG; }
   if (n <= 128 || n > 1024) { set_error("daco_pheromone_update_heads: n=%d outside 129..1024 (the sizes daco_tsp_sample_heads serves)", n); return DACO_E_TOOLARGE; }
@@ -668,7 +715,6 @@ extern "C" int daco_pheromone_update_heads(void *stream, int B, int n, int A, fl
   const size_t need = daco_tsp_sparse_workspace_bytes(B, n, A);
   if (sparse_workspace_bytes < need) { set_error("daco_pheromone_update_heads: sparse workspace %zu < %zu bytes", sparse_workspace_bytes, need); return DACO_E_WORKSPACE; }
   const HeadWs ws = HeadWs::carve(sparse_workspace, B, n, A);                // (the sampler's layout: dense rows, then head rows)
-  HeadEmit he;
   he.eta = eta; he.eta_bs = eta_bstride; he.hid = head_id;
   he.P = ws.P; he.hrow = ws.hrow;
   he.spl = head_slots / 16; he.race = race ? 1 : 0; he.nbr_grouped = nbr_grouped ? 1 : 0;
@@ -679,12 +725,17 @@ extern "C" int daco_pheromone_update_heads(void *stream, int B, int n, int A, fl
                                workspace, workspace_bytes, he);
 }
 
+extern "C" int daco_pheromone_update_heads(DACO_UPDATE_HEADS_PARAMS) { return update_heads_impl(HeadEmit{}, DACO_UPDATE_HEADS_ARGS); }
+
 // the same call in the uniform-tail mode (daco_head_rows.h): head_eta / tail_c from daco_head_eta, whose verdict the caller read
-extern "C" long daco_pheromone_update_heads_ut(void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,
-                                              float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,
-                                              const uint32_t *nbr_in, const float *weights, void *workspace, size_t workspace_bytes,
-                                              const uint16_t *head_id, int head_slots, int nbr_grouped, void *sparse_workspace,
-                                              size_t sparse_workspace_bytes, const float *head_eta, float tail_c) {
+#define DACO_UPDATE_UT_PARAMS void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,                          \
+                              float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,                    \
+                              const uint32_t *nbr_in, const float *weights, void *workspace, size_t workspace_bytes,                        \
+                              const uint16_t *head_id, int head_slots, int nbr_grouped, void *sparse_workspace,                             \
+                              size_t sparse_workspace_bytes, const float *head_eta, float tail_c
+#define DACO_UPDATE_UT_ARGS stream, B, n, A, tau, paths, costs, decay, elitist, clamp_min, clamp_max, floor_val, nbr_in, weights, workspace,    \
+                            workspace_bytes, head_id, head_slots, nbr_grouped, sparse_workspace, sparse_workspace_bytes, head_eta, tail_c
+static long update_heads_ut_impl(HeadEmit he, DACO_UPDATE_UT_PARAMS) {
   if (!head_eta || !head_id || !sparse_workspace || !(tail_c >= 0.0f)) { set_error("daco_pheromone_update_heads_ut: bad argument"); return DACO_E_BADARG; }
   if (head_slots != 64 && head_slots != 128) { set_error("daco_pheromone_update_heads_ut: head_slots = %d (64 or 128)", head_slots); return DACO_E_BADARG; }
   if (n <= 128 || n > 1024) { set_error("daco_pheromone_update_heads_ut: n=%d outside 129..1024 (the sizes daco_tsp_sample_heads serves)", n); return DACO_E_TOOLARGE; }
@@ -692,10 +743,46 @@ extern "C" long daco_pheromone_update_heads_ut(void *stream, int B, int n, int A
   const size_t need = daco_tsp_sparse_workspace_bytes(B, n, A);
   if (sparse_workspace_bytes < need) { set_error("daco_pheromone_update_heads_ut: sparse workspace %zu < %zu bytes", sparse_workspace_bytes, need); return DACO_E_WORKSPACE; }
   const HeadWs ws = HeadWs::carve(sparse_workspace, B, n, A);
-  HeadEmit he;
   he.hid = head_id; he.hrow = ws.hrow; he.heta = head_eta; he.tail_c = tail_c;      // (eta and P stay null: neither is touched)
   he.spl = head_slots / 16; he.nbr_grouped = nbr_grouped ? 1 : 0;
   he.dead = ws.ld; he.ch = ws.ld / 256;
   return pheromone_update_impl(stream, B, n, n, A, tau, paths, costs, decay, elitist, 1, clamp_min, clamp_max, floor_val, nbr_in, weights, 0,
                                workspace, workspace_bytes, he);
 }
+extern "C" long daco_pheromone_update_heads_ut(DACO_UPDATE_UT_PARAMS) { return update_heads_ut_impl(HeadEmit{}, DACO_UPDATE_UT_ARGS); }
+
+// ------------------------------------------------------------------ the record kept by the update launch
+// The three symmetric updates above with daco_track_best / daco_track_best_tours16 done by one of their workgroups (see
+// deposit_rows_kernel): for the plain ant system, whose update uses nothing the record computes.
+static bool record_block(HeadEmit &he, const char *what, const int64_t *paths, const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest) {
+  if (!lowest) { set_error("%s: bad argument (lowest)", what); return false; }
+  he.rec_lowest = lowest; he.rec_shortest = shortest;
+  he.rec_paths = tours16 ? nullptr : paths; he.rec_tours16 = tours16; he.rec_ld = tours_ld;
+  return true;
+}
+
+extern "C" long daco_pheromone_update_record(void *stream, int B, int n, int len, int A, float *tau,
+                                             const int64_t *paths, const float *costs, float decay, int elitist,
+                                             int symmetric, const float *clamp_min, const float *clamp_max,
+                                             float floor_val, const uint32_t *nbr_in, const float *weights, int hub,
+                                             void *workspace, size_t workspace_bytes, const uint16_t *tours16, int tours_ld,
+                                             float *lowest, int64_t *shortest) {
+  HeadEmit he;
+  if (!record_block(he, "daco_pheromone_update_record", paths, tours16, tours_ld, lowest, shortest)) return DACO_E_BADARG;
+  return pheromone_update_impl(stream, B, n, len, A, tau, paths, costs, decay, elitist, symmetric, clamp_min, clamp_max, floor_val, nbr_in,
+                               weights, hub, workspace, workspace_bytes, he);
+}
+extern "C" long daco_pheromone_update_heads_record(DACO_UPDATE_HEADS_PARAMS, const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest) {
+  HeadEmit he;
+  if (!record_block(he, "daco_pheromone_update_heads_record", paths, tours16, tours_ld, lowest, shortest)) return DACO_E_BADARG;
+  return update_heads_impl(he, DACO_UPDATE_HEADS_ARGS);
+}
+extern "C" long daco_pheromone_update_heads_ut_record(DACO_UPDATE_UT_PARAMS, const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest) {
+  HeadEmit he;
+  if (!record_block(he, "daco_pheromone_update_heads_ut_record", paths, tours16, tours_ld, lowest, shortest)) return DACO_E_BADARG;
+  return update_heads_ut_impl(he, DACO_UPDATE_UT_ARGS);
+}
+#undef DACO_UPDATE_HEADS_PARAMS
+#undef DACO_UPDATE_HEADS_ARGS
+#undef DACO_UPDATE_UT_PARAMS
+#undef DACO_UPDATE_UT_ARGS

@@ -232,6 +232,14 @@ struct HeadEmit {
   int nbr_grouped = 0;             // the update's table arrives as [B][ceil(A/8)][n][8] (written by daco_tsp_sample_heads(nbr_grouped = 1))
   const float *heta = nullptr;     // uniform tail: [B][n][16 spl] eta at the head's live ids (daco_head_eta); then eta and P are not touched
   float tail_c = 0.0f;             // uniform tail: eta outside the head
+  // the colony's record kept by the update launch (daco_pheromone_update*_record; rec_lowest = null: not kept): what
+  // track_best_kernel does for an update that uses none of its results -- lowest [B], shortest [B][n] or null, the tours as
+  // int64 paths [B][n][A] or (rec_tours16 != null) u16 rows [B][A][rec_ld]
+  float *rec_lowest = nullptr;
+  int64_t *rec_shortest = nullptr;
+  const int64_t *rec_paths = nullptr;
+  const uint16_t *rec_tours16 = nullptr;
+  int rec_ld = 0;
 };
 
 }  // namespace daco

@@ -688,7 +688,8 @@ scan_sparse_kernel(const SampleParams p) {
         __syncthreads();
       }
     }
-    if (SP_E(paths)) epi_paths<APB>(tours, SP_E(paths) + (size_t)b * n * A + abase, n, A, nant);
+    // (non-temporal: see epi_paths; the LDS-heads variant's few ants keep plain stores)
+    if (SP_E(paths)) epi_paths<APB, !LH>(tours, SP_E(paths) + (size_t)b * n * A + abase, n, A, nant);
     if constexpr (ST) {
       if (!SP_E(paths) && SP_E(tours16)) {
         // compact tours: the early parts are at their place already, the windows follow them (entries TE .. TE + SP_W - 1)
@@ -717,6 +718,10 @@ scan_sparse_kernel(const SampleParams p) {
       // (Measured and not kept, same file: the int64 path stores of a pass's steps issued between its gathers and their wait --
       // buffer stores switched off by offset, the wait vmcnt(1).  0.5543-0.5575 against 0.5568-0.5613 ms per iteration alone, 2-3 us
       // in the medians with overlapping ranges on top of the triangle: gathers that miss the L2 share the HBM side with the stores.)
+      // (Measured and not kept, profiles/iteration_tail_ab.txt: the tour lengths FIRST -- gathers while the L2 holds no write
+      // stream -- then paths and table in either order.  Five alternating runs of the headline iteration per side, ms: this order
+      // 0.5389-0.5415; lengths, paths, table 0.5380-0.5445; lengths, table, paths 0.5360-0.5396 (median 2.4 us ahead, ranges
+      // overlapping).  The order of the stages is not what the epilogue waits for.)
       // (LH: the flag array is four ants' worth; the head table is dead by now and holds the staging rows and the inverse table)
       // (ST: 32 edges of each ant per pass, staged behind the early parts; the sum takes them in the same order)
       // (Round 6, last session, measured and not kept: four chunks' gathers in flight together -- sixteen loads per lane -- made

@@ -37,11 +37,19 @@ struct TourSplit {
 };
 
 // pb = &paths[b][0][first ant of the group]; ants k >= nant of the group do not exist
-template <int G, class Tour>
+// NT: non-temporal stores -- nothing on the device reads the int64 paths again within the launch.  The head-row kernel at
+// n <= 512 asks for it: in a colony's loop its launch goes 453.9 -> 425.5 us and reads 32 MB less past the L2 (FETCH_SIZE 149 477
+// -> 133 838 KiB, WRITE_SIZE unchanged), the iteration 0.5353-0.5371 -> 0.5101-0.5138 ms; stand-alone launches gain 4-9 us only
+// (profiles/iteration_tail_ab.txt part D).  Inferred from that, not counted: the stream of paths (131 MB at TSP-500 x 512 x 64)
+// no longer takes the Infinity Cache from what the next launches read.  The other samplers keep plain stores, unmeasured.
+template <int G, bool NT = false, class Tour>
 __device__ __forceinline__ void epi_paths(const Tour &tour, int64_t *pb, int n, int A, int nant) {
   const int k = threadIdx.x & (G - 1);
   if (k < nant)
-    for (int t = threadIdx.x / G; t < n; t += 256 / G) pb[(size_t)t * A + k] = (int64_t)tour(k, t);
+    for (int t = threadIdx.x / G; t < n; t += 256 / G) {
+      if constexpr (NT) __builtin_nontemporal_store((int64_t)tour(k, t), &pb[(size_t)t * A + k]);
+      else pb[(size_t)t * A + k] = (int64_t)tour(k, t);
+    }
 }
 
 // where the length of edge u -> v is read: dist[u][v], or with `tri` (the caller's statement that dist[u][v] and dist[v][u] are

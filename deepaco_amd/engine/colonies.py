@@ -113,6 +113,9 @@ class BatchedTSP:
         # one number outside the head of every row -- checked on the device once per head table (head_eta_table) -- and this is True
         # (False: the path with dense rows P; the tests and A/B runs compare the two).  Same tours, costs and pheromone.
         self.uniform_tail = True
+        # the plain ant system (no elitist ant, no MMAS, no local search): the record is kept by the update's own launch
+        # (pheromone_update_(record=...)); False: track_best_ in front of the update, the sequence the tests compare against
+        self.record_in_update = True
         self._head_version = None       # heuristic._version the head table was built at (an in-place edit rebuilds table and verdict)
         self._head_ut = None            # (head table object, head_eta_table's answer for it)
         self._dist_sym = None           # (distances._version, dist_is_symmetric's answer): the tour lengths may gather from one triangle
@@ -219,10 +222,15 @@ class BatchedTSP:
                                                counters=self.nls_counters, events=ls_events)
             costs, nbr = (tour_costs(self.distances, paths) if ls_costs is None else ls_costs), None
         # in place: the best-so-far state lives at fixed addresses (a captured graph replays these very writes)
-        new_max = track_best_(costs, paths, self.lowest_cost, self.shortest_path,
-                              mmas_scale=self.n if self.min_max else None, tours16=tours16)
-        cmin, cmax = _mmas_bounds(self, new_max)
-        pheromone_update_(self.pheromone, paths, costs, self.decay, self.elitist, True, cmin, cmax, nbr=nbr, heads=heads)
+        if self.record_in_update and not self.elitist and not self.min_max and self.local_search is None:
+            # the plain ant system: the update uses nothing of the record, and one of its workgroups per instance keeps it
+            pheromone_update_(self.pheromone, paths, costs, self.decay, False, True, nbr=nbr, heads=heads,
+                              record=(self.lowest_cost, self.shortest_path, tours16))
+        else:
+            new_max = track_best_(costs, paths, self.lowest_cost, self.shortest_path,
+                                  mmas_scale=self.n if self.min_max else None, tours16=tours16)
+            cmin, cmax = _mmas_bounds(self, new_max)
+            pheromone_update_(self.pheromone, paths, costs, self.decay, self.elitist, True, cmin, cmax, nbr=nbr, heads=heads)
         self._heads_for = self._heads_state(heads["head"], heads["race"], heads["uniform_tail"]) if heads is not None else None
         return paths, costs
 

@@ -54,7 +54,7 @@ def track_best_(costs, paths, lowest, shortest=None, mmas_scale=None, tours16=No
 
 
 def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, clamp_min=None,
-                      clamp_max=None, floor=0.0, nbr=None, weights=None, hub=0, heads=None):
+                      clamp_max=None, floor=0.0, nbr=None, weights=None, hub=0, heads=None, record=None):
     """In-place ACO.update_pheronome for a batch (tsp/aco.py:95-118, cvrp/aco.py:107-130).
 
     tau [B,n,n] f32 contiguous (modified in place); clamp_min/clamp_max: [B] f32 tensors or None.
@@ -63,8 +63,23 @@ def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, c
     tsp_sample_sparse(..., workspace=workspace, heads_ready=True): the update also writes that call's head rows
     (daco_pheromone_update_heads: tau is read once per iteration instead of twice).  heads["uniform_tail"] = head_eta_table(eta,
     head): the uniform-tail mode where it applies (daco_pheromone_update_heads_ut: the same rows, eta not read, no dense rows
-    written); the next tsp_sample_sparse must then be given the same uniform_tail."""
+    written); the next tsp_sample_sparse must then be given the same uniform_tail.
+    record = (lowest [B], shortest [B,n] or None, tours16 or None): the launch also does track_best_(costs, paths, lowest, shortest,
+    tours16=tours16) -- for the update that uses none of its results (symmetric, no elitist ant, no clamps: the plain ant system);
+    the same record, bit for bit, with one launch less (daco_pheromone_update*_record)."""
     _require_gpu(tau, paths, costs, clamp_min, clamp_max)
+    rec, sfx = (), ""
+    if record is not None:
+        lowest, shortest, tours16 = record
+        _require_gpu(lowest, shortest, tours16)
+        assert symmetric and not elitist and clamp_min is None and clamp_max is None
+        assert lowest.dtype == torch.float32 and lowest.is_contiguous() and lowest.numel() == tau.shape[0]
+        assert shortest is None or (shortest.dtype == torch.int64 and shortest.is_contiguous() and tuple(shortest.shape) == tuple(tau.shape[:2]))
+        assert tours16 is None or (tours16.dtype == torch.int16 and tours16.is_contiguous() and tours16.shape[0] == tau.shape[0])
+        assert shortest is None or tours16 is not None or paths is not None
+        rec = (tours16.data_ptr() if tours16 is not None else None, int(tours16.shape[2]) if tours16 is not None else 0,
+               lowest.data_ptr(), shortest.data_ptr() if shortest is not None else None)
+        sfx = "_record"
     assert tau.dim() == 3 and tau.dtype == torch.float32 and tau.is_contiguous()
     B, n, _ = tau.shape
     if paths is None:                                        # (the table is all the deposit reads)
@@ -79,6 +94,16 @@ def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, c
         weights = _f32c(weights)
     dev = tau.device
     L = _lib.lib()
+
+    def call(name, *args):
+        """the entry point `name`, or its record-keeping form with the record block behind its arguments"""
+        rc = getattr(L, name + sfx)(*args, *rec)
+        _lib.check(rc, name + sfx)
+        return tau
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
     with _on(dev):
         ws = _workspace(dev, L.daco_pheromone_update_workspace_bytes(B, n, length, A), "update")
         if heads is not None:
@@ -86,34 +111,17 @@ def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, c
             eta, ebs = _bstride(heads["eta"], n)
             head, sws = heads["head"], heads["workspace"]
             _require_gpu(eta, head, sws)
+            grouped = int(bool(heads.get("nbr_grouped", False))) if nbr is not None else 0
             ut = heads.get("uniform_tail")
             if ut is not None and uniform_tail_applies(n, tau, eta, heads["alpha"], heads["beta"], heads.get("race", False)):
-                rc = L.daco_pheromone_update_heads_ut(_stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
-                                                      int(bool(elitist)), clamp_min.data_ptr() if clamp_min is not None else None,
-                                                      clamp_max.data_ptr() if clamp_max is not None else None, float(floor),
-                                                      nbr.data_ptr() if nbr is not None else None,
-                                                      weights.data_ptr() if weights is not None else None, ws.data_ptr(), ws.numel(),
-                                                      head.data_ptr(), int(head.shape[2]),
-                                                      int(bool(heads.get("nbr_grouped", False))) if nbr is not None else 0,
-                                                      sws.data_ptr(), sws.numel(), ut[0].data_ptr(), float(ut[1]))
-                _lib.check(rc, "daco_pheromone_update_heads_ut")
-                return tau
-            rc = L.daco_pheromone_update_heads(_stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
-                                               int(bool(elitist)), clamp_min.data_ptr() if clamp_min is not None else None,
-                                               clamp_max.data_ptr() if clamp_max is not None else None, float(floor),
-                                               nbr.data_ptr() if nbr is not None else None,
-                                               weights.data_ptr() if weights is not None else None, ws.data_ptr(), ws.numel(),
-                                               eta.data_ptr(), ebs, float(heads["alpha"]), float(heads["beta"]), head.data_ptr(),
-                                               int(head.shape[2]), int(bool(heads.get("race", False))),
-                                               int(bool(heads.get("nbr_grouped", False))) if nbr is not None else 0, sws.data_ptr(), sws.numel())
-            _lib.check(rc, "daco_pheromone_update_heads")
-            return tau
-        rc = L.daco_pheromone_update(_stream(dev), B, n, length, A, tau.data_ptr(), pptr,
-                                     costs.data_ptr(), float(decay), int(bool(elitist)), int(bool(symmetric)),
-                                     clamp_min.data_ptr() if clamp_min is not None else None,
-                                     clamp_max.data_ptr() if clamp_max is not None else None,
-                                     float(floor), nbr.data_ptr() if nbr is not None else None,
-                                     weights.data_ptr() if weights is not None else None, int(hub),
-                                     ws.data_ptr(), ws.numel())
-    _lib.check(rc, "daco_pheromone_update")
-    return tau
+                return call("daco_pheromone_update_heads_ut", _stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(),
+                            float(decay), int(bool(elitist)), ptr(clamp_min), ptr(clamp_max), float(floor), ptr(nbr), ptr(weights),
+                            ws.data_ptr(), ws.numel(), head.data_ptr(), int(head.shape[2]), grouped, sws.data_ptr(), sws.numel(),
+                            ut[0].data_ptr(), float(ut[1]))
+            return call("daco_pheromone_update_heads", _stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
+                        int(bool(elitist)), ptr(clamp_min), ptr(clamp_max), float(floor), ptr(nbr), ptr(weights), ws.data_ptr(),
+                        ws.numel(), eta.data_ptr(), ebs, float(heads["alpha"]), float(heads["beta"]), head.data_ptr(),
+                        int(head.shape[2]), int(bool(heads.get("race", False))), grouped, sws.data_ptr(), sws.numel())
+        return call("daco_pheromone_update", _stream(dev), B, n, length, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
+                    int(bool(elitist)), int(bool(symmetric)), ptr(clamp_min), ptr(clamp_max), float(floor), ptr(nbr), ptr(weights),
+                    int(hub), ws.data_ptr(), ws.numel())

@@ -555,6 +555,37 @@ long daco_pheromone_update_heads_ut(void *stream, int B, int n, int A, float *ta
                                    void *sparse_workspace, size_t sparse_workspace_bytes,
                                    const float *head_eta, float tail_c);
 
+/* daco_pheromone_update_record, daco_pheromone_update_heads_record, daco_pheromone_update_heads_ut_record -- the three symmetric
+ * updates above, which also keep the colony's record: daco_track_best (tours16 = NULL: the tour is read from `paths`, which must
+ * then be given) or daco_track_best_tours16 (tours16 [B][A][tours_ld] uint16, tours_ld >= n) done by one workgroup per instance
+ * of the update's own launch -- the first minimum of `costs` (ties: the lowest index); if it is < lowest[b], lowest[b] and
+ * shortest[b][0..n) (int64, or NULL) are replaced.  For the update that uses none of this: elitist = 0, no clamps, symmetric = 1
+ * (else DACO_E_BADARG); an elitist or MMAS colony calls daco_track_best first, as before.  tau, the head rows and the record are
+ * bit for bit those of the two calls in a row.  The first arguments are those of the call without `_record`; the status is the
+ * usual DACO_OK / DACO_E_* value typed `long`.  Added under DACO_VERSION 129: new entry points only. */
+long daco_pheromone_update_record(void *stream, int B, int n, int len, int A, float *tau,
+                                  const int64_t *paths, const float *costs, float decay, int elitist,
+                                  int symmetric, const float *clamp_min, const float *clamp_max,
+                                  float floor_val, const uint32_t *nbr, const float *weights, int hub,
+                                  void *workspace, size_t workspace_bytes,
+                                  const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest);
+long daco_pheromone_update_heads_record(void *stream, int B, int n, int A, float *tau,
+                                        const int64_t *paths, const float *costs, float decay, int elitist,
+                                        const float *clamp_min, const float *clamp_max, float floor_val,
+                                        const uint32_t *nbr, const float *weights, void *workspace, size_t workspace_bytes,
+                                        const float *eta, long eta_bstride, float alpha, float beta,
+                                        const uint16_t *head_id, int head_slots, int race, int nbr_grouped,
+                                        void *sparse_workspace, size_t sparse_workspace_bytes,
+                                        const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest);
+long daco_pheromone_update_heads_ut_record(void *stream, int B, int n, int A, float *tau,
+                                           const int64_t *paths, const float *costs, float decay, int elitist,
+                                           const float *clamp_min, const float *clamp_max, float floor_val,
+                                           const uint32_t *nbr, const float *weights, void *workspace, size_t workspace_bytes,
+                                           const uint16_t *head_id, int head_slots, int nbr_grouped,
+                                           void *sparse_workspace, size_t sparse_workspace_bytes,
+                                           const float *head_eta, float tail_c,
+                                           const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest);
+
 /* daco_allreduce_delta_tau -- the ant-sharded colony's one data-path collective (every rank builds the deposits
  * of ITS ants, delta-tau [B][n][n] f32 = daco_pheromone_update(decay = 1) onto zeros; the ranks sum them; every rank applies
  * tau <- decay * tau + delta) for hosts without torch.distributed: ncclAllReduce(sum, f32, in place) on `stream` through the
