@@ -31,36 +31,21 @@ SIGNATURES = {
     "daco_tsp_sparse_tours_offset": (_sz, [_i, _i, _i]),
     "daco_tsp_sparse_resident_per_cu": (_i, [_i, _i, _i]),
     "daco_tsp_sparse_split_tours": (_i, [_i]),
-    "daco_tsp_sample_sparse": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _i, _vp, _i, _u64, _u64, _vp, _u32, _i, _vp, _vp,
-                                    _vp, _l, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "daco_tsp_sample_race_head": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _i, _vp, _i, _u64, _u64, _vp, _u32, _i, _vp, _vp,
-                                       _vp, _l, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "daco_tsp_sample_heads": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _i, _vp, _i, _u64, _u64, _vp, _u32, _i, _vp, _vp,
-                                   _vp, _l, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "daco_tsp_sample_heads": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _i, _vp, _i, _u64, _u64, _vp, _u32, _i, _vp, _vp,
+                                   _vp, _l, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _f]),
+    # (both updates end with the record block: tours16, tours_ld, lowest, shortest)
+    "daco_pheromone_update": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp,
+                                   _sz, _vp, _i, _vp, _vp]),
     "daco_pheromone_update_heads": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _f, _vp, _vp, _vp, _sz,
-                                         _vp, _l, _f, _f, _vp, _i, _i, _i, _vp, _sz]),
-    "daco_tsp_sample_heads_ut": (_l, [_vp, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _i, _vp, _i, _u64, _u64, _vp, _u32, _i, _vp, _vp,
-                                      _vp, _l, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _f]),
-    "daco_pheromone_update_heads_ut": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _f, _vp, _vp, _vp, _sz,
-                                            _vp, _i, _i, _vp, _sz, _vp, _f]),
-    # (the updates that also keep the colony's record: the arguments of the call without `_record`, then tours16, tours_ld, lowest, shortest)
-    "daco_pheromone_update_record": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp,
-                                          _sz, _vp, _i, _vp, _vp]),
-    "daco_pheromone_update_heads_record": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _f, _vp, _vp, _vp, _sz,
-                                                _vp, _l, _f, _f, _vp, _i, _i, _i, _vp, _sz, _vp, _i, _vp, _vp]),
-    "daco_pheromone_update_heads_ut_record": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _f, _vp, _vp, _vp, _sz,
-                                                   _vp, _i, _i, _vp, _sz, _vp, _f, _vp, _i, _vp, _vp]),
+                                         _vp, _l, _f, _f, _vp, _i, _i, _i, _vp, _sz, _vp, _f, _vp, _i, _vp, _vp]),
     "daco_head_eta": (_l, [_vp, _i, _i, _vp, _l, _vp, _i, _vp, _vp]),
     "daco_allreduce_delta_tau": (_i, [_vp, _vp, _vp, _sz]),
     "daco_tour_costs": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _i, _vp]),
     "daco_pheromone_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "daco_pheromone_update": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp,
-                                   _sz]),
     "daco_prob_matrix": (_i, [_vp, _i, _i, _vp, _l, _vp, _l, _f, _f, _i, _vp, _sz]),
     "daco_pick_move": (_i, [_vp, _i, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp]),
     "daco_directed_table_bytes": (_sz, [_i, _i, _i]),
-    "daco_track_best": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f]),
-    "daco_track_best_tours16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f]),
+    "daco_track_best": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f]),
     "daco_cvrp_sample": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _f, _i, _vp, _i, _u64, _u64, _vp, _u32, _i, _i,
                               _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp, C.c_double, _vp, _vp]),
     "daco_sample_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _f, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp,
@@ -132,7 +117,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 129          # include/deepaco_hip.h DACO_VERSION this table was written against
+ABI_VERSION = 130          # include/deepaco_hip.h DACO_VERSION this table was written against
 
 
 class DacoError(RuntimeError):

@@ -564,25 +564,17 @@ extern "C" int daco_tour_costs(void *stream, int B, int n, int len, int A, const
   return launch_status("tour_costs_kernel");
 }
 
+// (tours16 given: the tour comes from those rows and `paths` is not read)
 extern "C" int daco_track_best(void *stream, int B, int len, int A, const float *costs, const int64_t *paths,
+                               const uint16_t *tours16, int tours_ld,
                                float *lowest, int64_t *shortest, int32_t *best_idx, float *mmas_max, float mmas_scale) {
-  if (B <= 0 || len <= 0 || A <= 0 || !costs || !lowest || (shortest && !paths)) {
-    set_error("daco_track_best: bad argument (B=%d len=%d A=%d)", B, len, A);
+  if (B <= 0 || len <= 0 || A <= 0 || !costs || !lowest || (tours16 ? tours_ld < len : (shortest && !paths))) {
+    if (tours16) set_error("daco_track_best: bad argument (B=%d len=%d A=%d ld=%d)", B, len, A, tours_ld);
+    else set_error("daco_track_best: bad argument (B=%d len=%d A=%d)", B, len, A);
     return DACO_E_BADARG;
   }
-  hipLaunchKernelGGL(track_best_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, len, A, costs, paths, lowest, shortest,
-                     best_idx, mmas_max, mmas_scale);
-  return launch_status("track_best_kernel");
-}
-
-extern "C" int daco_track_best_tours16(void *stream, int B, int len, int A, int ld, const float *costs, const uint16_t *tours16,
-                                       float *lowest, int64_t *shortest, int32_t *best_idx, float *mmas_max, float mmas_scale) {
-  if (B <= 0 || len <= 0 || A <= 0 || ld < len || !costs || !lowest || !tours16) {
-    set_error("daco_track_best_tours16: bad argument (B=%d len=%d A=%d ld=%d)", B, len, A, ld);
-    return DACO_E_BADARG;
-  }
-  hipLaunchKernelGGL(track_best_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, len, A, costs, (const int64_t *)nullptr, lowest, shortest,
-                     best_idx, mmas_max, mmas_scale, tours16, ld);
+  hipLaunchKernelGGL(track_best_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, len, A, costs, tours16 ? nullptr : paths, lowest, shortest,
+                     best_idx, mmas_max, mmas_scale, tours16, tours16 ? tours_ld : 0);
   return launch_status("track_best_kernel");
 }
 
@@ -689,100 +681,74 @@ static int pheromone_update_impl(void *stream, int B, int n, int len, int A, flo
   return launch_status("pheromone update");
 }
 
+// What the update launch does besides the deposit, from the arguments of its two exports: the colony's record (lowest given:
+// track_best_kernel's work done by one workgroup per instance, see deposit_rows_kernel -- for the plain ant system, whose update
+// uses nothing the record computes) and, for daco_pheromone_update_heads (ws given), the head rows of the sampler's workspace
+// in the dense-row or (head_eta given) the uniform-tail mode.
+static HeadEmit head_emit(const int64_t *paths, const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest,
+                          const HeadWs *ws = nullptr, bool vec4 = false, const float *eta = nullptr, long eta_bstride = 0,
+                          const uint16_t *head_id = nullptr, int head_slots = 64, int race = 0, int nbr_grouped = 0,
+                          const float *head_eta = nullptr, float tail_c = 0.0f) {
+  HeadEmit he;
+  if (lowest) {
+    he.rec_lowest = lowest; he.rec_shortest = shortest;
+    he.rec_paths = tours16 ? nullptr : paths; he.rec_tours16 = tours16; he.rec_ld = tours_ld;
+  }
+  if (!ws) return he;
+  he.hid = head_id; he.hrow = ws->hrow;                                       // (the sampler's layout: dense rows, then head rows)
+  he.spl = head_slots / 16; he.nbr_grouped = nbr_grouped ? 1 : 0;
+  he.dead = ws->ld;
+  if (head_eta) {                                                             // (eta and P stay null: neither is touched)
+    he.heta = head_eta; he.tail_c = tail_c;
+    he.ch = ws->ld / 256;
+  } else {
+    he.eta = eta; he.eta_bs = eta_bstride; he.P = ws->P;
+    he.race = race ? 1 : 0;
+    he.ch = vec4 ? ws->ld / 256 : -(ws->ld / 256);
+  }
+  return he;
+}
+
+// (a record tour or compact rows with no record to keep: a caller's slip, refused)
+static bool record_without_lowest(const char *what, const uint16_t *tours16, float *lowest, int64_t *shortest) {
+  if (lowest || (!shortest && !tours16)) return false;
+  set_error("%s: bad argument (lowest)", what);
+  return true;
+}
+
 extern "C" int daco_pheromone_update(void *stream, int B, int n, int len, int A, float *tau,
                                      const int64_t *paths, const float *costs, float decay, int elitist,
                                      int symmetric, const float *clamp_min, const float *clamp_max,
                                      float floor_val, const uint32_t *nbr_in, const float *weights, int hub,
-                                     void *workspace, size_t workspace_bytes) {
+                                     void *workspace, size_t workspace_bytes,
+                                     const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest) {
+  if (record_without_lowest("daco_pheromone_update", tours16, lowest, shortest)) return DACO_E_BADARG;
   return pheromone_update_impl(stream, B, n, len, A, tau, paths, costs, decay, elitist, symmetric, clamp_min, clamp_max, floor_val, nbr_in,
-                               weights, hub, workspace, workspace_bytes, HeadEmit{});
+                               weights, hub, workspace, workspace_bytes, head_emit(paths, tours16, tours_ld, lowest, shortest));
 }
 
-#define DACO_UPDATE_HEADS_PARAMS void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,                       \
-                                 float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,                 \
-                                 const uint32_t *nbr_in, const float *weights, void *workspace, size_t workspace_bytes,                     \
-                                 const float *eta, long eta_bstride, float alpha, float beta, const uint16_t *head_id,                      \
-                                 int head_slots, int race, int nbr_grouped, void *sparse_workspace, size_t sparse_workspace_bytes
-#define DACO_UPDATE_HEADS_ARGS stream, B, n, A, tau, paths, costs, decay, elitist, clamp_min, clamp_max, floor_val, nbr_in, weights, workspace, \
-                               workspace_bytes, eta, eta_bstride, alpha, beta, head_id, head_slots, race, nbr_grouped, sparse_workspace,    \
-                               sparse_workspace_bytes
-// (he: empty, or the record block of the *_record form)
-static int update_heads_impl(HeadEmit he, DACO_UPDATE_HEADS_PARAMS) {
-  if (!eta || !head_id || !sparse_workspace) { set_error("daco_pheromone_update_heads: bad argument"); return DACO_E_BADARG; }
-  if (head_slots != 64 && head_slots != 128) { set_error("daco_pheromone_update_heads: head_slots = %d (64 or 128)", head_slots); return DACO_E_BADARG; }
-  if (n <= 128 || n > 1024) { set_error("daco_pheromone_update_heads: n=%d outside 129..1024 (the sizes daco_tsp_sample_heads serves)", n); return DACO_E_TOOLARGE; }
-  if (alpha != 1.0f || beta != 1.0f) { set_error("daco_pheromone_update_heads: alpha = beta = 1 only (the rows of tau are formed here; other exponents take the sampler's own pass)"); return DACO_E_BADARG; }
+extern "C" int daco_pheromone_update_heads(void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,
+                                           float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,
+                                           const uint32_t *nbr_in, const float *weights, void *workspace, size_t workspace_bytes,
+                                           const float *eta, long eta_bstride, float alpha, float beta, const uint16_t *head_id,
+                                           int head_slots, int race, int nbr_grouped, void *sparse_workspace, size_t sparse_workspace_bytes,
+                                           const float *head_eta, float tail_c,
+                                           const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest) {
+  const char *const what = "daco_pheromone_update_heads";
+  if (record_without_lowest(what, tours16, lowest, shortest)) return DACO_E_BADARG;
+  const bool ut = head_eta != nullptr;                                        // the uniform-tail mode (daco_head_rows.h)
+  if ((ut ? !(tail_c >= 0.0f) : (!eta || tail_c != 0.0f)) || !head_id || !sparse_workspace) { set_error("%s: bad argument", what); return DACO_E_BADARG; }
+  if (head_slots != 64 && head_slots != 128) { set_error("%s: head_slots = %d (64 or 128)", what, head_slots); return DACO_E_BADARG; }
+  if (n <= 128 || n > 1024) { set_error("%s: n=%d outside 129..1024 (the sizes daco_tsp_sample_heads serves)", what, n); return DACO_E_TOOLARGE; }
+  if (alpha != 1.0f || beta != 1.0f) { set_error("%s: alpha = beta = 1 only (the rows of tau are formed here; other exponents take the sampler's own pass)", what); return DACO_E_BADARG; }
+  if (ut && race) { set_error("%s: the uniform-tail mode serves the scan draw (race = 0)", what); return DACO_E_BADARG; }
+  if (ut && ((n & 3) != 0 || ((uintptr_t)tau & 15) != 0)) { set_error("%s: the uniform-tail mode needs n %% 4 == 0 and 16-byte-aligned rows of tau (n=%d)", what, n); return DACO_E_BADARG; }
   const size_t need = daco_tsp_sparse_workspace_bytes(B, n, A);
-  if (sparse_workspace_bytes < need) { set_error("daco_pheromone_update_heads: sparse workspace %zu < %zu bytes", sparse_workspace_bytes, need); return DACO_E_WORKSPACE; }
-  const HeadWs ws = HeadWs::carve(sparse_workspace, B, n, A);                // (the sampler's layout: dense rows, then head rows)
-  he.eta = eta; he.eta_bs = eta_bstride; he.hid = head_id;
-  he.P = ws.P; he.hrow = ws.hrow;
-  he.spl = head_slots / 16; he.race = race ? 1 : 0; he.nbr_grouped = nbr_grouped ? 1 : 0;
-  he.dead = ws.ld;
-  const bool vec4 = rows_vec4(n, tau, (long)n * n, eta, eta_bstride);
-  he.ch = vec4 ? ws.ld / 256 : -(ws.ld / 256);
-  return pheromone_update_impl(stream, B, n, n, A, tau, paths, costs, decay, elitist, 1, clamp_min, clamp_max, floor_val, nbr_in, weights, 0,
-                               workspace, workspace_bytes, he);
-}
-
-extern "C" int daco_pheromone_update_heads(DACO_UPDATE_HEADS_PARAMS) { return update_heads_impl(HeadEmit{}, DACO_UPDATE_HEADS_ARGS); }
-
-// the same call in the uniform-tail mode (daco_head_rows.h): head_eta / tail_c from daco_head_eta, whose verdict the caller read
-#define DACO_UPDATE_UT_PARAMS void *stream, int B, int n, int A, float *tau, const int64_t *paths, const float *costs,                          \
-                              float decay, int elitist, const float *clamp_min, const float *clamp_max, float floor_val,                    \
-                              const uint32_t *nbr_in, const float *weights, void *workspace, size_t workspace_bytes,                        \
-                              const uint16_t *head_id, int head_slots, int nbr_grouped, void *sparse_workspace,                             \
-                              size_t sparse_workspace_bytes, const float *head_eta, float tail_c
-#define DACO_UPDATE_UT_ARGS stream, B, n, A, tau, paths, costs, decay, elitist, clamp_min, clamp_max, floor_val, nbr_in, weights, workspace,    \
-                            workspace_bytes, head_id, head_slots, nbr_grouped, sparse_workspace, sparse_workspace_bytes, head_eta, tail_c
-static long update_heads_ut_impl(HeadEmit he, DACO_UPDATE_UT_PARAMS) {
-  if (!head_eta || !head_id || !sparse_workspace || !(tail_c >= 0.0f)) { set_error("daco_pheromone_update_heads_ut: bad argument"); return DACO_E_BADARG; }
-  if (head_slots != 64 && head_slots != 128) { set_error("daco_pheromone_update_heads_ut: head_slots = %d (64 or 128)", head_slots); return DACO_E_BADARG; }
-  if (n <= 128 || n > 1024) { set_error("daco_pheromone_update_heads_ut: n=%d outside 129..1024 (the sizes daco_tsp_sample_heads serves)", n); return DACO_E_TOOLARGE; }
-  if ((n & 3) != 0 || ((uintptr_t)tau & 15) != 0) { set_error("daco_pheromone_update_heads_ut: the uniform-tail mode needs n %% 4 == 0 and 16-byte-aligned rows of tau (n=%d)", n); return DACO_E_BADARG; }
-  const size_t need = daco_tsp_sparse_workspace_bytes(B, n, A);
-  if (sparse_workspace_bytes < need) { set_error("daco_pheromone_update_heads_ut: sparse workspace %zu < %zu bytes", sparse_workspace_bytes, need); return DACO_E_WORKSPACE; }
+  if (sparse_workspace_bytes < need) { set_error("%s: sparse workspace %zu < %zu bytes", what, sparse_workspace_bytes, need); return DACO_E_WORKSPACE; }
   const HeadWs ws = HeadWs::carve(sparse_workspace, B, n, A);
-  he.hid = head_id; he.hrow = ws.hrow; he.heta = head_eta; he.tail_c = tail_c;      // (eta and P stay null: neither is touched)
-  he.spl = head_slots / 16; he.nbr_grouped = nbr_grouped ? 1 : 0;
-  he.dead = ws.ld; he.ch = ws.ld / 256;
+  const bool vec4 = !ut && rows_vec4(n, tau, (long)n * n, eta, eta_bstride);
   return pheromone_update_impl(stream, B, n, n, A, tau, paths, costs, decay, elitist, 1, clamp_min, clamp_max, floor_val, nbr_in, weights, 0,
-                               workspace, workspace_bytes, he);
+                               workspace, workspace_bytes,
+                               head_emit(paths, tours16, tours_ld, lowest, shortest, &ws, vec4, eta, eta_bstride, head_id, head_slots, race,
+                                         nbr_grouped, head_eta, tail_c));
 }
-extern "C" long daco_pheromone_update_heads_ut(DACO_UPDATE_UT_PARAMS) { return update_heads_ut_impl(HeadEmit{}, DACO_UPDATE_UT_ARGS); }
-
-// ------------------------------------------------------------------ the record kept by the update launch
-// The three symmetric updates above with daco_track_best / daco_track_best_tours16 done by one of their workgroups (see
-// deposit_rows_kernel): for the plain ant system, whose update uses nothing the record computes.
-static bool record_block(HeadEmit &he, const char *what, const int64_t *paths, const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest) {
-  if (!lowest) { set_error("%s: bad argument (lowest)", what); return false; }
-  he.rec_lowest = lowest; he.rec_shortest = shortest;
-  he.rec_paths = tours16 ? nullptr : paths; he.rec_tours16 = tours16; he.rec_ld = tours_ld;
-  return true;
-}
-
-extern "C" long daco_pheromone_update_record(void *stream, int B, int n, int len, int A, float *tau,
-                                             const int64_t *paths, const float *costs, float decay, int elitist,
-                                             int symmetric, const float *clamp_min, const float *clamp_max,
-                                             float floor_val, const uint32_t *nbr_in, const float *weights, int hub,
-                                             void *workspace, size_t workspace_bytes, const uint16_t *tours16, int tours_ld,
-                                             float *lowest, int64_t *shortest) {
-  HeadEmit he;
-  if (!record_block(he, "daco_pheromone_update_record", paths, tours16, tours_ld, lowest, shortest)) return DACO_E_BADARG;
-  return pheromone_update_impl(stream, B, n, len, A, tau, paths, costs, decay, elitist, symmetric, clamp_min, clamp_max, floor_val, nbr_in,
-                               weights, hub, workspace, workspace_bytes, he);
-}
-extern "C" long daco_pheromone_update_heads_record(DACO_UPDATE_HEADS_PARAMS, const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest) {
-  HeadEmit he;
-  if (!record_block(he, "daco_pheromone_update_heads_record", paths, tours16, tours_ld, lowest, shortest)) return DACO_E_BADARG;
-  return update_heads_impl(he, DACO_UPDATE_HEADS_ARGS);
-}
-extern "C" long daco_pheromone_update_heads_ut_record(DACO_UPDATE_UT_PARAMS, const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest) {
-  HeadEmit he;
-  if (!record_block(he, "daco_pheromone_update_heads_ut_record", paths, tours16, tours_ld, lowest, shortest)) return DACO_E_BADARG;
-  return update_heads_ut_impl(he, DACO_UPDATE_UT_ARGS);
-}
-#undef DACO_UPDATE_HEADS_PARAMS
-#undef DACO_UPDATE_HEADS_ARGS
-#undef DACO_UPDATE_UT_PARAMS
-#undef DACO_UPDATE_UT_ARGS

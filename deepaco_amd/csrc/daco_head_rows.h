@@ -232,7 +232,7 @@ struct HeadEmit {
   int nbr_grouped = 0;             // the update's table arrives as [B][ceil(A/8)][n][8] (written by daco_tsp_sample_heads(nbr_grouped = 1))
   const float *heta = nullptr;     // uniform tail: [B][n][16 spl] eta at the head's live ids (daco_head_eta); then eta and P are not touched
   float tail_c = 0.0f;             // uniform tail: eta outside the head
-  // the colony's record kept by the update launch (daco_pheromone_update*_record; rec_lowest = null: not kept): what
+  // the colony's record kept by the update launch (daco_pheromone_update / _heads with `lowest`; rec_lowest = null: not kept): what
   // track_best_kernel does for an update that uses none of its results -- lowest [B], shortest [B][n] or null, the tours as
   // int64 paths [B][n][A] or (rec_tours16 != null) u16 rows [B][A][rec_ld]
   float *rec_lowest = nullptr;

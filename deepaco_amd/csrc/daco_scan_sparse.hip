@@ -243,7 +243,7 @@ static_assert(SP_ST_LDS <= 160 * 1024 / 8 && SP_ST_DEAD % 16 == 0, "ST: eight wo
 static_assert(SP_ST_DEAD >= 16 * SP_EW * 2 + 4 * 512 * 2, "ST: early parts and the inverse table of four ants inside the dead bytes");
 
 // (ST's epilogue reads `p` again from the start of the kernel-argument segment: `p` must stay the kernel's FIRST explicit
-// argument, and every launch passes exactly this struct -- sample_sparse_impl is the only launch site.)
+// argument, and every launch passes exactly this struct -- daco_tsp_sample_heads is the only launch site.)
 static_assert(std::is_trivially_copyable<SampleParams>::value, "SampleParams is read back from the kernel-argument segment as plain bytes");
 // UT (scan draw only): the uniform-tail mode.  No dense rows P exist; the rare ways walk the row of tau (SpRowUT / SpRowTE above).
 // Only the code behind the rare-way branch differs: the step itself is the same instructions.
@@ -886,12 +886,17 @@ extern "C" int daco_tsp_sparse_resident_per_cu(int n, int head_slots, int race) 
   return nb;
 }
 
-static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, int nbr_grouped, const char *what, void *stream, int B, int n, int A, const float *tau, long tau_bstride, const float *eta,
-                                      long eta_bstride, float alpha, float beta, const uint16_t *head_id, int head_slots, const int64_t *start,
-                                      int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
-                                      uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
-                                      long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
-                                      size_t workspace_bytes, void *ev_begin, void *ev_end, const float *head_eta = nullptr, float tail_c = 0.0f) {
+// The one launch site of the head-row sampler.  race / heads_ready / head_live_max / nbr_grouped / dist_symmetric and the
+// uniform-tail mode (head_eta / tail_c from daco_head_eta, whose verdict the caller read) are described at the prototype.
+extern "C" int daco_tsp_sample_heads(void *stream, int race, int heads_ready, int head_live_max, int nbr_grouped, int dist_symmetric,
+                                     int B, int n, int A, const float *tau, long tau_bstride, const float *eta,
+                                     long eta_bstride, float alpha, float beta, const uint16_t *head_id, int head_slots, const int64_t *start,
+                                     int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
+                                     uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
+                                     long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
+                                     size_t workspace_bytes, void *ev_begin, void *ev_end, const float *head_eta, float tail_c) {
+  const char *const what = "daco_tsp_sample_heads";
+  if (!head_eta && tail_c != 0.0f) { set_error("%s: bad argument (head_eta)", what); return DACO_E_BADARG; }     // (a tail without its table)
   if (B <= 0 || A <= 0 || !tau || !eta || !head_id || !workspace || (!paths && !nbr && !costs)) {
     set_error("%s: bad argument (B=%d n=%d A=%d)", what, B, n, A);
     return DACO_E_BADARG;
@@ -907,6 +912,11 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   const HeadWs ws = HeadWs::carve(workspace, B, n, A);
   const int ld = ws.ld;
   const int spl = head_slots / 16;
+  const bool ut = head_eta != nullptr;                  // the uniform-tail mode
+  if (ut && (race || alpha != 1.0f || beta != 1.0f || !rows_vec4(n, tau, tau_bstride, eta, eta_bstride) || !(tail_c >= 0.0f))) {
+    set_error("%s: the uniform-tail mode serves the scan draw with alpha = beta = 1, n %% 4 == 0, 16-byte-aligned rows of tau and eta and tail_c >= 0 (n=%d)", what, n);
+    return DACO_E_BADARG;
+  }
   if (alpha != 1.0f || beta != 1.0f) {
     // the kernels take unit exponents: the powers are applied to the matrices first, into the tail of a `general` workspace
     const size_t need_g = daco_tsp_sparse_workspace_bytes_general(B, n, A);
@@ -926,11 +936,6 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
     alpha = beta = 1.0f;
   }
   const bool vec4 = rows_vec4(n, tau, tau_bstride, eta, eta_bstride);
-  const bool ut = head_eta != nullptr;                  // the uniform-tail mode (daco_tsp_sample_heads_ut)
-  if (ut && (race || !vec4 || alpha != 1.0f || beta != 1.0f || !(tail_c >= 0.0f))) {
-    set_error("%s: the uniform-tail mode serves the scan draw with alpha = beta = 1, n %% 4 == 0, 16-byte-aligned rows of tau and eta and tail_c >= 0 (n=%d)", what, n);
-    return DACO_E_BADARG;
-  }
   if (ut && !heads_ready) {
     const dim3 pg((unsigned)(((long)B * n + 3) / 4));
     if (ld <= 512) hipLaunchKernelGGL((sparse_prepass_ut_kernel<2>), pg, dim3(256), 0, s, B, n, ld / 256, tau, tau_bstride, head_eta, tail_c, head_id, ws.hrow, spl, ld);
@@ -950,7 +955,7 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   sp.start = start; sp.fixed_start = fixed_start;
   sp.tau = tau; sp.tau_bs = tau_bstride; sp.eta = eta; sp.eta_bs = eta_bstride; sp.tail_c = tail_c;
   sp.iter_dev = iter_offset; sp.gid_bstride = ant_gid_bstride;
-  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr; sp.nbr_grouped = nbr_grouped & 1; sp.dist_symmetric = (nbr_grouped >> 1) & 1;
+  sp.dist = dist; sp.dist_bs = dist_bstride; sp.costs = costs; sp.nbr = nbr; sp.nbr_grouped = nbr_grouped ? 1 : 0; sp.dist_symmetric = dist_symmetric ? 1 : 0;
   sp.hval = (const float *)ws.hrow; sp.hid = head_id; sp.stats = stats; sp.tours16 = ws.tours16;
   if (const int rc = record_event(ev_begin, s, "ev_begin")) return rc;
   // few ants (no more workgroups of four than the chip has CUs) and a head table that fits a CU's LDS: the LDS-heads variant
@@ -980,43 +985,4 @@ static int sample_sparse_impl(bool race, bool heads_ready, int head_live_max, in
   }
   if (const int rc = launch_status("scan_sparse_kernel")) return rc;
   return record_event(ev_end, s, "ev_end");
-}
-
-#define DACO_SPARSE_ARGS stream, B, n, A, tau, tau_bstride, eta, eta_bstride, alpha, beta, head_id, head_slots, start, fixed_start, seed, iter, \
-                         iter_offset, ant_gid0, ant_gid_bstride, paths, flags, dist, dist_bstride, costs, nbr, stats, workspace, \
-                         workspace_bytes, ev_begin, ev_end
-extern "C" int daco_tsp_sample_sparse(void *stream, int B, int n, int A, const float *tau, long tau_bstride, const float *eta,
-                                      long eta_bstride, float alpha, float beta, const uint16_t *head_id, int head_slots, const int64_t *start,
-                                      int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
-                                      uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
-                                      long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
-                                      size_t workspace_bytes, void *ev_begin, void *ev_end) {
-  return sample_sparse_impl(false, false, 0, 0, "daco_tsp_sample_sparse", DACO_SPARSE_ARGS);
-}
-extern "C" int daco_tsp_sample_race_head(void *stream, int B, int n, int A, const float *tau, long tau_bstride, const float *eta,
-                                         long eta_bstride, float alpha, float beta, const uint16_t *head_id, int head_slots, const int64_t *start,
-                                         int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
-                                         uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
-                                         long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
-                                         size_t workspace_bytes, void *ev_begin, void *ev_end) {
-  return sample_sparse_impl(true, false, 0, 0, "daco_tsp_sample_race_head", DACO_SPARSE_ARGS);
-}
-extern "C" int daco_tsp_sample_heads(void *stream, int race, int heads_ready, int head_live_max, int nbr_grouped, int B, int n, int A, const float *tau, long tau_bstride, const float *eta,
-                                     long eta_bstride, float alpha, float beta, const uint16_t *head_id, int head_slots, const int64_t *start,
-                                     int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
-                                     uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
-                                     long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
-                                     size_t workspace_bytes, void *ev_begin, void *ev_end) {
-  return sample_sparse_impl(race != 0, heads_ready != 0, head_live_max, nbr_grouped, "daco_tsp_sample_heads", DACO_SPARSE_ARGS);
-}
-// daco_tsp_sample_heads for the scan draw in the uniform-tail mode: head_eta / tail_c from daco_head_eta, whose verdict the caller read
-extern "C" long daco_tsp_sample_heads_ut(void *stream, int heads_ready, int head_live_max, int nbr_grouped, int B, int n, int A, const float *tau, long tau_bstride, const float *eta,
-                                        long eta_bstride, const uint16_t *head_id, int head_slots, const int64_t *start,
-                                        int fixed_start, uint64_t seed, uint64_t iter, const uint64_t *iter_offset,
-                                        uint32_t ant_gid0, int ant_gid_bstride, int64_t *paths, int32_t *flags, const float *dist,
-                                        long dist_bstride, float *costs, uint32_t *nbr, unsigned long long *stats, void *workspace,
-                                        size_t workspace_bytes, void *ev_begin, void *ev_end, const float *head_eta, float tail_c) {
-  if (!head_eta) { set_error("daco_tsp_sample_heads_ut: bad argument (head_eta)"); return DACO_E_BADARG; }
-  const float alpha = 1.0f, beta = 1.0f;
-  return sample_sparse_impl(false, heads_ready != 0, head_live_max, nbr_grouped, "daco_tsp_sample_heads_ut", DACO_SPARSE_ARGS, head_eta, tail_c);
 }

@@ -178,7 +178,7 @@ class BatchedTSP:
         # (_iter_dev: device-side iteration counter of a captured graph; self.iteration then stays frozen)
         # events: torch.cuda.Event pair re-recorded around the construction kernel; ls_events: a pair recorded (on the
         # current stream, which is the stream the library launches on) right before / after the local-search launches
-        # sampler="race" after sparsify(k): the same tours from the head rows (daco_tsp_sample_race_head), an eighth of the noise
+        # sampler="race" after sparsify(k): the same tours from the head rows (daco_tsp_sample_heads, race = 1), an eighth of the noise
         return self._step(events, _iter_dev, ls_events, want_paths)
 
     def _step(self, events=None, _iter_dev=None, ls_events=None, want_paths=True, resolved=None):

@@ -77,7 +77,7 @@ def _rows(t, B, dtype=torch.float32):
 
 def _ptr(t):
     """A tensor's address, or NULL for None.  A call per argument: like _mode and _batch_of it is kept out of tsp_sample,
-    tsp_sample_sparse, cvrp_sample, track_best_ and pheromone_update_, whose host time is a 20-node colony's iteration time."""
+    tsp_sample_sparse, cvrp_sample and track_best_, whose host time is a 20-node colony's iteration time."""
     return t.data_ptr() if t is not None else None
 
 

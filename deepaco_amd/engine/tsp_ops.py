@@ -112,7 +112,7 @@ def sparsify_heuristic(dist, k, numer=None, path=None):
 def sparse_head(weights, k, top=None, path=None, batch=None):
     """Head table of scan_sparse for `weights` [B,n,n] or [n,n] (the colony passes its heuristic): per row the k (<= 127)
     largest entries, ids ascending (ties at the k-th value: the smaller id) -- [B,n,S] int16 holding uint16 ids with S = 64
-    slots for k <= 63, else 128; the unused slots 0, the last slot = k (include/deepaco_hip.h daco_tsp_sample_sparse;
+    slots for k <= 63, else 128; the unused slots 0, the last slot = k (include/deepaco_hip.h daco_tsp_sample_heads;
     oracle.sparse_head_ids is the same rule).
     path 'hip' (the default for n <= 1024; _setup_path): one launch of daco_sparse_head; a [n,n] matrix with batch=B is read once
     and its table written B times.  'torch': the expression below -- the same ids on every input.
@@ -155,7 +155,7 @@ def sparse_head(weights, k, top=None, path=None, batch=None):
     return ids
 
 
-SPARSE_MIN_N, SPARSE_MAX_N = 129, 1024        # sizes daco_tsp_sample_sparse / _race_head cover
+SPARSE_MIN_N, SPARSE_MAX_N = 129, 1024        # sizes daco_tsp_sample_heads covers
 
 
 def auto_head_k(heuristic, mass=0.98, want_top=False, path=None):
@@ -333,25 +333,25 @@ def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, f
                       batch=None, events=None, dist=None, want_nbr=False, iter_dev=None, ant_gid_bstride=0, want_stats=False,
                       want_paths=True, race=False, workspace=None, heads_ready=False, head_live_max=0, nbr_grouped=False, flags=None,
                       uniform_tail=None, dist_symmetric=False):
-    """ACO.gen_path on head / tail rows (sampler "scan_sparse", include/deepaco_hip.h daco_tsp_sample_sparse): the
+    """ACO.gen_path on head / tail rows (sampler "scan_sparse", include/deepaco_hip.h daco_tsp_sample_heads): the
     distribution of tsp_sample(mode="scan"), 384 / 768 bytes per step instead of a row while the head has a live candidate.
     head: sparse_head(heuristic, k).  Returns (paths, flags, costs|None, nbr|None[, stats]).
-    race=True: daco_tsp_sample_race_head -- the exponential race of mode="race" on the head rows, with the tours of the dense
-    race kernel (same seed), one variate per head slot and step instead of n.
+    race=True: the exponential race of mode="race" on the head rows, with the tours of the dense race kernel (same seed), one
+    variate per head slot and step instead of n.
     workspace: a sparse_workspace() tensor the caller keeps (default: the per-stream scratch); heads_ready=True: it already holds
     this iteration's head rows (pheromone_update_(heads=...) wrote them for these very tensors) and the pass over tau is skipped
-    (include/deepaco_hip.h daco_tsp_sample_heads) -- the same tours.
+    -- the same tours.
     head_live_max: the k the head table was built with (sparse_head(.., k)), or 0: lets a launch of few ants (one instance, a few
     hundred ants) keep the head rows in LDS -- the same tours, about half the time at TSP-500 x 512 ants x 1 instance.
     nbr_grouped: the update's table as [B, ceil(A/8), n, 8] (written in 1 KB pieces; pheromone_update_(heads={..., "nbr_grouped": True})
     takes it) instead of [B, n, A]; the returned tensor keeps the shape [B, n, A] either way (same bytes, opaque to the caller).
-    uniform_tail: head_eta_table(eta, head), or None -- the uniform-tail mode (include/deepaco_hip.h daco_tsp_sample_heads_ut): the
+    uniform_tail: head_eta_table(eta, head), or None -- the uniform-tail mode (include/deepaco_hip.h, head_eta / tail_c): the
     same tours; the pass over tau reads no eta and writes no dense rows, the rare ways of a step walk the row of tau.  Taken where
     uniform_tail_applies(), ignored elsewhere.  With heads_ready=True the workspace's head rows must come from a call in the same
     mode or the dense rows from a call out of it: the caller's key (BatchedTSP._heads_state) holds the mode.
     dist_symmetric: the caller's statement that every instance of `dist` is bitwise symmetric (dist_is_symmetric(dist), checked
     once per matrix): at n <= 512 the fused tour lengths then read each edge from the upper triangle -- the same costs from half
-    the cache lines (include/deepaco_hip.h daco_tsp_sample_heads, nbr_grouped + 2).  Never set it for a matrix that is not."""
+    the cache lines (include/deepaco_hip.h, dist_symmetric).  Never set it for a matrix that is not."""
     _require_gpu(tau, eta, start, head, workspace)
     assert not heads_ready or workspace is not None
     n = tau.shape[-1]
@@ -381,34 +381,22 @@ def tsp_sample_sparse(tau, eta, n_ants, head, alpha=1.0, beta=1.0, start=None, f
             raise ValueError(f"scan_sparse serves 129 <= n <= 1024 (n = {n})")
         ws = workspace if workspace is not None else _workspace(dev, nbytes, "sample_sparse")
         assert ws.numel() >= nbytes
-        table_bits = int(bool(nbr_grouped)) | (2 if dist_symmetric and dist is not None else 0)     # (the library's nbr_grouped argument)
+        heta, tail_c = None, 0.0
         if uniform_tail is not None and uniform_tail_applies(n, tau, eta, alpha, beta, race):
             heta, tail_c = uniform_tail
             assert heta.dtype == torch.float32 and heta.is_contiguous() and tuple(heta.shape) == tuple(head.shape)
-            rc = L.daco_tsp_sample_heads_ut(_stream(dev), int(bool(heads_ready)), int(head_live_max), table_bits, B, n, n_ants,
-                                            tau.data_ptr(), tbs, eta.data_ptr(), ebs, head.data_ptr(), int(head.shape[2]),
-                                            start.data_ptr() if start is not None else None, int(fixed_start), int(seed) & (2 ** 64 - 1),
-                                            int(it), iter_dev.data_ptr() if iter_dev is not None else None, int(ant_gid0) & 0xFFFFFFFF,
-                                            int(ant_gid_bstride), paths.data_ptr() if paths is not None else None, flags.data_ptr(),
-                                            dist.data_ptr() if dist is not None else None, dbs,
-                                            costs.data_ptr() if costs is not None else None,
-                                            nbr.data_ptr() if nbr is not None else None,
-                                            stats.data_ptr() if stats is not None else None, ws.data_ptr(), ws.numel(),
-                                            events[0].cuda_event if events else None, events[1].cuda_event if events else None,
-                                            heta.data_ptr(), float(tail_c))
-            _lib.check(rc, "daco_tsp_sample_heads_ut")
-            out = (paths, flags, costs, nbr)
-            return out + (stats,) if want_stats else out
-        rc = L.daco_tsp_sample_heads(_stream(dev), int(bool(race)), int(bool(heads_ready)), int(head_live_max), table_bits, B, n, n_ants, tau.data_ptr(), tbs, eta.data_ptr(), ebs, float(alpha),
-                                      float(beta), head.data_ptr(), int(head.shape[2]), start.data_ptr() if start is not None else None,
-                                      int(fixed_start), int(seed) & (2 ** 64 - 1), int(it),
-                                      iter_dev.data_ptr() if iter_dev is not None else None, int(ant_gid0) & 0xFFFFFFFF,
-                                      int(ant_gid_bstride), paths.data_ptr() if paths is not None else None, flags.data_ptr(),
-                                      dist.data_ptr() if dist is not None else None, dbs,
-                                      costs.data_ptr() if costs is not None else None,
-                                      nbr.data_ptr() if nbr is not None else None,
-                                      stats.data_ptr() if stats is not None else None, ws.data_ptr(), ws.numel(),
-                                      events[0].cuda_event if events else None, events[1].cuda_event if events else None)
+        rc = L.daco_tsp_sample_heads(_stream(dev), int(bool(race)), int(bool(heads_ready)), int(head_live_max), int(bool(nbr_grouped)),
+                                     int(bool(dist_symmetric and dist is not None)), B, n, n_ants, tau.data_ptr(), tbs, eta.data_ptr(), ebs,
+                                     float(alpha), float(beta), head.data_ptr(), int(head.shape[2]),
+                                     start.data_ptr() if start is not None else None, int(fixed_start), int(seed) & (2 ** 64 - 1), int(it),
+                                     iter_dev.data_ptr() if iter_dev is not None else None, int(ant_gid0) & 0xFFFFFFFF,
+                                     int(ant_gid_bstride), paths.data_ptr() if paths is not None else None, flags.data_ptr(),
+                                     dist.data_ptr() if dist is not None else None, dbs,
+                                     costs.data_ptr() if costs is not None else None,
+                                     nbr.data_ptr() if nbr is not None else None,
+                                     stats.data_ptr() if stats is not None else None, ws.data_ptr(), ws.numel(),
+                                     events[0].cuda_event if events else None, events[1].cuda_event if events else None,
+                                     heta.data_ptr() if heta is not None else None, float(tail_c))
     _lib.check(rc, "daco_tsp_sample_heads")
     out = (paths, flags, costs, nbr)
     return out + (stats,) if want_stats else out

@@ -2,7 +2,7 @@
 import torch
 
 from .. import _lib
-from .common import _bstride, _f32c, _on, _require_gpu, _stream, _workspace
+from .common import _bstride, _f32c, _on, _ptr, _require_gpu, _stream, _workspace
 from .tsp_ops import uniform_tail_applies
 
 
@@ -37,15 +37,12 @@ def track_best_(costs, paths, lowest, shortest=None, mmas_scale=None, tours16=No
         if paths is None:
             assert tours16 is not None and tours16.dtype == torch.int16 and tours16.is_contiguous() and shortest is not None
             assert tuple(tours16.shape[:2]) == (B, A)
-            rc = _lib.lib().daco_track_best_tours16(_stream(dev), B, int(shortest.shape[1]), A, int(tours16.shape[2]), costs.data_ptr(),
-                                                    tours16.data_ptr(), lowest.data_ptr(), shortest.data_ptr(), None,
-                                                    mx.data_ptr() if mx is not None else None,
-                                                    float(mmas_scale) if mmas_scale is not None else 0.0)
-            _lib.check(rc, "daco_track_best_tours16")
-            return mx
-        length = paths.shape[1]
-        assert paths.is_contiguous() and tuple(paths.shape) == (B, length, A)
-        rc = _lib.lib().daco_track_best(_stream(dev), B, length, A, costs.data_ptr(), paths.data_ptr(), lowest.data_ptr(),
+            length, rows, ld = int(shortest.shape[1]), tours16, int(tours16.shape[2])
+        else:
+            length, rows, ld = paths.shape[1], None, 0
+            assert paths.is_contiguous() and tuple(paths.shape) == (B, length, A)
+        rc = _lib.lib().daco_track_best(_stream(dev), B, length, A, costs.data_ptr(), paths.data_ptr() if paths is not None else None,
+                                        rows.data_ptr() if rows is not None else None, ld, lowest.data_ptr(),
                                         shortest.data_ptr() if shortest is not None else None, None,
                                         mx.data_ptr() if mx is not None else None,
                                         float(mmas_scale) if mmas_scale is not None else 0.0)
@@ -62,13 +59,13 @@ def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, c
     heads (symmetric only): dict(eta, alpha, beta, head, race, workspace) of a colony whose next construction is
     tsp_sample_sparse(..., workspace=workspace, heads_ready=True): the update also writes that call's head rows
     (daco_pheromone_update_heads: tau is read once per iteration instead of twice).  heads["uniform_tail"] = head_eta_table(eta,
-    head): the uniform-tail mode where it applies (daco_pheromone_update_heads_ut: the same rows, eta not read, no dense rows
+    head): the uniform-tail mode where it applies (the same call with head_eta: the same rows, eta not read, no dense rows
     written); the next tsp_sample_sparse must then be given the same uniform_tail.
     record = (lowest [B], shortest [B,n] or None, tours16 or None): the launch also does track_best_(costs, paths, lowest, shortest,
     tours16=tours16) -- for the update that uses none of its results (symmetric, no elitist ant, no clamps: the plain ant system);
-    the same record, bit for bit, with one launch less (daco_pheromone_update*_record)."""
+    the same record, bit for bit, with one launch less (the record arguments of either entry point)."""
     _require_gpu(tau, paths, costs, clamp_min, clamp_max)
-    rec, sfx = (), ""
+    rec = (None, 0, None, None)                              # (tours16, tours_ld, lowest, shortest: no record kept)
     if record is not None:
         lowest, shortest, tours16 = record
         _require_gpu(lowest, shortest, tours16)
@@ -77,9 +74,7 @@ def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, c
         assert shortest is None or (shortest.dtype == torch.int64 and shortest.is_contiguous() and tuple(shortest.shape) == tuple(tau.shape[:2]))
         assert tours16 is None or (tours16.dtype == torch.int16 and tours16.is_contiguous() and tours16.shape[0] == tau.shape[0])
         assert shortest is None or tours16 is not None or paths is not None
-        rec = (tours16.data_ptr() if tours16 is not None else None, int(tours16.shape[2]) if tours16 is not None else 0,
-               lowest.data_ptr(), shortest.data_ptr() if shortest is not None else None)
-        sfx = "_record"
+        rec = (_ptr(tours16), int(tours16.shape[2]) if tours16 is not None else 0, lowest.data_ptr(), _ptr(shortest))
     assert tau.dim() == 3 and tau.dtype == torch.float32 and tau.is_contiguous()
     B, n, _ = tau.shape
     if paths is None:                                        # (the table is all the deposit reads)
@@ -88,40 +83,32 @@ def pheromone_update_(tau, paths, costs, decay, elitist=False, symmetric=True, c
     else:
         _, length, A = paths.shape
         paths = paths.contiguous()
-    pptr = paths.data_ptr() if paths is not None else None
     costs = _f32c(costs)
     if weights is not None:
         weights = _f32c(weights)
     dev = tau.device
     L = _lib.lib()
-
-    def call(name, *args):
-        """the entry point `name`, or its record-keeping form with the record block behind its arguments"""
-        rc = getattr(L, name + sfx)(*args, *rec)
-        _lib.check(rc, name + sfx)
-        return tau
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
-
     with _on(dev):
         ws = _workspace(dev, L.daco_pheromone_update_workspace_bytes(B, n, length, A), "update")
-        if heads is not None:
-            assert symmetric and length == n
-            eta, ebs = _bstride(heads["eta"], n)
-            head, sws = heads["head"], heads["workspace"]
-            _require_gpu(eta, head, sws)
-            grouped = int(bool(heads.get("nbr_grouped", False))) if nbr is not None else 0
-            ut = heads.get("uniform_tail")
-            if ut is not None and uniform_tail_applies(n, tau, eta, heads["alpha"], heads["beta"], heads.get("race", False)):
-                return call("daco_pheromone_update_heads_ut", _stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(),
-                            float(decay), int(bool(elitist)), ptr(clamp_min), ptr(clamp_max), float(floor), ptr(nbr), ptr(weights),
-                            ws.data_ptr(), ws.numel(), head.data_ptr(), int(head.shape[2]), grouped, sws.data_ptr(), sws.numel(),
-                            ut[0].data_ptr(), float(ut[1]))
-            return call("daco_pheromone_update_heads", _stream(dev), B, n, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
-                        int(bool(elitist)), ptr(clamp_min), ptr(clamp_max), float(floor), ptr(nbr), ptr(weights), ws.data_ptr(),
-                        ws.numel(), eta.data_ptr(), ebs, float(heads["alpha"]), float(heads["beta"]), head.data_ptr(),
-                        int(head.shape[2]), int(bool(heads.get("race", False))), grouped, sws.data_ptr(), sws.numel())
-        return call("daco_pheromone_update", _stream(dev), B, n, length, A, tau.data_ptr(), pptr, costs.data_ptr(), float(decay),
-                    int(bool(elitist)), int(bool(symmetric)), ptr(clamp_min), ptr(clamp_max), float(floor), ptr(nbr), ptr(weights),
-                    int(hub), ws.data_ptr(), ws.numel())
+        if heads is None:
+            rc = L.daco_pheromone_update(_stream(dev), B, n, length, A, tau.data_ptr(), _ptr(paths), costs.data_ptr(), float(decay),
+                                         int(bool(elitist)), int(bool(symmetric)), _ptr(clamp_min), _ptr(clamp_max), float(floor),
+                                         _ptr(nbr), _ptr(weights), int(hub), ws.data_ptr(), ws.numel(), *rec)
+            _lib.check(rc, "daco_pheromone_update")
+            return tau
+        assert symmetric and length == n
+        eta, ebs = _bstride(heads["eta"], n)
+        head, sws = heads["head"], heads["workspace"]
+        _require_gpu(eta, head, sws)
+        race = bool(heads.get("race", False))
+        ut = heads.get("uniform_tail")
+        if ut is None or not uniform_tail_applies(n, tau, eta, heads["alpha"], heads["beta"], race):
+            ut = (None, 0.0)
+        rc = L.daco_pheromone_update_heads(_stream(dev), B, n, A, tau.data_ptr(), _ptr(paths), costs.data_ptr(), float(decay),
+                                           int(bool(elitist)), _ptr(clamp_min), _ptr(clamp_max), float(floor), _ptr(nbr), _ptr(weights),
+                                           ws.data_ptr(), ws.numel(), eta.data_ptr(), ebs, float(heads["alpha"]), float(heads["beta"]),
+                                           head.data_ptr(), int(head.shape[2]), int(race),
+                                           int(bool(heads.get("nbr_grouped", False))) if nbr is not None else 0, sws.data_ptr(), sws.numel(),
+                                           _ptr(ut[0]), float(ut[1]), *rec)
+    _lib.check(rc, "daco_pheromone_update_heads")
+    return tau

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 129 /* 0.1.22: bumped whenever an entry point's signature or the draw stream of a mode changes (120: daco_tsp_sample_sparse; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads (the sparse workspace still begins with the dense rows P: see daco_tsp_sample_sparse); 126: daco_tsp_sparse_tours_offset / daco_track_best_tours16, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats, and daco_cvrp_knn_graph; daco_head_eta / daco_tsp_sample_heads_ut / daco_pheromone_update_heads_ut (the uniform-tail mode of the head-row path) were added under 129 in the same way: same draws, same head rows, no existing signature changed -- the number stays where tests/test_mkp_grad_spec.py holds it) */
+#define DACO_VERSION 130 /* 0.1.23: bumped whenever an entry point's signature or the draw stream of a mode changes (120: the head-row sampler; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads (the sparse workspace still begins with the dense rows P: see daco_tsp_sample_heads); 126: daco_tsp_sparse_tours_offset / the record from tours16 rows, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats, and daco_cvrp_knn_graph; daco_head_eta and the uniform-tail mode of the head-row path were added under 129 in the same way: same draws, same head rows, no existing signature changed; 130: one entry point per head-row call -- daco_tsp_sample_heads, daco_pheromone_update, daco_pheromone_update_heads and daco_track_best take their modes (race, uniform tail, the record kept by the update, tours16 rows) as arguments and the exports that stood beside them are gone; same draws, same kernels) */
 
 /* error codes */
 #define DACO_OK 0
@@ -115,11 +115,13 @@ int daco_tsp_sample(void *stream, int B, int n, int A,
                     void *workspace, size_t workspace_bytes, void *ev_begin, void *ev_end);
 
 /* ---------------------------------------------------------------------------------------------
- * daco_tsp_sample_sparse -- ACO.gen_path on HEAD / TAIL rows (sampler "scan_sparse"); replaces
+ * daco_tsp_sample_heads -- ACO.gen_path on HEAD / TAIL rows (sampler "scan_sparse"); replaces
  *   tsp/aco.py:134-177 with the roulette of tsp_nls/aco.py:260-275, for heuristics made k-sparse by
  *   tsp/aco.py:52-67 (sparsify: k live entries per row, 1e-10 elsewhere) -- the reference's inference setting.
+ * The one entry point of the head-row sampler; its modes (race on head rows, head rows left by the update, uniform tail) are
+ * arguments, described after the draw.
  *
- * Same distribution as daco_tsp_sample(DACO_SCAN): p_k = tau^alpha * eta^beta * [k unvisited].  A row is split into a
+ * race = 0, the scan draw.  Same distribution as daco_tsp_sample(DACO_SCAN): p_k = tau^alpha * eta^beta * [k unvisited].  A row is split into a
  * head (up to 63 or 127 candidates, head_id) and the tail (the rest).  A step draws r = u * (H + T) with H the head's
  * live mass and T the tail's static mass: inside the head -> inverse CDF over 64 / 128 slots (384 / 768 bytes instead of a
  * row of 4n); past the head -> inverse CDF over all tail entries, and if that lands on a visited one the step draws once
@@ -127,77 +129,30 @@ int daco_tsp_sample(void *stream, int B, int n, int A,
  * fallback: the outcome is the categorical above, a step reads the row at most twice); no live head candidate -> the
  * dense masked draw of the 64-lane scan specification.  Its own uniform stream: tours differ from DACO_SCAN's under the
  * same seed, the distribution does not.  Specification: oracle/daco_oracle.c draw_scan_sparse.
+ * race = 1, the race on head rows.  daco_tsp_sample(DACO_RACE_PHILOX) on the same head rows, with the SAME tours (same seed,
+ * same noise indexing by node id): the exponential race of torch.multinomial's one-sample path (tsp/aco.py:174-175) is won
+ * by a head candidate whenever its key L/p is below what any tail candidate could draw, L_min / max_tail(p); that is checked
+ * every step and the dense race runs for the ant otherwise.  head_slots variates per step instead of n.
  *   129 <= n <= 1024.
  *   head_slots  64 or 128: slots per row of head_id (four / eight per lane of the 16-lane row)
  *   head_id  [B][n][head_slots] uint16: slots 0..cnt-1 the head's node ids (any subset of the row; the colony passes the
  *            k largest heuristic entries, ids ascending), the other slots 0, the last slot = cnt (<= head_slots - 1)
  *   paths, flags, dist / costs, nbr, start / fixed_start, seed / iter / iter_offset / ant_gid0 / ant_gid_bstride,
  *   ev_begin / ev_end: as daco_tsp_sample (log-probabilities are not produced: an inference sampler)
- *   stats    optional out [3] uint64 (caller zeroes): dense masked draws (no live head candidate, or after a rejection), tail walks, rejections
+ *   stats    optional out [3] uint64 (caller zeroes): dense masked draws (no live head candidate, or after a rejection), tail walks,
+ *            rejections; race = 1: stats[0] = steps that took the dense race
  *   workspace  daco_tsp_sparse_workspace_bytes(B, n, A) bytes of device scratch, in this order: the dense rows
  *              P = tau^alpha * eta^beta [B][n][ld] f32 (ld = 512 for n <= 512, else 1024; zeros past n) that the steps which leave
  *              the head walk; the head rows of this iteration (16 lanes x {4 or 8 f32 values, as many u16 ids} per row of tau);
  *              the tours as uint16 [B][A][ld] at daco_tsp_sparse_tours_offset.  Both P and the head rows are written by the pass
- *              over tau of this call, or by daco_pheromone_update_heads.  In the uniform-tail mode (daco_tsp_sample_heads_ut,
- *              daco_pheromone_update_heads_ut) the region of P is left alone -- neither written nor read -- and keeps its place.
+ *              over tau of this call, or by daco_pheromone_update_heads.  In the uniform-tail mode (head_eta given, here and there)
+ *              the region of P is left alone -- neither written nor read -- and keeps its place.
  *              alpha, beta other than 1: the kernels themselves take unit exponents; tau^alpha and eta^beta are formed first (one
  *              elementwise launch; x^2 = x x and x^0 = 1 exactly) into a workspace of daco_tsp_sparse_workspace_bytes_general(B, n, A)
  *              bytes (= the above + two [B][n][n] f32 matrices), which such a call needs (DACO_E_WORKSPACE otherwise).
- */
-size_t daco_tsp_sparse_workspace_bytes(int B, int n, int A);
-size_t daco_tsp_sparse_workspace_bytes_general(int B, int n, int A);
-/* daco_tsp_sparse_tours_offset -- where the workspace keeps the tours in their compact form: uint16 [B][A][ld], ld = 512 (n <= 512) or
- * 1024, entry t of ant a = the node visited at step t (entries >= n: undefined).  Valid after a call of daco_tsp_sample_sparse /
- * _race_head / _heads with n > 512 (the tours are built there), and for n <= 512 after a call with paths = NULL (nbr or costs given): the
- * colony loop of ACO.run (tsp/aco.py:75-92) keeps `paths` to itself -- costs, best tour and deposit are all it takes from them -- so
- * its iteration asks for no int64 [B][n][A] tensor (131 MB per iteration at TSP-500 x 512 x 64) and hands these rows to
- * daco_track_best_tours16. */
-size_t daco_tsp_sparse_tours_offset(int B, int n, int A);
-/* daco_tsp_sparse_resident_per_cu -- how many workgroups of the construction kernel a compute unit holds at a time
- * (hipOccupancyMaxActiveBlocksPerMultiprocessor) for the instantiation and the dynamic LDS that daco_tsp_sample_sparse / _race_head /
- * _heads launch for these arguments when the launch has more than six and at most eight workgroups of 16 ants per compute unit
- * (another launch of the scan draw on 64-slot heads at n <= 512 has no badly filled second round to remove and keeps whole tours
- * in LDS, six workgroups per compute unit; few ants of one instance take the LDS-heads variant).  The scan draw on 64-slot
- * heads at n <= 512 keeps a 352-entry window of each tour in LDS and parks the first max(0, roundup16(n - 352)) entries in the
- * workspace's tours16 rows (also in a call that returns int64 paths), so that eight workgroups fit: 2 048 workgroups -- TSP-500 x 512
- * ants x 64 instances -- are resident at once on 256 compute units.  0: bad arguments, or the query failed. */
-int daco_tsp_sparse_resident_per_cu(int n, int head_slots, int race);
-/* daco_tsp_sparse_split_tours -- which launches of the scan draw on 64-slot heads at n <= 512 take the split-tour variant:
- * -1 (default) those with more than six and at most eight workgroups per compute unit, 0 none, 1 all of them (what the tests of the variant and
- * A/B runs set; the tours are the same either way).  Process-wide, not thread-safe against concurrent launches.  Returns the
- * previous mode; any other argument only queries. */
-int daco_tsp_sparse_split_tours(int mode);
-int daco_tsp_sample_sparse(void *stream, int B, int n, int A,
-                           const float *tau, long tau_bstride, const float *eta, long eta_bstride,
-                           float alpha, float beta, const uint16_t *head_id, int head_slots,
-                           const int64_t *start, int fixed_start,
-                           uint64_t seed, uint64_t iter, const uint64_t *iter_offset, uint32_t ant_gid0,
-                           int ant_gid_bstride,
-                           int64_t *paths, int32_t *flags,
-                           const float *dist, long dist_bstride, float *costs, uint32_t *nbr,
-                           unsigned long long *stats,
-                           void *workspace, size_t workspace_bytes, void *ev_begin, void *ev_end);
-
-/* daco_tsp_sample_race_head -- daco_tsp_sample(DACO_RACE_PHILOX) on the same head rows, with the SAME tours (same seed,
- * same noise indexing by node id): the exponential race of torch.multinomial's one-sample path (tsp/aco.py:174-175) is won
- * by a head candidate whenever its key L/p is below what any tail candidate could draw, L_min / max_tail(p); that is checked
- * every step and the dense race runs for the ant otherwise.  head_slots variates per step instead of n.  Arguments as
- * daco_tsp_sample_sparse (stats[0] = steps that took the dense race). */
-int daco_tsp_sample_race_head(void *stream, int B, int n, int A,
-                              const float *tau, long tau_bstride, const float *eta, long eta_bstride,
-                              float alpha, float beta, const uint16_t *head_id, int head_slots,
-                              const int64_t *start, int fixed_start,
-                              uint64_t seed, uint64_t iter, const uint64_t *iter_offset, uint32_t ant_gid0,
-                              int ant_gid_bstride,
-                              int64_t *paths, int32_t *flags,
-                              const float *dist, long dist_bstride, float *costs, uint32_t *nbr,
-                              unsigned long long *stats,
-                              void *workspace, size_t workspace_bytes, void *ev_begin, void *ev_end);
-
-/* daco_tsp_sample_heads -- the two calls above behind switches, for a colony loop that keeps its workspace (tsp/aco.py:75-92
- * ACO.run: sample -> costs -> best -> update, again and again):
- *   race         0: daco_tsp_sample_sparse, 1: daco_tsp_sample_race_head
- *   heads_ready  0: the head rows are formed first (one pass over tau and eta, as the two calls above do);
+ * The switches, for a colony loop that keeps its workspace (tsp/aco.py:75-92 ACO.run: sample -> costs -> best -> update, again
+ * and again):
+ *   heads_ready  0: the head rows are formed first (one pass over tau and eta);
  *                1: `workspace` already holds this iteration's head rows -- daco_pheromone_update_heads wrote them when it
  *                   finished the rows of tau, for the same tau / eta / alpha / beta / head_id / head_slots / race -- and no
  *                   pass over tau runs.  The caller vouches that tau has not changed since.  Same tours either way.
@@ -210,12 +165,47 @@ int daco_tsp_sample_race_head(void *stream, int B, int n, int A,
  *   nbr_grouped  0: nbr as [B][n][A] (what daco_pheromone_update takes); 1: nbr as [B][ceil(A/8)][n][8] -- the eight ants' entries
  *                of a node together, so that the sampler writes the table in 1 KB pieces instead of 32-byte runs and the update
  *                reads it in runs of R x 32 bytes (daco_pheromone_update_heads(nbr_grouped = 1) takes this form).
- *                + 2 (bit 1, either layout): the caller states that every instance of `dist` is bitwise symmetric --
- *                dist[u][v] and dist[v][u] hold the same bits, which it has checked once for this matrix.  At n <= 512 the fused
- *                tour lengths then read each edge from the upper triangle, dist[min(u, v)][max(u, v)]: the same costs bit for bit
- *                from half the cache lines.  Without the bit (or on a matrix that is not symmetric, where it must not be set)
- *                every edge is read as dist[u_k][u_{k-1}].  daco_tsp_sample_heads_ut takes the same two bits. */
-int daco_tsp_sample_heads(void *stream, int race, int heads_ready, int head_live_max, int nbr_grouped, int B, int n, int A,
+ *   dist_symmetric  1: the caller states that every instance of `dist` is bitwise symmetric -- dist[u][v] and dist[v][u] hold the
+ *                same bits, which it has checked once for this matrix.  At n <= 512 the fused tour lengths then read each edge
+ *                from the upper triangle, dist[min(u, v)][max(u, v)]: the same costs bit for bit from half the cache lines.
+ *                0 (and always on a matrix that is not symmetric): every edge is read as dist[u_k][u_{k-1}].
+ *   head_eta, tail_c   NULL / 0, or the UNIFORM-TAIL mode, for a heuristic that is one number c outside the head of every row
+ *                (what ACO.sparsify writes, tsp/aco.py:52-67: 1e-10 off the k nearest edges): what daco_head_eta wrote for this
+ *                eta and head_id, after the caller has read its verdict and found it good.  The same tours, costs, table and
+ *                stats, bit for bit.  What differs is the memory touched: the pass over tau (heads_ready = 0) reads tau and
+ *                head_eta only and writes the head rows only; the dense-row region of the workspace is neither written nor read;
+ *                the rare ways of a step (tail walk, draw without a live head candidate) read the row of tau and multiply by
+ *                tail_c, and only the draw after a rejected tail walk reads the rows of tau and eta.  Needs race = 0,
+ *                alpha = beta = 1, n % 4 == 0, 16-byte-aligned rows of tau and eta and tail_c >= 0 (DACO_E_BADARG otherwise: the
+ *                caller then passes head_eta = NULL; a tail_c without head_eta is refused too).  The head rows a workspace
+ *                holds are the same bytes in both modes, the dense rows are not: a caller that leaves the mode runs one call
+ *                with heads_ready = 0.
+ */
+size_t daco_tsp_sparse_workspace_bytes(int B, int n, int A);
+size_t daco_tsp_sparse_workspace_bytes_general(int B, int n, int A);
+/* daco_tsp_sparse_tours_offset -- where the workspace keeps the tours in their compact form: uint16 [B][A][ld], ld = 512 (n <= 512) or
+ * 1024, entry t of ant a = the node visited at step t (entries >= n: undefined).  Valid after a call of
+ * daco_tsp_sample_heads with n > 512 (the tours are built there), and for n <= 512 after a call with paths = NULL (nbr or costs given): the
+ * colony loop of ACO.run (tsp/aco.py:75-92) keeps `paths` to itself -- costs, best tour and deposit are all it takes from them -- so
+ * its iteration asks for no int64 [B][n][A] tensor (131 MB per iteration at TSP-500 x 512 x 64) and hands these rows to
+ * daco_track_best (tours16). */
+size_t daco_tsp_sparse_tours_offset(int B, int n, int A);
+/* daco_tsp_sparse_resident_per_cu -- how many workgroups of the construction kernel a compute unit holds at a time
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor) for the instantiation and the dynamic LDS that daco_tsp_sample_heads
+ * launches for these arguments when the launch has more than six and at most eight workgroups of 16 ants per compute unit
+ * (another launch of the scan draw on 64-slot heads at n <= 512 has no badly filled second round to remove and keeps whole tours
+ * in LDS, six workgroups per compute unit; few ants of one instance take the LDS-heads variant).  The scan draw on 64-slot
+ * heads at n <= 512 keeps a 352-entry window of each tour in LDS and parks the first max(0, roundup16(n - 352)) entries in the
+ * workspace's tours16 rows (also in a call that returns int64 paths), so that eight workgroups fit: 2 048 workgroups -- TSP-500 x 512
+ * ants x 64 instances -- are resident at once on 256 compute units.  0: bad arguments, or the query failed. */
+int daco_tsp_sparse_resident_per_cu(int n, int head_slots, int race);
+/* daco_tsp_sparse_split_tours -- which launches of the scan draw on 64-slot heads at n <= 512 take the split-tour variant:
+ * -1 (default) those with more than six and at most eight workgroups per compute unit, 0 none, 1 all of them (what the tests of the variant and
+ * A/B runs set; the tours are the same either way).  Process-wide, not thread-safe against concurrent launches.  Returns the
+ * previous mode; any other argument only queries. */
+int daco_tsp_sparse_split_tours(int mode);
+int daco_tsp_sample_heads(void *stream, int race, int heads_ready, int head_live_max, int nbr_grouped, int dist_symmetric,
+                          int B, int n, int A,
                           const float *tau, long tau_bstride, const float *eta, long eta_bstride,
                           float alpha, float beta, const uint16_t *head_id, int head_slots,
                           const int64_t *start, int fixed_start,
@@ -224,30 +214,8 @@ int daco_tsp_sample_heads(void *stream, int race, int heads_ready, int head_live
                           int64_t *paths, int32_t *flags,
                           const float *dist, long dist_bstride, float *costs, uint32_t *nbr,
                           unsigned long long *stats,
-                          void *workspace, size_t workspace_bytes, void *ev_begin, void *ev_end);
-
-/* daco_tsp_sample_heads_ut -- daco_tsp_sample_heads(race = 0, alpha = beta = 1) in the UNIFORM-TAIL mode, for a heuristic that
- * is one number c outside the head of every row (what ACO.sparsify writes, tsp/aco.py:52-67: 1e-10 off the k nearest edges):
- *   head_eta, tail_c   what daco_head_eta wrote for this eta and head_id, after the caller has read its verdict and found it good
- * The same tours, costs, table and stats as daco_tsp_sample_heads, bit for bit.  What differs is the memory touched: the pass
- * over tau (heads_ready = 0) reads tau and head_eta only and writes the head rows only; the dense-row region of the workspace
- * is neither written nor read; the rare ways of a step (tail walk, draw without a live head candidate) read the row of tau and
- * multiply by tail_c, and only the draw after a rejected tail walk reads the rows of tau and eta.  Needs n % 4 == 0 and
- * 16-byte-aligned rows of tau and eta (DACO_E_BADARG otherwise: the caller then takes daco_tsp_sample_heads).  The head rows a
- * workspace holds are the same bytes in both modes, the dense rows are not: a caller that leaves the mode runs one call with
- * heads_ready = 0.  The status is the usual DACO_OK / DACO_E_* value typed `long`, for the reason given at
- * daco_rcpsp_net_forward (daco_pheromone_update_heads_ut likewise); the refusals are held by tests/test_uniform_tail_refusals.py. */
-long daco_tsp_sample_heads_ut(void *stream, int heads_ready, int head_live_max, int nbr_grouped, int B, int n, int A,
-                             const float *tau, long tau_bstride, const float *eta, long eta_bstride,
-                             const uint16_t *head_id, int head_slots,
-                             const int64_t *start, int fixed_start,
-                             uint64_t seed, uint64_t iter, const uint64_t *iter_offset, uint32_t ant_gid0,
-                             int ant_gid_bstride,
-                             int64_t *paths, int32_t *flags,
-                             const float *dist, long dist_bstride, float *costs, uint32_t *nbr,
-                             unsigned long long *stats,
-                             void *workspace, size_t workspace_bytes, void *ev_begin, void *ev_end,
-                             const float *head_eta, float tail_c);
+                          void *workspace, size_t workspace_bytes, void *ev_begin, void *ev_end,
+                          const float *head_eta, float tail_c);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_cvrp_sample -- replaces the CVRP ACO.gen_path / pick_move / update_visit_mask /
@@ -308,12 +276,12 @@ int daco_cvrp_sample(void *stream, int B, int n, int A,
  *   int64 in/out or NULL; best_idx [B] int32 out or NULL (first minimum, torch.min semantics);
  *   mmas_max [B] f32 out or NULL = (1 / lowest) * mmas_scale, the two roundings of the reference's
  *   `problem_size / lowest_cost` on a tensor (reciprocal, then multiply).
+ *   tours16, tours_ld   NULL / 0, or the tours in the compact form of daco_tsp_sparse_tours_offset, [B][A][tours_ld] uint16 with
+ *   tours_ld >= len (DACO_E_BADARG otherwise): the tour is then read from these rows and `paths` is not; shortest stays int64.
  */
 int daco_track_best(void *stream, int B, int len, int A, const float *costs, const int64_t *paths,
+                    const uint16_t *tours16, int tours_ld,
                     float *lowest, int64_t *shortest, int32_t *best_idx, float *mmas_max, float mmas_scale);
-/* the same bookkeeping on the compact tours of daco_tsp_sparse_tours_offset: tours16 [B][A][ld] uint16; shortest stays int64 [B][len] */
-int daco_track_best_tours16(void *stream, int B, int len, int A, int ld, const float *costs, const uint16_t *tours16,
-                            float *lowest, int64_t *shortest, int32_t *best_idx, float *mmas_max, float mmas_scale);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_prob_matrix + daco_pick_move -- ACO.pick_move as a step-wise service
@@ -517,13 +485,20 @@ int daco_tour_costs(void *stream, int B, int n, int len, int A, const float *dis
  *         pctsp/bpp, the dummy end node in op/mkp); every other node is left at most once;
  *         -1 if there is none (sop, smtwtp).  Edges (hub,hub) of one ant collapse to one add.
  *   workspace: daco_pheromone_update_workspace_bytes(B, n, len, A)
+ *   tours16, tours_ld, lowest, shortest   the colony's record kept by the update's own launch; lowest = NULL: not kept (then
+ *         shortest and tours16 must be NULL too).  What daco_track_best does -- the first minimum of `costs` (ties: the lowest
+ *         index); if it is < lowest[b], lowest[b] and shortest[b][0..n) (int64, or NULL) are replaced -- done by one workgroup per
+ *         instance, with the tour read from tours16 ([B][A][tours_ld] uint16, tours_ld >= n) or, tours16 = NULL, from `paths`, which
+ *         must then be given.  For the update that uses none of this: elitist = 0, no clamps, symmetric = 1 (else DACO_E_BADARG);
+ *         an elitist or MMAS colony calls daco_track_best first.  tau and the record are bit for bit those of the two calls in a row.
  */
 size_t daco_pheromone_update_workspace_bytes(int B, int n, int len, int A);
 int daco_pheromone_update(void *stream, int B, int n, int len, int A, float *tau,
                           const int64_t *paths, const float *costs, float decay, int elitist,
                           int symmetric, const float *clamp_min, const float *clamp_max,
                           float floor_val, const uint32_t *nbr, const float *weights, int hub,
-                          void *workspace, size_t workspace_bytes);
+                          void *workspace, size_t workspace_bytes,
+                          const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest);
 
 /* daco_pheromone_update_heads -- daco_pheromone_update(symmetric = 1) for a colony whose next construction runs on head rows
  * (tsp/aco.py:95-118 followed by the next iteration's tsp/aco.py:165-172): the workgroup that has just finished rows of tau
@@ -534,6 +509,11 @@ int daco_pheromone_update(void *stream, int B, int n, int len, int A, float *tau
  *   nbr_grouped        the layout of `nbr` (see daco_tsp_sample_heads); a NULL nbr is rebuilt from `paths` either way (paths may be
  *                      NULL when nbr is given: the table is all the deposit reads)
  *   sparse_workspace   the sampler's workspace (daco_tsp_sparse_workspace_bytes(B, n, A)); its head rows are (re)written
+ *   head_eta, tail_c   NULL / 0, or the uniform-tail mode as the sampler will be called: the same tau and the same head rows, bit for
+ *                      bit, formed from the rows of tau the workgroup holds on chip, head_eta and tail_c.  eta is not read (it may be
+ *                      NULL) and the workspace's dense rows are not written (at TSP-500 x 64 instances: 64 MB less read and 65.5 MB
+ *                      less written per call).  race = 0, n % 4 == 0, a 16-byte-aligned tau and tail_c >= 0, else DACO_E_BADARG.
+ *   tours16, tours_ld, lowest, shortest   the record, as daco_pheromone_update keeps it
  *   129 <= n <= 1024; the other arguments as daco_pheromone_update (len = n, hub unused) */
 int daco_pheromone_update_heads(void *stream, int B, int n, int A, float *tau,
                                 const int64_t *paths, const float *costs, float decay, int elitist,
@@ -541,50 +521,9 @@ int daco_pheromone_update_heads(void *stream, int B, int n, int A, float *tau,
                                 const uint32_t *nbr, const float *weights, void *workspace, size_t workspace_bytes,
                                 const float *eta, long eta_bstride, float alpha, float beta,
                                 const uint16_t *head_id, int head_slots, int race, int nbr_grouped,
-                                void *sparse_workspace, size_t sparse_workspace_bytes);
-
-/* daco_pheromone_update_heads_ut -- daco_pheromone_update_heads(race = 0, alpha = beta = 1) in the uniform-tail mode (see
- * daco_tsp_sample_heads_ut): the same tau and the same head rows, bit for bit, formed from the rows of tau the workgroup holds
- * on chip, head_eta and tail_c.  eta is not read and the workspace's dense rows are not written (at TSP-500 x 64 instances:
- * 64 MB less read and 65.5 MB less written per call).  n % 4 == 0 and a 16-byte-aligned tau, else DACO_E_BADARG. */
-long daco_pheromone_update_heads_ut(void *stream, int B, int n, int A, float *tau,
-                                   const int64_t *paths, const float *costs, float decay, int elitist,
-                                   const float *clamp_min, const float *clamp_max, float floor_val,
-                                   const uint32_t *nbr, const float *weights, void *workspace, size_t workspace_bytes,
-                                   const uint16_t *head_id, int head_slots, int nbr_grouped,
-                                   void *sparse_workspace, size_t sparse_workspace_bytes,
-                                   const float *head_eta, float tail_c);
-
-/* daco_pheromone_update_record, daco_pheromone_update_heads_record, daco_pheromone_update_heads_ut_record -- the three symmetric
- * updates above, which also keep the colony's record: daco_track_best (tours16 = NULL: the tour is read from `paths`, which must
- * then be given) or daco_track_best_tours16 (tours16 [B][A][tours_ld] uint16, tours_ld >= n) done by one workgroup per instance
- * of the update's own launch -- the first minimum of `costs` (ties: the lowest index); if it is < lowest[b], lowest[b] and
- * shortest[b][0..n) (int64, or NULL) are replaced.  For the update that uses none of this: elitist = 0, no clamps, symmetric = 1
- * (else DACO_E_BADARG); an elitist or MMAS colony calls daco_track_best first, as before.  tau, the head rows and the record are
- * bit for bit those of the two calls in a row.  The first arguments are those of the call without `_record`; the status is the
- * usual DACO_OK / DACO_E_* value typed `long`.  Added under DACO_VERSION 129: new entry points only. */
-long daco_pheromone_update_record(void *stream, int B, int n, int len, int A, float *tau,
-                                  const int64_t *paths, const float *costs, float decay, int elitist,
-                                  int symmetric, const float *clamp_min, const float *clamp_max,
-                                  float floor_val, const uint32_t *nbr, const float *weights, int hub,
-                                  void *workspace, size_t workspace_bytes,
-                                  const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest);
-long daco_pheromone_update_heads_record(void *stream, int B, int n, int A, float *tau,
-                                        const int64_t *paths, const float *costs, float decay, int elitist,
-                                        const float *clamp_min, const float *clamp_max, float floor_val,
-                                        const uint32_t *nbr, const float *weights, void *workspace, size_t workspace_bytes,
-                                        const float *eta, long eta_bstride, float alpha, float beta,
-                                        const uint16_t *head_id, int head_slots, int race, int nbr_grouped,
-                                        void *sparse_workspace, size_t sparse_workspace_bytes,
-                                        const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest);
-long daco_pheromone_update_heads_ut_record(void *stream, int B, int n, int A, float *tau,
-                                           const int64_t *paths, const float *costs, float decay, int elitist,
-                                           const float *clamp_min, const float *clamp_max, float floor_val,
-                                           const uint32_t *nbr, const float *weights, void *workspace, size_t workspace_bytes,
-                                           const uint16_t *head_id, int head_slots, int nbr_grouped,
-                                           void *sparse_workspace, size_t sparse_workspace_bytes,
-                                           const float *head_eta, float tail_c,
-                                           const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest);
+                                void *sparse_workspace, size_t sparse_workspace_bytes,
+                                const float *head_eta, float tail_c,
+                                const uint16_t *tours16, int tours_ld, float *lowest, int64_t *shortest);
 
 /* daco_allreduce_delta_tau -- the ant-sharded colony's one data-path collective (every rank builds the deposits
  * of ITS ants, delta-tau [B][n][n] f32 = daco_pheromone_update(decay = 1) onto zeros; the ranks sum them; every rank applies
@@ -876,7 +815,7 @@ int daco_heu_matrix(void *stream, int B, int n, int E, const int64_t *edge_index
  */
 long daco_sparsify(void *stream, int B, int n, int k, const float *dist, long dist_bstride, const float *numer,
                   long numer_bstride, float *out);
-/* daco_sparse_head: the head table daco_tsp_sample_sparse takes (head_id above).  weights [B][n][n] f32 (w_bstride between
+/* daco_sparse_head: the head table daco_tsp_sample_heads takes (head_id above).  weights [B][n][n] f32 (w_bstride between
  *   instances); per row the k (1 .. 127, <= n) entries largest by (value descending, column ascending), their column ids in
  *   ascending order in slots 0 .. k-1 of ids [B][n][S] uint16, S = 64 for k <= 63, else 128; the other slots 0, slot S-1 = k.
  *   Every slot is written by this call.  w_bstride = 0: one matrix for the batch -- each row is read once and its table
@@ -892,7 +831,7 @@ long daco_sparse_head(void *stream, int B, int n, int k, const float *weights, l
  */
 long daco_head_stats(void *stream, int B, int n, const float *weights, long w_bstride, int k_lds, double mass,
                     double mass_lds, int32_t *counts);
-/* daco_head_eta: what the uniform-tail mode of the head-row path (daco_tsp_sample_heads_ut, daco_pheromone_update_heads_ut)
+/* daco_head_eta: what the uniform-tail mode of the head-row path (daco_tsp_sample_heads, daco_pheromone_update_heads with head_eta)
  *   needs of a heuristic, once per head table.  eta [B][n][n] f32 (eta_bstride between instances, 0: one matrix), head_id
  *   [B][n][head_slots] as daco_sparse_head wrote it (head_slots 64 or 128).
  *   head_eta [B][n][head_slots] f32 = eta at the live slots' ids (slot m < the row's count, id < n), +0 in every other slot.

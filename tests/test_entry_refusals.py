@@ -48,6 +48,9 @@ _SIB = dict(kind=3, B=1, n=100, A=4, tau=P, eta=P, alpha=1.0, beta=1.0, aux_vec=
 _UPD = dict(B=1, n=100, len=100, A=4, tau=P, paths=P, costs=P, decay=0.9, symmetric=1, workspace=P)
 _UPDH = dict(B=1, n=200, A=4, tau=P, paths=P, costs=P, decay=0.9, workspace=P, workspace_bytes=1 << 40, eta=P, alpha=1.0, beta=1.0,
              head_id=P, head_slots=64, sparse_workspace=P)
+_UPDU = dict(B=1, n=200, A=4, tau=P, paths=P, costs=P, decay=0.9, workspace=P, workspace_bytes=1 << 40, alpha=1.0, beta=1.0, head_id=P,
+             head_slots=64, sparse_workspace=P, head_eta=P, tail_c=0.5)           # (the uniform-tail mode: no eta)
+_REC = dict(lowest=P, shortest=P)
 _RCPSP = dict(B=1, n=30, A=4, R=2, horizon=64, E=60, duration=P, resources=P, capacity=P, earliest_start=P, latest_start=P, succ_ptr=P,
               succ_idx=P, routes=P, costs=P)
 _RCPSP_S = dict(_RCPSP, indegree=P, adjacency=P, tau=P, eta=P, alpha=1.0, beta=1.0, gamma=1.0, c=0.5, mode=_lib.SCAN, workspace=P)
@@ -68,8 +71,8 @@ REFUSED = [
     ("daco_tour_costs", BADARG, "bad argument", {}),
     ("daco_track_best", BADARG, "bad argument", {}),
     ("daco_track_best", BADARG, "bad argument", dict(B=1, len=5, A=4, costs=P, lowest=P, shortest=P)),      # a record tour without paths
-    ("daco_track_best_tours16", BADARG, "bad argument", {}),
-    ("daco_track_best_tours16", BADARG, "ld=4", dict(B=1, len=5, A=4, ld=4, costs=P, lowest=P, tours16=P)),
+    ("daco_track_best", BADARG, "bad argument", {}),                                                       # (this row and the next: the tours16 form)
+    ("daco_track_best", BADARG, "ld=4", dict(B=1, len=5, A=4, tours_ld=4, costs=P, lowest=P, tours16=P)),
     # dense samplers
     ("daco_tsp_sample", BADARG, "bad argument", {}),
     ("daco_tsp_sample", TOOLARGE, "DACO_MAX_NODES", dict(_TSP, n=5000)),
@@ -119,14 +122,14 @@ REFUSED = [
     ("daco_mkpv_update", BADARG, "bad argument", {}),
     ("daco_mkpv_update", TOOLARGE, "exceed", dict(B=1, n=100000, A=4, rows=4, sols=P, objs=P, Q=P, tau=P)),
     # head-row samplers and the update that writes their rows
-    ("daco_tsp_sample_sparse", BADARG, "bad argument", {}),
-    ("daco_tsp_sample_sparse", BADARG, "head_slots = 5", dict(_HEADS, head_slots=5)),
-    ("daco_tsp_sample_sparse", TOOLARGE, "129..1024", dict(_HEADS, n=128)),
-    ("daco_tsp_sample_sparse", TOOLARGE, "129..1024", dict(_HEADS, n=1025)),
-    ("daco_tsp_sample_sparse", WORKSPACE, "workspace 16 <", dict(_HEADS, workspace_bytes=16)),
-    ("daco_tsp_sample_race_head", BADARG, "bad argument", {}),
-    ("daco_tsp_sample_race_head", TOOLARGE, "129..1024", dict(_HEADS, n=128)),
-    ("daco_tsp_sample_race_head", WORKSPACE, "workspace 16 <", dict(_HEADS, workspace_bytes=16)),
+    ("daco_tsp_sample_heads", BADARG, "bad argument", {}),
+    ("daco_tsp_sample_heads", BADARG, "head_slots = 5", dict(_HEADS, head_slots=5)),
+    ("daco_tsp_sample_heads", TOOLARGE, "129..1024", dict(_HEADS, n=128)),
+    ("daco_tsp_sample_heads", TOOLARGE, "129..1024", dict(_HEADS, n=1025)),
+    ("daco_tsp_sample_heads", WORKSPACE, "workspace 16 <", dict(_HEADS, workspace_bytes=16)),
+    ("daco_tsp_sample_heads", BADARG, "bad argument", dict(race=1)),                # (three rows: the race on head rows)
+    ("daco_tsp_sample_heads", TOOLARGE, "129..1024", dict(_HEADS, race=1, n=128)),
+    ("daco_tsp_sample_heads", WORKSPACE, "workspace 16 <", dict(_HEADS, race=1, workspace_bytes=16)),
     ("daco_tsp_sample_heads", BADARG, "bad argument", {}),
     ("daco_tsp_sample_heads", TOOLARGE, "129..1024", dict(_HEADS, n=1025)),
     ("daco_tsp_sample_heads", TOOLARGE, "32-bit offsets", dict(_HEADS, n=1024, A=1 << 20)),
@@ -203,13 +206,26 @@ REFUSED = [
     ("daco_sibling_sample", BADARG, "SOP needs n - 1 = 99 noise steps, got 100", dict(_SIB, mode=_lib.RACE_NOISE, noise=P, noise_steps=100)),
     ("daco_sibling_sample", BADARG, "SOP needs n - 1 = 99 noise steps, got 98", dict(_SIB, mode=_lib.RACE_NOISE, noise=P, noise_steps=98)),
     ("daco_pheromone_update", TOOLARGE, "n=4097 exceeds DACO_MAX_NODES", dict(_UPD, n=4097, len=4097)),   # (4096 runs: test_gpu_32)
+    # the record kept by the update launch: a tour to keep but no record (lowest), and an update that would have to read the
+    # record it keeps (elitist ant, clamps, directed deposit)
+    ("daco_pheromone_update", BADARG, "lowest", dict(_UPD, shortest=P)),
+    ("daco_pheromone_update_heads", BADARG, "lowest", dict(_UPDH, shortest=P)),
+    ("daco_pheromone_update_heads", BADARG, "lowest", dict(_UPDU, shortest=P)),
+    ("daco_pheromone_update", BADARG, "bad argument", dict(_REC)),
+    ("daco_pheromone_update_heads", BADARG, "bad argument", dict(_REC)),
+    ("daco_pheromone_update_heads", BADARG, "bad argument", dict(_REC, tail_c=0.5)),
+    ("daco_pheromone_update", BADARG, "the record is kept by", dict(_UPD, **_REC, workspace_bytes=1 << 40, elitist=1)),
+    ("daco_pheromone_update", BADARG, "the record is kept by", dict(_UPD, **_REC, workspace_bytes=1 << 40, clamp_min=P, clamp_max=P)),
+    ("daco_pheromone_update", BADARG, "the record is kept by", dict(_UPD, **_REC, workspace_bytes=1 << 40, symmetric=0)),
+    ("daco_pheromone_update", BADARG, "the record is kept by", dict(_UPD, lowest=P, shortest=P, paths=None, nbr=P, workspace_bytes=1 << 40)),   # a tour from nowhere
+    ("daco_pheromone_update", BADARG, "the record is kept by", dict(_UPD, **_REC, workspace_bytes=1 << 40, tours16=P, tours_ld=64)),            # rows shorter than n
 ]
 
 
 HAS_WORKSPACE = ["daco_tsp_sample", "daco_cvrp_sample", "daco_prob_matrix", "daco_pick_move", "daco_sibling_sample", "daco_rcpsp_sample",
-                 "daco_tsp_sample_sparse", "daco_tsp_sample_race_head", "daco_tsp_sample_heads", "daco_pheromone_update",
-                 "daco_pheromone_update_heads", "daco_two_opt_prepare", "daco_gnn_forward", "daco_gnn_train_forward",
-                 "daco_gnn_train_backward", "daco_transformer_forward", "daco_transformer_forward_train", "daco_transformer_backward"]
+                 "daco_tsp_sample_heads", "daco_pheromone_update", "daco_pheromone_update_heads", "daco_two_opt_prepare",
+                 "daco_gnn_forward", "daco_gnn_train_forward", "daco_gnn_train_backward", "daco_transformer_forward",
+                 "daco_transformer_forward_train", "daco_transformer_backward"]
 HAS_SIZE_PLAN = [s for s in HAS_WORKSPACE if not s.startswith("daco_gnn")] + [
     "daco_rcpsp_schedule", "daco_rcpsp_backward", "daco_mkpv_sample", "daco_mkpv_backward", "daco_mkpv_update", "daco_sample_backward",
     "daco_sibling_backward", "daco_two_opt", "daco_two_opt_nbr", "daco_two_opt_auto", "daco_tsp_nls", "daco_cvrp_local_search",

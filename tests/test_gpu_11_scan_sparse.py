@@ -1,4 +1,4 @@
-"""sampler "scan_sparse" (csrc/daco_scan_sparse.hip, include/deepaco_hip.h daco_tsp_sample_sparse) through the C ABI against its
+"""sampler "scan_sparse" (csrc/daco_scan_sparse.hip, include/deepaco_hip.h daco_tsp_sample_heads) through the C ABI against its
 CPU restatement (oracle draw_scan_sparse, which tests/test_scan_sparse_oracle.py holds against the reference's categorical,
 tsp/aco.py:165-177): tours bit for bit -- head steps, tail walks with rejections, dense steps --, the counts of the three
 kinds of step, the fused tour lengths and the update's table; and the colony surface."""
@@ -142,7 +142,7 @@ def test_scan_sparse_colony_surface():
                                             (500, 32, 2, "ksparse", -1), (1000, 10, 1, "ksparse", -1), (640, 9, 1, "random_head", 2),
                                             (400, 12, 1, "wide_random_head", -1)])
 def test_race_on_head_rows_equals_the_dense_race(n, A, B, kind, fixed):
-    """daco_tsp_sample_race_head: the exponential race of DACO_RACE_PHILOX (torch.multinomial's arithmetic, tsp/aco.py:174-175)
+    """daco_tsp_sample_heads(race = 1): the exponential race of DACO_RACE_PHILOX (torch.multinomial's arithmetic, tsp/aco.py:174-175)
     generated for the 64 / 128 head slots only, the dense race for an ant whenever a tail candidate could still win.  Same noise
     indexing by node id: the tours must be the dense race's bit for bit -- against the oracle's race and against the dense
     kernel -- whatever the head is (k-sparse: a few dense steps late in the tours; an arbitrary subset of a dense heuristic:
@@ -476,7 +476,7 @@ def test_learned_heuristic_of_one_instance_takes_the_lds_heads():
 def test_colony_iteration_without_int64_paths(n, A, B, k, kw):
     """BatchedTSP.step(want_paths=False) -- what run() passes: the construction kernel leaves the tours as compact u16 rows in its
     workspace (daco_tsp_sparse_tours_offset) instead of the int64 [B, n, A] tensor, the best tour is copied from those rows
-    (daco_track_best_tours16), the deposit takes the table.  Against the colony that materialises the paths every step: the same
+    (daco_track_best on tours16 rows), the deposit takes the table.  Against the colony that materialises the paths every step: the same
     costs, records, best tours and pheromone, iteration by iteration; the compact rows are the paths."""
     from deepaco_amd import engine
     d = instance(n, 7 + n, "ksparse", B)[0].to(dev())

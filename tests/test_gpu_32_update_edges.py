@@ -152,11 +152,11 @@ def test_track_best_equals_rule(case):
     for form in ("paths", "tours16"):
         best = torch.full((case.B,), -7, dtype=torch.int32, device=dev())
         if form == "paths":
-            rc = _lib.lib().daco_track_best(stream, case.B, case.len, case.A, costs.data_ptr(), paths.data_ptr(), low.data_ptr(), None,
+            rc = _lib.lib().daco_track_best(stream, case.B, case.len, case.A, costs.data_ptr(), paths.data_ptr(), None, 0, low.data_ptr(), None,
                                             best.data_ptr(), None, 0.0)
         else:
-            rc = _lib.lib().daco_track_best_tours16(stream, case.B, case.len, case.A, case.ld, costs.data_ptr(), tours16.data_ptr(),
-                                                    low.data_ptr(), shortest.data_ptr(), best.data_ptr(), None, 0.0)
+            rc = _lib.lib().daco_track_best(stream, case.B, case.len, case.A, costs.data_ptr(), None, tours16.data_ptr(), case.ld,
+                                            low.data_ptr(), shortest.data_ptr(), best.data_ptr(), None, 0.0)
         _lib.check(rc, "daco_track_best")
         torch.cuda.synchronize()
         assert best.cpu().tolist() == want["best_idx"].tolist(), f"{case.id} {form}: best_idx"

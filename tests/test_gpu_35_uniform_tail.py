@@ -1,5 +1,5 @@
-"""The uniform-tail mode of the head-row path (daco_head_eta, daco_tsp_sample_heads_ut,
-daco_pheromone_update_heads_ut): for a heuristic that is ONE number c outside the head of every row, head rows are formed
+"""The uniform-tail mode of the head-row path (daco_head_eta, head_eta / tail_c of
+daco_tsp_sample_heads and daco_pheromone_update_heads): for a heuristic that is ONE number c outside the head of every row, head rows are formed
 without reading eta or writing the dense rows P, and the rare ways of a step walk the row of tau times c.  Everything the mode
 produces must equal the path with dense rows bit for bit -- tours, costs, pheromone, record, head rows, the counts of the three
 rare ways -- and the CPU oracle (as tests/test_gpu_11_scan_sparse.py holds the path with dense rows to it); the dense-row

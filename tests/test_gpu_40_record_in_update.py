@@ -1,4 +1,4 @@
-"""The colony's record kept by the update launch (daco_pheromone_update*_record; csrc/daco_costs_update.hip, deposit_rows_kernel:
+"""The colony's record kept by the update launch (the record arguments of daco_pheromone_update / _heads; csrc/daco_costs_update.hip, deposit_rows_kernel:
 the workgroup of an instance's last slab does what track_best_kernel does) against the three-launch sequence sampler ->
 track_best -> update of the same build: lowest_cost, shortest_path, pheromone and tours equal after every iteration -- with
 int64 paths and with compact u16 tours, on the head-row path (uniform tail and dense rows) and on the dense scan sampler, three
@@ -184,8 +184,8 @@ def test_update_refuses_a_record_it_would_have_to_read():
     ws = torch.zeros(1 << 20, dtype=torch.uint8, device=dev())
     args = lambda elitist, cl: (None, 1, n, n, A, t.data_ptr(), p.data_ptr(), c.data_ptr(), 0.9, elitist, 1, cl, cl, 0.0, None, None, 0,
                                 ws.data_ptr(), ws.numel(), None, 0, low.data_ptr(), None)
-    assert L.daco_pheromone_update_record(*args(1, None)) == -1 and b"record" in L.daco_last_error()
-    assert L.daco_pheromone_update_record(*args(0, low.data_ptr())) == -1 and b"record" in L.daco_last_error()
+    assert L.daco_pheromone_update(*args(1, None)) == -1 and b"record" in L.daco_last_error()
+    assert L.daco_pheromone_update(*args(0, low.data_ptr())) == -1 and b"record" in L.daco_last_error()
 
 
 @pytest.mark.parametrize("n,k,sampler", [(500, 50, "auto"), (100, None, "scan")])

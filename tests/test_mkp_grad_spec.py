@@ -17,7 +17,7 @@ from deepaco_amd import _lib
 
 def test_training_exports_sizes_and_argument_checks():
     L = _lib.lib()
-    assert L.daco_version() == _lib.ABI_VERSION == 129
+    assert L.daco_version() == _lib.ABI_VERSION == 130
     for name in ("daco_transformer_saved_floats", "daco_transformer_train_workspace_bytes", "daco_transformer_forward_train",
                  "daco_transformer_backward"):
         assert hasattr(L, name) and name in _lib.SIGNATURES

@@ -1,9 +1,10 @@
-"""The three exports of the uniform-tail mode (include/deepaco_hip.h: daco_head_eta, daco_tsp_sample_heads_ut,
-daco_pheromone_update_heads_ut) exist and refuse what their contract refuses before anything is launched (no GPU here: a
+"""The uniform-tail mode (include/deepaco_hip.h: daco_head_eta, and head_eta / tail_c of daco_tsp_sample_heads and
+daco_pheromone_update_heads) exists and refuses what their contract refuses before anything is launched (no GPU here: a
 launch would come back as DACO_E_HIP, -3)."""
 import pytest
 
 from deepaco_amd import _lib
+from test_entry_refusals import header_argnames
 
 P = 4096                       # a non-null, 16-byte-aligned "device pointer" no refused call ever dereferences
 BADARG, TOOLARGE, WORKSPACE = -1, -2, -4
@@ -12,8 +13,9 @@ BIG = 1 << 40
 
 def test_the_exports_exist():
     L = _lib.lib()
-    for name in ("daco_head_eta", "daco_tsp_sample_heads_ut", "daco_pheromone_update_heads_ut"):
-        assert hasattr(L, name) and name in _lib.SIGNATURES and _lib.SIGNATURES[name][0] is _lib._l
+    assert hasattr(L, "daco_head_eta") and _lib.SIGNATURES["daco_head_eta"][0] is _lib._l
+    for name in ("daco_tsp_sample_heads", "daco_pheromone_update_heads"):
+        assert hasattr(L, name) and _lib.SIGNATURES[name][0] is _lib._i and "head_eta" in header_argnames()[name]
 
 
 def _head_eta(B=1, n=200, eta=P, ids=P, slots=64, out=P, verdict=P):
@@ -21,13 +23,13 @@ def _head_eta(B=1, n=200, eta=P, ids=P, slots=64, out=P, verdict=P):
 
 
 def _sample(B=1, n=200, A=8, tau=P, eta=P, ids=P, slots=64, paths=P, ws=P, ws_bytes=BIG, heta=P, c=1e-10, fixed_start=-1):
-    return _lib.lib().daco_tsp_sample_heads_ut(None, 0, 0, 0, B, n, A, tau, n * n, eta, n * n, ids, slots, None, fixed_start, 1, 0, None, 0, 0,
-                                               paths, P, None, 0, None, None, None, ws, ws_bytes, None, None, heta, c)
+    return _lib.lib().daco_tsp_sample_heads(None, 0, 0, 0, 0, 0, B, n, A, tau, n * n, eta, n * n, 1.0, 1.0, ids, slots, None, fixed_start, 1, 0,
+                                            None, 0, 0, paths, P, None, 0, None, None, None, ws, ws_bytes, None, None, heta, c)
 
 
 def _update(B=1, n=200, A=8, tau=P, costs=P, nbr=P, ws=P, ws_bytes=BIG, ids=P, slots=64, sws=P, sws_bytes=BIG, heta=P, c=1e-10):
-    return _lib.lib().daco_pheromone_update_heads_ut(None, B, n, A, tau, None, costs, 0.9, 0, None, None, 0.0, nbr, None, ws, ws_bytes,
-                                                     ids, slots, 0, sws, sws_bytes, heta, c)
+    return _lib.lib().daco_pheromone_update_heads(None, B, n, A, tau, None, costs, 0.9, 0, None, None, 0.0, nbr, None, ws, ws_bytes,
+                                                  None, 0, 1.0, 1.0, ids, slots, 0, 0, sws, sws_bytes, heta, c, None, 0, None, None)
 
 
 @pytest.mark.parametrize("call, kw, code, words", [

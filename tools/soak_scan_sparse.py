@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised soak of sampler "scan_sparse" (daco_tsp_sample_sparse) against its CPU restatement (oracle draw_scan_sparse):
+"""Randomised soak of sampler "scan_sparse" (daco_tsp_sample_heads) against its CPU restatement (oracle draw_scan_sparse):
 random sizes, ant counts, head widths (64 / 128 slots), head contents (k-sparse heuristic, arbitrary subsets, tiny heads),
 start modes and WEIGHT SCALES -- heavy-tailed pheromone so that running sums absorb small terms and the rounding branches
 (no running sum reaches the remainder -> the lane's last positive slot; r past the head by an ulp) are taken.
