@@ -5,7 +5,7 @@
 
 namespace daco {
 
-// ---- parameter block layout (floats), built by the host (deepaco_amd/net.py pack_params)
+// ---- parameter block layout (floats), built by the host: the one walk deepaco_amd/net.py BlockNet._slots
 // [0]               v_lin0.W [32][feats] | v_lin0.b [32]
 // then              e_lin0.W [32]        | e_lin0.b [32]
 // then 12 x layer:  WvT [32 c][128 c']  (x1|x2|x3|x4 outputs, transposed) | bv [128]

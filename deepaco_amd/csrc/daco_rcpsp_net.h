@@ -7,7 +7,7 @@
 
 namespace daco {
 
-// ---- parameter block (floats), built by deepaco_amd/rcpsp/net.py (pack_params, pack_params_train): the layout of daco_gnn.h
+// ---- parameter block (floats), built by the walk of deepaco_amd/net.py (BlockNet._slots, rcpsp.net.Net uses it): the layout of daco_gnn.h
 // with 64 instead of 32 floats for e_lin0.weight
 // [0]               v_lin0.W [32][5] | v_lin0.b [32]
 // then              e_lin0.W [32][2] | e_lin0.b [32]                                                      (RN_OFF_ELIN)

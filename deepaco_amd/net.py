@@ -238,134 +238,217 @@ class _GnnTrainFn(torch.autograd.Function):
         return (gflat,) + (None,) * 9
 
 
-class Net(nn.Module):
-    """feats: node-feature width (2 = coordinates in tsp/, 1 in tsp_nls/ and cvrp/);
-    with_phe: also create the unused par_net_phe head that tsp/ checkpoints contain;
-    node_update=False: the sop/ and smtwtp/ variant whose node states are never updated (sop/net.py:43).  The kernels
-    run it as the same layer with the node BatchNorm's scale and shift set to zero: x + silu(0) = x exactly."""
+def _same(t):
+    return t
 
-    def __init__(self, feats=2, with_phe=True, node_update=True):
+
+def _detached(t):
+    return t.detach()
+
+
+def _unbias(count):
+    """count / (count - 1): from a batch variance to the unbiased one BatchNorm1d tracks.  A Python number stays one (Net:
+    every graph has the same counts); a tensor [G] of per-graph counts becomes float32 [G, 1] (rcpsp.net.Net).  The two
+    roundings need not agree in the last bit: each caller keeps its own."""
+    if torch.is_tensor(count):
+        c = count.to(torch.float32).view(-1, 1)
+        return c / (c - 1).clamp(min=1)
+    return count / max(count - 1, 1)
+
+
+class BlockNet(nn.Module):
+    """What Net and rcpsp.net.Net share: the kernels' flat parameter block (csrc/daco_gnn.h, csrc/daco_rcpsp_net.h) of a
+    module tree `emb_net` (an EmbNet) + `par_net_heu`, and the BatchNorm bookkeeping around it.  `_slots()` is the one
+    statement of the block's order; the training block, the folded eval block and `_flat_specs()` are read off it."""
+
+    _WHO = "deepaco_amd.Net"              # (the class prefix of the refusals)
+    _NO_STATS = ("Net.pack_params folds the BatchNorm running statistics; this network tracks none "
+                 "(track_running_stats=False): forward() / forward_batch() run the statistics kernels instead")
+    _DEAD_NODE_LAYERS = ()                # layers whose node update feeds nothing and enters the training block detached
+
+    def __init__(self):
         super().__init__()
-        self.emb_net = EmbNet(feats=feats, node_update=node_update)
-        if with_phe:
-            self.par_net_phe = ParNet()
-        self.par_net_heu = ParNet()
-        self._packed = None
-        self._packed_key = None
+        self._packed = self._packed_key = None
+
+    def _param_floats(self):
+        """The size of the block as the library states it."""
+        raise NotImplementedError
 
     # ------------------------------------------------------------------ reference surface
-    def forward(self, pyg):
-        """tsp/net.py:84-88.  Every mode runs on the HIP kernels:
-          training mode                        -> daco_gnn_train_forward / _backward, per-graph batch statistics (+ the running
-                                                  statistics' update, for every BatchNorm1d configuration)
-          eval mode under autograd             -> the same kernels with the running statistics as constants (fixed_stats)
-          eval mode without a gradient         -> daco_gnn_forward (BatchNorm folded into scale / shift)
-        (The module tree itself -- EmbNet / ParNet.forward as torch ops -- stays callable for cross-checks; forward() never is.)"""
-        x = pyg.x
-        if not x.is_cuda:
-            raise _lib.DacoError("deepaco_amd.Net runs on a HIP device only (got CPU tensors)")
-        needs_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        # BatchNorm1d(track_running_stats=False) normalises with the batch statistics in eval mode too: there is nothing to fold
-        # into scale / shift, the statistics kernels run (without a graph under no_grad) -- ADVICE r5
-        if self.training or needs_graph or not self._bn_config()[0]:
-            return self.forward_train_hip(pyg)
-        return self.forward_hip(pyg)
-
-    def _bn_config(self):
-        """(tracks running statistics, momentum | None) -- one configuration for all BatchNorm modules of the network."""
-        bns = [bn.module for bn in list(self.emb_net.v_bns) + list(self.emb_net.e_bns)]
-        cfg = {(bool(bn.track_running_stats and bn.running_mean is not None), bn.momentum) for bn in bns}
-        if len(cfg) != 1:
-            raise _lib.DacoError("deepaco_amd.Net: the BatchNorm modules of one network must share track_running_stats / momentum")
-        return next(iter(cfg))
-
     def freeze_gnn(self):
         for param in self.emb_net.parameters():
             param.requires_grad = False
 
     @staticmethod
     def reshape(pyg, vector):
-        '''Turn phe/heu vector into matrix with zero padding (tsp/net.py:94-102)'''
+        '''Turn phe/heu vector into matrix with zero padding (tsp/net.py:94-102, rcpsp/net.py:111-119)'''
         n_nodes = pyg.x.shape[0]
         matrix = torch.zeros(size=(n_nodes, n_nodes), device=pyg.x.device, dtype=vector.dtype)
         matrix[pyg.edge_index[0], pyg.edge_index[1]] = vector
         return matrix
 
-    # ------------------------------------------------------------------ HIP training path
-    def pack_params_train(self):
-        """Flat parameter block for the training kernels, built from the live parameters with differentiable ops
-        (views + one cat), so that autograd hands the flat gradient back to every nn.Parameter.  Layout of
-        csrc/daco_gnn.hip with gamma / beta in the BatchNorm slots."""
+    # ------------------------------------------------------------------ the block's order, once
+    def _slots(self):
+        """(kind, module(s), dead) in block order: v_lin0 | e_lin0 | 12 x (WvT | bv | We | be | bn_v | bn_e) | head.
+        'lin': weight [out][in], bias.  'node': the four node linears of a layer as one [32 in][128 out] matrix (linear q in
+        columns 32 q .. 32 q + 31), then their 128 biases.  'bn': the two vectors of a BatchNorm (gamma, beta when training;
+        scale, shift folded).  'zero': a BatchNorm slot that holds zeros in both blocks -- the node BatchNorm without the node
+        update (sop / smtwtp): x + silu(0) = x exactly.  dead: the slot's node-update tensors (v_lins1, v_lins2, v_bns) feed
+        nothing the loss sees and enter the training block detached, so their .grad stays None as in the reference (AdamW
+        decays a parameter whose gradient is zero and skips one whose gradient is None)."""
         e = self.emb_net
-        parts = [e.v_lin0.weight.reshape(-1), e.v_lin0.bias, e.e_lin0.weight.reshape(-1), e.e_lin0.bias]
+        yield "lin", e.v_lin0, False
+        yield "lin", e.e_lin0, False
         for i in range(DEPTH):
-            # without the node update (sop / smtwtp: the reference never calls v_lins1, v_lins2, v_bns, so their .grad stays
-            # None and AdamW's decoupled weight decay leaves them alone) those slices enter the block detached
-            live = (lambda t: t) if e.node_update else (lambda t: t.detach())
-            Wv = torch.cat([live(e.v_lins1[i].weight), live(e.v_lins2[i].weight), e.v_lins3[i].weight, e.v_lins4[i].weight], 0)   # [128, 32]
-            bv = torch.cat([live(e.v_lins1[i].bias), live(e.v_lins2[i].bias), e.v_lins3[i].bias, e.v_lins4[i].bias], 0)
-            vg, vb = e.v_bns[i].module.weight, e.v_bns[i].module.bias
-            if not e.node_update:                              # gamma = beta = 0: the node state passes through unchanged
-                vg, vb = torch.zeros_like(vg), torch.zeros_like(vb)
-            parts += [Wv.t().reshape(-1), bv, e.e_lins0[i].weight.reshape(-1), e.e_lins0[i].bias,
-                      vg, vb, e.e_bns[i].module.weight, e.e_bns[i].module.bias]
-        h = self.par_net_heu.lins
-        parts += [h[0].weight.reshape(-1), h[0].bias, h[1].weight.reshape(-1), h[1].bias, h[2].weight.reshape(-1), h[2].bias]
+            dead = not e.node_update or i in self._DEAD_NODE_LAYERS
+            yield "node", (e.v_lins1[i], e.v_lins2[i], e.v_lins3[i], e.v_lins4[i]), dead
+            yield "lin", e.e_lins0[i], False
+            yield ("bn" if e.node_update else "zero"), e.v_bns[i].module, dead
+            yield "bn", e.e_bns[i].module, False
+        for lin in self.par_net_heu.lins:
+            yield "lin", lin, False
+
+    def _cat(self, bn_slot):
+        """The block as one cat of the live tensors; bn_slot(bn): the two vectors of a 'bn' slot."""
+        parts = []
+        for kind, m, dead in self._slots():
+            enter = _detached if dead else _same
+            if kind == "lin":
+                parts += [m.weight, m.bias]
+            elif kind == "node":
+                Wv = torch.cat([enter(m[0].weight), enter(m[1].weight), m[2].weight, m[3].weight], 0)      # [128, 32]
+                parts += [Wv.t(), torch.cat([enter(m[0].bias), enter(m[1].bias), m[2].bias, m[3].bias], 0)]
+            elif kind == "bn":
+                parts += [enter(t) for t in bn_slot(m)]
+            else:
+                parts += [torch.zeros_like(m.weight), torch.zeros_like(m.bias)]
         return torch.cat([p.float().reshape(-1) for p in parts])
 
-    # ------------------------------------------------------------------ one flat parameter block (round 6)
+    def pack_params_train(self):
+        """Flat parameter block for the training kernels (gamma / beta in the BatchNorm slots), built from the live
+        parameters with differentiable ops (views + cats), so that autograd hands the flat gradient back to every
+        nn.Parameter -- except the dead slices of `_slots()`."""
+        return self._cat(lambda bn: (bn.weight, bn.bias))
+
     def _flat_specs(self):
-        """(parameter, offset, shape, stride) of every parameter the kernels read inside the training block (the layout
-        pack_params_train writes; csrc/daco_gnn.hip).  The four node linears of a layer are one [32 in][128 out] matrix there:
-        linear q's weight [out][in] is the strided view (1, 128) at column 32 q."""
-        e = self.emb_net
+        """(parameter, offset, shape, stride) of every parameter the kernels read inside the training block, and the
+        block's size."""
         specs, off = [], 0
-
-        def put(p, shape, stride):
-            nonlocal off
-            specs.append((p, off, shape, stride))
-            off += p.numel()
-
-        put(e.v_lin0.weight, (UNITS, e.feats), (e.feats, 1))
-        put(e.v_lin0.bias, (UNITS,), (1,))
-        put(e.e_lin0.weight, (UNITS, 1), (1, 1))
-        put(e.e_lin0.bias, (UNITS,), (1,))
-        for i in range(DEPTH):
-            lins = (e.v_lins1[i], e.v_lins2[i], e.v_lins3[i], e.v_lins4[i])
-            for q, lin in enumerate(lins):
-                specs.append((lin.weight, off + UNITS * q, (UNITS, UNITS), (1, 4 * UNITS)))
-            off += 4 * UNITS * UNITS
-            for q, lin in enumerate(lins):
-                specs.append((lin.bias, off + UNITS * q, (UNITS,), (1,)))
-            off += 4 * UNITS
-            put(e.e_lins0[i].weight, (UNITS, UNITS), (UNITS, 1))
-            put(e.e_lins0[i].bias, (UNITS,), (1,))
-            for bn in (e.v_bns[i].module, e.e_bns[i].module):
-                put(bn.weight, (UNITS,), (1,))
-                put(bn.bias, (UNITS,), (1,))
-        for lin in self.par_net_heu.lins:
-            put(lin.weight, tuple(lin.weight.shape), (lin.weight.shape[1], 1))
-            put(lin.bias, tuple(lin.bias.shape), (1,))
+        for kind, m, _ in self._slots():
+            if kind == "node":              # linear q's weight [out][in] is the strided view (1, 128) at column 32 q
+                specs += [(lin.weight, off + UNITS * q, (UNITS, UNITS), (1, 4 * UNITS)) for q, lin in enumerate(m)]
+                off += 4 * UNITS * UNITS
+                specs += [(lin.bias, off + UNITS * q, (UNITS,), (1,)) for q, lin in enumerate(m)]
+                off += 4 * UNITS
+            else:
+                for p in (m.weight, m.bias):
+                    specs.append((p, off, tuple(p.shape), (p.shape[1], 1) if p.dim() == 2 else (1,)))
+                    off += p.numel()
         return specs, off
 
+    # ------------------------------------------------------------------ the folded block and its cache
+    @staticmethod
+    def _fold(bn):
+        """Eval-mode BatchNorm as y = x * scale + shift."""
+        scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+        return scale, bn.bias - bn.running_mean * scale
+
+    def pack_params(self):
+        """Flat f32 parameter block for the inference kernels (BatchNorm folded into scale / shift), cached.
+        The cache's rule.  The key is the `_version` of every parameter and buffer, the device, and -- after
+        flatten_parameters(), whose views' own counters never move -- the flat block's `_version`: an in-place write, a
+        load_state_dict, an eager optimizer step on either form and an eager running-statistics update are all seen.  What no
+        counter sees is dropped by hand: `invalidate_packed()`, which pipeline.TspNlsTrainer.step calls on every step (a
+        graph replay runs no Python at all), and which a change of mode -- train(mode) with mode != self.training -- calls,
+        so that a validation loop's eval() picks up `.data` writes (an EMA's copies) made while training.  A call that leaves
+        the mode as it is keeps the block.  Out of reach: a `.data` write between two eval-mode forwards with no change of
+        mode in between needs invalidate_packed().  (transformer.TransformerModel keeps no cache: its pack is one cat of 44
+        tensors; this one is about 150 small ops, the folds included.)"""
+        holder = getattr(self, "_flat_holder", None)
+        key = tuple(t._version for t in list(self.parameters()) + list(self.buffers())) + (
+            next(self.parameters()).device, None if holder is None else holder[0]._version)
+        if self._packed is not None and self._packed_key == key:
+            return self._packed
+        if not self._bn_config()[0]:
+            raise _lib.DacoError(self._NO_STATS)
+        with torch.no_grad():
+            flat = self._cat(self._fold)
+        assert flat.numel() == self._param_floats()
+        self._packed, self._packed_key = flat, key
+        return flat
+
+    def invalidate_packed(self):
+        """Drop the cached folded block: the next pack_params() builds it again (see pack_params)."""
+        self._packed = self._packed_key = None
+
+    def train(self, mode=True):
+        if mode != self.training:
+            self.invalidate_packed()
+        return super().train(mode)
+
+    # ------------------------------------------------------------------ BatchNorm bookkeeping
+    def _bn_config(self):
+        """(tracks running statistics, momentum | None) -- one configuration for all BatchNorm modules of the network."""
+        bns = [bn.module for bn in list(self.emb_net.v_bns) + list(self.emb_net.e_bns)]
+        cfg = {(bool(bn.track_running_stats and bn.running_mean is not None), bn.momentum) for bn in bns}
+        if len(cfg) != 1:
+            raise _lib.DacoError(f"{self._WHO}: the BatchNorm modules of one network must share track_running_stats / momentum")
+        return next(iter(cfg))
+
+    @torch.no_grad()
+    def _update_running_stats(self, stats, count_e, count_v):
+        """BatchNorm1d's training-mode side effect, from the statistics the kernels report, as G successive reference forwards
+        (one per graph) would leave it: momentum m: running = (1 - m) * running + m * batch per graph (variance unbiased);
+        momentum None (cumulative average): running = (k * running + sum of the batches) / (k + G), k = num_batches_tracked.
+        stats [12, 2, G, 32, 2] (edge 0 / node 1; mean, biased variance); count_e, count_v: the rows behind an edge / a node
+        statistic, a number or a tensor [G] (see _unbias)."""
+        tracks, momentum = self._bn_config()
+        if not tracks:
+            return
+        G = stats.shape[2]
+        # all BatchNorms at once (a dozen launches instead of eight per module: the step is made of small kernels)
+        e = self.emb_net
+        which = [0, 1] if e.node_update else [0]                       # (the reference never calls the node BatchNorms of sop / smtwtp)
+        bns = [(i, w, (e.e_bns[i] if w == 0 else e.v_bns[i]).module) for i in range(DEPTH) for w in which]
+        mean = stats[..., 0]                                           # [12, 2, G, 32]
+        var = torch.stack((stats[:, 0, :, :, 1] * _unbias(count_e), stats[:, 1, :, :, 1] * _unbias(count_v)), dim=1)
+        rm, rv = [bn.running_mean for _, _, bn in bns], [bn.running_var for _, _, bn in bns]
+        nbt = [bn.num_batches_tracked for _, _, bn in bns]
+        if momentum is None:
+            k = float(nbt[0])                                          # (one host read; the cumulative average's weight)
+            add_m, add_v = mean.sum(2) / (k + G), var.sum(2) / (k + G)
+            keep = k / (k + G)
+        else:
+            m = momentum
+            decay = ((1 - m) ** torch.arange(G - 1, -1, -1, device=stats.device, dtype=torch.float32)).view(1, 1, G, 1)   # oldest graph first
+            add_m, add_v = m * (decay * mean).sum(2), m * (decay * var).sum(2)
+            keep = (1 - m) ** G
+        torch._foreach_mul_(rm + rv, keep)
+        torch._foreach_add_(rm, [add_m[i, w] for i, w, _ in bns])
+        torch._foreach_add_(rv, [add_v[i, w] for i, w, _ in bns])
+        torch._foreach_add_(nbt, G)
+
+    # ------------------------------------------------------------------ one flat parameter block (round 6)
     def flatten_parameters(self):
         """Re-seat every parameter the kernels read as a VIEW of one flat f32 block in the training kernels' layout and return
         that block as a single leaf nn.Parameter (VERDICT r5: the training step re-packed ~100 tensors with torch.cat every
         step and autograd split the flat gradient back into ~100 pieces -- two hundred launches of a few microseconds each).
         After this call
-          * the training forward hands the block to daco_gnn_train_forward as it is (no pack), the backward's flat gradient IS
+          * the training forward hands the block to the training kernels as it is (no pack), the backward's flat gradient IS
             the block's .grad, and every parameter's .grad is a view of it (set when the gradient arrives);
           * an elementwise optimizer may be built on [block] alone -- `torch.optim.AdamW(net.train_parameters(), ...)` -- and is
             then one fused update of one tensor: AdamW's update and decoupled weight decay are elementwise, so this is the
-            update `AdamW(net.parameters())` makes, element for element; clip_grad_norm_ over [block] is the same norm;
+            update `AdamW(net.parameters())` makes, element for element, wherever that optimizer sees a gradient;
+            clip_grad_norm_ over [block] is the same norm.  It is NOT the same update for layer 11's v_lins1 / v_lins2 /
+            v_bns, which feed nothing: their gradient is None in the reference (AdamW skips them) and zero in the block, so
+            weight decay shrinks them every step.  No output depends on them; a checkpoint's values of them differ;
           * state_dict / load_state_dict / eval-mode inference see the same module tree (load copies into the views).
         Moving or casting the module afterwards (.to / .double / .cuda) gives the parameters storages of their own again: the
         next training forward notices and raises; call flatten_parameters() again (and rebuild the optimizer).
         Only for networks whose every covered parameter is trained (node_update=True, nothing frozen): AdamW leaves a parameter
         without a gradient alone, a flat block cannot."""
-        e = self.emb_net
         specs, total = self._flat_specs()
-        if not e.node_update or any(not p.requires_grad for p, _, _, _ in specs):
+        if not self.emb_net.node_update or any(not p.requires_grad for p, _, _, _ in specs):
             raise _lib.DacoError("Net.flatten_parameters: every parameter of the block must be trained (node_update=True, none "
                                  "frozen): the optimizer's weight decay would move the ones the reference never touches")
         if any(p.dtype != torch.float32 for p, _, _, _ in specs):
@@ -386,7 +469,7 @@ class Net(nn.Module):
                 for p, off, shape, stride in specs:
                     p.grad = g.as_strided(shape, stride, off)
         block.register_post_accumulate_grad_hook(spread)
-        self._packed = None
+        self.invalidate_packed()
         return block
 
     def __deepcopy__(self, memo):
@@ -414,43 +497,54 @@ class Net(nn.Module):
                                      "moved or cast afterwards): call flatten_parameters() again and rebuild the optimizer")
         return block
 
+    def _train_block(self):
+        """What the training kernels read: the flat block after flatten_parameters(), else the differentiable pack."""
+        flat = self._flat_block()
+        if flat is None:
+            return self.pack_params_train()
+        return flat if torch.is_grad_enabled() else flat.detach()
+
     def train_parameters(self):
         """What to hand the optimizer: [the flat block] after flatten_parameters(), else the parameters that receive a gradient."""
         block = self._flat_block()
         return [block] if block is not None else [p for p in self.parameters() if p.requires_grad]
 
-    @torch.no_grad()
-    def _update_running_stats(self, stats, count_e, count_v):
-        """BatchNorm1d's training-mode side effect, from the statistics the kernels report, as G successive reference forwards
-        (one per graph) would leave it: momentum m: running = (1 - m) * running + m * batch per graph (variance unbiased);
-        momentum None (cumulative average): running = (k * running + sum of the batches) / (k + G), k = num_batches_tracked."""
-        tracks, momentum = self._bn_config()
-        if not tracks:
-            return
-        G = stats.shape[2]
-        # all 24 BatchNorms at once (a dozen launches instead of eight per module: the step is made of small kernels)
-        e = self.emb_net
-        which = [0, 1] if e.node_update else [0]                       # (the reference never calls the node BatchNorms of sop / smtwtp)
-        bns = [(i, w, (e.e_bns[i] if w == 0 else e.v_bns[i]).module) for i in range(DEPTH) for w in which]
-        mean = stats[..., 0]                                           # [12, 2, G, 32]
-        var = torch.stack((stats[:, 0, :, :, 1] * (count_e / max(count_e - 1, 1)),
-                           stats[:, 1, :, :, 1] * (count_v / max(count_v - 1, 1))), dim=1)      # unbiased, as BatchNorm1d tracks it
-        rm, rv = [bn.running_mean for _, _, bn in bns], [bn.running_var for _, _, bn in bns]
-        nbt = [bn.num_batches_tracked for _, _, bn in bns]
-        if momentum is None:
-            k = float(nbt[0])                                          # (one host read; the cumulative average's weight)
-            add_m, add_v = mean.sum(2) / (k + G), var.sum(2) / (k + G)
-            keep = k / (k + G)
-        else:
-            m = momentum
-            decay = ((1 - m) ** torch.arange(G - 1, -1, -1, device=stats.device, dtype=torch.float32)).view(1, 1, G, 1)   # oldest graph first
-            add_m, add_v = m * (decay * mean).sum(2), m * (decay * var).sum(2)
-            keep = (1 - m) ** G
-        torch._foreach_mul_(rm + rv, keep)
-        torch._foreach_add_(rm, [add_m[i, w] for i, w, _ in bns])
-        torch._foreach_add_(rv, [add_v[i, w] for i, w, _ in bns])
-        torch._foreach_add_(nbt, G)
 
+class Net(BlockNet):
+    """feats: node-feature width (2 = coordinates in tsp/, 1 in tsp_nls/ and cvrp/);
+    with_phe: also create the unused par_net_phe head that tsp/ checkpoints contain;
+    node_update=False: the sop/ and smtwtp/ variant whose node states are never updated (sop/net.py:43).  The kernels
+    run it as the same layer with the node BatchNorm's scale and shift set to zero: x + silu(0) = x exactly."""
+
+    def __init__(self, feats=2, with_phe=True, node_update=True):
+        super().__init__()
+        self.emb_net = EmbNet(feats=feats, node_update=node_update)
+        if with_phe:
+            self.par_net_phe = ParNet()
+        self.par_net_heu = ParNet()
+
+    def _param_floats(self):
+        return _lib.lib().daco_gnn_param_floats(self.emb_net.feats)
+
+    # ------------------------------------------------------------------ reference surface
+    def forward(self, pyg):
+        """tsp/net.py:84-88.  Every mode runs on the HIP kernels:
+          training mode                        -> daco_gnn_train_forward / _backward, per-graph batch statistics (+ the running
+                                                  statistics' update, for every BatchNorm1d configuration)
+          eval mode under autograd             -> the same kernels with the running statistics as constants (fixed_stats)
+          eval mode without a gradient         -> daco_gnn_forward (BatchNorm folded into scale / shift)
+        (The module tree itself -- EmbNet / ParNet.forward as torch ops -- stays callable for cross-checks; forward() never is.)"""
+        x = pyg.x
+        if not x.is_cuda:
+            raise _lib.DacoError("deepaco_amd.Net runs on a HIP device only (got CPU tensors)")
+        needs_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        # BatchNorm1d(track_running_stats=False) normalises with the batch statistics in eval mode too: there is nothing to fold
+        # into scale / shift, the statistics kernels run (without a graph under no_grad) -- ADVICE r5
+        if self.training or needs_graph or not self._bn_config()[0]:
+            return self.forward_train_hip(pyg)
+        return self.forward_hip(pyg)
+
+    # ------------------------------------------------------------------ HIP training path
     def _running_stats_block(self):
         """[12][2][32][2] (mean, variance) of the edge (0) and node (1) BatchNorm of every layer: fixed_stats of the kernels."""
         e = self.emb_net
@@ -468,9 +562,7 @@ class Net(nn.Module):
         n, feats = x.shape
         src, dst, rowptr, perm = _csr_graph(pyg, n, x.device)
         attr = pyg.edge_attr.float().contiguous().view(-1)
-        flat = self._flat_block()
-        if flat is None or not torch.is_grad_enabled():
-            flat = self.pack_params_train() if flat is None else flat.detach()
+        flat = self._train_block()
         tracks, _ = self._bn_config()
         # BatchNorm1d normalises with the batch statistics in training mode -- and in eval mode too when it tracks none
         fixed = self._running_stats_block() if (not self.training and tracks) else None
@@ -487,35 +579,6 @@ class Net(nn.Module):
         return self.forward_train_hip(_merge_graphs(x, edge_index, edge_attr, k_sparse), graphs=B).view(B, E)
 
     # ------------------------------------------------------------------ HIP inference path
-    def pack_params(self):
-        """Flat f32 parameter block in the layout csrc/daco_gnn.hip documents (BatchNorm folded)."""
-        key = tuple(t._version for t in list(self.parameters()) + list(self.buffers())) + (next(self.parameters()).device,)
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        e = self.emb_net
-        with torch.no_grad():
-            parts = [e.v_lin0.weight.reshape(-1), e.v_lin0.bias, e.e_lin0.weight.reshape(-1), e.e_lin0.bias]
-            if not self._bn_config()[0]:
-                raise _lib.DacoError("Net.pack_params folds the BatchNorm running statistics; this network tracks none "
-                                     "(track_running_stats=False): forward() / forward_batch() run the statistics kernels instead")
-            for i in range(DEPTH):
-                Wv = torch.cat([m[i].weight for m in (e.v_lins1, e.v_lins2, e.v_lins3, e.v_lins4)], 0)   # [128, 32]
-                bv = torch.cat([m[i].bias for m in (e.v_lins1, e.v_lins2, e.v_lins3, e.v_lins4)], 0)
-                parts += [Wv.t().contiguous().reshape(-1), bv, e.e_lins0[i].weight.reshape(-1), e.e_lins0[i].bias]
-                for bn in (e.v_bns[i].module, e.e_bns[i].module):
-                    scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-                    shift = bn.bias - bn.running_mean * scale
-                    if bn is e.v_bns[i].module and not e.node_update:
-                        scale, shift = torch.zeros_like(scale), torch.zeros_like(shift)
-                    parts += [scale, shift]
-            h = self.par_net_heu.lins
-            parts += [h[0].weight.reshape(-1), h[0].bias, h[1].weight.reshape(-1), h[1].bias, h[2].weight.reshape(-1),
-                      h[2].bias]
-            flat = torch.cat([p.float().reshape(-1) for p in parts]).contiguous()
-        assert flat.numel() == _lib.lib().daco_gnn_param_floats(e.feats)
-        self._packed, self._packed_key = flat, key
-        return flat
-
     @torch.no_grad()
     def forward_batch(self, x, edge_index, edge_attr, k_sparse=None):
         """Eval-mode forward for B graphs of equal size in ONE pass of the HIP kernels: the graphs are laid side

@@ -217,6 +217,7 @@ class TspNlsTrainer:
             self._graph = g
             g.replay()                                                # (a capture records; this runs the step)
         self.steps_done += 1
+        self.net.invalidate_packed()         # (a replay moves weights and running statistics behind every version counter)
         return self._out
 
 

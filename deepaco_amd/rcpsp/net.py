@@ -56,8 +56,13 @@ def relation_from_edges(n, edge_index, edge_attr):
     return rel.view(n, n)
 
 
-class Net(nn.Module):
+class Net(_net.BlockNet):
     GRAD_PATHS = ("torch", "hip")
+    _WHO = "rcpsp.Net"
+    _NO_STATS = "rcpsp.Net.pack_params folds the BatchNorm running statistics; this network tracks none"
+    # the last layer's node update (v_lins1.11, v_lins2.11, v_bns.11) feeds nothing: its .grad stays None as on the torch-op
+    # path; the reference still calls v_bns.11, so all 24 BatchNorms track their statistics
+    _DEAD_NODE_LAYERS = (DEPTH - 1,)
 
     def __init__(self, grad_path="torch"):
         super().__init__()
@@ -66,8 +71,9 @@ class Net(nn.Module):
         self.grad_path = grad_path
         self.emb_net = EmbNet()
         self.par_net_heu = ParNet()
-        self._packed = None
-        self._packed_key = None
+
+    def _param_floats(self):
+        return _lib.lib().daco_rcpsp_net_param_floats()
 
     # ------------------------------------------------------------------ reference surface
     def forward(self, pyg, require_phe=False, require_heu=False):
@@ -87,79 +93,7 @@ class Net(nn.Module):
         self._check_feats(pyg.x.shape[1])
         return self.par_net_heu(self.emb_net(pyg.x, pyg.edge_index, pyg.edge_attr))
 
-    def freeze_gnn(self):
-        for param in self.emb_net.parameters():
-            param.requires_grad = False
-
-    @staticmethod
-    def reshape(pyg, vector):
-        '''Turn phe/heu vector into matrix with zero padding (rcpsp/net.py:111-119)'''
-        n_nodes = pyg.x.shape[0]
-        matrix = torch.zeros(size=(n_nodes, n_nodes), device=pyg.x.device, dtype=vector.dtype)
-        matrix[pyg.edge_index[0], pyg.edge_index[1]] = vector
-        return matrix
-
     # ------------------------------------------------------------------ HIP training path
-    def _param_block(self, dead, bn_slots):
-        """One walk over the flat parameter block in the layout of csrc/daco_rcpsp_net.h: v_lin0, e_lin0, then
-        WvT | bv | We | be | bn_v | bn_e for the 12 layers, then the head.  dead(t): how a tensor of the last layer's node
-        update (v_lins1.11, v_lins2.11, v_bns.11: it feeds nothing) enters; bn_slots(bn): the two vectors of a BatchNorm slot."""
-        e = self.emb_net
-        parts = [e.v_lin0.weight, e.v_lin0.bias, e.e_lin0.weight, e.e_lin0.bias]
-        for i in range(DEPTH):
-            same = lambda t: t                                                                # noqa: E731
-            live = dead if i == DEPTH - 1 else same
-            lins = ((e.v_lins1[i], live), (e.v_lins2[i], live), (e.v_lins3[i], same), (e.v_lins4[i], same))
-            Wv = torch.cat([enter(m.weight) for m, enter in lins], 0)                        # [128, 32]
-            parts += [Wv.t(), torch.cat([enter(m.bias) for m, enter in lins], 0), e.e_lins0[i].weight, e.e_lins0[i].bias,
-                      *(live(t) for t in bn_slots(e.v_bns[i].module)), *bn_slots(e.e_bns[i].module)]
-        for lin in self.par_net_heu.lins:
-            parts += [lin.weight, lin.bias]
-        return torch.cat([p.float().reshape(-1) for p in parts])
-
-    def pack_params_train(self):
-        """Flat parameter block for the training kernels (the layout of csrc/daco_rcpsp_net.h with gamma / beta in the
-        BatchNorm slots), built from the live parameters with differentiable ops, so that autograd hands the flat gradient back
-        to every nn.Parameter.  The last layer's node update (v_lins1.11, v_lins2.11, v_bns.11) feeds nothing: those slices
-        enter detached, so their .grad stays None as on the torch-op path (AdamW decays a parameter whose gradient is zero
-        and skips one whose gradient is None)."""
-        return self._param_block(lambda t: t.detach(), lambda bn: (bn.weight, bn.bias))
-
-    @torch.no_grad()
-    def _update_running_stats(self, stats, count_e, n):
-        """BatchNorm1d's training-mode side effect for all 24 BatchNorms (v_bns.11 included: the reference calls it, its output
-        is dead), from the statistics the kernel reports, as B successive single-project reference forwards would leave
-        them -- the rule of deepaco_amd.net.Net._update_running_stats with every project's own edge count.  stats
-        [12, 2, B, 32, 2], count_e [B]."""
-        e = self.emb_net
-        bns = [(i, w, (e.e_bns[i] if w == 0 else e.v_bns[i]).module) for i in range(DEPTH) for w in (0, 1)]
-        cfg = {(bool(bn.track_running_stats and bn.running_mean is not None), bn.momentum) for _, _, bn in bns}
-        if len(cfg) != 1:
-            raise _lib.DacoError("rcpsp.Net: the BatchNorm modules of one network must share track_running_stats / momentum")
-        tracks, momentum = next(iter(cfg))
-        if not tracks:
-            return
-        B = stats.shape[2]
-        ce = count_e.to(torch.float32).view(B, 1)
-        mean = stats[..., 0]                                                              # [12, 2, B, 32]
-        var = torch.stack((stats[:, 0, :, :, 1] * (ce / (ce - 1).clamp(min=1)),
-                           stats[:, 1, :, :, 1] * (n / max(n - 1, 1))), dim=1)             # unbiased, as BatchNorm1d tracks it
-        rm, rv = [bn.running_mean for _, _, bn in bns], [bn.running_var for _, _, bn in bns]
-        nbt = [bn.num_batches_tracked for _, _, bn in bns]
-        if momentum is None:
-            k = float(nbt[0])
-            add_m, add_v = mean.sum(2) / (k + B), var.sum(2) / (k + B)
-            keep = k / (k + B)
-        else:
-            m = momentum
-            decay = ((1 - m) ** torch.arange(B - 1, -1, -1, device=stats.device, dtype=torch.float32)).view(1, 1, B, 1)
-            add_m, add_v = m * (decay * mean).sum(2), m * (decay * var).sum(2)
-            keep = (1 - m) ** B
-        torch._foreach_mul_(rm + rv, keep)
-        torch._foreach_add_(rm, [add_m[i, w] for i, w, _ in bns])
-        torch._foreach_add_(rv, [add_v[i, w] for i, w, _ in bns])
-        torch._foreach_add_(nbt, B)
-
     def forward_relation_train(self, x, relation, eps=1e-10):
         """x [B, n, 5], relation [B, n, n] uint8 on a HIP device -> heu [B, n, n] of the training-mode network, differentiable
         with respect to the parameters (autograd.RcpspNetFn); updates the BatchNorm running statistics."""
@@ -167,7 +101,7 @@ class Net(nn.Module):
         if not self.training:
             raise _lib.DacoError("rcpsp.Net: the HIP gradient path is the training-mode network (batch statistics): call .train()")
         self._check_graph(x)
-        flat = self.pack_params_train()
+        flat = self._train_block()
         if flat.device != x.device:
             raise _lib.DacoError(f"rcpsp.Net: parameters on {flat.device}, graph on {x.device}")
         heu, stats = RcpspNetFn.apply(flat, x, relation, float(eps))
@@ -206,24 +140,6 @@ class Net(nn.Module):
         self._check_feats(x.shape[-1])
         if x.shape[-2] > engine.RCPSP_NET_MAX_N:
             raise _lib.DacoTooLarge(f"rcpsp.Net: n={x.shape[-2]} exceeds {engine.RCPSP_NET_MAX_N}")
-
-    def pack_params(self):
-        """Flat f32 parameter block in the layout csrc/daco_rcpsp_net.h documents (BatchNorm folded), cached."""
-        key = tuple(t._version for t in list(self.parameters()) + list(self.buffers())) + (next(self.parameters()).device,)
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-
-        def folded(bn):
-            if not bn.track_running_stats or bn.running_mean is None:
-                raise _lib.DacoError("rcpsp.Net.pack_params folds the BatchNorm running statistics; this network tracks none")
-            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-            return scale, bn.bias - bn.running_mean * scale
-
-        with torch.no_grad():
-            flat = self._param_block(lambda t: t, folded)
-        assert flat.numel() == _lib.lib().daco_rcpsp_net_param_floats()
-        self._packed, self._packed_key = flat, key
-        return flat
 
     @torch.no_grad()
     def forward_relation(self, x, relation, eps=1e-10, want_logit=False, want_emb=False):

@@ -376,7 +376,8 @@ def test_trainer_captured_steps_train():
     assert int(net.emb_net.e_bns[3].module.num_batches_tracked) == 12 * 6
     assert float(c) < first
     assert torch.equal(net.pack_params_train().detach(), trainer.block.detach())
-    # eval-mode inference sees the trained values (the folded block is rebuilt from the views' version counter)
+    # eval-mode inference sees the trained values: no version counter moved under the replays (the views' never do), the folded
+    # block is rebuilt because trainer.step() drops it (Net.invalidate_packed) and because eval() changes the mode
     net.eval()
     from deepaco_amd import engine
     _, ei, ea = engine.tsp_knn_graph(coords, 8, want_dist=False)
@@ -384,6 +385,35 @@ def test_trainer_captured_steps_train():
     x[:, 0] = 1.0
     h1 = net.forward_batch(x, ei, ea, k_sparse=8)
     assert torch.isfinite(h1).all()
+
+
+def test_eval_forward_follows_replayed_steps():
+    """A validation loop: captured steps, eval() + forward_batch, more replayed steps WITHOUT touching the mode, forward_batch
+    again.  A replay runs no Python, so no version counter sees the new weights or running statistics; the second forward
+    must still be the network's as it stands -- bitwise the forward of a fresh Net loaded from state_dict()."""
+    from deepaco_amd import engine
+    from deepaco_amd.pipeline import TspNlsTrainer
+    from deepaco_amd.tsp_nls.net import Net
+    torch.manual_seed(13)
+    B, n, k = 2, 20, 5
+    net = Net().to(dev())
+    trainer = TspNlsTrainer(net, B=B, n=n, n_ants=4, k_sparse=k, lr=1e-3, graph=True)
+    coords = torch.rand(B, n, 2, device=dev())
+    for _ in range(4):
+        trainer.step(coords)
+    assert trainer._graph is not None
+    _, ei, ea = engine.tsp_knn_graph(coords, k, want_dist=False)
+    x = torch.zeros(B, n, 1, device=dev())
+    x[:, 0] = 1.0
+    net.eval()
+    h1 = net.forward_batch(x, ei, ea, k_sparse=k)
+    for _ in range(3):
+        trainer.step(coords)
+    h2 = net.forward_batch(x, ei, ea, k_sparse=k)
+    assert not torch.equal(h1, h2)
+    fresh = Net().to(dev())
+    fresh.load_state_dict(net.state_dict())
+    assert torch.equal(h2, fresh.eval().forward_batch(x, ei, ea, k_sparse=k))
 
 
 @pytest.mark.parametrize("name", ["g5_net_tsp_tsp100", "g5_net_tsp_tsp20", "g5_net_tsp_nls_tsp100"])

@@ -300,3 +300,31 @@ def test_train_rcpsp_batch(B):
     assert moved == {k for k, g in ref.items() if g is not None}
     assert all(int(bn.module.num_batches_tracked) == int(sd["emb_net.v_bns.0.module.num_batches_tracked"]) + B
                for bn in list(net.emb_net.v_bns) + list(net.emb_net.e_bns))
+
+
+# ------------------------------------------------------------------ 6. the flat parameter block
+def test_the_flattened_network_trains_through_its_block():
+    """After flatten_parameters() (net.BlockNet) the training forward hands the block to the kernels as it is and the backward's
+    flat gradient is the block's .grad: the same launches on the same bytes as the packed block of an unflattened twin (the
+    kernels use no atomics), so the heuristic, the gradient and the running statistics are bitwise the twin's; the dead slices
+    (v_lins1.11, v_lins2.11, v_bns.11), whose .grad is None in the twin, are zero in the block."""
+    f = fixture("J301_1", 30)
+    twin, net = make_net(f["sd"]), make_net(f["sd"])
+    block = net.flatten_parameters()
+    specs, _ = net._flat_specs()
+    name_of = {id(p): k for k, p in net.named_parameters()}
+    x, rel, coef = T(f["graph"]["x"])[None], T(f["rel"])[None], T(f["coef"])[None]
+    heu_t = twin.forward_relation_train(x, rel)
+    (heu_t * coef).sum().backward()
+    heu = net.forward_relation_train(x, rel)
+    (heu * coef).sum().backward()
+    assert torch.equal(heu.detach(), heu_t.detach())
+    grads = dict(twin.named_parameters())
+    for p, off, shape, stride in specs:
+        want = grads[name_of[id(p)]].grad
+        got = block.grad.as_strided(shape, stride, off)
+        assert p.grad is not None and p.grad.data_ptr() == got.data_ptr(), name_of[id(p)]
+        assert torch.equal(got, want) if want is not None else (tspec.is_dead(name_of[id(p)]) and not got.any()), name_of[id(p)]
+    for (k, v), (_, w) in zip(net.state_dict().items(), twin.state_dict().items()):
+        if "running_" in k or "num_batches" in k:
+            assert torch.equal(v, w), k
