@@ -46,7 +46,13 @@
 //            pairs whose polar sectors overlap); O(n^2 * route length) direct evaluation, no insertion tables.
 // (asym[k]: f64 sum over the route's edges before position k of d[s[t+1]][s[t]] - d[s[t]][s[t+1]] -- what the edges cost
 // more walked backwards; exactly 0 for a symmetric matrix, the perturbation matrix 1/(eta/rowmax + 1e-5) is not symmetric.)
-// Moves between routes must keep every route within capacity.  The distance matrix is staged in LDS when it fits
+// Moves between routes must keep every route within capacity.
+// A column is normalised before the search and written back whatever the move cap (0 included): doubled depots are squeezed
+// out, a missing closing depot is appended, the rows after the L entries are zero.  A column without a customer (every entry
+// the depot) is the sequence 0, L = 1: it has no candidate, so no move is made whatever the cap (lens = 1, moves = 0).  A
+// column whose last row holds a customer gets its closing depot appended past the column: lens = Lmax + 1 at most, the
+// column holds the first Lmax entries of the sequence.
+// The distance matrix is staged in LDS when it fits
 // (n <= 160: every gather of the search is then an LDS read).
 // Bookkeeping per move is wave-parallel: route ids from ballots over 64 positions at a time, one lane per route for the
 // (sequential, f64) loads and reversal sums, the new sequence gathered by all threads through a table of at most six source
@@ -142,6 +148,8 @@ cvrp_ls_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, const fl
   }
   __syncthreads();
   int L = shared_i[0];
+  // a column without a customer squeezes to L < 3: no candidate exists (the pair loops step by W = L - 1, which would be 0)
+  if (L < 3) count = 0;
   int moves = 0;
   for (; moves < count; ++moves) {
     // ---- tables.  Wave 0: route of every position and the routes' opening depots (ballots over 64 positions)

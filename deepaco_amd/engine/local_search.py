@@ -111,6 +111,10 @@ def cvrp_local_search_(dist, demand, capacity, paths, max_moves, want_stats=Fals
     paths [B,Lmax,A] or [Lmax,A] int64 (route sequences as gen_path returns them).  Best improvement over HGS's move
     families (relocate 1 / 2 / 2 reversed, swap 1-1 / 2-1 / 2-2, 2-opt, 2-opt* both ways; SWAP* when none of them
     improves), hard capacity, at most max_moves moves per solution (csrc/daco_cvrp_ls.hip has the specification).
+    Every column is normalised and written back, with max_moves = 0 too: doubled depots are squeezed out, the rows after the
+    sequence's lens entries are zero.  A column of depots only comes back as it is, lens = 1 and moves = 0.  A column whose last row
+    holds a customer has no room for the closing depot the search appends: lens counts it (Lmax + 1 unless moves emptied a
+    route) and the column holds the first Lmax entries of the sequence.
     Returns paths (and lens, moves [B,A])."""
     _require_gpu(dist, demand, paths)
     n = dist.shape[-1]

@@ -662,9 +662,11 @@ int daco_gnn_train_backward(void *stream, int n, int E, int feats, int G, const 
  *   dist     [B][n][n] f32 (dist_bstride elements between instances, 0 = shared); need not be symmetric
  *   demand   [B][n] f32, demand[.][0] = 0;  capacity: vehicle capacity in the same unit
  *   paths    in/out [B][Lmax][A] int64: column (b, a) is ant a's route sequence 0 a b 0 c d 0 ... zero-padded
- *            (the layout of ACO.gen_path, cvrp/aco.py:138-165); rewritten in place without empty routes
+ *            (the layout of ACO.gen_path, cvrp/aco.py:138-165); rewritten in place without empty routes, with
+ *            max_moves = 0 too; a column of depots only comes back unchanged (lens 1, moves 0)
  *   max_moves  moves applied at most per solution (the reference's `count`/`limit`)
- *   lens     out [B][A] int32 or NULL: entries used by each solution (including the closing depot)
+ *   lens     out [B][A] int32 or NULL: entries used by each solution (including the closing depot; Lmax + 1 for a
+ *            column whose last row holds a customer -- the column then holds the first Lmax entries)
  *   moves    out [B][A] int32 or NULL: moves applied
  */
 int daco_cvrp_local_search(void *stream, int B, int n, int A, int Lmax, const float *dist, long dist_bstride,

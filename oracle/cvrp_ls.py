@@ -25,6 +25,11 @@ SWAP* (kind 9, evaluated only when no candidate of kinds 0-8 is below -1e-6): u 
 r2 > r1, change = ((remU + remV) + insU) + insV, remU = D(a,c) - (D(a,u) + D(u,c)), insU = the cheaper of "in place of v"
 (D(e,u) + D(u,g)) - D(e,g) and the cheapest (D(s[p],u) + D(u,s[p+1])) - D(s[p],s[p+1]) over r2's positions p (opening depot
 included) not next to v; ties: the smallest p, and the place of v before any p.
+A column is normalised before the search and written back whatever the move cap (0 included): doubled depots are squeezed
+out, a missing closing depot is appended, the rows after the L entries are zero.  A column without a customer (every entry
+the depot) is the sequence 0, L = 1: it has no candidate, so no move is made whatever the cap (lens = 1, moves = 0).  A
+column whose last row holds a customer gets its closing depot appended past the column: lens = Lmax + 1 at most, the
+column holds the first Lmax entries of the sequence.
 Pure Python / numpy scalars: small cases only.
 """
 import numpy as np

@@ -3,7 +3,10 @@
 CPU restatement (oracle/cvrp_ls.py, an independent pure-Python implementation of the same specification): random small
 instances -- Euclidean, integer-grid (ties), row-scaled and random asymmetric matrices (the reversal terms), tight and loose
 capacities, normalised demands with exact fits, move caps -- sequences, lengths and move counts must be identical.
-usage: tools/soak_cvrp_ls.py [seconds] [seed]"""
+usage: tools/soak_cvrp_ls.py [seconds] [seed] [min customers] [max customers]
+(customers default to 4..33: one 64-position chunk of the kernel's bookkeeping; 60..150 draws sequences of two and three chunks
+and the LDS opt-in sizes -- the time is checked between cases, and one uncapped case of the pure-Python restatement takes minutes
+there)"""
 import json
 import os
 import sys
@@ -19,13 +22,16 @@ from oracle import cvrp_ls as ols  # noqa: E402
 dev = torch.device("cuda:0")
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 20260927
+cust_lo = int(sys.argv[3]) if len(sys.argv) > 3 else 4
+cust_hi = int(sys.argv[4]) if len(sys.argv) > 4 else 33
+assert 1 <= cust_lo <= cust_hi
 rng = np.random.default_rng(seed)
 t_end = time.time() + budget
 cases = sols = moves_total = 0
 applied = []
 kinds = {}
 while time.time() < t_end:
-    n = int(rng.integers(4, 34))                               # customers
+    n = int(rng.integers(cust_lo, cust_hi + 1))                # customers
     A = int(rng.integers(1, 7))
     kind = str(rng.choice(["euclid", "grid", "rowscaled", "asym"]))
     c = rng.random((n + 1, 2)).astype(np.float32)
@@ -67,5 +73,5 @@ while time.time() < t_end:
     sols += A
     kinds[kind] = kinds.get(kind, 0) + 1
 print(json.dumps({"soak": "cvrp_ls_kernel == oracle/cvrp_ls.py (sequences, lengths, move counts)", "seconds": budget, "seed": seed,
-                  "cases": cases, "solutions": sols, "moves": moves_total,
+                  "customers": [cust_lo, cust_hi], "cases": cases, "solutions": sols, "moves": moves_total,
                   "moves_by_kind": {ols.KINDS[k]: applied.count(k) for k in range(len(ols.KINDS))}, "kinds": kinds, "mismatches": 0}))
