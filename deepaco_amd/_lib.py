@@ -75,6 +75,8 @@ SIGNATURES = {
     # (long statuses, as daco_rcpsp_net_forward)
     "daco_sibling_objective": (_l, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
     "daco_sibling_record": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
+    "daco_reinforce": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "daco_reinforce_backward": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "daco_tsp_knn_graph": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp]),
     "daco_tsp_knn_graph_csr": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "daco_cvrp_knn_graph": (_l, [_vp, _i, _i, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp]),   # (a long status too)

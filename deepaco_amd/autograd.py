@@ -9,6 +9,11 @@ import torch
 from . import engine
 
 
+def _own_output(out, given):
+    """A Function's output must not be one of its input objects: the caller's flag words come back as an alias of them."""
+    return out.detach() if given is not None and out is given else out
+
+
 class TspSampleFn(torch.autograd.Function):
     """(heuristic [n,n]) -> (paths [n,A], log_probs [n-1,A], flags [1]); grad flows to heuristic only."""
 
@@ -36,13 +41,16 @@ class TspBatchSampleFn(torch.autograd.Function):
     forward, one daco_sample_backward launch backward (the batched tsp_nls/train.py step)."""
 
     @staticmethod
-    def forward(ctx, heuristic, pheromone, n_ants, alpha, beta, mode, norm_passes, fixed_start, seed, it, iter_dev=None):
-        # (iter_dev: int64 device scalar added to `it` by the kernel -- a captured training step advances it)
+    def forward(ctx, heuristic, pheromone, n_ants, alpha, beta, mode, norm_passes, fixed_start, seed, it, iter_dev=None,
+                ant_gid0=0, flags=None):
+        # (iter_dev: int64 device scalar added to `it` by the kernel -- a captured training step advances it;
+        #  ant_gid0: the id of the first ant; flags: the caller's sticky flag words [B], OR-ed into and handed back)
         eta = heuristic.detach().contiguous()
         B = eta.shape[0]
-        paths, logp, rowsum, flags = engine.tsp_sample(
+        paths, logp, rowsum, out_flags = engine.tsp_sample(
             pheromone, eta, n_ants, alpha, beta, mode=mode, norm_passes=norm_passes, fixed_start=fixed_start,
-            seed=seed, it=it, require_prob=True, batch=B, iter_dev=iter_dev)
+            seed=seed, it=it, ant_gid0=ant_gid0, require_prob=True, batch=B, iter_dev=iter_dev, flags=flags)
+        flags = _own_output(out_flags, flags)
         ctx.save_for_backward(pheromone, eta, paths, rowsum)
         ctx.ab = (alpha, beta)
         ctx.mark_non_differentiable(paths, flags)
@@ -52,7 +60,7 @@ class TspBatchSampleFn(torch.autograd.Function):
     def backward(ctx, _gp, glogp, _gf):
         tau, eta, paths, rowsum = ctx.saved_tensors
         grad = engine.sample_backward(tau, eta, ctx.ab[0], ctx.ab[1], paths, rowsum, glogp.contiguous())
-        return (grad,) + (None,) * 10
+        return (grad,) + (None,) * 12
 
 
 class TspEdgeSampleFn(torch.autograd.Function):
@@ -124,12 +132,14 @@ class CvrpBatchSampleFn(torch.autograd.Function):
     Instance b draws what a single colony with ant_gid0 + b * n_ants as its first ant id draws."""
 
     @staticmethod
-    def forward(ctx, heuristic, pheromone, demand, capacity, n_ants, alpha, beta, mode, noise, seed, it, ant_gid0=0):
+    def forward(ctx, heuristic, pheromone, demand, capacity, n_ants, alpha, beta, mode, noise, seed, it, ant_gid0=0, flags=None):
+        # (flags: the caller's sticky flag words [B], OR-ed into and handed back instead of fresh zeros)
         eta = heuristic.detach().contiguous()
         B = eta.shape[0]
-        paths, logp, rowsum, lens, flags = engine.cvrp_sample(
+        paths, logp, rowsum, lens, out_flags = engine.cvrp_sample(
             pheromone, eta, demand, capacity, n_ants, alpha, beta, mode=mode, noise=noise, seed=seed, it=it, ant_gid0=ant_gid0,
-            require_prob=True, batch=B)
+            require_prob=True, batch=B, flags=flags)
+        flags = _own_output(out_flags, flags)
         ctx.save_for_backward(pheromone, eta, paths, rowsum, lens, demand)
         ctx.misc = (alpha, beta, capacity)
         ctx.mark_non_differentiable(paths, lens, flags)
@@ -140,7 +150,61 @@ class CvrpBatchSampleFn(torch.autograd.Function):
         tau, eta, paths, rowsum, lens, demand = ctx.saved_tensors
         a, b, cap = ctx.misc
         grad = engine.sample_backward(tau, eta, a, b, paths, rowsum, glogp.contiguous(), lens=lens, demand=demand, capacity=cap)
+        return (grad,) + (None,) * 12
+
+
+class SiblingBatchSampleFn(torch.autograd.Function):
+    """B sop / pctsp / op / mkp colonies at once: (heuristic [B,n,n], pheromone [B,n,n]) -> (paths [B,rows,A], log_probs
+    [B,rows-1,A], lens [B,A] (empty for sop, whose routes all have n nodes), flags [B]); rows = 2n + 1 as the sampler allots
+    them (n for sop), nothing trimmed.  One daco_sibling_sample launch forward, one daco_sibling_backward launch for the whole
+    batch backward.  Instance b draws what a single colony with ant_gid0 + b * n_ants as its first ant id draws.
+    kw: the kind's instance data as engine.sibling_sample takes it (aux_vec, aux_mat, scalar0, item_weights); flags: the
+    caller's sticky flag words [B], OR-ed into and handed back instead of fresh zeros."""
+
+    @staticmethod
+    def forward(ctx, heuristic, pheromone, kind, n_ants, alpha, beta, mode, seed, it, ant_gid0, kw, flags=None):
+        eta = heuristic.detach().float().contiguous()
+        tau = pheromone.detach().float().contiguous()
+        if eta.dim() != 3:
+            raise ValueError(f"SiblingBatchSampleFn: heuristic [B,n,n] expected, got {tuple(eta.shape)}")
+        paths, logp, rowsum, lens, out_flags = engine.sibling_sample(kind, tau, eta, n_ants, alpha, beta, mode=mode, seed=seed, it=it,
+                                                                     ant_gid0=ant_gid0, require_prob=True, flags=flags, **kw)
+        flags = _own_output(out_flags, flags)
+        out_lens = lens if lens is not None else torch.empty(0, dtype=torch.int32, device=paths.device)
+        ctx.save_for_backward(tau, eta, paths, rowsum, out_lens)
+        ctx.meta = (kind, alpha, beta, {k: v for k, v in kw.items() if k in ("aux_vec", "aux_mat", "scalar0", "item_weights")})
+        ctx.mark_non_differentiable(paths, out_lens, flags)
+        return paths, logp, out_lens, flags
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _gp, glogp, _gl, _gf):
+        tau, eta, paths, rowsum, lens = ctx.saved_tensors
+        kind, alpha, beta, kw = ctx.meta
+        grad = engine.sibling_backward(kind, tau, eta, alpha, beta, paths, rowsum, glogp.contiguous(),
+                                       lens=lens if lens.numel() else None, **kw)
         return (grad,) + (None,) * 11
+
+
+class ReinforceFn(torch.autograd.Function):
+    """The REINFORCE tail in one launch each way: (obj [B,A], log_probs [B,R,A], lens [B,A] int32 | None, d, sign) ->
+    loss [B], loss[b] = sum_a adv[b,a] * sum_{r live} log_probs[b,r,a] / A with adv = sign * (obj - mean_a obj) and the live
+    rows r < max_a lens[b,a] - d (all without lens): daco_reinforce.  The gradient flows to log_probs only (the objectives
+    are the baseline's data, as under the reference's no_grad): daco_reinforce_backward writes g[b] adv[b,a] / A on the live
+    rows and zeros past them straight into the [B,R,A] buffer the sampler's backward reads.  The batch loss is .mean()."""
+
+    @staticmethod
+    def forward(ctx, obj, log_probs, lens, d, sign):
+        loss, adv, live = engine.reinforce(obj.detach(), log_probs.detach(), lens, d, sign)
+        ctx.save_for_backward(adv, live)
+        ctx.rows = log_probs.shape[1]
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        adv, live = ctx.saved_tensors
+        return None, engine.reinforce_backward(g.contiguous(), adv, live, ctx.rows), None, None, None
 
 
 class SiblingSampleFn(torch.autograd.Function):

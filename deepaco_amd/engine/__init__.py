@@ -17,6 +17,7 @@ from .mkp_ops import (BatchedMKPVec, mkpv_backward, mkpv_check_flags, mkpv_sampl
 from .rcpsp_ops import (RCPSP_FLAG_ORDER, RCPSP_FLAG_RESOURCE, RCPSP_MAX_HORIZON, RCPSP_MAX_N, RCPSP_MAX_R, RCPSP_NET_MAX_N,  # noqa: F401
                         BatchedRCPSP, rcpsp_backward, rcpsp_check_flags, rcpsp_net_backward, rcpsp_net_forward,
                         rcpsp_net_forward_train, rcpsp_sample, rcpsp_schedule)
+from .reinforce_ops import reinforce, reinforce_backward  # noqa: F401
 from .sibling_colonies import (BATCHED_SIBLINGS, OBJ_KINDS, BatchedBPP, BatchedMKP, BatchedOP, BatchedPCTSP, BatchedSMTWTP,  # noqa: F401
                                BatchedSOP, sibling_objective, sibling_record_)
 from .sibling_ops import SIB_KINDS, PickService, sibling_backward, sibling_sample  # noqa: F401

@@ -455,6 +455,29 @@ class BatchedCVRP:
             paths = paths[:, :int(lens.max())].contiguous()
         return paths, costs
 
+    def sample(self):
+        """The batched form of cvrp/aco.py:66-69 (`ACO.sample()`): one construction with log-probabilities for all B colonies.
+        Returns (costs [B, A], log_probs [B, 2n, A], lens [B, A] int32); the log-probabilities carry gradient to self.heuristic
+        when it requires grad (assign the differentiable [B, n, n] matrix to `heuristic` after construction).  Instance b draws
+        with the ant ids ant_gid0 + b*A + a of iteration self.iteration, as _step() does, and the iteration advances.  Nothing is
+        trimmed (that would need the longest route on the host): an ant's rows past its route are the depot, and the rows past
+        an instance's longest ant hold the padding's log(1 - 2^-23) (autograd.ReinforceFn leaves them out).  The colony's
+        sticky flag words are OR-ed into, not read (check_feasible() reads them)."""
+        if torch.is_grad_enabled() and self.heuristic.requires_grad:
+            from ..autograd import CvrpBatchSampleFn
+            paths, log_probs, lens, flags = CvrpBatchSampleFn.apply(self.heuristic, self.pheromone, self.demand, float(self.capacity),
+                                                                    self.n_ants, self.alpha, self.beta, self.sampler, None, self.seed,
+                                                                    self.iteration, self.ant_gid0, self._flags)
+        else:
+            paths, log_probs, _, lens, flags = cvrp_sample(self.pheromone, self.heuristic, self.demand, self.capacity, self.n_ants,
+                                                           self.alpha, self.beta, mode=self.sampler, seed=self.seed, it=self.iteration,
+                                                           ant_gid0=self.ant_gid0, require_prob=True, batch=self.B, flags=self._flags)
+        self.iteration += 1
+        self.last_lens, self.last_flags, self.last_paths = lens, self._flags, paths
+        with torch.no_grad():
+            costs = tour_costs(self.distances, paths, closed=False)
+        return costs, log_probs, lens
+
     def check_feasible(self):
         """Raise like the reference's Categorical if any draw so far had no feasible candidate (syncs; the flag words are sticky)."""
         _raise_flags(self.last_flags, ((1, ValueError, "BatchedCVRP: a transition row had no feasible candidate"),

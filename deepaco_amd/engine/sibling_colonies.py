@@ -3,7 +3,9 @@
 An iteration is the problem's existing construction launch, daco_sibling_objective (objective, elitist key and deposit amount
 of every ant), daco_sibling_record (the record step of the reference's run() on the device) and the directed deposit with the
 hub and floor the single-instance classes of deepaco_amd/siblings.py pass; nothing in run() synchronises with the host.
-Instance b draws with the ant ids ant_gid0 + b*A + a, so it is the one-instance colony with ant_gid0 = b*A, bit for bit."""
+Instance b draws with the ant ids ant_gid0 + b*A + a, so it is the one-instance colony with ant_gid0 = b*A, bit for bit.
+sample() is the batched ACO.sample() of the six directories: one construction with log-probabilities that carry gradient to the
+heuristic (set_heuristic), scored by the same objective launch -- the training steps of pipeline.train_sibling_batch."""
 import torch
 
 from .. import _lib
@@ -160,11 +162,46 @@ class _BatchedSibling:
         _raise_flags(self._flags, ((1, ValueError, f"{who}: a transition row had no feasible candidate"),
                                    (2, RuntimeError, f"{who}: solution buffer too short")))
 
-    def _sibling(self, kind, **kw):
-        paths, _, _, lens, _ = sibling_sample(kind, self.pheromone, self.heuristic, self.n_ants, self.alpha, self.beta,
-                                              mode=self.sampler, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0,
-                                              flags=self._flags, **kw)
-        return paths, lens
+    def _sibling(self, kind, require_prob=False, **kw):
+        if require_prob and self._wants_grad():
+            from ..autograd import SiblingBatchSampleFn
+            paths, logp, lens, _ = SiblingBatchSampleFn.apply(self.heuristic, self.pheromone, kind, self.n_ants, self.alpha, self.beta,
+                                                              self.sampler, self.seed, self.iteration, self.ant_gid0, kw, self._flags)
+            return paths, (lens if lens.numel() else None), logp
+        paths, logp, _, lens, _ = sibling_sample(kind, self.pheromone, self.heuristic, self.n_ants, self.alpha, self.beta,
+                                                 mode=self.sampler, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0,
+                                                 require_prob=require_prob, flags=self._flags, **kw)
+        return (paths, lens, logp) if require_prob else (paths, lens)
+
+    def _wants_grad(self):
+        return torch.is_grad_enabled() and self.heuristic.requires_grad
+
+    def embed_heuristic(self, heu):
+        """The matrix the construction reads, from the problem's own [B, n, n] heuristic (the network's output, say): a dummy
+        node or a fixed column is added where the reference's constructor adds one.  Differentiable; __init__ goes through it."""
+        return heu.float()
+
+    def set_heuristic(self, heu):
+        """Replace the heuristic by embed_heuristic(heu) WITHOUT detaching it: sample() then carries gradient to `heu`."""
+        h = self.embed_heuristic(heu)
+        assert tuple(h.shape) == tuple(self.heuristic.shape), f"heuristic {tuple(self.heuristic.shape)} expected, got {tuple(h.shape)}"
+        self.heuristic = h if h.is_contiguous() else h.contiguous()
+        return self
+
+    def sample(self):
+        """The batched form of the directory's ACO.sample(): one construction with log-probabilities for all B colonies.
+        Returns (obj [B, A] -- float64 for BPP, whose objective is -fitness --, log_probs [B, R, A], lens [B, A] int32 | None);
+        the log-probabilities carry gradient to self.heuristic when it requires grad (set_heuristic).  Instance b draws with the
+        ant ids ant_gid0 + b*A + a of iteration self.iteration, as _step() does, and the iteration advances.  R is what the
+        sampler allots (2n where routes vary in length, nothing trimmed: that would need the longest route on the host); the
+        rows past an instance's longest ant hold the padding's log(1 - 2^-23) (autograd.ReinforceFn leaves them out).
+        The colony's sticky flag words are OR-ed into, not read (check_feasible() reads them)."""
+        paths, lens, log_probs = self._construct(require_prob=True)
+        self.iteration += 1
+        self.last_lens, self.last_paths = lens, paths
+        with torch.no_grad():
+            obj = self._objective(paths, lens)[0]
+        return obj, log_probs, lens
 
 
 def _heuristic(h, B, n):
@@ -197,12 +234,17 @@ class BatchedSMTWTP(_BatchedSibling):
     lowest_cost = property(lambda self: self._best[0])
     best_sol = property(lambda self: self._best[1])
 
-    def _construct(self):
+    def _construct(self, require_prob=False):
         mode = "scan_wave" if self.sampler == "scan" else self.sampler       # (the draw of siblings.SMTWTP)
-        paths, _, _, _ = tsp_sample(self.pheromone, self.heuristic, self.n_ants, self.alpha, self.beta, mode=mode,
-                                    norm_passes=1, fixed_start=0, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0,
-                                    batch=self.B, flags=self._flags)
-        return paths, None
+        if require_prob and self._wants_grad():
+            from ..autograd import TspBatchSampleFn
+            paths, logp, _ = TspBatchSampleFn.apply(self.heuristic, self.pheromone, self.n_ants, self.alpha, self.beta, mode, 1, 0,
+                                                    self.seed, self.iteration, None, self.ant_gid0, self._flags)
+            return paths, None, logp
+        paths, logp, _, _ = tsp_sample(self.pheromone, self.heuristic, self.n_ants, self.alpha, self.beta, mode=mode,
+                                       norm_passes=1, fixed_start=0, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0,
+                                       require_prob=require_prob, batch=self.B, flags=self._flags)
+        return (paths, None, logp) if require_prob else (paths, None)
 
     def _objective(self, paths, lens):
         return sibling_objective("smtwtp", paths, None, self.processing_time, self.due_time, self.weights, n=self.n)
@@ -233,8 +275,8 @@ class BatchedSOP(_BatchedSibling):
     def _mmas(self):
         return self.n, None
 
-    def _construct(self):
-        return self._sibling("sop", aux_vec=self._pending, aux_mat=self._before)
+    def _construct(self, require_prob=False):
+        return self._sibling("sop", require_prob, aux_vec=self._pending, aux_mat=self._before)
 
     def _objective(self, paths, lens):
         return sibling_objective("sop", paths, None, mat=self.distances)
@@ -268,8 +310,8 @@ class BatchedPCTSP(_BatchedSibling):
     def _mmas(self):
         return self.n - 1, None
 
-    def _construct(self):
-        return self._sibling("pctsp", aux_vec=self.prizes, scalar0=self.min_prizes)
+    def _construct(self, require_prob=False):
+        return self._sibling("pctsp", require_prob, aux_vec=self.prizes, scalar0=self.min_prizes)
 
     def _objective(self, paths, lens):
         return sibling_objective("pctsp", paths, lens, self.penalties, mat=self.distances)
@@ -301,8 +343,7 @@ class BatchedOP(_BatchedSibling):
         self.prizes = torch.cat((self.prizes, torch.zeros((B, 1), device=dev)), dim=1).contiguous()
         d = torch.cat((self.distances, torch.full((B, 1, n), 1e10, device=dev)), dim=1)
         self.distances = torch.cat((d, torch.zeros((B, n + 1, 1), device=dev)), dim=2).contiguous()
-        h = torch.cat((self.heuristic, torch.zeros((B, 1, n), device=dev)), dim=1)
-        self.heuristic = _heuristic(torch.cat((h, torch.ones((B, n + 1, 1), device=dev)), dim=2), B, n + 1)
+        self.heuristic = _heuristic(self.embed_heuristic(self.heuristic), B, n + 1)
         self._home = self.distances[:, :, 0].contiguous()
         self.pheromone = torch.ones_like(self.distances) if pheromone is None else _f32c(pheromone).clone()
         self._best = self._record(2 * (n + 1) + 1, 0.0)
@@ -314,11 +355,17 @@ class BatchedOP(_BatchedSibling):
     def sparsify(self, k_sparse):
         self.heuristic = sparsify_heuristic(self.distances, k_sparse, numer=self.prizes, path=self.setup_path)
 
+    def embed_heuristic(self, heu):
+        """[B, n, n] -> [B, n+1, n+1]: the dummy end node's row of zeros and column of ones (op/aco.py:65-85)"""
+        B, n, dev = heu.shape[0], self.n, heu.device
+        h = torch.cat((heu.float(), torch.zeros((B, 1, n), device=dev)), dim=1)
+        return torch.cat((h, torch.ones((B, n + 1, 1), device=dev)), dim=2)
+
     def _mmas(self):
         return self.n, self.Q
 
-    def _construct(self):
-        return self._sibling("op", aux_vec=self._home, aux_mat=self.distances, scalar0=float(self.max_len))
+    def _construct(self, require_prob=False):
+        return self._sibling("op", require_prob, aux_vec=self._home, aux_mat=self.distances, scalar0=float(self.max_len))
 
     def _objective(self, paths, lens):
         return sibling_objective("op", paths, lens, self.prizes, scale=self.Q)
@@ -339,19 +386,30 @@ class BatchedBPP(_BatchedSibling):
         self.capacity, self.demand = capacity, _f32c(demand)
         self._setup(B, demand.device, n_ants, decay, alpha, beta, elitist, False, None, sampler, seed, ant_gid0)
         self._init_pheromone(pheromone, n)
-        heuristic = self.demand.unsqueeze(1).repeat(1, n, 1) if heuristic is None else _f32c(heuristic.detach()).clone()
-        heuristic[:, :, 0] = 1e-5
-        self.heuristic = _heuristic(heuristic, B, n)
+        heuristic = self.demand.unsqueeze(1).repeat(1, n, 1) if heuristic is None else heuristic.detach()
+        self.heuristic = _heuristic(self.embed_heuristic(heuristic), B, n)
         self._best = self._record(2 * n + 1, 0.0, torch.float64)
 
     best_fitness = property(lambda self: self._best[0])
     shortest_path = property(lambda self: self._best[1])
 
-    def _construct(self):
-        paths, _, _, lens, _ = cvrp_sample(self.pheromone, self.heuristic, self.demand, self.capacity, self.n_ants, self.alpha,
-                                           self.beta, mode=self.sampler, seed=self.seed, it=self.iteration,
-                                           ant_gid0=self.ant_gid0, batch=self.B, flags=self._flags)
-        return paths, lens
+    def embed_heuristic(self, heu):
+        """a copy whose column 0 (opening a bin) is 1e-5 (bpp/aco.py:61: `self.heuristic[:, 0] = 1e-5`)"""
+        h = heu.float().clone()
+        h[:, :, 0] = 1e-5
+        return h
+
+    def _construct(self, require_prob=False):
+        if require_prob and self._wants_grad():
+            from ..autograd import CvrpBatchSampleFn
+            paths, logp, lens, _ = CvrpBatchSampleFn.apply(self.heuristic, self.pheromone, self.demand, float(self.capacity), self.n_ants,
+                                                           self.alpha, self.beta, self.sampler, None, self.seed, self.iteration,
+                                                           self.ant_gid0, self._flags)
+            return paths, lens, logp
+        paths, logp, _, lens, _ = cvrp_sample(self.pheromone, self.heuristic, self.demand, self.capacity, self.n_ants, self.alpha,
+                                              self.beta, mode=self.sampler, seed=self.seed, it=self.iteration,
+                                              ant_gid0=self.ant_gid0, require_prob=require_prob, batch=self.B, flags=self._flags)
+        return (paths, lens, logp) if require_prob else (paths, lens)
 
     def _objective(self, paths, lens):
         return sibling_objective("bpp", paths, lens, self.demand, capacity=self.capacity, elitist=self.elitist)
@@ -379,15 +437,20 @@ class BatchedMKP(_BatchedSibling):
         # dummy node n (mkp/aco.py:60-64)
         self.prize = torch.cat((prize, torch.zeros((B, 1), device=dev)), dim=1).contiguous()
         self.weight = torch.cat((weight, torch.zeros((B, 1, m), device=dev)), dim=1).contiguous()
-        h = torch.cat((heu, torch.zeros((B, 1, n), device=dev)), dim=1)
-        self.heuristic = _heuristic(torch.cat((h, 1e-10 * torch.ones((B, n + 1, 1), device=dev)), dim=2), B, n + 1)
+        self.heuristic = _heuristic(self.embed_heuristic(heu), B, n + 1)
         self._best = self._record(2 * (n + 1) + 1, 0.0)
 
     alltime_best_obj = property(lambda self: self._best[0])
     alltime_best_sol = property(lambda self: self._best[1])
 
-    def _construct(self):
-        return self._sibling("mkp", item_weights=self.weight, scalar0=float(self.n // 2))
+    def embed_heuristic(self, heu):
+        """[B, n, n] -> [B, n+1, n+1]: the dummy item's row of zeros and column of 1e-10 (mkp/aco.py:60-64)"""
+        B, n, dev = heu.shape[0], self.n, heu.device
+        h = torch.cat((heu.float(), torch.zeros((B, 1, n), device=dev)), dim=1)
+        return torch.cat((h, 1e-10 * torch.ones((B, n + 1, 1), device=dev)), dim=2)
+
+    def _construct(self, require_prob=False):
+        return self._sibling("mkp", require_prob, item_weights=self.weight, scalar0=float(self.n // 2))
 
     def _objective(self, paths, lens):
         return sibling_objective("mkp", paths, lens, self.prize, scale=self.Q)

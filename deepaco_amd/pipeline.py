@@ -435,17 +435,270 @@ def infer_rcpsp_batch(instances, n_ants, t_aco, heuristic=None, seed=0, sampler=
 
 
 @torch.no_grad()
-def infer_sibling_batch(problem, data, n_ants, t_aco, heuristic=None, seed=0, **aco_kw):
+def infer_sibling_batch(problem, data, n_ants, t_aco, heuristic=None, seed=0, net=None, **aco_kw):
     """The test loops of the sibling problems (op/test.py, mkp/test.py and the notebooks of smtwtp, sop, pctsp, bpp: one colony
     per instance, the record read at every checkpoint of t_aco) for B instances of one size at once.  problem: 'smtwtp', 'sop',
     'pctsp', 'op', 'bpp' or 'mkp'; data: the tuple of batched tensors of that problem's engine.Batched* constructor (e.g.
     (distances [B,n,n], prizes [B,n], max_len) for 'op'); heuristic [B,.,.] as that constructor takes it, or None for the
-    reference's default; aco_kw: anything else the constructor takes.  Returns (records [len(t_aco), B], colony)."""
+    reference's default; net: the directory's Net, whose sibling_heuristic_batch(problem, net.eval(), data) is the heuristic
+    instead (giving a heuristic as well is an error; 'op' then needs its k_sparse); aco_kw: anything else the constructor takes.
+    Returns (records [len(t_aco), B], colony)."""
+    if net is not None:
+        if heuristic is not None:
+            raise ValueError("infer_sibling_batch: give either a heuristic or a network, not both")
+        heuristic = sibling_heuristic_batch(problem, net.eval(), data, k_sparse=aco_kw.get("k_sparse"))
+        aco_kw = {k: v for k, v in aco_kw.items() if k != "k_sparse"}      # (the graph's: the colony sparsifies nothing it is given)
     colony = engine.BATCHED_SIBLINGS[problem](*data, n_ants=n_ants, heuristic=heuristic, seed=seed, **aco_kw)
     out, done = [], 0
     for t in t_aco:
         out.append(colony.run(t - done).clone())
         done = t
+    return torch.stack(out), colony
+
+
+# ------------------------------------------------------------------ cvrp/ and the six siblings: network -> colonies, batched
+SIBLING_PROBLEMS = ("cvrp", "smtwtp", "sop", "pctsp", "op", "bpp", "mkp")
+# REINFORCE sign: +1 minimises sum (obj - baseline) log p (cvrp, smtwtp, sop, pctsp, bpp), -1 maximises: (baseline - obj)
+# (op/train.ipynb, mkp/train.py:26)
+SIBLING_SIGN = {"cvrp": 1, "smtwtp": 1, "sop": 1, "pctsp": 1, "bpp": 1, "op": -1, "mkp": -1}
+LOSS_PATHS = ("hip", "torch")
+
+
+def _check_problem(problem):
+    if problem not in SIBLING_PROBLEMS:
+        raise ValueError(f"problem must be one of {SIBLING_PROBLEMS} (got {problem!r})")
+
+
+def _complete_edges(B, n, dev):
+    """[B, 2, n n] int64: edge j n + t runs j -> t (source-major, the layout _merge_graphs(k_sparse=n) writes down in closed form)"""
+    nodes = torch.arange(n, device=dev)
+    ei = torch.stack((torch.repeat_interleave(nodes, n), nodes.repeat(n)))
+    return ei.unsqueeze(0).expand(B, 2, n * n).contiguous()
+
+
+def sop_adjacency(prec_cons):
+    """sop/utils.py:23-28 from the precedence matrix: u -> v may be used unless u == v or v has to precede u, which is
+    prec_cons[u, v] = 1 (adjacency_mat_gen clears the entries preceding_mat_gen sets).  [.., n, n] -> [.., n, n]."""
+    n = prec_cons.shape[-1]
+    return (1 - prec_cons.float()) * (1 - torch.eye(n, device=prec_cons.device))
+
+
+@torch.no_grad()
+def sibling_graph_batch(problem, data, k_sparse=None):
+    """The network's graphs of B instances of one of cvrp/, smtwtp/, pctsp/, op/, bpp/, mkp/ on the device, without a sort or a
+    host read: (x [B,n,f] f32, edge_index [B,2,E] int64 with ids local to each graph, edge_attr [B,E] f32).  data: the tuple of
+    batched tensors the problem's colony takes -- cvrp (demands [B,n], distances [B,n,n]), smtwtp (due_time, weights,
+    processing_time [B,n]; the graph has the dummy job 0 in front: n + 1 nodes), pctsp (distances, prizes, penalties), op
+    (distances [B,n,n] with 1e9 on the diagonal, prizes [B,n], max_len), bpp (demand [B,n],), mkp (prize [B,n], weight [B,n,m]).
+    The complete graphs (all but op) come in SOURCE-MAJOR order, edge j n + t = j -> t: the regular layout whose row pointer
+    Net.forward_batch(..., k_sparse=n) writes down as arange * n.  pctsp/utils.py lists its edges this way already; cvrp, smtwtp,
+    bpp and mkp list them destination-major (`u = nodes.repeat(n)`: edge e runs e % n -> e // n), so edge e of the reference's
+    list is edge (e % n) n + e // n here and edge_attr is permuted to match -- the network's output is the same function of the
+    graph, listed in another order.  smtwtp's first feature is due_time / n (instance_gen hands out due_norm * n).
+    op: the k_sparse nearest neighbours per node, nearest first, as op/utils.py:26-49 takes them (torch.topk on the distances:
+    the reference's own call, batched; the diagonal's 1e9 keeps a node out of its own list), with the depot distance (0 for the
+    depot itself) and the prizes as node features; edge j k + t leaves node j: Net.forward_batch(..., k_sparse=k).
+    sop is not built here: its graph is nonzero(adj), its size depends on the data (see sibling_heuristic_batch)."""
+    _check_problem(problem)
+    if problem == "sop":
+        raise ValueError("sibling_graph_batch: sop's graph is nonzero(adj) -- ragged; sibling_heuristic_batch runs it per instance")
+    if problem == "cvrp":
+        demands, distances = data
+        B, n = demands.shape
+        return demands.float().unsqueeze(2), _complete_edges(B, n, demands.device), distances.float().transpose(1, 2).reshape(B, n * n)
+    if problem == "smtwtp":
+        due_time, weights, processing_time = data
+        B, n = due_time.shape
+        dev = due_time.device
+        x = torch.cat((torch.zeros((B, 1, 2), device=dev), torch.stack((due_time.float() / n, weights.float()), dim=2)), dim=1)
+        padded = torch.cat((torch.zeros((B, 1), device=dev), processing_time.float()), dim=1)           # attribute of u -> v: v's processing time
+        return x, _complete_edges(B, n + 1, dev), padded.unsqueeze(1).expand(B, n + 1, n + 1).reshape(B, (n + 1) ** 2)
+    if problem == "pctsp":
+        distances, prizes, penalties = data
+        B, n = prizes.shape
+        return torch.stack((prizes.float(), penalties.float()), dim=2), _complete_edges(B, n, prizes.device), distances.float().reshape(B, n * n)
+    if problem == "bpp":
+        demand = data[0]
+        B, n = demand.shape
+        return demand.float().unsqueeze(2), _complete_edges(B, n, demand.device), torch.ones((B, n * n), device=demand.device)
+    if problem == "mkp":
+        prize, weight = data
+        B, n = prize.shape
+        # attribute of u -> v: u's prize (`prize.repeat(n)` on the destination-major list)
+        return weight.float().contiguous(), _complete_edges(B, n, prize.device), prize.float().unsqueeze(2).expand(B, n, n).reshape(B, n * n)
+    distances, prizes = data[0], data[1]
+    if not k_sparse:
+        raise ValueError("sibling_graph_batch: 'op' needs k_sparse")
+    B, n = prizes.shape
+    k = int(k_sparse)
+    dev = prizes.device
+    home = distances[:, :, 0].float().clone()
+    home[:, 0] = 0.0
+    near_d, near_i = torch.topk(distances.float(), k=k, dim=2, largest=False)
+    src = torch.repeat_interleave(torch.arange(n, device=dev), k).unsqueeze(0).expand(B, n * k)
+    ei = torch.stack((src, near_i.reshape(B, n * k)), dim=1).contiguous()
+    ei._daco_ids_ok = (n, ei._version)           # (topk's indices are in range by construction: Net.reshape_batch reads nothing back)
+    return torch.stack((home, prizes.float()), dim=2), ei, near_d.reshape(B, n * k)
+
+
+def _sop_heuristic_batch(net, data):
+    """sop: the single-instance forward per instance (graph = nonzero(adj): one host read per instance), matrices stacked"""
+    from .net import GraphData
+    distances, prec_cons = data
+    adj = sop_adjacency(prec_cons)
+    mats = []
+    for b in range(distances.shape[0]):
+        d = distances[b].float()
+        pyg = GraphData(x=d[0, :].unsqueeze(-1), edge_index=torch.nonzero(adj[b]).T, edge_attr=d[adj[b].bool()].unsqueeze(-1))
+        mats.append(net.reshape(pyg, net(pyg)) + EPS)
+    return torch.stack(mats)
+
+
+def sibling_heuristic_batch(problem, net, data, k_sparse=None):
+    """The heuristic matrices [B,n,n] of B instances from the directory's network, by the directory's own recipe: graphs
+    (sibling_graph_batch) -> one forward for the batch -- Net.forward_batch_train under autograd when the network is in training
+    mode (per-graph BatchNorm statistics, the running statistics updated as B successive forwards leave them), Net.forward_batch
+    in eval mode -- -> the recipe of the train cell / file, quirks included:
+      cvrp, bpp     heu_vec.reshape(n, n) + 1e-10
+      mkp           m = heu_vec.reshape(n, n); m / (m.min() + 1e-10) + 1e-10
+      pctsp         (v / (v.min() + EPS) + EPS).reshape(n, n)
+      smtwtp, op    Net.reshape(pyg, vec) + EPS        (smtwtp: n + 1 nodes, the dummy job first; op: k_sparse is required)
+      sop           Net.reshape(pyg, vec) + EPS, the single-instance forward once per instance and the matrices stacked: its
+                    graph is nonzero(adj), whose size depends on the data.  Its colony, sampler and backward are still one launch
+                    each for the batch.
+    The plain reshapes of cvrp, bpp and mkp ignore edge direction: edge e of their destination-major lists runs
+    (e % n) -> (e // n) and lands at [e // n][e % n], so entry [i][j] is the network's value for the edge j -> i.  On the
+    source-major run that matrix is the transposed VIEW of the [n, n] output -- no scatter, no indexed assignment.  The minimum
+    of mkp and pctsp is per instance and gradient flows through it as through torch's .min()."""
+    _check_problem(problem)
+    if problem == "sop":
+        return _sop_heuristic_batch(net, data)
+    x, ei, ea = sibling_graph_batch(problem, data, k_sparse=k_sparse)
+    B, n = x.shape[0], x.shape[1]
+    k = int(k_sparse) if problem == "op" else n
+    if net.training:
+        heu = net.forward_batch_train(x, ei, ea, k_sparse=k)
+    else:
+        heu = net.forward_batch(x, ei, ea, k_sparse=k)
+    if problem == "op":
+        return net.reshape_batch(n, ei, heu, eps=EPS)
+    if problem == "pctsp":
+        heu = heu / (heu.amin(dim=1, keepdim=True) + EPS) + EPS
+    mat = heu.view(B, n, n)
+    if problem in ("smtwtp", "pctsp"):
+        return mat + EPS if problem == "smtwtp" else mat
+    mat = mat.transpose(1, 2)                                         # (cvrp, bpp, mkp: the direction-blind reshape)
+    if problem == "mkp":
+        return mat / (mat.amin(dim=(1, 2), keepdim=True) + 1e-10) + 1e-10
+    return mat + 1e-10
+
+
+def _reinforce_tail(obj, log_probs, lens, sign, loss_path):
+    """per-instance REINFORCE losses -> their mean.  'hip': autograd.ReinforceFn, one launch each way; 'torch': the torch-op
+    tail (row mask from the longest route, masked sums, baseline, advantage), the comparator."""
+    if loss_path not in LOSS_PATHS:
+        raise ValueError(f"loss_path must be one of {LOSS_PATHS} (got {loss_path!r})")
+    d = 1                                # lens count nodes: an ant of lens nodes made lens - 1 draws
+    if loss_path == "hip":
+        from .autograd import ReinforceFn
+        return ReinforceFn.apply(obj, log_probs, lens, d, sign).mean()
+    B, R, A = log_probs.shape
+    with torch.no_grad():
+        o = obj.float()
+        adv = sign * (o - o.mean(dim=1, keepdim=True))
+    if lens is not None:
+        rows = torch.arange(R, device=log_probs.device).view(1, -1, 1)
+        log_probs = log_probs * (rows < (lens.max(dim=1).values.view(B, 1, 1) - d))
+    return ((adv * log_probs.sum(dim=1)).sum(dim=1) / A).mean()
+
+
+def _sibling_loss(problem, net, data, n_ants, seed=0, it=0, ant_gid0=0, loss_path="torch", k_sparse=None, **aco_kw):
+    """The forward half of a train_instance of smtwtp/, sop/, pctsp/, op/, bpp/ or mkp/ for B instances: heuristic matrices
+    (sibling_heuristic_batch, under autograd) -> B fresh colonies (pheromone ones, the directory's defaults; aco_kw: anything
+    else the engine.Batched* constructor takes) -> sample() with log-probabilities (one launch) -> the REINFORCE loss of every
+    instance with the mean objective as baseline, averaged over the instances.  Private: the body of train_sibling_batch with
+    what the tests need.  ant_gid0: the id of the first ant (instance b of a batch draws what a single instance with
+    ant_gid0 = b * n_ants draws); loss_path: 'torch' (the torch-op tail: the default, because the whole step -- bound by the
+    host's launches at these sizes -- measured no faster with the kernel, DESIGN section 3.18) or 'hip' (autograd.ReinforceFn, one
+    launch each way: the checked, opt-in path).
+    -> (loss, colony, dict(obj, log_probs, lens, heu_mat, paths))"""
+    _check_problem(problem)
+    if problem == "cvrp":
+        raise ValueError("_sibling_loss: cvrp has its own _cvrp_loss (distances and demands, BatchedCVRP)")
+    heu_mat = sibling_heuristic_batch(problem, net, data, k_sparse=k_sparse)
+    col = engine.BATCHED_SIBLINGS[problem](*data, n_ants=n_ants, heuristic=heu_mat.detach(), seed=seed, ant_gid0=ant_gid0, **aco_kw)
+    col.iteration = int(it)
+    col.set_heuristic(heu_mat)
+    obj, log_probs, lens = col.sample()
+    loss = _reinforce_tail(obj, log_probs, lens, SIBLING_SIGN[problem], loss_path)
+    return loss, col, dict(obj=obj, log_probs=log_probs, lens=lens, heu_mat=heu_mat, paths=col.last_paths)
+
+
+def _cvrp_loss(net, demands, distances, n_ants, seed=0, it=0, ant_gid0=0, loss_path="torch", **aco_kw):
+    """_sibling_loss for cvrp/train.ipynb:32-49: demands [B,n+1], distances [B,n+1,n+1] (node 0 the depot, 1e-10 on the
+    diagonal) -> heu_vec.reshape(n+1, n+1) + 1e-10 -> B fresh engine.BatchedCVRP colonies (capacity 50 unless aco_kw says
+    otherwise) -> sample() -> sum_a (cost_a - mean) sum_t logp[t, a] / n_ants per instance, averaged over the instances.
+    -> (loss, colony, dict(obj, log_probs, lens, heu_mat, paths))"""
+    heu_mat = sibling_heuristic_batch("cvrp", net, (demands, distances))
+    col = engine.BatchedCVRP(distances, demands, n_ants=n_ants, heuristic=heu_mat.detach(), seed=seed, ant_gid0=ant_gid0, **aco_kw)
+    col.iteration = int(it)
+    col.heuristic = heu_mat
+    obj, log_probs, lens = col.sample()
+    loss = _reinforce_tail(obj, log_probs, lens, SIBLING_SIGN["cvrp"], loss_path)
+    return loss, col, dict(obj=obj, log_probs=log_probs, lens=lens, heu_mat=heu_mat, paths=col.last_paths)
+
+
+def train_sibling_batch(problem, net, optimizer, data, n_ants, seed=0, it=0, **aco_kw):
+    """One optimisation step of the train_instance of smtwtp/, sop/, pctsp/, op/, bpp/ (train.ipynb) or mkp/ (train.py:15-31)
+    for B instances of one size at once: graphs -> Net in training mode (one forward for the batch, per-graph BatchNorm
+    statistics; sop: one forward per instance) -> the directory's recipe from network output to heuristic matrix -> B fresh
+    colonies (pheromone ones, the directory's defaults) -> sample() with log-probabilities (one launch) -> the REINFORCE tail
+    averaged over the instances (loss_path="torch", the default: torch ops; loss_path="hip": daco_reinforce, one launch each
+    way -- see _sibling_loss) -> backward -> optimizer.step().  Nothing is clipped: none of these train files clips.  op and mkp
+    maximise (baseline - obj), the others minimise (obj - baseline).
+    data: the tuple the problem's engine.Batched* constructor takes; op needs k_sparse=, loss_path=, bpp's capacity and the like
+    go through aco_kw.  Returns (loss, mean objective) as detached device tensors; nothing is read on the host (sop's graphs
+    excepted)."""
+    net.train()
+    loss, _, ex = _sibling_loss(problem, net, data, n_ants, seed, it, **aco_kw)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    return loss.detach(), ex["obj"].float().mean()
+
+
+def train_cvrp_batch(net, optimizer, demands, distances, n_ants, seed=0, it=0, **aco_kw):
+    """One optimisation step of cvrp/train.ipynb:32-52 (`train_instance`) for B instances at once, on the device end to end:
+    complete graphs in source-major order (no sort, no host read) -> Net in training mode (HIP kernels, per-graph BatchNorm
+    statistics) -> heu_vec.reshape(n+1, n+1) + 1e-10 -> B fresh colonies sampled with log-probabilities (one launch) -> the
+    REINFORCE tail with the mean cost as baseline (torch ops by default; loss_path="hip" in aco_kw: daco_reinforce /
+    daco_reinforce_backward, see _sibling_loss) -> backward (one daco_sample_backward launch, the GNN backward kernels) ->
+    optimizer.step(); the notebook clips nothing.
+    demands [B,n+1], distances [B,n+1,n+1] as cvrp/utils.py builds them.  Returns (loss, mean cost) as detached device tensors."""
+    net.train()
+    loss, _, ex = _cvrp_loss(net, demands, distances, n_ants, seed, it, **aco_kw)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    return loss.detach(), ex["obj"].mean()
+
+
+@torch.no_grad()
+def infer_cvrp_batch(demands, distances, n_ants, t_aco, net=None, heuristic=None, seed=0, **aco_kw):
+    """The batched counterpart of cvrp/test.py:14-39 (`infer_instance`): demands [B,n+1], distances [B,n+1,n+1] -> heuristic (the
+    network in eval mode through sibling_heuristic_batch; a matrix [B,n+1,n+1]; or None: 1 / distance) -> B colonies -> the
+    lowest cost at every checkpoint of t_aco.  Giving both a network and a heuristic is an error.
+    Returns (best costs [len(t_aco), B], colony)."""
+    if net is not None:
+        if heuristic is not None:
+            raise ValueError("infer_cvrp_batch: give either a heuristic or a network, not both")
+        heuristic = sibling_heuristic_batch("cvrp", net.eval(), (demands, distances)).contiguous()
+    colony = engine.BatchedCVRP(distances, demands, n_ants=n_ants, heuristic=heuristic, seed=seed, **aco_kw)
+    out, done = [], 0
+    for t in t_aco:
+        colony.run(t - done)
+        done = t
+        out.append(colony.lowest_cost.clone())
     return torch.stack(out), colony
 
 

@@ -186,10 +186,11 @@ class SMTWTP(_Base):
 
     @torch.no_grad()
     def gen_path_costs(self, paths):
-        jobs = (paths - 1).T                                             # [A, n]
-        finish = torch.cumsum(self.processing_time[jobs], dim=1)
-        late = (finish - self.due_time[jobs]).clamp(min=0)
-        return (self.weights[jobs] * late).sum(dim=1)
+        """smtwtp/aco.py:97-111 for paths [n, A] (jobs + 1): daco_sibling_objective, the launch engine.BatchedSMTWTP scores
+        with -- one statement of the sum's order for the class and its batched form (include/deepaco_hip.h)."""
+        full = torch.cat((torch.zeros((1, paths.shape[1]), dtype=torch.int64, device=paths.device), paths.to(torch.int64)))
+        return engine.sibling_objective("smtwtp", full.unsqueeze(0).contiguous(), None, self.processing_time.unsqueeze(0),
+                                        self.due_time.unsqueeze(0), self.weights.unsqueeze(0), n=self.n)[0][0]
 
     def gen_path(self, require_prob=False, *, _noise=None, _stepwise=False):
         """A permutation of the jobs drawn after the dummy start node: exactly the fused TSP kernel with
@@ -451,7 +452,10 @@ class OP(_Base):
 
     @torch.no_grad()
     def gen_sol_obj(self, solutions):
-        return self.prizes[solutions.T].sum(dim=1)
+        """op/aco.py:141-147 for solutions [L, A]: daco_sibling_objective, the launch engine.BatchedOP scores with -- one
+        statement of the sum's order for the class and its batched form (include/deepaco_hip.h)."""
+        return engine.sibling_objective("op", solutions.to(torch.int64).unsqueeze(0).contiguous(), None, self.prizes.unsqueeze(0),
+                                        scale=torch.as_tensor(self.Q, dtype=torch.float32, device=self.device).reshape(1))[0][0]
 
     def _close(self, travel, cur, mask):
         """op/aco.py:195-220 for all ants at once: close the current node and every candidate from
@@ -527,17 +531,11 @@ class BPP(_Base):
 
     @torch.no_grad()
     def gen_path_costs(self, paths):
-        """-fitness, fitness = sum over bins (fill/C)^2 / #bins (bpp/aco.py:26-40,121-126), float64."""
-        u = paths.T
-        A, L = u.shape
-        fill = self.demand.double()[u]
-        bin_id = torch.cumsum((u == 0).long(), dim=1) - 1                 # bin index of every position
-        n_open = int(bin_id.max()) + 1
-        sums = torch.zeros(A, n_open, dtype=torch.float64, device=u.device).scatter_add_(1, bin_id, fill)
-        f = ((sums / self.capacity) ** 2).sum(dim=1)
-        tail = (torch.flip(u, [1]) != 0).long().argmax(dim=1)             # trailing zeros
-        n_bins = L - tail - self.problem_size + 1
-        return -(f / n_bins)
+        """-fitness, fitness = sum over bins (fill/C)^2 / #bins (bpp/aco.py:26-40,121-126), float64, for paths [L, A]:
+        daco_sibling_objective, the launch engine.BatchedBPP scores with -- one statement of the sums' order for the class and
+        its batched form (include/deepaco_hip.h), and no host read for the number of bins."""
+        return engine.sibling_objective("bpp", paths.to(torch.int64).unsqueeze(0).contiguous(), None, self.demand.unsqueeze(0),
+                                        capacity=float(self.capacity), elitist=self.elitist)[0][0]
 
     def gen_path(self, require_prob=False, *, _noise=None):
         mode = "race_noise" if _noise is not None else self.sampler

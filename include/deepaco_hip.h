@@ -389,6 +389,37 @@ long daco_sibling_record(void *stream, int rule, int B, int len, int A, const fl
                         int64_t *best_sol, int32_t *best_idx, float *mmas_max, float mmas_n, const float *mmas_scale);
 
 /* ---------------------------------------------------------------------------------------------
+ * daco_reinforce / daco_reinforce_backward -- the REINFORCE tail between a sampler and its backward, one launch each way:
+ * the baseline, the masked log-probability sums, the loss of every instance and its gradient (cvrp/train.ipynb:44-49 and
+ * the train cells / files of smtwtp, sop, pctsp, op, bpp, mkp, for B instances at once).
+ *   obj [B][A] f32 the ants' objectives;  log_probs [B][R][A] f32 as the samplers write them;  lens [B][A] int32 or NULL;
+ *   d: the row offset (a sampler whose lens count nodes has lens - 1 draws: d = 1);  sign: +1 minimises, -1 maximises.
+ * Forward, per instance b:
+ *   live   = R without lens, else max_a lens[b][a] - d clamped to 0..R: the rows the reference's loop produced.  Rows past
+ *            it hold the padding's log(1 - 2^-23) and do not count.
+ *   s[a]   = sum_{r < live} log_probs[b][r][a]               r ascending
+ *   mean   = (sum_a obj[b][a]) / A                            a ascending
+ *   adv[a] = sign * (obj[b][a] - mean)                        (the product with +-1 is exact)
+ *   loss   = (sum_a adv[a] * s[a]) / A                        a ascending
+ * Outputs: loss [B] f32, adv [B][A] f32, live [B] int32.  The batch loss is the mean of loss, the caller's.
+ * Backward, given g [B] f32 (d batch loss / d loss[b]), adv and live of the forward:
+ *   grad_log_probs[b][r][a] = (g[b] * adv[b][a]) / A for r < live[b], +0.0f for live[b] <= r < R
+ * (live outside 0..R is clamped); every one of the B R A words is written, nothing else is.
+ * The arithmetic is part of the contract (tests/reinforce_spec.py restates it): every sum starts at +0.0f and is sequential
+ * in the order given; a product is rounded before it is added (no fused multiply-add: the library is built with
+ * -ffp-contract=off, and the file says so again); the divisions are IEEE, by (float)A.
+ * Forward: one workgroup per instance, one lane per ant (strided for A > 256); backward: elementwise over slabs of an
+ * instance's R A words.  No atomics, no workspace.  Both refuse a null pointer
+ * (lens excepted) and B, A, R <= 0 with DACO_E_BADARG, sign other than +-1 and d < 0 likewise, before any HIP call.  The
+ * status is the usual DACO_OK / DACO_E_* value typed `long`, for the reason given at daco_rcpsp_net_forward; the refusals are
+ * held by tests/test_reinforce_refusals.py.
+ */
+long daco_reinforce(void *stream, int B, int R, int A, const float *obj, const float *log_probs, const int32_t *lens, int d,
+                    int sign, float *loss, float *adv, int32_t *live);
+long daco_reinforce_backward(void *stream, int B, int R, int A, const float *g, const float *adv, const int32_t *live,
+                             float *grad_log_probs);
+
+/* ---------------------------------------------------------------------------------------------
  * daco_sibling_backward -- daco_sample_backward for the fused sibling constructions: the gradient of
  * sum(grad_logp * log_probs) w.r.t. eta for solutions drawn by daco_sibling_sample (same kind, aux_vec,
  * aux_mat, scalar0, item_weights; paths / rowsum / lens as that call returned them).  aux_mat is the
