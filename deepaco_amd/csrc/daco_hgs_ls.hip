@@ -1234,7 +1234,8 @@ static int hgs_local_search(void *stream, int B, int n, int A, int Lmax, int nst
   for (int s = 0; s < nstages; ++s) {
     if (!matrices[s] || !tables[s] || counts[s] < 0) { set_error("%s: stage %d: null matrix / table or negative count", who, s); return DACO_E_BADARG; }
     p.st[s].tc = matrices[s]; p.st[s].tct = (matrices_t && matrices_t[s]) ? matrices_t[s] : matrices[s]; p.st[s].bstride = bstrides[s]; p.st[s].tables = (const unsigned char *)tables[s];
-    p.st[s].table_bytes = HgsLayout(n, nb_granular).total; p.st[s].count = counts[s];
+    // (bstride 0: one matrix -- and the one table set made of it -- shared by the B instances)
+    p.st[s].table_bytes = bstrides[s] ? HgsLayout(n, nb_granular).total : 0; p.st[s].count = counts[s];
   }
   p.demand = demand; p.cap = capacity; p.paths = paths; p.status = status; p.stats = stats;
   p.queue = (uint32_t *)workspace;

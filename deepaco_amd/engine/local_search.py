@@ -219,9 +219,7 @@ def hgs_local_search_(paths, stages, demand, capacity=1000.001, demand_scale=100
     tabs = (C.c_void_p * S)(*[st[0].tables.data_ptr() for st in stages])
     counts = (C.c_int * S)(*[int(st[1]) for st in stages])
     for st in stages:
-        assert st[0].n == n and st[0].nb_granular == g and st[0].B in (1, B)
-        if st[0].B == 1 and B > 1:
-            raise ValueError("hgs_local_search_: one table set per instance is needed (B tables)")
+        assert st[0].n == n and st[0].nb_granular == g and st[0].B in (1, B)      # (B == 1: stride 0, one matrix and table set for all)
     L = _lib.lib()
     if use_swap_star:
         xy = positions.to(dev).double()

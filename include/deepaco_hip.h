@@ -726,7 +726,8 @@ int daco_cvrp_local_search(void *stream, int B, int n, int A, int Lmax, const fl
  *   neural_swapstar is three: distances / limit, heuristic-derived matrix / 10, distances / limit), the routes of a stage
  *   handed to the next as the reference's files do (non-empty routes, in export order).
  *   matrices[s], bstrides[s], tables[s], counts[s]   stage s: its matrix [B][n][n] f64, the tables daco_hgs_prepare made
- *            of it, and `count` (the loop bound of LocalSearch.cpp:17)
+ *            of it, and `count` (the loop bound of LocalSearch.cpp:17); bstrides[s] = 0: ONE matrix [n][n] (transpose
+ *            included) and the one table set made of it, shared by the B instances
  *   matrices_t[s]   the transposed copy of matrices[s] (same stride), or NULL (the array itself may be NULL) for a symmetric
  *            matrix: timeCost[v][u] with u the node being improved is read as row u of the transpose, so that a wavefront's 64
  *            gathers fall on a few cache lines instead of 64 (the same numbers either way)

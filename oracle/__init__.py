@@ -328,7 +328,8 @@ def hgs_local_search(positions, matrix, demands, seq, count, capacity=1000.001, 
     HGS-CVRP-main/Program/LocalSearch.cpp as cvrp_nls/swapstar.py:324-346 drives it: demands * 1000, capacity 1000.001).
     positions [n,2], matrix [n,n], demands [n] float64 (depot first); seq: zero-separated node sequence (a column of
     `paths`).  Returns (sequence [out_len] int64 as merge_subroutes lays it out, status) -- status 1: HGS would have thrown and
-    the reference keeps its input -- and, with want_stats, (moves, loops, rng draws, pairs evaluated)."""
+    the reference keeps its input -- and, with want_stats, [moves, loops, rng draws, pairs evaluated, moves of a client towards the
+    first empty route, the largest index that route had, the largest client id so moved (-1 without such a move)]."""
     pos = np.ascontiguousarray(positions, dtype=np.float64)
     m = np.ascontiguousarray(matrix, dtype=np.float64)
     n = m.shape[0]
@@ -337,7 +338,7 @@ def hgs_local_search(positions, matrix, demands, seq, count, capacity=1000.001, 
     s = np.ascontiguousarray(seq, dtype=np.int32)
     out_len = len(s) + 2 if out_len is None else out_len
     out = np.zeros(out_len, dtype=np.int32)
-    st = np.zeros(4, dtype=np.int64)
+    st = np.zeros(7, dtype=np.int64)
     f = lib().hgs_local_search
     f.restype = C.c_int
     f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_int,

@@ -466,7 +466,9 @@ void hgs_correlated(int n, const double* tc, int nb_granular, int* out, int* out
  *   cap (1000.001), seq_in: the solution as a zero-separated node sequence of len_in entries (a column of `paths`),
  *   count: the loop bound of LocalSearch::run, nb_granular (20), seed (the value HGS reads: 1; 0 gives the same stream).
  *   seq_out [out_len]: "0 c1 .. ck" per non-empty route in export order, zero padded (cvrp_nls/aco.py:22-33 merge_subroutes).
- *   stats (may be NULL): [0] moves applied, [1] loops run, [2] RNG draws, [3] (U,V) pairs evaluated.
+ *   stats (may be NULL, 7 entries): [0] moves applied, [1] loops run, [2] RNG draws, [3] (U,V) pairs evaluated, [4] moves of a
+ *   client towards the first empty route (LocalSearch.cpp:60-71), [5] the largest index that route had and [6] the largest
+ *   client id among those moves (-1 without one) -- what tests/hgs_ls_edge_cases.py builds its claims on.
  * Returns 0; 1 when HGS throws (distances / demands out of scale, Params.cpp:106-114; infeasible or incomplete input,
  * Individual.cpp:68-71; fleet too small) -- the Python side then keeps the input routes (swapstar.py:262-271, :341-345),
  * which is what seq_out holds; -1 bad argument. */
@@ -487,7 +489,8 @@ int hgs_local_search(int n, const double* xs, const double* ys, const double* tc
     { int k = 0; memset(seq_out, 0, sizeof(int) * out_len);
       for (int r = 0; r < R; ++r) { if (k + 1 + rlen[r] > out_len) { free(rstart); free(rlen); return -1; }
                                     seq_out[k++] = 0; for (int i = 0; i < rlen[r]; ++i) seq_out[k++] = seq_in[rstart[r] + i]; } }
-    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    if (stats) { stats[0] = stats[1] = stats[2] = stats[3] = stats[4] = 0; stats[5] = stats[6] = -1; }
+    long emptyMoves = 0, emptyMaxRoute = -1, emptyMaxClient = -1;
 
     /* Params (Params.cpp:25-121) */
     double totalDemand = 0., maxDemand = 0., maxDist = 0.;
@@ -617,10 +620,12 @@ int hgs_local_search(int n, const double* xs, const double* ys, const double* tc
                 if (er >= 0) {
                     s->V = DEP(s, er);
                     set_u(s); set_v(s);
-                    if (move1(s)) continue;
-                    if (move2(s)) continue;
-                    if (move3(s)) continue;
-                    if (move9(s)) continue;
+                    if (move1(s) || move2(s) || move3(s) || move9(s)) {      /* (first that applies, as the reference's chain of ifs) */
+                        ++emptyMoves;
+                        if (er > emptyMaxRoute) emptyMaxRoute = er;
+                        if (s->U > emptyMaxClient) emptyMaxClient = s->U;
+                        continue;
+                    }
                 }
             }
         }
@@ -651,7 +656,8 @@ int hgs_local_search(int n, const double* xs, const double* ys, const double* tc
         seq_out[k++] = 0;
         while (!ISDEPOT(s, node)) { seq_out[k++] = node; node = s->next[node]; }
     }
-    if (stats) { stats[0] = s->nbMoves; stats[1] = loops; stats[2] = draws; stats[3] = s->evals; }
+    if (stats) { stats[0] = s->nbMoves; stats[1] = loops; stats[2] = draws; stats[3] = s->evals;
+                 stats[4] = emptyMoves; stats[5] = emptyMaxRoute; stats[6] = emptyMaxClient; }
 
     free(ang); free(orderNodes); free(orderRoutes); free(tmp); free(corrBuf); free(s->corrLen); free(s->corr);
     free(s->next); free(s->prev); free(s->route); free(s->pos); free(s->whenRI); free(s->cumLoad); free(s->cumTime);

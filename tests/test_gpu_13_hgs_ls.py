@@ -15,6 +15,8 @@ from conftest import GOLDEN
 
 import oracle
 
+from hgs_ls_edge_cases import expected_order, parse_tables
+
 pytestmark = pytest.mark.gpu
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "g11_hgs_ls_n*.npz")))
 
@@ -73,23 +75,12 @@ def test_tables_equal_the_oracles_correlated_vertices():
         torch.cuda.synchronize()
         raw = t.tables.cpu().numpy()
         lists, lens = oracle.hgs_correlated(m, 20)
-        a16 = lambda x: (x + 15) & ~15
-        o_order = 64
-        o_len = o_order + a16(2 * (n - 1))
-        o_off = o_len + a16(2 * n)
-        o_ent = o_off + a16(4 * n)
-        assert raw[:8].view(np.float64)[0] == m.max()
-        glen = raw[o_len:o_len + 2 * n].view(np.uint16)
-        goff = raw[o_off:o_off + 4 * n].view(np.uint32)
-        np.testing.assert_array_equal(glen, lens.astype(np.uint16))
+        got = parse_tables(raw, n, 20, t.table_bytes)
+        assert got["max_dist"] == m.max()
+        np.testing.assert_array_equal(got["lens"], lens.astype(np.uint16))
         for i in range(1, n):
-            e = raw[o_ent + 2 * goff[i]: o_ent + 2 * (goff[i] + glen[i])].view(np.uint16)
-            np.testing.assert_array_equal(e, lists[i, :lens[i]].astype(np.uint16))
-        order = raw[o_order:o_order + 2 * (n - 1)].view(np.uint16)
-        nc = n - 1
-        _, d1 = oracle.hgs_shuffle(np.arange(nc), seed=1)                          # the draws of Individual's own shuffle
-        want, _ = oracle.hgs_shuffle(np.arange(1, nc + 1), seed=1, skip_draws=d1)
-        np.testing.assert_array_equal(order, want.astype(np.uint16))
+            np.testing.assert_array_equal(got["lists"][i], lists[i, :lens[i]].astype(np.uint16))
+        np.testing.assert_array_equal(got["order"], expected_order(n - 1).astype(np.uint16))
 
 
 def random_solutions(rng, n, cap, A):

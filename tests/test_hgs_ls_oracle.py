@@ -134,9 +134,10 @@ def ref_library(which):
         return None
 
 
-def ref_local_search(lib, pos, d, dem, seq, sw, callid):
+def ref_local_search(lib, pos, d, dem, seq, sw, callid, nb_granular=20, count=100):
     """The routes the reference's library returns for the solution `seq` (called as cvrp_nls/swapstar.py does, through /tmp
-    route files): [0] + route for every route, concatenated."""
+    route files): [0] + route for every route, concatenated.  nb_granular: nbGranular of the parameter structure (20 in the
+    reference); count: the loop bound."""
     import ctypes as C
     import sys
 
@@ -154,12 +155,12 @@ def ref_local_search(lib, pos, d, dem, seq, sw, callid):
     with open(f"/tmp/route-{callid}", "w") as f:
         for i, r in enumerate(routes):
             f.write(f"Route #{i + 1}: " + " ".join(map(str, r)) + "\n")
-    ap = FullAP(20, 25, 40, 4, 5, 100, 0.2, 0.85, 1.2, 1, 20000, 500, 0.0, sw)
+    ap = FullAP(int(nb_granular), 25, 40, 4, 5, 100, 0.2, 0.85, 1.2, 1, 20000, 500, 0.0, sw)
     x, y = np.ascontiguousarray(pos[:, 0]), np.ascontiguousarray(pos[:, 1])
     m, s, dm = np.ascontiguousarray(d).reshape(-1), np.zeros(n + 1), np.ascontiguousarray(dem * 1000)
     lib.local_search(n + 1, x.ctypes.data_as(dp), y.ctypes.data_as(dp), m.ctypes.data_as(dp), s.ctypes.data_as(dp),
                      dm.ctypes.data_as(dp), 1000.001, sys.float_info.max, b'\0', len(routes), C.byref(ap), b'\0',
-                     callid, 100)
+                     callid, int(count))
     got = []
     with open(f"/tmp/swapstar-result-{callid}") as f:
         for line in f:
