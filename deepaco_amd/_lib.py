@@ -59,6 +59,10 @@ SIGNATURES = {
     "daco_gnn_train_workspace_bytes": (_sz, [_i, _i, _i]),
     "daco_gnn_train_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "daco_gnn_train_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
+    # (ragged: edge_off after G; long statuses, as daco_rcpsp_net_forward)
+    "daco_gnn_train_forward_ragged": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "daco_gnn_train_backward_ragged": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                            _sz]),
     "daco_cvrp_local_search": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _f, _vp, _i, _vp, _vp]),
     "daco_hgs_table_bytes": (_sz, [_i, _i]),
     "daco_hgs_prepare": (_i, [_vp, _i, _i, _vp, _l, _i, _vp]),
@@ -80,6 +84,8 @@ SIGNATURES = {
     "daco_tsp_knn_graph": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp]),
     "daco_tsp_knn_graph_csr": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "daco_cvrp_knn_graph": (_l, [_vp, _i, _i, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp]),   # (a long status too)
+    "daco_sop_graph_count": (_l, [_vp, _i, _i, _vp, _vp, _vp]),
+    "daco_sop_graph_fill": (_l, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "daco_heu_matrix": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp]),
     # (long statuses, as daco_rcpsp_net_forward)
     "daco_sparsify": (_l, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _vp]),

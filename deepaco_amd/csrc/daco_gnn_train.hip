@@ -5,7 +5,8 @@
 // of the ONE graph being trained on, :21,24,43-44), MLP/ParNet.forward :59-75, and what autograd derives from
 // them for tsp_nls/train.py:15-44 (loss.backward()).  G equal-sized graphs may be laid side by side (n = G*n_g
 // nodes, E = G*E_g edges, node ids offset per graph): every graph normalises with its own statistics, exactly as G
-// separate reference forwards would.
+// separate reference forwards would.  The *_ragged entries take G graphs of equal node count whose edge counts differ (sop/:
+// the graph is nonzero(adj)): graph g owns edges [edge_off[g], edge_off[g+1]) and normalises over its own count.
 //
 // Per layer (x [n,32], w [E,32]):
 //   X = x Wv^T + bv = (x1|x2|x3|x4)                     node_post of the previous layer (MFMA-free: n is small)
@@ -56,13 +57,38 @@ __device__ inline Stat load_stat(const float2 *tab, int g, int c, int /*count*/)
   const float2 t = tab[(size_t)g * 32 + c];
   return Stat{t.x, t.y};
 }
+// Which graph a row (an edge, or a node) belongs to.  The kernels below are templates over one of these two; `of(r)` is the
+// graph of row r, `of(r, s)` the same for a caller that holds the edge's source node s in a register already.
+//   EqualGraphs   graphs of `per` rows each, listed graph after graph: r / per.  One int, passed where the kernels used to take
+//                 `Eg` / `Rg`: these instantiations are the kernels as they were.
+//   RaggedGraphs  graphs of n_g nodes each whose edge counts differ (graph g owns edges [edge_off[g], edge_off[g + 1]), in any
+//                 order inside the graph): the graph of an edge is that of its source node, src[e] / n_g -- the register the
+//                 kernel holds, or one 4-byte load where it holds none.  Always in [0, G) for node ids in [0, n).
+struct EqualGraphs {
+  int per;
+  __device__ int of(int r) const { return r / per; }
+  __device__ int of(int r, int /*s*/) const { return r / per; }
+};
+struct RaggedGraphs {
+  const int *src;
+  int ng;
+  __device__ int of(int e) const { return src[e] / ng; }
+  __device__ int of(int /*e*/, int s) const { return s / ng; }
+};
+
+// the rows behind an edge statistic of graph g: `count_e`, or the graph's own edge_off[g + 1] - edge_off[g] (ragged; a graph
+// without edges -- nothing reads its entries -- counts one row, so that no table entry is a 0 / 0)
+__device__ inline int edge_count(const int *edge_off, int g, int count_e) {
+  return edge_off ? max(edge_off[g + 1] - edge_off[g], 1) : count_e;
+}
+
 // forward table: (mean, rstd); backward table: (sum(g_y) / count, sum(g_y * zhat) / count)
 // (the edge and the node BatchNorm of a layer in one launch: their sums and their tables are neighbours in memory; the first
-// G * 32 entries count `count_e` rows each, the next G * 32 `count_v`)
-__global__ void gnn_t_stat_table(int G, int count_e, int count_v, const double *sums, float2 *tab, int backward) {
+// G * 32 entries count `count_e` rows each -- edge_off: see edge_count --, the next G * 32 `count_v`)
+__global__ void gnn_t_stat_table(int G, int count_e, int count_v, const int *edge_off, const double *sums, float2 *tab, int backward) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= 2 * G * 32) return;
-  const int count = idx < G * 32 ? count_e : count_v;
+  const int count = idx < G * 32 ? edge_count(edge_off, idx >> 5, count_e) : count_v;
   const double s = sums[(size_t)idx * 2], q = sums[(size_t)idx * 2 + 1];
   if (backward) { tab[idx] = make_float2((float)(s / count), (float)(q / count)); return; }
   const double m = s / count;
@@ -83,8 +109,9 @@ __global__ void gnn_t_fixed_table(int G, const float *fixed, float2 *tab) {
 
 // ------------------------------------------------------------------ forward
 // ze = w We^T + be + x3[src] + x4[dst] for one 32-edge tile per wave; channel sums of the tile -> f64 atomics
+template <class GR>
 __global__ void __launch_bounds__(256)
-gnn_t_edge_pre(int E, int Eg, const int *src, const int *dst, const float *We, const float *be, const float *X,
+gnn_t_edge_pre(int E, GR gr, const int *src, const int *dst, const float *We, const float *be, const float *X,
                const float *w0, float *ze, double *sums) {
   __shared__ __attribute__((aligned(16))) float tile_s[4][32][36];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -94,7 +121,7 @@ gnn_t_edge_pre(int E, int Eg, const int *src, const int *dst, const float *We, c
   const int o = lane & 31, h = lane >> 5, c0 = (lane & 7) * 4;
   // the workgroup's 128 edges in one graph (uniform): the four waves' sums are added in LDS and flushed once
   const int wg0 = blockIdx.x * 128, wg1 = min(wg0 + 127, E - 1);
-  const bool one_graph = wg0 / Eg == wg1 / Eg;
+  const bool one_graph = gr.of(wg0) == gr.of(wg1);
   if (e0 >= E) {                                            // (a wave past the end: nothing to do but the workgroup's barrier)
     if (one_graph) { red[wave][lane] = 0.0; __syncthreads(); }
     return;
@@ -142,9 +169,9 @@ gnn_t_edge_pre(int E, int Eg, const int *src, const int *dst, const float *We, c
   __builtin_amdgcn_wave_barrier();
   // lanes 0..31: sum of channel o over the tile's edges, lanes 32..63: sum of squares; flushed per graph
   double accd = 0.0;
-  int gcur = e0 / Eg;
+  int gcur = gr.of(e0);
   for (int el = 0; el < 32 && e0 + el < E; ++el) {
-    const int g = (e0 + el) / Eg;
+    const int g = gr.of(e0 + el);
     if (g != gcur) { unsafeAtomicAdd(sums + ((size_t)gcur * 32 + o) * 2 + h, accd); accd = 0.0; gcur = g; }
     const float v = tile[el][o];
     accd += h ? (double)v * (double)v : (double)v;
@@ -207,13 +234,14 @@ gnn_t_node_pre(int n, int ng, const int *dst, const int *rowptr, const int *perm
 }
 
 // w' = w + silu(gamma * (ze - mean) * rstd + beta)
+template <class GR>
 __global__ void __launch_bounds__(256)
-gnn_t_edge_post(int E, int Eg, const float *gamma, const float *beta, const float2 *sums, const float *w0, const float *ze,
+gnn_t_edge_post(int E, GR gr, const float *gamma, const float *beta, const float2 *sums, const float *w0, const float *ze,
                 float *w1) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long)E * TU) return;
   const int e = (int)(idx >> 5), c = (int)(idx & 31);
-  const Stat st = load_stat(sums, e / Eg, c, Eg);
+  const Stat st = load_stat(sums, gr.of(e), c, 0);
   const float y = fmaf((ze[idx] - st.mean) * st.rstd, gamma[c], beta[c]);
   w1[idx] = w0[idx] + t_silu(y);
 }
@@ -467,8 +495,9 @@ gnn_t_head_bwd(int E, const float *hp, const float *w, const float *heu, const f
 }
 
 // sum(g_y), sum(g_y * zhat) per channel and graph for an [R,32] tensor (edges or nodes); g_y = gout * dsilu(y)
+template <class GR>
 __global__ void __launch_bounds__(256)
-gnn_t_bwd_stats(int R, int Rg, const float *gamma, const float *beta, const float2 *fsums, const float *z, const float *gout,
+gnn_t_bwd_stats(int R, GR gr, const float *gamma, const float *beta, const float2 *fsums, const float *z, const float *gout,
                 double *bsums) {
   // 8 rows per pass and workgroup-pass; thread = (row slot, channel); rows of one workgroup: a contiguous chunk
   // (round 6: the adds to one word of `bsums` execute one after the other in the L2 -- ~75 ns apiece -- and every thread used to
@@ -478,7 +507,7 @@ gnn_t_bwd_stats(int R, int Rg, const float *gamma, const float *beta, const floa
   const int il = threadIdx.x >> 5, o = threadIdx.x & 31;
   const int rows_per_wg = 256;
   const int r0 = blockIdx.x * rows_per_wg, r1 = min(R, r0 + rows_per_wg);
-  const bool one_graph = r0 < r1 && r0 / Rg == (r1 - 1) / Rg;           // uniform
+  const bool one_graph = r0 < r1 && gr.of(r0) == gr.of(r1 - 1);         // uniform
   double s1 = 0.0, s2 = 0.0;
   int gcur = -1;
   // (Round 6, last session: eight of a thread's rows at a time, their loads issued together.  One row per iteration -- with the
@@ -498,11 +527,11 @@ gnn_t_bwd_stats(int R, int Rg, const float *gamma, const float *beta, const floa
     for (int u = 0; u < UN; ++u) {
       const int r = rb + 8 * u;
       if (r < r1) {
-        const int g = r / Rg;
+        const int g = gr.of(r);
         if (g != gcur) {
           if (gcur >= 0) { unsafeAtomicAdd(bsums + ((size_t)gcur * 32 + o) * 2, s1); unsafeAtomicAdd(bsums + ((size_t)gcur * 32 + o) * 2 + 1, s2); }
           s1 = s2 = 0.0; gcur = g;
-          st = load_stat(fsums, g, o, Rg);
+          st = load_stat(fsums, g, o, 0);
         }
         const float zh = (zz[u] - st.mean) * st.rstd;
         const float gy = gg[u] * t_dsilu(fmaf(zh, gam, bet));
@@ -518,7 +547,7 @@ gnn_t_bwd_stats(int R, int Rg, const float *gamma, const float *beta, const floa
       double t = 0.0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) t += red[j][oo][k];
-      unsafeAtomicAdd(bsums + ((size_t)(r0 / Rg) * 32 + oo) * 2 + k, t);
+      unsafeAtomicAdd(bsums + ((size_t)gr.of(r0) * 32 + oo) * 2 + k, t);
     }
   } else if (gcur >= 0) { unsafeAtomicAdd(bsums + ((size_t)gcur * 32 + o) * 2, s1); unsafeAtomicAdd(bsums + ((size_t)gcur * 32 + o) * 2 + 1, s2); }
 }
@@ -555,8 +584,9 @@ gnn_t_node_bwd_apply(int n, int ng, const int *rowptr, const float *gamma, const
 }
 
 // edge side of a layer's backward, waves walk 32-edge tiles
+template <class GR>
 __global__ void __launch_bounds__(256)
-gnn_t_edge_bwd(int E, int Eg, const int *src, const int *dst, const float *We, const float *gamma, const float *beta,
+gnn_t_edge_bwd(int E, GR gr, const int *src, const int *dst, const float *We, const float *gamma, const float *beta,
                const float2 *fsums, const float2 *bsums, const float *X, const float *w0, const float *ze, const float *gmsg,
                float *gw /* in: grad wrt w', out: grad wrt w */, float *gX, float *gWe, float *gbe,
                float *c2buf /* [E][32] d/d x2[dst] per edge, or null */, float *gzbuf /* [E][32] g_ze per edge */) {
@@ -578,13 +608,13 @@ gnn_t_edge_bwd(int E, int Eg, const int *src, const int *dst, const float *We, c
     const int e0 = tix * 32;
     // the statistics of the lane's four channels, once per tile when the tile lies inside one graph (32 edges, graphs of Eg edges:
     // almost always) instead of once per element: sixteen 8-byte loads per lane and tile instead of thirty-two per pass
-    const int g_first = e0 / Eg, g_last = (min(e0 + 31, E - 1)) / Eg;
+    const int g_first = gr.of(e0), g_last = gr.of(min(e0 + 31, E - 1));
     const bool one_graph = g_first == g_last;
     Stat st_t[4];
     float2 bs_t[4];
     if (one_graph) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { st_t[k] = load_stat(fsums, g_first, c0 + k, Eg); bs_t[k] = bsums[(size_t)g_first * 32 + c0 + k]; }
+      for (int k = 0; k < 4; ++k) { st_t[k] = load_stat(fsums, g_first, c0 + k, 0); bs_t[k] = bsums[(size_t)g_first * 32 + c0 + k]; }
     }
     // edge-major pass: g_ze per element, scatter-adds, gate path; tiles tw = w, tg = g_ze
     // (Round 6, last session: the four passes' loads are issued together -- ids and rows first, then the two gathers that need the
@@ -612,7 +642,7 @@ gnn_t_edge_bwd(int E, int Eg, const int *src, const int *dst, const float *We, c
       float4 wv = make_float4(0.f, 0.f, 0.f, 0.f), gz = wv;
       gate_term[q] = wv;
       if (e < E) {
-        const int g = e / Eg, s = sq[q], d = dq[q];
+        const int s = sq[q], d = dq[q], g = gr.of(e, s);
         wv = wvq[q];
         const float4 zz = zzq[q];
         const float4 go = gres[q];
@@ -623,7 +653,7 @@ gnn_t_edge_bwd(int E, int Eg, const int *src, const int *dst, const float *We, c
         const float gmc[4] = {gm.x, gm.y, gm.z, gm.w}, x2c[4] = {x2.x, x2.y, x2.z, x2.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const Stat st = one_graph ? st_t[k] : load_stat(fsums, g, c0 + k, Eg);
+          const Stat st = one_graph ? st_t[k] : load_stat(fsums, g, c0 + k, 0);
           const float2 bm = one_graph ? bs_t[k] : bsums[(size_t)g * 32 + c0 + k];
           gzc[k] = bn_bwd_m(gc[k], zc[k], st, gam[k], bet[k], bm);
           const float gate = t_sigmoid(wc[k]);
@@ -920,12 +950,12 @@ gnn_t_edge_init_bwd(int E, const float *attr, const float *W, const float *b, co
 }
 
 // mean / biased variance of every BatchNorm (for the running-statistics update on the host side)
-__global__ void gnn_t_export_stats(int G, int count_e, int count_v, const double *fsums_all, float *out) {
+__global__ void gnn_t_export_stats(int G, int count_e, int count_v, const int *edge_off, const double *fsums_all, float *out) {
   // fsums_all: [12][2 (e, v)][G][32][2]; out: [12][2][G][32][2] (mean, biased var)
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= 12 * 2 * G * 32) return;
   const int which = (idx / (G * 32)) & 1;
-  const int cnt = which == 0 ? count_e : count_v;
+  const int cnt = which == 0 ? edge_count(edge_off, (idx >> 5) % G, count_e) : count_v;
   const double s = fsums_all[(size_t)idx * 2], q = fsums_all[(size_t)idx * 2 + 1];
   const double m = s / cnt;
   double v = q / cnt - m * m;
@@ -981,24 +1011,28 @@ extern "C" size_t daco_gnn_train_workspace_bytes(int n, int E, int G) {
   return carve(nullptr, n, E, G).total;
 }
 
-static int check_train_args(const char *what, int n, int E, int feats, int G) {
-  if (n <= 0 || E <= 0 || feats < 1 || feats > 8 || G <= 0 || n % G || E % G) {
-    set_error("%s: bad argument (n=%d E=%d feats=%d G=%d; n and E must be multiples of G)", what, n, E, feats, G);
+// (ragged: the graphs' edge counts are the caller's edge_off [G + 1] on the device; E need not be a multiple of G)
+static int check_train_args(const char *what, int n, int E, int feats, int G, bool ragged = false) {
+  if (n <= 0 || E <= 0 || feats < 1 || feats > 8 || G <= 0 || n % G || (!ragged && E % G)) {
+    set_error(ragged ? "%s: bad argument (n=%d E=%d feats=%d G=%d; n must be a multiple of G)"
+                     : "%s: bad argument (n=%d E=%d feats=%d G=%d; n and E must be multiples of G)", what, n, E, feats, G);
     return DACO_E_BADARG;
   }
   return DACO_OK;
 }
 
-extern "C" int daco_gnn_train_forward(void *stream, int n, int E, int feats, int G, const float *x, const int32_t *src,
-                                      const int32_t *dst, const int32_t *rowptr, const int32_t *perm, const float *edge_attr,
-                                      const float *params, float *heu, float *stats_out, const float *fixed_stats,
-                                      void *workspace, size_t workspace_bytes) {
-  if (int rc = check_train_args("daco_gnn_train_forward", n, E, feats, G)) return rc;
-  if (!x || !src || !dst || !rowptr || !edge_attr || !params || !heu || !workspace) { set_error("daco_gnn_train_forward: null pointer"); return DACO_E_BADARG; }
-  if (workspace_bytes < daco_gnn_train_workspace_bytes(n, E, G)) { set_error("daco_gnn_train_forward: workspace too small"); return DACO_E_WORKSPACE; }
+// The body of both forward entries.  gr: how an edge finds its graph (EqualGraphs{E / G} with edge_off = NULL, or
+// RaggedGraphs{src, n / G} with the graphs' edge ranges in edge_off); the launch sequence is the same.
+template <class GR>
+static int train_forward_body(const char *what, void *stream, int n, int E, int feats, int G, GR gr, const int32_t *edge_off,
+                              const float *x, const int32_t *src, const int32_t *dst, const int32_t *rowptr, const int32_t *perm,
+                              const float *edge_attr, const float *params, float *heu, float *stats_out, const float *fixed_stats,
+                              void *workspace, size_t workspace_bytes) {
+  if (!x || !src || !dst || !rowptr || !edge_attr || !params || !heu || !workspace) { set_error("%s: null pointer", what); return DACO_E_BADARG; }
+  if (workspace_bytes < daco_gnn_train_workspace_bytes(n, E, G)) { set_error("%s: workspace too small", what); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
   TrainWs t = carve(workspace, n, E, G);
-  const int ng = n / G, Eg = E / G;
+  const int ng = n / G, Eg = E / G;                         // (Eg: the count of an edge statistic when edge_off is NULL)
   const int node_blocks = (n + 7) / 8, tile_blocks = (E + 127) / 128;
   const unsigned ew_blocks = (unsigned)(((long)E * 32 + 255) / 256);
   if (zero_async(t.fsums, (size_t)12 * 2 * G * 32 * 2 * 8, s) != hipSuccess) { set_error("zero fill failed"); return DACO_E_HIP; }
@@ -1010,32 +1044,52 @@ extern "C" int daco_gnn_train_forward(void *stream, int n, int E, int feats, int
     double *fe = t.fsums + ((size_t)l * 2 + 0) * G * 64, *fv = t.fsums + ((size_t)l * 2 + 1) * G * 64;
     float2 *fte = t.ftab + ((size_t)l * 2 + 0) * G * 32, *ftv = t.ftab + ((size_t)l * 2 + 1) * G * 32;
     const unsigned tb = (unsigned)((2 * G * 32 + 255) / 256);
-    hipLaunchKernelGGL(gnn_t_edge_pre, dim3(tile_blocks), dim3(256), 0, s, E, Eg, src, dst, We, be, t.X[l], t.w[l], t.ze[l], fe);
+    hipLaunchKernelGGL(gnn_t_edge_pre<GR>, dim3(tile_blocks), dim3(256), 0, s, E, gr, src, dst, We, be, t.X[l], t.w[l], t.ze[l], fe);
     hipLaunchKernelGGL(gnn_t_node_pre, dim3(node_blocks), dim3(256), 0, s, n, ng, dst, rowptr, perm, t.X[l], t.w[l], t.zv[l], fv);
     if (fixed_stats) {   // evaluation-mode BatchNorm: the caller's running statistics ([12][2 (e, v)][32][2 (mean, var)])
       hipLaunchKernelGGL(gnn_t_fixed_table, dim3(tb), dim3(256), 0, s, G, fixed_stats + (size_t)l * 2 * 64, fte);
     } else {
-      hipLaunchKernelGGL(gnn_t_stat_table, dim3(tb), dim3(256), 0, s, G, Eg, ng, fe, fte, 0);      // (fv / ftv follow fe / fte)
+      hipLaunchKernelGGL(gnn_t_stat_table, dim3(tb), dim3(256), 0, s, G, Eg, ng, edge_off, fe, fte, 0);      // (fv / ftv follow fe / fte)
     }
-    hipLaunchKernelGGL(gnn_t_edge_post, dim3(ew_blocks), dim3(256), 0, s, E, Eg, ge, bee, fte, t.w[l], t.ze[l], t.w[l + 1]);
+    hipLaunchKernelGGL(gnn_t_edge_post<GR>, dim3(ew_blocks), dim3(256), 0, s, E, gr, ge, bee, fte, t.w[l], t.ze[l], t.w[l + 1]);
     const float *WTn = l < 11 ? params + off_layer(feats, l + 1) : nullptr;
     hipLaunchKernelGGL(gnn_t_node_post, dim3(node_blocks), dim3(256), 0, s, n, ng, gv, bv_, ftv, t.x[l], t.zv[l], t.x[l + 1], WTn,
                        WTn ? WTn + 32 * 128 : nullptr, l < 11 ? t.X[l + 1] : nullptr);
   }
   hipLaunchKernelGGL(gnn_t_head_fwd, dim3(tile_blocks), dim3(256), 0, s, E, params + off_head(feats), t.w[12], heu);
   if (stats_out)
-    hipLaunchKernelGGL(gnn_t_export_stats, dim3((12 * 2 * G * 32 + 255) / 256), dim3(256), 0, s, G, Eg, ng, t.fsums, stats_out);
+    hipLaunchKernelGGL(gnn_t_export_stats, dim3((12 * 2 * G * 32 + 255) / 256), dim3(256), 0, s, G, Eg, ng, edge_off, t.fsums, stats_out);
   return launch_status("gnn train forward");
 }
 
-extern "C" int daco_gnn_train_backward(void *stream, int n, int E, int feats, int G, const float *x, const int32_t *src,
-                                       const int32_t *dst, const int32_t *rowptr, const int32_t *perm, const int32_t *rowptr_dst,
-                                       const int32_t *perm_dst, const float *edge_attr, const float *params, const float *heu,
-                                       const float *grad_heu, float *grad_params, int fixed_stats, void *workspace,
-                                       size_t workspace_bytes) {
-  if (int rc = check_train_args("daco_gnn_train_backward", n, E, feats, G)) return rc;
-  if (!x || !src || !dst || !rowptr || !edge_attr || !params || !heu || !grad_heu || !grad_params || !workspace) { set_error("daco_gnn_train_backward: null pointer"); return DACO_E_BADARG; }
-  if (workspace_bytes < daco_gnn_train_workspace_bytes(n, E, G)) { set_error("daco_gnn_train_backward: workspace too small"); return DACO_E_WORKSPACE; }
+extern "C" int daco_gnn_train_forward(void *stream, int n, int E, int feats, int G, const float *x, const int32_t *src,
+                                      const int32_t *dst, const int32_t *rowptr, const int32_t *perm, const float *edge_attr,
+                                      const float *params, float *heu, float *stats_out, const float *fixed_stats,
+                                      void *workspace, size_t workspace_bytes) {
+  if (int rc = check_train_args("daco_gnn_train_forward", n, E, feats, G)) return rc;
+  return train_forward_body("daco_gnn_train_forward", stream, n, E, feats, G, EqualGraphs{E / G}, nullptr, x, src, dst, rowptr, perm,
+                            edge_attr, params, heu, stats_out, fixed_stats, workspace, workspace_bytes);
+}
+
+extern "C" long daco_gnn_train_forward_ragged(void *stream, int n, int E, int feats, int G, const int32_t *edge_off, const float *x,
+                                             const int32_t *src, const int32_t *dst, const int32_t *rowptr, const int32_t *perm,
+                                             const float *edge_attr, const float *params, float *heu, float *stats_out,
+                                             const float *fixed_stats, void *workspace, size_t workspace_bytes) {
+  if (int rc = check_train_args("daco_gnn_train_forward_ragged", n, E, feats, G, true)) return rc;
+  if (!edge_off || !src) { set_error("daco_gnn_train_forward_ragged: null pointer"); return DACO_E_BADARG; }
+  return train_forward_body("daco_gnn_train_forward_ragged", stream, n, E, feats, G, RaggedGraphs{src, n / G}, edge_off, x, src, dst,
+                            rowptr, perm, edge_attr, params, heu, stats_out, fixed_stats, workspace, workspace_bytes);
+}
+
+// The body of both backward entries (gr, edge_off: see train_forward_body).
+template <class GR>
+static int train_backward_body(const char *what, void *stream, int n, int E, int feats, int G, GR gr, const int32_t *edge_off,
+                               const float *x, const int32_t *src, const int32_t *dst, const int32_t *rowptr, const int32_t *perm,
+                               const int32_t *rowptr_dst, const int32_t *perm_dst, const float *edge_attr, const float *params,
+                               const float *heu, const float *grad_heu, float *grad_params, int fixed_stats, void *workspace,
+                               size_t workspace_bytes) {
+  if (!x || !src || !dst || !rowptr || !edge_attr || !params || !heu || !grad_heu || !grad_params || !workspace) { set_error("%s: null pointer", what); return DACO_E_BADARG; }
+  if (workspace_bytes < daco_gnn_train_workspace_bytes(n, E, G)) { set_error("%s: workspace too small", what); return DACO_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
   TrainWs t = carve(workspace, n, E, G);
   const int ng = n / G, Eg = E / G;
@@ -1076,16 +1130,16 @@ extern "C" int daco_gnn_train_backward(void *stream, int n, int E, int feats, in
     const float2 *fte = t.ftab + ((size_t)l * 2 + 0) * G * 32, *ftv = t.ftab + ((size_t)l * 2 + 1) * G * 32;
     float2 *bte = t.btab, *btv = t.btab + (size_t)G * 32;
     const unsigned tb = (unsigned)((2 * G * 32 + 255) / 256);
-    hipLaunchKernelGGL(gnn_t_bwd_stats, dim3((E + 255) / 256), dim3(256), 0, s, E, Eg, ge, bee, fte, t.ze[l], t.gw, be_s);
-    hipLaunchKernelGGL(gnn_t_bwd_stats, dim3((n + 255) / 256), dim3(256), 0, s, n, ng, gv, bv_, ftv, t.zv[l], t.gx, bv_s);
+    hipLaunchKernelGGL(gnn_t_bwd_stats<GR>, dim3((E + 255) / 256), dim3(256), 0, s, E, gr, ge, bee, fte, t.ze[l], t.gw, be_s);
+    hipLaunchKernelGGL(gnn_t_bwd_stats<EqualGraphs>, dim3((n + 255) / 256), dim3(256), 0, s, n, EqualGraphs{ng}, gv, bv_, ftv, t.zv[l], t.gx, bv_s);
     if (fixed_stats) {   // the statistics were constants of the forward: g_z = gamma * rstd * g_y, no batch terms
       if (l == 11 && zero_async(t.btab, (size_t)2 * G * 32 * 8, s) != hipSuccess) { set_error("zero fill failed"); return DACO_E_HIP; }   // (nobody writes it in this mode)
     } else {
-      hipLaunchKernelGGL(gnn_t_stat_table, dim3(tb), dim3(256), 0, s, G, Eg, ng, be_s, bte, 1);    // (bv_s / btv follow be_s / bte)
+      hipLaunchKernelGGL(gnn_t_stat_table, dim3(tb), dim3(256), 0, s, G, Eg, ng, edge_off, be_s, bte, 1);    // (bv_s / btv follow be_s / bte)
     }
     hipLaunchKernelGGL(gnn_t_node_bwd_apply, dim3(node_blocks), dim3(256), 0, s, n, ng, rowptr, gv, bv_, ftv, btv, t.zv[l], t.gx,
                        t.gX, t.gmsg, gather ? 0 : 1);
-    hipLaunchKernelGGL(gnn_t_edge_bwd, dim3(egrid), dim3(256), 0, s, E, Eg, src, dst, We, ge, bee, fte, bte, t.X[l], t.w[l], t.ze[l],
+    hipLaunchKernelGGL(gnn_t_edge_bwd<GR>, dim3(egrid), dim3(256), 0, s, E, gr, src, dst, We, ge, bee, fte, bte, t.X[l], t.w[l], t.ze[l],
                        t.gmsg, t.gw, t.gX, gWe, gbe, gather ? t.c2buf : nullptr, gather ? t.gzbuf : nullptr);
     if (gather)
       hipLaunchKernelGGL(gnn_t_gather_bwd, dim3(node_blocks), dim3(256), 0, s, n, rowptr, perm, rowptr_dst, perm_dst, t.c2buf,
@@ -1100,4 +1154,27 @@ extern "C" int daco_gnn_train_backward(void *stream, int n, int E, int feats, in
   hipLaunchKernelGGL(gnn_t_edge_init_bwd, dim3(E / 64 + 1 < 128 ? E / 64 + 1 : 128), dim3(256), 0, s, E, edge_attr, W0e, W0e + 32, t.gw,
                      grad_params + 32 * feats + 32, grad_params + 32 * feats + 64);
   return launch_status("gnn train backward");
+}
+
+extern "C" int daco_gnn_train_backward(void *stream, int n, int E, int feats, int G, const float *x, const int32_t *src,
+                                       const int32_t *dst, const int32_t *rowptr, const int32_t *perm, const int32_t *rowptr_dst,
+                                       const int32_t *perm_dst, const float *edge_attr, const float *params, const float *heu,
+                                       const float *grad_heu, float *grad_params, int fixed_stats, void *workspace,
+                                       size_t workspace_bytes) {
+  if (int rc = check_train_args("daco_gnn_train_backward", n, E, feats, G)) return rc;
+  return train_backward_body("daco_gnn_train_backward", stream, n, E, feats, G, EqualGraphs{E / G}, nullptr, x, src, dst, rowptr, perm,
+                             rowptr_dst, perm_dst, edge_attr, params, heu, grad_heu, grad_params, fixed_stats, workspace,
+                             workspace_bytes);
+}
+
+extern "C" long daco_gnn_train_backward_ragged(void *stream, int n, int E, int feats, int G, const int32_t *edge_off, const float *x,
+                                              const int32_t *src, const int32_t *dst, const int32_t *rowptr, const int32_t *perm,
+                                              const int32_t *rowptr_dst, const int32_t *perm_dst, const float *edge_attr,
+                                              const float *params, const float *heu, const float *grad_heu, float *grad_params,
+                                              int fixed_stats, void *workspace, size_t workspace_bytes) {
+  if (int rc = check_train_args("daco_gnn_train_backward_ragged", n, E, feats, G, true)) return rc;
+  if (!edge_off || !src) { set_error("daco_gnn_train_backward_ragged: null pointer"); return DACO_E_BADARG; }
+  return train_backward_body("daco_gnn_train_backward_ragged", stream, n, E, feats, G, RaggedGraphs{src, n / G}, edge_off, x, src,
+                             dst, rowptr, perm, rowptr_dst, perm_dst, edge_attr, params, heu, grad_heu, grad_params, fixed_stats,
+                             workspace, workspace_bytes);
 }

@@ -197,9 +197,123 @@ heu_scatter_kernel(int B, int n, int E, const int64_t *edge_index, const float *
   out[((size_t)b * n + (size_t)sidx) * n + (size_t)didx] = heu[idx] + add;
 }
 
+// ---- sop/: the network's graph is nonzero(adj) (sop/utils.py:52-57), adj[u][v] = 1 unless u == v or prec[u][v] = 1 -- its
+// size depends on the data.  B instances as one block-diagonal graph in exactly torch.nonzero's order (instance after instance,
+// source-major, destinations ascending): a count pass (one wavefront per row (b, u), a ballot per 64 columns), a scan of the row
+// counts on the device, and a fill pass that compacts every row with the same ballots -- a lane's slot is the row's base + the
+// kept columns before it (mbcnt): no sort, no atomics on the output.
+__device__ inline bool sop_edge(const float *prow, int n, int u, int v) { return v < n && v != u && prow[v] == 0.0f; }
+
+__global__ void __launch_bounds__(256)
+sop_graph_count_kernel(int rows, int n, const float *prec, int32_t *cnt) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int u = row % n;
+  const float *prow = prec + (size_t)row * n;
+  int total = 0;
+  for (int v0 = 0; v0 < n; v0 += 64) total += __popcll(__ballot(sop_edge(prow, n, u, v0 + lane)));
+  if (lane == 0) cnt[row] = total;
+}
+
+// rowptr[0 .. rows) holds the row counts on entry and their exclusive sums on return, rowptr[rows] = E; edge_off[b] =
+// rowptr[b n].  One workgroup: rows = B n is a few thousand.
+__global__ void __launch_bounds__(1024)
+sop_graph_scan_kernel(int rows, int n, int32_t *rowptr, int32_t *edge_off) {
+  __shared__ int wsum[16], carry_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) carry_s = 0;
+  __syncthreads();
+  for (int base = 0; base < rows; base += 1024) {
+    const int i = base + tid;
+    const int v = i < rows ? rowptr[i] : 0;
+    int inc = v;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { const int o = __shfl_up(inc, s, 64); if (lane >= s) inc += o; }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int off = carry_s;
+    for (int w = 0; w < wave; ++w) off += wsum[w];
+    if (i < rows) {
+      rowptr[i] = off + inc - v;
+      if (i % n == 0) edge_off[i / n] = off + inc - v;
+    }
+    __syncthreads();
+    if (tid == 1023) carry_s = off + inc;
+    __syncthreads();
+  }
+  if (tid == 0) { rowptr[rows] = carry_s; edge_off[rows / n] = carry_s; }
+}
+
+// E: the size of the caller's outputs.  A call whose E is not rowptr[rows] writes no edge at all and raises *bad (sticky: the
+// caller clears it): every slot the pass writes is below rowptr[rows] = E.
+__global__ void __launch_bounds__(256)
+sop_graph_fill_kernel(int rows, int n, int E, const float *prec, const float *dist, const int32_t *rowptr, int32_t *src32,
+                      int32_t *dst32, float *edge_attr, int64_t *cell, int32_t *bad) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  if (rowptr[rows] != E) {
+    if (row == 0 && lane == 0) *bad = 1;
+    return;
+  }
+  const int u = row % n;
+  const float *prow = prec + (size_t)row * n, *drow = dist + (size_t)row * n;
+  int at = max(rowptr[row], 0);
+  const int end = min(rowptr[row + 1], E);
+  for (int v0 = 0; v0 < n; v0 += 64) {
+    const int v = v0 + lane;
+    const bool keep = sop_edge(prow, n, u, v);
+    const unsigned long long m = __ballot(keep);
+    const int slot = at + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    if (keep && slot < end) {                               // (slot < end always, unless prec changed between the passes)
+      src32[slot] = row;
+      dst32[slot] = row - u + v;
+      edge_attr[slot] = drow[v];
+      cell[slot] = (int64_t)row * n + v;
+    }
+    at += __popcll(m);
+  }
+}
+
 }  // namespace daco
 
 using namespace daco;
+
+static long sop_graph_args(const char *what, int B, int n) {
+  if (B <= 0 || n < 2) { set_error("%s: bad argument (B=%d n=%d; B >= 1, n >= 2)", what, B, n); return DACO_E_BADARG; }
+  if ((long)B * n * n >= 0x80000000L) {
+    set_error("%s: B * n * n = %ld cells do not fit 31 bits", what, (long)B * n * n);
+    return DACO_E_TOOLARGE;
+  }
+  return DACO_OK;
+}
+
+extern "C" long daco_sop_graph_count(void *stream, int B, int n, const float *prec, int32_t *rowptr, int32_t *edge_off) {
+  if (const long rc = sop_graph_args("daco_sop_graph_count", B, n)) return rc;
+  if (!prec || !rowptr || !edge_off) { set_error("daco_sop_graph_count: bad argument (null pointer)"); return DACO_E_BADARG; }
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = B * n;
+  hipLaunchKernelGGL(sop_graph_count_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rows, n, prec, rowptr);
+  hipLaunchKernelGGL(sop_graph_scan_kernel, dim3(1), dim3(1024), 0, s, rows, n, rowptr, edge_off);
+  return launch_status("sop_graph_count_kernel / sop_graph_scan_kernel");
+}
+
+extern "C" long daco_sop_graph_fill(void *stream, int B, int n, int E, const float *prec, const float *dist, const int32_t *rowptr,
+                                    int32_t *src32, int32_t *dst32, float *edge_attr, int64_t *cell, int32_t *bad) {
+  if (const long rc = sop_graph_args("daco_sop_graph_fill", B, n)) return rc;
+  if (E < 1 || (long)E > (long)B * n * (n - 1)) {
+    set_error("daco_sop_graph_fill: bad argument (E=%d; 1 <= E <= B n (n - 1) = %ld)", E, (long)B * n * (n - 1));
+    return DACO_E_BADARG;
+  }
+  if (!prec || !dist || !rowptr || !src32 || !dst32 || !edge_attr || !cell || !bad) {
+    set_error("daco_sop_graph_fill: bad argument (null pointer)");
+    return DACO_E_BADARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = B * n;
+  hipLaunchKernelGGL(sop_graph_fill_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rows, n, E, prec, dist, rowptr, src32,
+                     dst32, edge_attr, cell, bad);
+  return launch_status("sop_graph_fill_kernel");
+}
 
 static int knn_graph_launch(const char *what, void *stream, int B, int n, int k, const float *coords, float diag, float *dist,
                             int64_t *edge_src, int64_t *edge_dst, float *edge_attr, int32_t *src32, int32_t *dst32) {

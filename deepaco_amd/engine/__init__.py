@@ -20,7 +20,7 @@ from .rcpsp_ops import (RCPSP_FLAG_ORDER, RCPSP_FLAG_RESOURCE, RCPSP_MAX_HORIZON
 from .reinforce_ops import reinforce, reinforce_backward  # noqa: F401
 from .sibling_colonies import (BATCHED_SIBLINGS, OBJ_KINDS, BatchedBPP, BatchedMKP, BatchedOP, BatchedPCTSP, BatchedSMTWTP,  # noqa: F401
                                BatchedSOP, sibling_objective, sibling_record_)
-from .sibling_ops import SIB_KINDS, PickService, sibling_backward, sibling_sample  # noqa: F401
+from .sibling_ops import SIB_KINDS, PickService, SopGraph, sibling_backward, sibling_sample, sop_graph  # noqa: F401
 from .tsp_ops import (SPARSE_MAX_N, SPARSE_MIN_N, auto_head_k, dist_is_symmetric, head_eta_table, head_table, heu_matrix, resolve_sampler,  # noqa: F401
                       sparse_head, sparse_tours16, sparse_workspace, sparsify_heuristic, take_auto_top, tsp_edge_backward, tsp_edge_logp,
                       tsp_knn_graph, tsp_sample, tsp_sample_sparse, uniform_tail_applies)

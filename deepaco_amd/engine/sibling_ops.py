@@ -28,6 +28,61 @@ def _sibling_aux(B, n, aux_vec, aux_mat, item_weights):
 SIB_KINDS = {"sop": 3, "pctsp": 4, "op": 5, "mkp": 6}
 
 
+class SopGraph:
+    """What sop_graph returns: the graphs of B instances of n nodes as one block-diagonal graph of E edges.  src32, dst32 [E]
+    int32 (node ids b n + u), rowptr [B n + 1] int32, edge_off [B + 1] int32 (= rowptr[b n]), edge_attr [E] f32, cell [E] int64
+    (the flat index (b n + u) n + v into [B,n,n]); bad: the fill pass's flag word [1] int32, nonzero when E was wrong."""
+
+    def __init__(self, B, n, E, src32, dst32, rowptr, edge_off, edge_attr, cell, bad):
+        self.B, self.n, self.E = B, n, E
+        self.src32, self.dst32, self.rowptr, self.edge_off = src32, dst32, rowptr, edge_off
+        self.edge_attr, self.cell, self.bad = edge_attr, cell, bad
+
+
+def sop_graph(prec_cons, distances, n_edges=None, check=True):
+    """Batched gen_pyg_data of sop/utils.py:52-57 on the device: prec_cons [B,n,n] with 0 / 1 entries (preceding_mat_gen),
+    distances [B,n,n] -> SopGraph, the batch's block-diagonal graph in exactly the order
+    torch.nonzero(pipeline.sop_adjacency(prec_cons[b])).T lists each instance (instances one after the other, source-major,
+    destinations ascending; u -> v exists iff u != v and prec_cons[b,u,v] == 0).  Two passes of one wavefront per row -- count
+    (+ the scan that leaves rowptr) and fill; between them E = rowptr[B n] is read back, four bytes, to size the outputs.
+    n_edges: the caller's E -- nothing is read between the passes.  The fill pass compares it with rowptr[B n] on the device; a
+    wrong value writes no edge and raises the graph's flag word `bad`, which is read here once everything is queued (a
+    DacoError) -- check=False leaves that read to the caller, and the call touches the host not at all."""
+    B, n = (prec_cons.shape[0], prec_cons.shape[1]) if prec_cons.dim() == 3 else (0, 0)
+    if prec_cons.dim() != 3 or prec_cons.shape[2] != n or tuple(distances.shape) != tuple(prec_cons.shape):
+        raise _lib.DacoError(f"sop_graph: prec_cons [B,n,n] and distances [B,n,n] expected, got {tuple(prec_cons.shape)} and "
+                             f"{tuple(distances.shape)}")
+    if B < 1 or n < 2:
+        raise _lib.DacoError(f"sop_graph: B >= 1 and n >= 2 expected (got B={B}, n={n})")
+    if B * n * n >= 2 ** 31:
+        raise _lib.DacoTooLarge(f"sop_graph: B * n * n = {B * n * n} cells do not fit 31 bits")
+    if n_edges is not None and not 1 <= int(n_edges) <= B * n * (n - 1):
+        raise _lib.DacoError(f"sop_graph: n_edges = {n_edges} outside [1, B n (n - 1) = {B * n * (n - 1)}]")
+    _require_gpu(prec_cons, distances)
+    prec, dist = _f32c(prec_cons), _f32c(distances)
+    dev = prec.device
+    L = _lib.lib()
+    with _on(dev):
+        i32 = torch.empty(B * n + 1 + B + 1, dtype=torch.int32, device=dev)
+        rowptr, edge_off = i32[:B * n + 1], i32[B * n + 1:]
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(L.daco_sop_graph_count(_stream(dev), B, n, prec.data_ptr(), rowptr.data_ptr(), edge_off.data_ptr()),
+                   "daco_sop_graph_count")
+        E = int(n_edges) if n_edges is not None else int(rowptr[B * n])
+        if E < 1:
+            raise _lib.DacoError("sop_graph: the precedence constraints leave no edge at all")
+        e32 = torch.empty(2 * E, dtype=torch.int32, device=dev)
+        src32, dst32 = e32[:E], e32[E:]
+        attr = torch.empty(E, dtype=torch.float32, device=dev)
+        cell = torch.empty(E, dtype=torch.int64, device=dev)
+        _lib.check(L.daco_sop_graph_fill(_stream(dev), B, n, E, prec.data_ptr(), dist.data_ptr(), rowptr.data_ptr(),
+                                         src32.data_ptr(), dst32.data_ptr(), attr.data_ptr(), cell.data_ptr(), bad.data_ptr()),
+                   "daco_sop_graph_fill")
+    if n_edges is not None and check and int(bad):
+        raise _lib.DacoError(f"sop_graph: n_edges = {E} is not the graphs' edge count {int(rowptr[B * n])}: nothing was written")
+    return SopGraph(B, n, E, src32, dst32, rowptr, edge_off, attr, cell, bad)
+
+
 def sibling_sample(kind, tau, eta, n_ants, alpha=1.0, beta=1.0, aux_vec=None, aux_mat=None, scalar0=0.0,
                    item_weights=None, mode="scan", start=None, noise=None, seed=0, it=0, ant_gid0=0,
                    require_prob=False, Lmax=None, flags=None):

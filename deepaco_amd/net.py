@@ -13,6 +13,7 @@ forward(pyg):
     statistics are updated from the statistics the kernels report (every BatchNorm1d configuration: momentum, cumulative
     average, no running statistics);
   * eval mode with a gradient required -> the same kernels, the running statistics as constants (`fixed_stats`).
+forward_graphs(x, graph): the same three modes for B graphs of equal node count whose edge counts differ (sop/), in one pass.
 There is no torch-op path in forward(): the module tree (EmbNet / ParNet.forward) stays callable for cross-checks only.
 `pyg` only needs `.x`, `.edge_index`, `.edge_attr` (torch_geometric is not required).
 """
@@ -193,8 +194,9 @@ class _GnnTrainFn(torch.autograd.Function):
     """heu = Net(graph) in training mode; the backward returns d loss / d (flat parameter block)."""
 
     @staticmethod
-    def forward(ctx, flat, x, attr, src, dst, rowptr, perm, feats, G, fixed=None):
+    def forward(ctx, flat, x, attr, src, dst, rowptr, perm, feats, G, fixed=None, edge_off=None):
         # (perm may be None; the destination CSR is derived here, once per forward, for the backward)
+        # edge_off [G + 1] int32: G graphs with differing edge counts (daco_gnn_train_*_ragged); None: equal-sized graphs
         n, E = x.shape[0], src.numel()
         L = _lib.lib()
         dev = x.device
@@ -204,13 +206,16 @@ class _GnnTrainFn(torch.autograd.Function):
             # the activations the backward reads stay in this block: one per forward call, kept by ctx
             ws = torch.empty(L.daco_gnn_train_workspace_bytes(n, E, G), dtype=torch.uint8, device=dev)
             flat = flat.detach().contiguous()
-            rc = L.daco_gnn_train_forward(engine._stream(dev), n, E, feats, G, x.data_ptr(), src.data_ptr(), dst.data_ptr(),
-                                          rowptr.data_ptr(), perm.data_ptr() if perm is not None else None, attr.data_ptr(),
-                                          flat.data_ptr(), heu.data_ptr(), stats.data_ptr(),
-                                          fixed.data_ptr() if fixed is not None else None, ws.data_ptr(), ws.numel())
-        _lib.check(rc, "daco_gnn_train_forward")
+            tail = (x.data_ptr(), src.data_ptr(), dst.data_ptr(), rowptr.data_ptr(), perm.data_ptr() if perm is not None else None,
+                    attr.data_ptr(), flat.data_ptr(), heu.data_ptr(), stats.data_ptr(),
+                    fixed.data_ptr() if fixed is not None else None, ws.data_ptr(), ws.numel())
+            if edge_off is None:
+                rc = L.daco_gnn_train_forward(engine._stream(dev), n, E, feats, G, *tail)
+            else:
+                rc = L.daco_gnn_train_forward_ragged(engine._stream(dev), n, E, feats, G, edge_off.data_ptr(), *tail)
+        _lib.check(rc, "daco_gnn_train_forward" if edge_off is None else "daco_gnn_train_forward_ragged")
         ctx.save_for_backward(flat, x, attr, src, dst, rowptr, heu)
-        ctx.ws, ctx.feats, ctx.G, ctx.perm, ctx.fixed = ws, feats, G, perm, fixed is not None
+        ctx.ws, ctx.feats, ctx.G, ctx.perm, ctx.fixed, ctx.edge_off = ws, feats, G, perm, fixed is not None, edge_off
         ctx.mark_non_differentiable(stats)
         return heu, stats
 
@@ -228,14 +233,16 @@ class _GnnTrainFn(torch.autograd.Function):
             gflat = torch.empty_like(flat)
             gheu = gheu.float().contiguous()
             perm = ctx.perm                     # (destination CSR: None -> the library builds it in the workspace)
-            rc = L.daco_gnn_train_backward(engine._stream(dev), n, E, ctx.feats, ctx.G, x.data_ptr(), src.data_ptr(),
-                                           dst.data_ptr(), rowptr.data_ptr(), perm.data_ptr() if perm is not None else None,
-                                           None, None, attr.data_ptr(), flat.data_ptr(),
-                                           heu.data_ptr(), gheu.data_ptr(), gflat.data_ptr(), int(ctx.fixed), ctx.ws.data_ptr(),
-                                           ctx.ws.numel())
-        _lib.check(rc, "daco_gnn_train_backward")
+            tail = (x.data_ptr(), src.data_ptr(), dst.data_ptr(), rowptr.data_ptr(), perm.data_ptr() if perm is not None else None,
+                    None, None, attr.data_ptr(), flat.data_ptr(), heu.data_ptr(), gheu.data_ptr(), gflat.data_ptr(), int(ctx.fixed),
+                    ctx.ws.data_ptr(), ctx.ws.numel())
+            if ctx.edge_off is None:
+                rc = L.daco_gnn_train_backward(engine._stream(dev), n, E, ctx.feats, ctx.G, *tail)
+            else:
+                rc = L.daco_gnn_train_backward_ragged(engine._stream(dev), n, E, ctx.feats, ctx.G, ctx.edge_off.data_ptr(), *tail)
+        _lib.check(rc, "daco_gnn_train_backward" if ctx.edge_off is None else "daco_gnn_train_backward_ragged")
         ctx.ws = None
-        return (gflat,) + (None,) * 9
+        return (gflat,) + (None,) * 10
 
 
 def _same(t):
@@ -577,6 +584,33 @@ class Net(BlockNet):
         BatchNorm statistics, exactly as B separate training forwards.  k_sparse: see _merge_graphs."""
         B, E = x.shape[0], edge_index.shape[2]
         return self.forward_train_hip(_merge_graphs(x, edge_index, edge_attr, k_sparse), graphs=B).view(B, E)
+
+    def forward_graphs(self, x, graph):
+        """One pass for B graphs of n nodes each whose edge counts differ (sop/: the graph is nonzero(adj)): x [B,n,feats],
+        graph: what engine.sop_graph returned for the batch (the block-diagonal int32 graph with its row pointer, the graphs'
+        edge ranges edge_off and the attributes) -> heu [E], instance b's values at [edge_off[b], edge_off[b + 1]) in the order
+        its own forward() lists them.  The modes are forward()'s: training mode, or a gradient needed -> the ragged training
+        kernels (every graph normalised with its own statistics over its own edge count; the running statistics updated as B
+        successive forwards leave them; in eval mode the running statistics as constants); eval mode without a gradient ->
+        daco_gnn_forward on the merged CSR.  No sortedness test, no host read."""
+        if not x.is_cuda:
+            raise _lib.DacoError("deepaco_amd.Net runs on a HIP device only (got CPU tensors)")
+        B, n, feats = x.shape
+        if (B, n) != (graph.B, graph.n):
+            raise _lib.DacoError(f"Net.forward_graphs: x [{B},{n},.] does not fit a graph of {graph.B} x {graph.n} nodes")
+        xf = x.float().contiguous().view(B * n, feats)
+        needs_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        tracks, _ = self._bn_config()
+        if self.training or needs_graph or not tracks:
+            fixed = self._running_stats_block() if (not self.training and tracks) else None
+            heu, stats = _GnnTrainFn.apply(self._train_block(), xf, graph.edge_attr, graph.src32, graph.dst32, graph.rowptr, None,
+                                           feats, B, fixed, graph.edge_off)
+            if self.training:
+                self._update_running_stats(stats, graph.edge_off[1:] - graph.edge_off[:-1], n)
+            return heu
+        merged = GraphData(x=xf, edge_index=None, edge_attr=graph.edge_attr)
+        merged._daco_graph = (graph.src32, graph.dst32, graph.rowptr, None)
+        return self.forward_hip(merged)
 
     # ------------------------------------------------------------------ HIP inference path
     @torch.no_grad()

@@ -435,18 +435,20 @@ def infer_rcpsp_batch(instances, n_ants, t_aco, heuristic=None, seed=0, sampler=
 
 
 @torch.no_grad()
-def infer_sibling_batch(problem, data, n_ants, t_aco, heuristic=None, seed=0, net=None, **aco_kw):
+def infer_sibling_batch(problem, data, n_ants, t_aco, heuristic=None, seed=0, net=None, graph_path="torch", **aco_kw):
     """The test loops of the sibling problems (op/test.py, mkp/test.py and the notebooks of smtwtp, sop, pctsp, bpp: one colony
     per instance, the record read at every checkpoint of t_aco) for B instances of one size at once.  problem: 'smtwtp', 'sop',
     'pctsp', 'op', 'bpp' or 'mkp'; data: the tuple of batched tensors of that problem's engine.Batched* constructor (e.g.
     (distances [B,n,n], prizes [B,n], max_len) for 'op'); heuristic [B,.,.] as that constructor takes it, or None for the
     reference's default; net: the directory's Net, whose sibling_heuristic_batch(problem, net.eval(), data) is the heuristic
-    instead (giving a heuristic as well is an error; 'op' then needs its k_sparse); aco_kw: anything else the constructor takes.
+    instead (giving a heuristic as well is an error; 'op' then needs its k_sparse; graph_path: see sibling_heuristic_batch --
+    'hip' is sop's one-pass network forward); aco_kw: anything else the constructor takes.
     Returns (records [len(t_aco), B], colony)."""
+    _check_graph_path(problem, graph_path)
     if net is not None:
         if heuristic is not None:
             raise ValueError("infer_sibling_batch: give either a heuristic or a network, not both")
-        heuristic = sibling_heuristic_batch(problem, net.eval(), data, k_sparse=aco_kw.get("k_sparse"))
+        heuristic = sibling_heuristic_batch(problem, net.eval(), data, k_sparse=aco_kw.get("k_sparse"), graph_path=graph_path)
         aco_kw = {k: v for k, v in aco_kw.items() if k != "k_sparse"}      # (the graph's: the colony sparsifies nothing it is given)
     colony = engine.BATCHED_SIBLINGS[problem](*data, n_ants=n_ants, heuristic=heuristic, seed=seed, **aco_kw)
     out, done = [], 0
@@ -498,7 +500,8 @@ def sibling_graph_batch(problem, data, k_sparse=None):
     op: the k_sparse nearest neighbours per node, nearest first, as op/utils.py:26-49 takes them (torch.topk on the distances:
     the reference's own call, batched; the diagonal's 1e9 keeps a node out of its own list), with the depot distance (0 for the
     depot itself) and the prizes as node features; edge j k + t leaves node j: Net.forward_batch(..., k_sparse=k).
-    sop is not built here: its graph is nonzero(adj), its size depends on the data (see sibling_heuristic_batch)."""
+    sop is not built here: its graph is nonzero(adj), its size depends on the data (see sop_graph_batch and
+    sibling_heuristic_batch)."""
     _check_problem(problem)
     if problem == "sop":
         raise ValueError("sibling_graph_batch: sop's graph is nonzero(adj) -- ragged; sibling_heuristic_batch runs it per instance")
@@ -554,7 +557,39 @@ def _sop_heuristic_batch(net, data):
     return torch.stack(mats)
 
 
-def sibling_heuristic_batch(problem, net, data, k_sparse=None):
+GRAPH_PATHS = ("torch", "hip")
+
+
+def _check_graph_path(problem, graph_path):
+    if graph_path not in GRAPH_PATHS:
+        raise ValueError(f"graph_path must be one of {GRAPH_PATHS} (got {graph_path!r})")
+    if graph_path == "hip" and problem != "sop":
+        raise ValueError(f"graph_path='hip' is sop's batched graph build (engine.sop_graph); {problem!r} has one graph path: its "
+                         "graphs are regular and sibling_graph_batch writes them down")
+
+
+@torch.no_grad()
+def sop_graph_batch(data, n_edges=None):
+    """sop's graphs for B instances on the device: data = (distances [B,n,n], prec_cons [B,n,n]), what engine.BatchedSOP takes
+    -> (x [B,n,1] = distances[:, 0, :], graph = engine.sop_graph(prec_cons, distances, n_edges)): the batch as one
+    block-diagonal graph in the order gen_pyg_data lists each instance, for Net.forward_graphs.  One 4-byte host read (the
+    edge count), none with n_edges."""
+    distances, prec_cons = data
+    d = distances.float()
+    return d[:, 0, :].unsqueeze(-1), engine.sop_graph(prec_cons, d, n_edges=n_edges)
+
+
+def _sop_heuristic_batch_hip(net, data, n_edges=None):
+    """sop, graph_path='hip': graph build (two passes), ONE forward for the batch, then Net.reshape(pyg, vec) + EPS for the
+    batch as zeros(B n n).index_put(cell, heu) -- differentiable, every non-edge exactly EPS."""
+    x, graph = sop_graph_batch(data, n_edges=n_edges)
+    B, n = graph.B, graph.n
+    heu = net.forward_graphs(x, graph)
+    flat = torch.zeros(B * n * n, dtype=heu.dtype, device=heu.device).index_put((graph.cell,), heu)
+    return flat.view(B, n, n) + EPS
+
+
+def sibling_heuristic_batch(problem, net, data, k_sparse=None, graph_path="torch"):
     """The heuristic matrices [B,n,n] of B instances from the directory's network, by the directory's own recipe: graphs
     (sibling_graph_batch) -> one forward for the batch -- Net.forward_batch_train under autograd when the network is in training
     mode (per-graph BatchNorm statistics, the running statistics updated as B successive forwards leave them), Net.forward_batch
@@ -563,16 +598,20 @@ def sibling_heuristic_batch(problem, net, data, k_sparse=None):
       mkp           m = heu_vec.reshape(n, n); m / (m.min() + 1e-10) + 1e-10
       pctsp         (v / (v.min() + EPS) + EPS).reshape(n, n)
       smtwtp, op    Net.reshape(pyg, vec) + EPS        (smtwtp: n + 1 nodes, the dummy job first; op: k_sparse is required)
-      sop           Net.reshape(pyg, vec) + EPS, the single-instance forward once per instance and the matrices stacked: its
-                    graph is nonzero(adj), whose size depends on the data.  Its colony, sampler and backward are still one launch
-                    each for the batch.
+      sop           Net.reshape(pyg, vec) + EPS.  Its graph is nonzero(adj), whose size depends on the data.  graph_path='torch'
+                    (the default): the single-instance forward once per instance and the matrices stacked; graph_path='hip':
+                    engine.sop_graph builds the B ragged graphs on the device and Net.forward_graphs runs them in one pass
+                    (every graph with its own statistics and its own edge count), one host read of four bytes per batch.  Its
+                    colony, sampler and backward are one launch each for the batch either way.
+    graph_path='hip' with any other problem is a ValueError: their graphs are regular and have one path.
     The plain reshapes of cvrp, bpp and mkp ignore edge direction: edge e of their destination-major lists runs
     (e % n) -> (e // n) and lands at [e // n][e % n], so entry [i][j] is the network's value for the edge j -> i.  On the
     source-major run that matrix is the transposed VIEW of the [n, n] output -- no scatter, no indexed assignment.  The minimum
     of mkp and pctsp is per instance and gradient flows through it as through torch's .min()."""
     _check_problem(problem)
+    _check_graph_path(problem, graph_path)
     if problem == "sop":
-        return _sop_heuristic_batch(net, data)
+        return _sop_heuristic_batch_hip(net, data) if graph_path == "hip" else _sop_heuristic_batch(net, data)
     x, ei, ea = sibling_graph_batch(problem, data, k_sparse=k_sparse)
     B, n = x.shape[0], x.shape[1]
     k = int(k_sparse) if problem == "op" else n
@@ -612,7 +651,8 @@ def _reinforce_tail(obj, log_probs, lens, sign, loss_path):
     return ((adv * log_probs.sum(dim=1)).sum(dim=1) / A).mean()
 
 
-def _sibling_loss(problem, net, data, n_ants, seed=0, it=0, ant_gid0=0, loss_path="torch", k_sparse=None, **aco_kw):
+def _sibling_loss(problem, net, data, n_ants, seed=0, it=0, ant_gid0=0, loss_path="torch", k_sparse=None, graph_path="torch",
+                  **aco_kw):
     """The forward half of a train_instance of smtwtp/, sop/, pctsp/, op/, bpp/ or mkp/ for B instances: heuristic matrices
     (sibling_heuristic_batch, under autograd) -> B fresh colonies (pheromone ones, the directory's defaults; aco_kw: anything
     else the engine.Batched* constructor takes) -> sample() with log-probabilities (one launch) -> the REINFORCE loss of every
@@ -620,12 +660,12 @@ def _sibling_loss(problem, net, data, n_ants, seed=0, it=0, ant_gid0=0, loss_pat
     what the tests need.  ant_gid0: the id of the first ant (instance b of a batch draws what a single instance with
     ant_gid0 = b * n_ants draws); loss_path: 'torch' (the torch-op tail: the default, because the whole step -- bound by the
     host's launches at these sizes -- measured no faster with the kernel, DESIGN section 3.18) or 'hip' (autograd.ReinforceFn, one
-    launch each way: the checked, opt-in path).
+    launch each way: the checked, opt-in path); graph_path: see sibling_heuristic_batch ('hip': sop's one-pass forward).
     -> (loss, colony, dict(obj, log_probs, lens, heu_mat, paths))"""
     _check_problem(problem)
     if problem == "cvrp":
         raise ValueError("_sibling_loss: cvrp has its own _cvrp_loss (distances and demands, BatchedCVRP)")
-    heu_mat = sibling_heuristic_batch(problem, net, data, k_sparse=k_sparse)
+    heu_mat = sibling_heuristic_batch(problem, net, data, k_sparse=k_sparse, graph_path=graph_path)
     col = engine.BATCHED_SIBLINGS[problem](*data, n_ants=n_ants, heuristic=heu_mat.detach(), seed=seed, ant_gid0=ant_gid0, **aco_kw)
     col.iteration = int(it)
     col.set_heuristic(heu_mat)
@@ -648,19 +688,21 @@ def _cvrp_loss(net, demands, distances, n_ants, seed=0, it=0, ant_gid0=0, loss_p
     return loss, col, dict(obj=obj, log_probs=log_probs, lens=lens, heu_mat=heu_mat, paths=col.last_paths)
 
 
-def train_sibling_batch(problem, net, optimizer, data, n_ants, seed=0, it=0, **aco_kw):
+def train_sibling_batch(problem, net, optimizer, data, n_ants, seed=0, it=0, graph_path="torch", **aco_kw):
     """One optimisation step of the train_instance of smtwtp/, sop/, pctsp/, op/, bpp/ (train.ipynb) or mkp/ (train.py:15-31)
     for B instances of one size at once: graphs -> Net in training mode (one forward for the batch, per-graph BatchNorm
-    statistics; sop: one forward per instance) -> the directory's recipe from network output to heuristic matrix -> B fresh
+    statistics; sop: one forward per instance, or with graph_path="hip" one forward for the batch on the graphs engine.sop_graph
+    builds) -> the directory's recipe from network output to heuristic matrix -> B fresh
     colonies (pheromone ones, the directory's defaults) -> sample() with log-probabilities (one launch) -> the REINFORCE tail
     averaged over the instances (loss_path="torch", the default: torch ops; loss_path="hip": daco_reinforce, one launch each
     way -- see _sibling_loss) -> backward -> optimizer.step().  Nothing is clipped: none of these train files clips.  op and mkp
     maximise (baseline - obj), the others minimise (obj - baseline).
     data: the tuple the problem's engine.Batched* constructor takes; op needs k_sparse=, loss_path=, bpp's capacity and the like
-    go through aco_kw.  Returns (loss, mean objective) as detached device tensors; nothing is read on the host (sop's graphs
-    excepted)."""
+    go through aco_kw.  Returns (loss, mean objective) as detached device tensors; nothing is read on the host but the size of
+    sop's graphs (graph_path="torch": one read per instance; "hip": four bytes per batch)."""
+    _check_graph_path(problem, graph_path)
     net.train()
-    loss, _, ex = _sibling_loss(problem, net, data, n_ants, seed, it, **aco_kw)
+    loss, _, ex = _sibling_loss(problem, net, data, n_ants, seed, it, graph_path=graph_path, **aco_kw)
     optimizer.zero_grad()
     loss.backward()
     optimizer.step()

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DACO_VERSION 130 /* 0.1.23: bumped whenever an entry point's signature or the draw stream of a mode changes (120: the head-row sampler; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads (the sparse workspace still begins with the dense rows P: see daco_tsp_sample_heads); 126: daco_tsp_sparse_tours_offset / the record from tours16 rows, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats, and daco_cvrp_knn_graph; daco_head_eta and the uniform-tail mode of the head-row path were added under 129 in the same way: same draws, same head rows, no existing signature changed; 130: one entry point per head-row call -- daco_tsp_sample_heads, daco_pheromone_update, daco_pheromone_update_heads and daco_track_best take their modes (race, uniform tail, the record kept by the update, tours16 rows) as arguments and the exports that stood beside them are gone; same draws, same kernels) */
+#define DACO_VERSION 130 /* 0.1.23: bumped whenever an entry point's signature or the draw stream of a mode changes (120: the head-row sampler; 121: head_slots; 122: scan_sparse draws once after a rejection; 123: its workspace takes the ant count; 124: daco_hgs_*, daco_cvrp_sample takes ant_gid_bstride; 125: daco_tsp_sample_heads / daco_pheromone_update_heads (the sparse workspace still begins with the dense rows P: see daco_tsp_sample_heads); 126: daco_tsp_sparse_tours_offset / the record from tours16 rows, the sparse workspace holds the u16 tours at every n); 127: daco_mkpv_*, daco_transformer_*; 128: daco_transformer_forward sums attention tile by tile, other last bits above 128 tokens; 129: daco_transformer_forward_train / daco_transformer_backward; daco_rcpsp_* were added under 129 as well: new entry points only, no signature or draw stream of an existing one changed, and a library without them fails at symbol lookup when it is loaded; daco_tsp_sparse_resident_per_cu and daco_tsp_sparse_split_tours were added under 129 in the same way, with the split-tour variant of the construction kernel: same draws, same signatures -- profiles/counters.json and profiles/hbm_traffic.json were collected again with that kernel; daco_rcpsp_net_* were added under 129 too, new entry points only, and so were daco_rcpsp_net_train_*; daco_sibling_objective / daco_sibling_record with DACO_SIB_SMTWTP / DACO_SIB_BPP were added under 129 in the same way: tests/test_mkp_grad_spec.py holds the number at 129; daco_hgs_local_search_ss / daco_hgs_workspace_bytes_ss (SWAP*) were added under 129 likewise, and so were daco_sparsify / daco_sparse_head / daco_head_stats, and daco_cvrp_knn_graph; daco_head_eta and the uniform-tail mode of the head-row path were added under 129 in the same way: same draws, same head rows, no existing signature changed; 130: one entry point per head-row call -- daco_tsp_sample_heads, daco_pheromone_update, daco_pheromone_update_heads and daco_track_best take their modes (race, uniform tail, the record kept by the update, tours16 rows) as arguments and the exports that stood beside them are gone; same draws, same kernels; daco_sop_graph_count / daco_sop_graph_fill and daco_gnn_train_forward_ragged / daco_gnn_train_backward_ragged were added under 130: new entry points only, no existing signature, result or launch sequence changed) */
 
 /* error codes */
 #define DACO_OK 0
@@ -682,6 +682,27 @@ int daco_gnn_train_backward(void *stream, int n, int E, int feats, int G, const 
                             const int32_t *dst, const int32_t *rowptr, const int32_t *perm, const int32_t *rowptr_dst,
                             const int32_t *perm_dst, const float *edge_attr, const float *params, const float *heu,
                             const float *grad_heu, float *grad_params, int fixed_stats, void *workspace, size_t workspace_bytes);
+/* The same two for G graphs of n_g = n / G nodes each whose EDGE counts differ (sop/: the graph is nonzero(adj)).
+ *   edge_off   [G + 1] int32 on the device, the caller's: graph g owns edges [edge_off[g], edge_off[g + 1]), edge_off[0] = 0,
+ *              edge_off[G] = E; the graphs are listed one after the other, in any order inside a graph (perm as above), and
+ *              every edge of graph g has its source in [g n_g, (g + 1) n_g).  An edge finds its graph as src[e] / n_g.
+ * Every graph is normalised with its own statistics over its own edge_off[g + 1] - edge_off[g] edges (stats_out reports the
+ * biased variance over that count); the node statistics count n_g rows as before; fixed_stats as above (one table for every
+ * graph).  Everything else -- arguments, workspace (daco_gnn_train_workspace_bytes(n, E, G)), launch sequence -- is that of
+ * the two entries above, which are these bodies with edge_off = NULL and an edge's graph e / E_g.  n % G != 0, a NULL
+ * edge_off: DACO_E_BADARG.  A graph without edges is no training input (its statistics would be 0 / 0; it counts one row).
+ * The statuses are the usual DACO_OK / DACO_E_* values typed `long`, for the reason given at daco_rcpsp_net_forward; the
+ * refusals are held by tests/test_sop_graph_spec.py.
+ */
+long daco_gnn_train_forward_ragged(void *stream, int n, int E, int feats, int G, const int32_t *edge_off, const float *x,
+                                   const int32_t *src, const int32_t *dst, const int32_t *rowptr, const int32_t *perm,
+                                   const float *edge_attr, const float *params, float *heu, float *stats_out,
+                                   const float *fixed_stats, void *workspace, size_t workspace_bytes);
+long daco_gnn_train_backward_ragged(void *stream, int n, int E, int feats, int G, const int32_t *edge_off, const float *x,
+                                    const int32_t *src, const int32_t *dst, const int32_t *rowptr, const int32_t *perm,
+                                    const int32_t *rowptr_dst, const int32_t *perm_dst, const float *edge_attr,
+                                    const float *params, const float *heu, const float *grad_heu, float *grad_params,
+                                    int fixed_stats, void *workspace, size_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_cvrp_local_search -- replaces ACO.multiple_swap_star's per-ant CPU tasks
@@ -819,6 +840,24 @@ int daco_tsp_knn_graph_csr(void *stream, int B, int n, int k, const float *coord
  */
 long daco_cvrp_knn_graph(void *stream, int B, int n1, int k, const void *dist, int dist_f64, long dist_bstride,
                          int64_t *edge_index, float *edge_attr, int32_t *src32, int32_t *dst32, int32_t *rowptr, int32_t *perm);
+
+/* ---------------------------------------------------------------------------------------------
+ * daco_sop_graph_count / daco_sop_graph_fill -- replace gen_pyg_data of sop/utils.py:52-57 for a batch of instances
+ *   edge_index = nonzero(adj).T, edge_attr = distances[adj.bool()], adj[u][v] = 1 unless u == v or prec[u][v] = 1
+ * prec [B][n][n] f32 with 0 / 1 entries (the rows of preceding_mat_gen), dist [B][n][n] f32.  The batch as ONE block-diagonal
+ * graph in torch.nonzero's order: instance after instance, source-major, destinations ascending.
+ *   count:  rowptr [B n + 1] int32 = the CSR row pointer by source (rows without an out-edge are legal), edge_off [B + 1]
+ *           int32 = rowptr[b n]; E = rowptr[B n] is the one word a caller who does not know it reads back to size:
+ *   fill:   src32, dst32 [E] int32 global node ids b n + u, edge_attr [E] f32 = dist[b][u][v], cell [E] int64 = the flat index
+ *           (b n + u) n + v into [B][n][n].  The pass compares E with rowptr[B n] on the device: if they differ it writes no
+ *           edge and sets *bad = 1 (sticky; the caller clears it), so that a wrong E is never an out-of-bounds write.
+ * One wavefront per row, a ballot per 64 columns, mbcnt for a lane's slot: no sort, no atomics.
+ * Limits: B >= 1, n >= 2, 1 <= E <= B n (n - 1), every pointer (DACO_E_BADARG); B n n < 2^31 (DACO_E_TOOLARGE).  Refusals come
+ * before any HIP call; the status is typed `long` as daco_cvrp_knn_graph's, the refusals are held by tests/test_sop_graph_spec.py.
+ */
+long daco_sop_graph_count(void *stream, int B, int n, const float *prec, int32_t *rowptr, int32_t *edge_off);
+long daco_sop_graph_fill(void *stream, int B, int n, int E, const float *prec, const float *dist, const int32_t *rowptr,
+                         int32_t *src32, int32_t *dst32, float *edge_attr, int64_t *cell, int32_t *bad);
 
 /* ---------------------------------------------------------------------------------------------
  * daco_heu_matrix -- replaces Net.reshape for a batch, with the "+ eps" its callers add
