@@ -16,7 +16,9 @@
 // Layout: ant = 16 lanes (one DPP row), slot m = SPL * lane + v (SPL = 4 or 8).  Level 1 is the row scan of the 16 lane sums,
 // level 2 a compare tree on the winning lane's running sums; the winning lane stores the choice and the ant's lanes read it back.
 // The rare ways (tail walk, dense draw) are wave-cooperative: the 64 lanes serve one ant at a time (candidate
-// k = (c * 64 + lane) * 4 + v, the 64-lane scan).  Tours (u16) and visited flags (bytes, node order) live in LDS; paths / tour
+// k = (c * 64 + lane) * 4 + v, the 64-lane scan); the dense draw of an ant whose head has no live candidate -- the one way the
+// k-sparse heuristic takes, 28 times per wavefront and tour at the headline shape -- has a loop of its own in front of the
+// others' (profiles/dense_way_ab.txt).  Tours (u16) and visited flags (bytes, node order) live in LDS; paths / tour
 // lengths / the update's table leave the workgroup through the stages of daco_tour_epilogue.h (16 ants = one 128-byte run per row).
 #include "daco_sample_kernel.h"
 #include "daco_head_rows.h"
@@ -97,6 +99,7 @@ sparse_prepass_ut_kernel(int B, int n, int ch, const float *tau, long tau_bs, co
 // descriptor is four scalar registers built from the row index, which is uniform here.)
 typedef uint32_t sp_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t sp_u32x2 __attribute__((ext_vector_type(2)));
+typedef float sp_f32x2 __attribute__((ext_vector_type(2)));
 struct SpRowSrc { const float *p; };
 struct SpRowUT { __amdgpu_buffer_rsrc_t t; float c; };
 struct SpRowTE { __amdgpu_buffer_rsrc_t t, e; };
@@ -112,11 +115,16 @@ template <class Src> __device__ __forceinline__ int sp_lane_off(const Src &, int
   asm volatile("" : "+v"(lo));
   return lo;
 }
-__device__ __forceinline__ float4 sp_row4(const SpRowSrc &r, int c, int lo) { return *reinterpret_cast<const float4 *>(r.p + (c * 64 + lo) * 4); }
-__device__ __forceinline__ float4 sp_row4(const SpRowUT &r, int c, int lo) {
-  const sp_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(r.t, lo + c * 1024, 0, 0);
-  return make_float4(__uint_as_float(t.x) * r.c, __uint_as_float(t.y) * r.c, __uint_as_float(t.z) * r.c, __uint_as_float(t.w) * r.c);
+// (in two steps, the load as it comes and the values of it: a draw issues the loads of all its chunks before it uses the first)
+__device__ __forceinline__ float4 sp_row_ld(const SpRowSrc &r, int c, int lo) { return *reinterpret_cast<const float4 *>(r.p + (c * 64 + lo) * 4); }
+__device__ __forceinline__ float4 sp_row_val(const SpRowSrc &, float4 x) { return x; }
+__device__ __forceinline__ sp_u32x4 sp_row_ld(const SpRowUT &r, int c, int lo) { return __builtin_amdgcn_raw_buffer_load_b128(r.t, lo + c * 1024, 0, 0); }
+__device__ __forceinline__ float4 sp_row_val(const SpRowUT &r, sp_u32x4 t) {
+  // (as two pairs, the register pairs the load wrote: two packed multiplies by the scalar c and no moves in front of them)
+  const sp_f32x2 lo2 = sp_f32x2{__uint_as_float(t.x), __uint_as_float(t.y)} * r.c, hi2 = sp_f32x2{__uint_as_float(t.z), __uint_as_float(t.w)} * r.c;
+  return make_float4(lo2.x, lo2.y, hi2.x, hi2.y);
 }
+template <class Src> __device__ __forceinline__ float4 sp_row4(const Src &r, int c, int lo) { return sp_row_val(r, sp_row_ld(r, c, lo)); }
 __device__ __forceinline__ float4 sp_row4(const SpRowTE &r, int c, int lo) {
   const sp_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(r.t, lo + c * 1024, 0, 0), e = __builtin_amdgcn_raw_buffer_load_b128(r.e, lo + c * 1024, 0, 0);
   return make_float4(__uint_as_float(t.x) * __uint_as_float(e.x), __uint_as_float(t.y) * __uint_as_float(e.y),
@@ -124,11 +132,43 @@ __device__ __forceinline__ float4 sp_row4(const SpRowTE &r, int c, int lo) {
 }
 
 typedef const __attribute__((address_space(4))) SampleParams *sp_args_t;      // (the kernel's arguments as the segment holds them)
+// the rows of one instance: what a block of rare draws reads ONCE (uniform-tail mode: base, factor c from the argument segment) ...
+struct SpRowsP { const float *base; int ld; };
+struct SpRowsUT { const float *base; float c; };
+template <bool UT>
+__device__ __forceinline__ auto sp_rows_of(const float *base, sp_args_t pa, int b, int ld) {
+  if constexpr (UT) asm volatile("" : "+s"(pa));          // (read here, each time: the compiler cannot move the loads in front of the tour)
+  if constexpr (UT) return SpRowsUT{pa->tau + (size_t)b * pa->tau_bs, pa->tail_c};
+  else return SpRowsP{base, ld};
+}
+// ... and the row of one ant in them
+// (an instance's rows are n * ld <= 1024 * 1024 floats: the row's offset is a 32-bit product)
+__device__ __forceinline__ SpRowSrc sp_row_at(const SpRowsP &r, int row, int) { return SpRowSrc{r.base + (uint32_t)row * (uint32_t)r.ld}; }
+__device__ __forceinline__ SpRowUT sp_row_at(const SpRowsUT &r, int row, int n) { return SpRowUT{sp_row_rsrc(r.base + (uint32_t)row * (uint32_t)n, n), r.c}; }
 template <bool UT>
 __device__ __forceinline__ auto sp_row_of(const float *base, sp_args_t pa, int b, int row, int ld, int n) {
-  if constexpr (UT) asm volatile("" : "+s"(pa));          // (read here, each time: the compiler cannot move the loads in front of the tour)
-  if constexpr (UT) return SpRowUT{sp_row_rsrc(pa->tau + (size_t)b * pa->tau_bs + (size_t)row * n, n), pa->tail_c};
-  else return SpRowSrc{base + (size_t)row * ld};
+  return sp_row_at(sp_rows_of<UT>(base, pa, b, ld), row, n);
+}
+
+// add_with_carry (daco_sample_kernel.h) with the carry-out in vcc: no third scalar pair next to the two masks in flight (in the
+// split-tour kernel, which has none to spare, the pairs it took were restored from spill lanes after every draw)
+__device__ inline int sp_add_with_carry(int x, int y, uint64_t carry) {
+  int d;
+  asm("s_nop 1\n\tv_addc_co_u32_e64 %0, vcc, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "s"(carry) : "vcc");
+  return d;
+}
+// count_below<8> (daco_sample_kernel.h: the number of j with run[j] < t, run[] nondecreasing) without the level of the
+// sixteen-entry search that eight sums do not have: three probes over sums 0 .. 6, and sum 7 on top (below t only if all are)
+__device__ inline int sp_count_below8(const float (&run)[16], float t) {
+  auto pick = [](uint64_t m, float a, float b) { return __builtin_amdgcn_inverse_ballot_w64(m) ? a : b; };
+  const uint64_t m2 = __builtin_amdgcn_fcmpf(run[3], t, FCMP_OLT);
+  const uint64_t m1 = __builtin_amdgcn_fcmpf(pick(m2, run[5], run[1]), t, FCMP_OLT);
+  const float e0 = pick(m1, run[2], run[0]), e1 = pick(m1, run[6], run[4]);
+  const uint64_t m0 = __builtin_amdgcn_fcmpf(pick(m2, e1, e0), t, FCMP_OLT);
+  int x = __builtin_amdgcn_inverse_ballot_w64(m2) ? 1 : 0;
+  x = sp_add_with_carry(x, x, m1);
+  x = sp_add_with_carry(x, x, m0);
+  return sp_add_with_carry(x, 0, __builtin_amdgcn_fcmpf(run[7], t, FCMP_OLT));
 }
 
 template <int CHD, bool TAIL, class Src>
@@ -136,15 +176,11 @@ __device__ __forceinline__ int sparse_row_walk(const Src &rowp, const uint8_t *f
   constexpr int NJ = CHD * 4;
   float run[16];
   float acc = 0.0f;
-  uint32_t pos = 0;                                      // slots with a positive term (a term can be absorbed by the running sum)
   const int lo = sp_lane_off(rowp, lane);
-#pragma unroll
-  for (int c = 0; c < CHD; ++c) {
+  constexpr bool TE = std::is_same<Src, SpRowTE>::value;
+  // the lane's flag factors of chunk c
+  auto factors = [&](int c, float (&f)[4]) {
     const int k0 = (c * 64 + lane) * 4;
-    // (two rows: one chunk's vectors in flight at a time -- this draw is the rarest way and must not set the kernel's registers)
-    if constexpr (std::is_same<Src, SpRowTE>::value) __builtin_amdgcn_sched_barrier(0);
-    const float4 rv = sp_row4(rowp, c, lo);
-    float f[4];
     if constexpr (TAIL) {
       const uint32_t w = bm[(k0 >> 5) & 31] >> (k0 & 31);
       f[0] = (w & 1u) ? 0.0f : 1.0f; f[1] = (w & 2u) ? 0.0f : 1.0f; f[2] = (w & 4u) ? 0.0f : 1.0f; f[3] = (w & 8u) ? 0.0f : 1.0f;
@@ -152,12 +188,27 @@ __device__ __forceinline__ int sparse_row_walk(const Src &rowp, const uint8_t *f
       const uint32_t ff = *reinterpret_cast<const uint32_t *>(flg + k0);          // four flag bytes (v_cvt_f32_ubyte0..3)
       f[0] = (float)(ff & 0xFFu); f[1] = (float)((ff >> 8) & 0xFFu); f[2] = (float)((ff >> 16) & 0xFFu); f[3] = (float)(ff >> 24);
     }
+  };
+  // one row: the loads of all chunks leave together (one memory round trip per draw: left to itself the scheduler, short of
+  // registers in the split-tour kernel, issued a chunk's load behind the sums of the chunk before)
+  typename std::conditional<std::is_same<Src, SpRowUT>::value, sp_u32x4, float4>::type raw[TE ? 1 : CHD];
+  if constexpr (!TE) {
+#pragma unroll
+    for (int c = 0; c < CHD; ++c) raw[c] = sp_row_ld(rowp, c, lo);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int c = 0; c < CHD; ++c) {
+    // (two rows: one chunk's vectors in flight at a time -- this draw is the rarest way and must not set the kernel's registers)
+    if constexpr (TE) __builtin_amdgcn_sched_barrier(0);
+    float4 rv;
+    if constexpr (TE) rv = sp_row4(rowp, c, lo); else rv = sp_row_val(rowp, raw[c]);
+    float f[4];
+    factors(c, f);
     acc = __builtin_fmaf(rv.x, f[0], acc); run[4 * c + 0] = acc;
     acc = __builtin_fmaf(rv.y, f[1], acc); run[4 * c + 1] = acc;
     acc = __builtin_fmaf(rv.z, f[2], acc); run[4 * c + 2] = acc;
     acc = __builtin_fmaf(rv.w, f[3], acc); run[4 * c + 3] = acc;
-    pos |= (rv.x * f[0] > 0.0f ? 1u : 0u) << (4 * c) | (rv.y * f[1] > 0.0f ? 2u : 0u) << (4 * c) |
-           (rv.z * f[2] > 0.0f ? 4u : 0u) << (4 * c) | (rv.w * f[3] > 0.0f ? 8u : 0u) << (4 * c);
   }
 #pragma unroll
   for (int j = NJ; j < 16; ++j) run[j] = __builtin_inff();
@@ -168,9 +219,9 @@ __device__ __forceinline__ int sparse_row_walk(const Src &rowp, const uint8_t *f
     const float S = readlane_f(incl, 63);
     if (!(S > 0.0f)) return -1;
     r = ur * S;
-    r = r > 0.0f ? r : 1.401298464e-45f;
+    r = fmaxf(r, 1.401298464e-45f);                      // (kept > 0; a NaN gives the denormal, as `r > 0 ? r : denormal` does)
   }
-  uint64_t m = __ballot(incl >= r && part > 0.0f);
+  uint64_t m = __builtin_amdgcn_fcmpf(incl, r, SP_FCMP_OGE) & __builtin_amdgcn_fcmpf(part, 0.0f, SP_FCMP_OGT);
   int L;
   if (m == 0) {
     if constexpr (!TAIL) return -1;
@@ -182,9 +233,22 @@ __device__ __forceinline__ int sparse_row_walk(const Src &rowp, const uint8_t *f
   }
   const float excl = L ? readlane_f(incl, L - 1) : 0.0f;
   const float thr = fmaxf(r - excl, 1.401298464e-45f);   // (> 0: a slot is reached only by a positive term)
-  const int cnt = count_below<NJ>(run, thr);
+  const int cnt = NJ == 8 ? sp_count_below8(run, thr) : count_below<NJ>(run, thr);
   int jsel = readlane_i(cnt, L);
-  if (jsel >= NJ) {                                      // no running sum reached thr: the lane's last positive entry
+  if (__builtin_expect(jsel >= NJ, 0)) {                 // no running sum reached thr: the lane's last positive entry
+    // slots with a positive term (a term can be absorbed by the running sum), from the same products formed again: row and
+    // flags are as they were (the choice is stored by the caller), and nothing of them lives through the draw for this branch
+    // (read again behind the barrier: merged with the first reads, 8 * CHD registers stayed live down to here)
+    asm volatile("" ::: "memory");
+    uint32_t pos = 0;
+#pragma unroll
+    for (int c = 0; c < CHD; ++c) {
+      const float4 rv = sp_row4(rowp, c, lo);
+      float f[4];
+      factors(c, f);
+      pos |= (rv.x * f[0] > 0.0f ? 1u : 0u) << (4 * c) | (rv.y * f[1] > 0.0f ? 2u : 0u) << (4 * c) |
+             (rv.z * f[2] > 0.0f ? 4u : 0u) << (4 * c) | (rv.w * f[3] > 0.0f ? 8u : 0u) << (4 * c);
+    }
     const uint32_t pl = (uint32_t)readlane_i((int)pos, L);
     jsel = pl ? 31 - __builtin_clz(pl) : 0;
   }
@@ -312,7 +376,7 @@ scan_sparse_kernel(const SampleParams p) {
   const uint32_t t16o = (uint32_t)((wave * APW + q) * FL + s);
 #define SP_T(t) (TG ? ((t) & 15) : (t))
   bool infeasible = false;
-  unsigned long long n_dense = 0, n_tail = 0, n_rej = 0;
+  unsigned n_dense = 0, n_tail = 0, n_rej = 0;             // (per wavefront: at most 2 * 4 * n)
   // LH: per-lane constants of the LDS row read (lanes past the live records read the empty record), the tail total's place
   uint32_t lh_rb = 0, lh_rbsel = 0, lh_loff = 0, lh_toff = 0;
   if constexpr (LH) {
@@ -477,7 +541,7 @@ scan_sparse_kernel(const SampleParams p) {
             const uint32_t gidg = (uint32_t)readlane_i((int)gid, gl);
             const uint8_t *flg = flag_mem + (wave * APW + g) * FLP;
             const auto rowp = SP_ROW_OF(pv);
-            n_dense += a0 + g < A ? 1ull : 0ull;
+            n_dense += a0 + g < A ? 1u : 0u;
             float dk = __builtin_inff();
             int di = 0x7fffffff;
 #pragma unroll
@@ -560,65 +624,84 @@ scan_sparse_kernel(const SampleParams p) {
             uint64_t any = first | (first >> 8);
             any |= any >> 4; any |= any >> 2; any |= any >> 1;
             uint64_t rare = ~any & 0x0001000100010001ull;
-            while (rare) {
+            // no live head candidate (H = 0, lane 15 of the ant holds H): the dense masked draw with this step's uniform.  The only
+            // rare way the k-sparse heuristic takes, late in the tour in every wavefront at once and often for several ants of a
+            // step: its loop comes first and carries nothing of the other ways; the rows' base is read once for the step's draws.
+            uint64_t dense = rare & (~__builtin_amdgcn_fcmpf(incl, 0.0f, SP_FCMP_OGT) >> 15);
+            rare &= ~dense;
+            if (dense) {
+              const auto rows = sp_rows_of<UT>(Pb, (sp_args_t)__builtin_amdgcn_kernarg_segment_ptr(), b, p.ld);
+              // (counted for the step at once: the wavefront's first min(4, A - a0) groups are ants, a spare group repeats ant A-1)
+              n_dense += (unsigned)__builtin_popcountll(dense & (~0ull >> (64 - 16 * (A - a0 < APW ? A - a0 : APW))));
+              do {
+                const int gl = __builtin_ctzll(dense);        // lane 0 of the group
+                dense &= dense - 1;
+                const int g = gl >> 4;
+                const int pv = readlane_i(prev, gl);
+                const float ug = readlane_f(ucur, gl);        // (ucur: already rotated, lane 0 holds this step's)
+                int choice_g = sparse_row_walk<CHD, false>(sp_row_at(rows, pv, n), flag_mem + (wave * APW + g) * FLP, nullptr, lane, ug);
+                if (choice_g < 0) { infeasible = true; choice_g = 0; }
+                if (lane == gl) { fl[choice_g] = 0; tour[SP_T(t)] = (uint16_t)choice_g; }
+              } while (dense);
+            }
+            while (__builtin_expect(rare != 0, 0)) {            // r past a live head: the tail walk
               const int gl = __builtin_ctzll(rare);           // lane 0 of the group
               rare &= rare - 1;
+              // (the id words taken anew: what the bitmap below derives from them is formed here, per walk, and holds no registers
+              // over the draws above -- hoisted in front of this loop it spilled into scratch memory in the split-tour kernel)
+              if constexpr (SPL == 8) asm volatile("" : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3));
+              else asm volatile("" : "+v"(w0), "+v"(w1));
               const int g = gl >> 4;
               const int pv = readlane_i(prev, gl);
               const float Hg = readlane_f(incl, gl + 15);
-              const float ug = readlane_f(ucur, gl), rg = readlane_f(r, gl);     // (ucur: already rotated, lane 0 holds this step's)
+              const float rg = readlane_f(r, gl);
               const uint32_t gidg = (uint32_t)readlane_i((int)gid, gl);
               const uint8_t *flg = flag_mem + (wave * APW + g) * FLP;
               const auto rowp = SP_ROW_OF(pv);
               int choice_g = -1;
-              const unsigned long long real = a0 + g < A ? 1ull : 0ull;      // (a spare group repeats ant A-1: not counted)
-              if (!(Hg > 0.0f)) {                               // no live head candidate: the dense masked draw with this uniform
-                n_dense += real;
-                choice_g = sparse_row_walk<CHD, false>(rowp, flg, nullptr, lane, ug);
-              } else {
-                n_tail += real;
-                // the head's nodes as a bitmap, from the ids the ant's own lanes hold (an empty slot holds an id >= n)
-                if (lane < 32) bm_s[wave][lane] = 0u;
-                asm volatile("" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-                if (q == g) {
+              const unsigned real = a0 + g < A ? 1u : 0u;      // (a spare group repeats ant A-1: not counted)
+              n_tail += real;
+              // the head's nodes as a bitmap, from the ids the ant's own lanes hold (an empty slot holds an id >= n)
+              if (lane < 32) bm_s[wave][lane] = 0u;
+              asm volatile("" ::: "memory");
+              __builtin_amdgcn_wave_barrier();
+              if (q == g) {
 #pragma unroll
-                  for (int v = 0; v < SPL; ++v) {
-                    const int idl = SP_ID(v);
-                    if (idl < n) atomicOr(&bm_s[wave][idl >> 5], 1u << (idl & 31));
-                  }
+                for (int v = 0; v < SPL; ++v) {
+                  const int idl = SP_ID(v);
+                  if (idl < n) atomicOr(&bm_s[wave][idl >> 5], 1u << (idl & 31));
                 }
-                asm volatile("" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-                float rp = rg - Hg;
-                rp = rp > 0.0f ? rp : 1.401298464e-45f;
-                const int j = sparse_row_walk<CHD, true>(rowp, flg, bm_s[wave], lane, rp);
-                if (j < 0) {                                    // a tail without mass: the head's last live candidate
-                  const bool live_lane = q == g && run[LAST] > 0.0f;
-                  const uint64_t ml = __ballot(live_lane);
-                  if (ml != 0) {
-                    const int Ll = 63 - __builtin_clzll(ml);
-                    int lastp;
-                    SP_LAST_POSITIVE(lastp);
-                    choice_g = readlane_i(lastp, Ll);
-                  }
-                } else if (flg[j] != 0) {                       // open: accepted
-                  choice_g = j;
+              }
+              asm volatile("" ::: "memory");
+              __builtin_amdgcn_wave_barrier();
+              float rp = rg - Hg;
+              rp = rp > 0.0f ? rp : 1.401298464e-45f;
+              const int j = sparse_row_walk<CHD, true>(rowp, flg, bm_s[wave], lane, rp);
+              if (j < 0) {                                    // a tail without mass: the head's last live candidate
+                const bool live_lane = q == g && run[LAST] > 0.0f;
+                const uint64_t ml = __ballot(live_lane);
+                if (ml != 0) {
+                  const int Ll = 63 - __builtin_clzll(ml);
+                  int lastp;
+                  SP_LAST_POSITIVE(lastp);
+                  choice_g = readlane_i(lastp, Ll);
+                }
+              } else if (flg[j] != 0) {                       // open: accepted
+                choice_g = j;
+              } else {
+                // visited: ONE more draw, the dense masked draw over all open candidates with the step's second uniform --
+                // x then has probability p_x / (H + T) + (T_visited / (H + T)) p_x / (H + T_open) = p_x / (H + T_open)
+                n_rej += real;
+                n_dense += real;
+                const u32x4 rb = rng_block(p.seed, iter_now, STREAM_SPARSE_RETRY, gidg, (uint32_t)t << 8);
+                if constexpr (UT) {
+                  // (eta is read from the kernel-argument segment here: not a pair of registers carried through the tour)
+                  sp_args_t pr_ = (sp_args_t)__builtin_amdgcn_kernarg_segment_ptr();
+                  asm volatile("" : "+s"(pr_));
+                  const SpRowTE rowe{rowp.t, sp_row_rsrc(pr_->eta + (size_t)b * pr_->eta_bs + (size_t)pv * n, n)};
+                  choice_g = sparse_row_walk<CHD, false>(rowe, flg, nullptr, lane, u01(rb.x));
                 } else {
-                  // visited: ONE more draw, the dense masked draw over all open candidates with the step's second uniform --
-                  // x then has probability p_x / (H + T) + (T_visited / (H + T)) p_x / (H + T_open) = p_x / (H + T_open)
-                  n_rej += real;
-                  n_dense += real;
-                  const u32x4 rb = rng_block(p.seed, iter_now, STREAM_SPARSE_RETRY, gidg, (uint32_t)t << 8);
-                  if constexpr (UT) {
-                    // (eta is read from the kernel-argument segment here: not a pair of registers carried through the tour)
-                    sp_args_t pr_ = (sp_args_t)__builtin_amdgcn_kernarg_segment_ptr();
-                    asm volatile("" : "+s"(pr_));
-                    const SpRowTE rowe{rowp.t, sp_row_rsrc(pr_->eta + (size_t)b * pr_->eta_bs + (size_t)pv * n, n)};
-                    choice_g = sparse_row_walk<CHD, false>(rowe, flg, nullptr, lane, u01(rb.x));
-                  } else {
-                    choice_g = sparse_row_walk<CHD, false>(rowp, flg, nullptr, lane, u01(rb.x));
-                  }
+                  choice_g = sparse_row_walk<CHD, false>(rowp, flg, nullptr, lane, u01(rb.x));
                 }
               }
               if (choice_g < 0) { infeasible = true; choice_g = 0; }
@@ -661,7 +744,7 @@ scan_sparse_kernel(const SampleParams p) {
   // lanes 63 -> 65, the reloads in the rare-way block and none in the step: profiles/tour_epilogue_once.txt part B)
   if (infeasible && SP_E(flags) && lane == 0) atomicOr(SP_E(flags) + b, 1);
   if (SP_E(stats) && lane == 0 && (n_dense | n_tail | n_rej)) {
-    atomicAdd(SP_E(stats) + 0, n_dense); atomicAdd(SP_E(stats) + 1, n_tail); atomicAdd(SP_E(stats) + 2, n_rej);
+    atomicAdd(SP_E(stats) + 0, (unsigned long long)n_dense); atomicAdd(SP_E(stats) + 1, (unsigned long long)n_tail); atomicAdd(SP_E(stats) + 2, (unsigned long long)n_rej);
   }
 
   // ------------------------------------------------------------------ epilogue: the workgroup's 16 tours leave

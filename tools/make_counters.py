@@ -23,10 +23,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 # workload directory -> (kernel substring, key in counters.json / hbm_traffic.json)
-# (scan_sparse_kernel<CHD, RACE, SPL, LH, ST>: the headline launch is the split-tour variant)
+# (scan_sparse_kernel<CHD, RACE, SPL, LH, ST, UT>: the headline launch is the split-tour variant in the uniform-tail mode; its passes
+# come from the colony's own loop: tools/profile.sh <tag> scan_sparse pmc -- python bench.py --no-cpu --no-extras --min-seconds 0
+# --steps 5 --precondition-seconds 0)
 WORKLOADS = {
     "headline": ("tsp_scan32_kernel", "tsp500_a512_b64_scan"),
-    "scan_sparse": ("scan_sparse_kernel<2, false, 4, false, true>", "tsp500_a512_b64_scan_sparse"),
+    "scan_sparse": ("scan_sparse_kernel<2, false, 4, false, true, true>", "tsp500_a512_b64_scan_sparse"),
     "c5_sparse": ("scan_sparse_kernel<4, false, 8, false, false>", "tsp1000_a2048_b64_scan_sparse"),
     "b1_lds_heads": ("scan_sparse_kernel<2, false, 4, true, false>", "tsp500_a512_b1_scan_sparse"),
     "deposit_heads": ("deposit_rows_kernel<true, 1, true>", "tsp500_a512_b64_update_heads"),
