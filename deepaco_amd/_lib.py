@@ -64,6 +64,11 @@ SIGNATURES = {
     "daco_gnn_train_backward_ragged": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
                                             _sz]),
     "daco_cvrp_local_search": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _f, _vp, _i, _vp, _vp]),
+    # (long statuses, as daco_rcpsp_net_forward)
+    "daco_cvrp_reinsert": (_l, [_vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _vp]),
+    "daco_cvrp_n1_move": (_l, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _f, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f,
+                               _vp]),
+    "daco_cvrp_adaptive_update": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "daco_hgs_table_bytes": (_sz, [_i, _i]),
     "daco_hgs_prepare": (_i, [_vp, _i, _i, _vp, _l, _i, _vp]),
     "daco_hgs_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),

@@ -1,0 +1,445 @@
+// daco_cvrp_adaptive.hip -- the three phases of the "adaptive elitist AS" that shares the reference's cvrp/aco.py (lines 207-383):
+//   improvement_phase      -> cvrp_reinsert_kernel   (cheapest-insertion rebuild of the selected ants' subroutes)
+//   intensification_phase  -> cvrp_n1_kernel         (the record of run(), :81-93, and the N1 relocation on a new record)
+//   update_pheronome / diversification_phase / the elite pool -> cvrp_adaptive_update_kernel (per instance, one of the two)
+// Restated in plain Python in tests/cvrp_adaptive_spec.py, which tests/golden/a1_*.npz pin on the reference itself.
+//
+// Arithmetic: an insertion's added length is
+// (d[p1][c] + d[c][p2]) - d[p1][p2] in float32, two roundings, no contraction (the Makefile's -ffp-contract=off); the minimum
+// over positions takes the smallest position among equals (the reference's min over (cost, i) tuples); a subroute's cost is the
+// double sum of its float32 deltas in insertion order, an ant's the double sum of those in subroute order.
+//
+// Lane mapping.  A wavefront owns one ant (reinsertion) or one instance (N1); the route under construction lives in LDS as u16
+// node ids and the 64 lanes take 64 consecutive insertion positions at a time: three gathers from the distance matrix per lane,
+// one (key, index) DPP reduction (daco_device.h wave_arg, ties to the smaller index), and a running minimum across the chunks
+// of 64 that is replaced on strict < only, so that a tie between two chunks keeps the earlier one.  A CVRP route under capacity
+// 50 holds about ten customers, so most lanes of a scan idle; the phases are a chain of gather latencies either way, and what a
+// block gains instead is one wavefront per selected ant, all of an instance's ants in flight at once.
+#include "daco_host.h"
+
+namespace daco {
+
+constexpr uint32_t STREAM_N1 = 4;            // the N1 draws' own stream of the counter-based generator (daco_device.h rng_block)
+constexpr int AD_POOL = 5;                   // pool_size of cvrp/aco.py:99
+constexpr int AD_TOPK = 5;                   // the literal 5 of cvrp/aco.py:342
+constexpr int AD_TRIALS = 5;                 // count = 5 of N1_neighbourhood
+
+// least added length of inserting c into rt[0 .. len-1] (len >= 2): the position i of the gap (rt[i], rt[i+1]) and its delta,
+// uniform over the wavefront
+__device__ inline KeyIdx best_gap(const float *d, int n, const uint16_t *rt, int len, int c, int lane) {
+  float bk = 0.0f;
+  int bi = -1;
+  for (int i0 = 0; i0 + 1 < len; i0 += 64) {
+    const int i = i0 + lane;
+    float k = __builtin_inff();
+    int id = 0x7fffffff;
+    if (i + 1 < len) {
+      const int p1 = rt[i], p2 = rt[i + 1];
+      const float s = d[(size_t)p1 * n + c] + d[(size_t)c * n + p2];
+      k = s - d[(size_t)p1 * n + p2];
+      id = i;
+    }
+    const KeyIdx r = wave_arg<false>(k, id);
+    if (bi < 0 || r.key < bk) { bk = r.key; bi = r.idx == 0x7fffffff ? i0 : r.idx; }   // (a chunk of NaN only: its first position)
+  }
+  return KeyIdx{bk, bi};
+}
+
+// first minimum of costs[0 .. A-1] (torch.min(dim=0)), uniform over the wavefront
+__device__ inline KeyIdx first_min(const float *costs, int A, int lane) {
+  float bk = __builtin_inff();
+  int bi = 0x7fffffff;
+  for (int a = lane; a < A; a += 64) {
+    const float c = costs[a];
+    if (c < bk) { bk = c; bi = a; }
+  }
+  KeyIdx r = wave_arg<false>(bk, bi);
+  if (r.idx == 0x7fffffff) r.idx = 0;
+  return r;
+}
+
+// ------------------------------------------------------------------ improvement_phase (cvrp/aco.py:336-357)
+// One workgroup per instance, NW wavefronts.  Wavefront 0 selects (all ants, or the AD_TOPK cheapest: AD_TOPK rounds of a
+// (cost, id) minimum over the ants not yet taken, so equal costs go to the smaller ant id), then wavefront w rebuilds the
+// selected ants w, w + NW, ...  LDS per wavefront: out[Lmax] u16, the ant's column, rewritten subroute by subroute | rt[n + 1]
+// u16, the subroute under construction.  The column goes back to global memory, with its cost and length, only if accepted.
+__global__ void __launch_bounds__(512)
+cvrp_reinsert_kernel(int n, int A, int Lmax, int K, const float *dist, long dist_bs, int64_t *paths, float *costs, int32_t *lens,
+                     int32_t *selected, int rt_ld) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t ad_lds[];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, NW = blockDim.x >> 6;
+  const float *d = dist + (size_t)b * dist_bs;
+  float *cb = costs + (size_t)b * A;
+  int32_t *sel = selected + (size_t)b * K;
+  if (wave == 0) {
+    if (K == A) {
+      for (int a = lane; a < A; a += 64) sel[a] = a;
+    } else {
+      uint64_t taken_lo = 0;                 // this lane's ants already selected: bit j = ant lane + 64 j, j < 64 (A <= 4096)
+      for (int r = 0; r < K; ++r) {
+        float bk = __builtin_inff();
+        int bi = 0x7fffffff;
+        for (int a = lane, j = 0; a < A; a += 64, ++j) {
+          if (j < 64 && ((taken_lo >> j) & 1)) continue;
+          const float c = cb[a];
+          if (c < bk || (c == bk && a < bi) || bi == 0x7fffffff) { bk = c; bi = a; }
+        }
+        const KeyIdx m = wave_arg<false>(bk, bi);
+        if ((m.idx & 63) == lane && m.idx != 0x7fffffff) taken_lo |= 1ull << (m.idx >> 6);
+        if (lane == 0) sel[r] = m.idx;
+      }
+    }
+    __threadfence_block();
+  }
+  __syncthreads();
+  uint16_t *out = ad_lds + (size_t)wave * rt_ld;
+  uint16_t *rt = out + Lmax;
+  for (int r = wave; r < K; r += NW) {
+    const int a = sel[r];
+    int64_t *p = paths + (size_t)b * Lmax * A + a;
+    int last = -1;                                          // the column's last customer
+    for (int k0 = 0; k0 < Lmax; k0 += 64) {
+      const int k = k0 + lane;
+      const int v = k < Lmax ? (int)p[(size_t)k * A] : 0;
+      if (k < Lmax) out[k] = (uint16_t)v;
+      const uint64_t nz = __ballot(v != 0);
+      if (nz) last = k0 + 63 - __builtin_clzll(nz);
+    }
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    // the depots up to the one that closes the last subroute, in order; (start, j): two consecutive ones
+    double total = 0.0;
+    int start = -1, w = 0;                                  // w: entries of the rebuilt column written so far
+    const int end = last + 2 <= Lmax ? last + 2 : Lmax;     // (a column whose last row is a customer: that open tail is no subroute, :209-217)
+    for (int k0 = 0; k0 < end; k0 += 64) {
+      const int k = k0 + lane;
+      uint64_t zero = __ballot(k < end && out[k] == 0);
+      while (zero) {
+        const int j = k0 + __builtin_ctzll(zero);
+        zero &= zero - 1;
+        if (start >= 0 && j - start > 1) {
+          // rebuild out[start + 1 .. j - 1] from [0, 0], customers in their order in the path
+          const int m = min(j - start - 1, n - 1);          // (n - 1 customers at the most: rt holds n + 1 entries)
+          if (lane == 0) { rt[0] = 0; rt[1] = 0; }
+          __builtin_amdgcn_wave_barrier();
+          __threadfence_block();
+          double sub = 0.0;
+          for (int t = 0; t < m; ++t) {
+            const int c = out[start + 1 + t], len = t + 2;
+            const KeyIdx g = best_gap(d, n, rt, len, c, lane);
+            sub += (double)g.key;
+            // rt[g.idx + 1 .. len - 1] move up by one, from the tail, 64 at a time; c takes rt[g.idx + 1]
+            for (int hi = len - 1; hi > g.idx; hi -= 64) {
+              const int i = hi - lane;
+              const int v = i > g.idx ? rt[i] : 0;
+              __builtin_amdgcn_wave_barrier();
+              if (i > g.idx) rt[i + 1] = (uint16_t)v;
+              __builtin_amdgcn_wave_barrier();
+              __threadfence_block();
+            }
+            if (lane == 0) rt[g.idx + 1] = (uint16_t)c;
+            __builtin_amdgcn_wave_barrier();
+            __threadfence_block();
+          }
+          total += sub;
+          // merge_subroutes (:240-251): the subroute without its closing depot, packed (w <= start: its source is consumed)
+          for (int i = lane; i <= m; i += 64) out[w + i] = rt[i];
+          w += m + 1;
+          __builtin_amdgcn_wave_barrier();
+          __threadfence_block();
+        }
+        start = j;
+      }
+    }
+    // `if new_cost < costs[i]` (:355): torch compares in float32, and stores the float32 rounding
+    const float nc = (float)total;
+    if (nc < cb[a]) {
+      for (int k = lane; k < Lmax; k += 64) p[(size_t)k * A] = k < w ? (int64_t)out[k] : 0;
+      if (lane == 0) {
+        cb[a] = nc;
+        if (lens) lens[(size_t)b * A + a] = w + 1 <= Lmax ? w + 1 : Lmax;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// ------------------------------------------------------------------ the record and intensification_phase (cvrp/aco.py:81-93, 254-286, 359-376)
+// a draw of random.randint(lo, hi) from a uniform u in [0, 1): lo + min(floor(u * (hi - lo + 1)), hi - lo), the product in float32
+__device__ inline int draw_int(float u, int lo, int hi) {
+  const int span = hi - lo;
+  int k = (int)floorf(u * (float)(span + 1));
+  k = k < span ? k : span;
+  return lo + (k < 0 ? 0 : k);
+}
+
+// One wavefront per instance.  LDS: rt[Lmax] u16 the record's route | sstart[n] u16 row of each subroute's opening depot |
+// scnt[n] u16 its customers | load[n] f32 its demand, summed in float32 in route order.
+__global__ void __launch_bounds__(64)
+cvrp_n1_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, const float *demand, float capacity, const float *noise,
+               uint64_t seed, uint64_t iter, uint32_t inst_gid0, int64_t *paths, float *costs, int32_t *lens, float *lowest,
+               int64_t *shortest, int32_t *improved, int track, float *mmas_max, float mmas_scale, int32_t *moved, int n_ld) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t ad_lds[];
+  uint16_t *rt = ad_lds, *sstart = rt + ((Lmax + 1) & ~1), *scnt = sstart + n_ld;
+  float *load = (float *)(scnt + n_ld);
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float *d = dist + (size_t)b * dist_bs, *dem = demand + (size_t)b * n;
+  float *cb = costs + (size_t)b * A;
+  int64_t *sp = shortest + (size_t)b * Lmax;
+  const KeyIdx best = first_min(cb, A, lane);
+  float low = lowest[b];
+  int imp;
+  if (track) {                                              // `if best_cost < self.lowest_cost` (:83-85)
+    imp = best.key < low;
+    if (imp) {
+      low = best.key;
+      for (int k = lane; k < Lmax; k += 64) sp[k] = paths[((size_t)b * Lmax + k) * A + best.idx];
+    }
+    if (lane == 0) improved[b] = imp;
+  } else {
+    imp = improved[b] != 0;
+  }
+  int did = 0;
+  if (imp) {
+    int last = -1;
+    for (int k0 = 0; k0 < Lmax; k0 += 64) {
+      const int k = k0 + lane;
+      const int v = k < Lmax ? (int)(track ? paths[((size_t)b * Lmax + k) * A + best.idx] : sp[k]) : 0;
+      if (k < Lmax) rt[k] = (uint16_t)v;
+      const uint64_t nz = __ballot(v != 0);
+      if (nz) last = k0 + 63 - __builtin_clzll(nz);
+    }
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    // get_subroutes(end_with_zero=True): (start, j) consecutive depots with a customer between them
+    int S = 0, start = -1;
+    const int end = last + 2 <= Lmax ? last + 2 : Lmax;
+    for (int k0 = 0; k0 < end; k0 += 64) {
+      const int k = k0 + lane;
+      uint64_t zero = __ballot(k < end && rt[k] == 0);
+      while (zero) {
+        const int j = k0 + __builtin_ctzll(zero);
+        zero &= zero - 1;
+        if (start >= 0 && j - start > 1) {
+          if (S < n) {                                      // (a route of valid node ids has fewer subroutes than nodes)
+            if (lane == 0) { sstart[S] = (uint16_t)start; scnt[S] = (uint16_t)min(j - start - 1, n - 1); }
+            ++S;
+          }
+        }
+        start = j;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    for (int s = lane; s < S; s += 64) {                    // self.demand[r].sum() per subroute (:363)
+      float x = 0.0f;
+      const int s0 = sstart[s], m = scnt[s];
+      for (int t = 1; t <= m; ++t) x = x + dem[rt[s0 + t]];
+      load[s] = x;
+    }
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    // best_insertion = (None, 0.0): source subroute, node index in it, target subroute, index in the target the node goes before
+    float bdelta = 0.0f;
+    int bs = -1, bni = 0, bt = 0, bpos = 0;
+    for (int t = 0; t < AD_TRIALS && S > 0; ++t) {
+      float u0, u1;
+      if (noise) {
+        u0 = noise[((size_t)b * AD_TRIALS + t) * 2];
+        u1 = noise[((size_t)b * AD_TRIALS + t) * 2 + 1];
+      } else {
+        const u32x4 r = rng_block(seed, iter, STREAM_N1, inst_gid0 + (uint32_t)b, (uint32_t)t);
+        u0 = u01(r.x);
+        u1 = u01(r.y);
+      }
+      const int si = draw_int(u0, 0, S - 1);
+      const int s0 = sstart[si], m = scnt[si];
+      const int ni = draw_int(u1, 1, m);
+      const int pred = rt[s0 + ni - 1], node = rt[s0 + ni], next = rt[s0 + ni + 1];
+      const float dn = dem[node];
+      const float g0 = d[(size_t)pred * n + next] - d[(size_t)pred * n + node];
+      const float gain = g0 - d[(size_t)node * n + next];
+      for (int i = 0; i < S; ++i) {
+        if (i == si || !(load[i] + dn <= capacity)) continue;
+        const KeyIdx g = best_gap(d, n, rt + sstart[i], (int)scnt[i] + 2, node, lane);
+        const float cand = g.key + gain;
+        if (cand < bdelta) { bdelta = cand; bs = si; bni = ni; bt = i; bpos = g.idx + 1; }
+      }
+    }
+    if (bs >= 0) {
+      // the move on the packed route: the node at row prm leaves (with its subroute's opening depot if it was alone) and
+      // enters before the element at row pins; every other element keeps its order
+      did = 1;
+      const int s0 = sstart[bs], vanish = scnt[bs] == 1, prm = s0 + bni, pins = sstart[bt] + bpos;
+      const int node = rt[prm];
+      const int used = end - vanish;                        // rows of the new route, its closing depot included
+      const int bi = best.idx;
+      for (int k = lane; k < Lmax; k += 64) {
+        if (k >= used) {
+          sp[k] = 0;
+          paths[((size_t)b * Lmax + k) * A + bi] = 0;
+        }
+      }
+      for (int k = lane; k < end; k += 64) {
+        if (k == prm || (vanish && k == s0)) continue;
+        const int to = k - (k > prm ? 1 : 0) - (vanish && k > s0 ? 1 : 0) + (k >= pins ? 1 : 0);
+        sp[to] = rt[k];
+        paths[((size_t)b * Lmax + to) * A + bi] = rt[k];
+      }
+      low = low + bdelta;                                   // self.lowest_cost = ogcost + best_neighbour[1] (:374)
+      if (lane == 0) {
+        const int to = pins - (prm < pins ? 1 : 0) - (vanish && s0 < pins ? 1 : 0);
+        sp[to] = node;
+        paths[((size_t)b * Lmax + to) * A + bi] = node;
+        cb[bi] = low;
+        if (lens) lens[(size_t)b * A + bi] = used;
+      }
+    }
+    if (lane == 0) lowest[b] = low;
+  }
+  if (lane == 0) {
+    if (mmas_max) mmas_max[b] = (1.0f / low) * mmas_scale;  // n / lowest_cost as rtruediv computes it (daco_track_best)
+    if (moved) moved[b] = did;
+  }
+}
+
+// ------------------------------------------------------------------ update_pheronome | diversification_phase, and the pool
+// A workgroup owns R rows of one instance's tau.  It reads the routes whose edges are deposited -- the best ant's column for an
+// improved instance, the pool's entries from the front for the others --, keeps for each route the successor of each of its
+// rows' customers (a customer is left once per route) and, if it owns the depot's row, the SET of the depot's successors as a
+// bitmap (so the padding's depot-to-depot edge counts once, like every duplicate of an index pair in the reference's
+// `tau[u, v] += w`), and then walks its elements once: x = tau * f (+ 0.01), + w per route that holds the edge, in pool order.
+// The workgroup of an improved instance's first slab also pushes (shortest, lowest) to the front of that instance's pool; no
+// other workgroup of an improved instance reads the pool.
+constexpr int AD_ROWS = 64;
+__global__ void __launch_bounds__(256)
+cvrp_adaptive_update_kernel(int n, int A, int Lmax, int R, float *tau, const int64_t *paths, const float *costs, const int32_t *improved,
+                            float decay, const float *clamp_min, const float *clamp_max, float floor_val, const int64_t *shortest,
+                            const float *lowest, int64_t *pool_routes, float *pool_costs, int32_t *pool_state) {
+  __shared__ int nxt[AD_POOL][AD_ROWS];
+  __shared__ uint32_t hubm[AD_POOL][(DACO_MAX_NODES + 31) / 32];
+  __shared__ float wts[AD_POOL];
+  __shared__ int best_s;
+  const int bpi = (n + R - 1) / R;
+  const int b = blockIdx.x / bpi, i0 = (blockIdx.x - b * bpi) * R, Rv = min(R, n - i0);
+  const int tid = threadIdx.x, W = (n + 31) / 32;
+  const int imp = improved[b] != 0;
+  const int count = min(max(pool_state[2 * b], 0), AD_POOL), front = ((pool_state[2 * b + 1] % AD_POOL) + AD_POOL) % AD_POOL;
+  const int routes = imp ? 1 : count;
+  for (int i = tid; i < AD_POOL * AD_ROWS; i += 256) (&nxt[0][0])[i] = -1;
+  for (int i = tid; i < routes * W; i += 256) hubm[i / W][i % W] = 0u;
+  if (imp && tid < 64) {
+    const KeyIdx m = first_min(costs + (size_t)b * A, A, tid);
+    if (tid == 0) { best_s = m.idx; wts[0] = 1.0f / m.key; }
+  }
+  if (!imp && tid < count) wts[tid] = 1.0f / pool_costs[(size_t)b * AD_POOL + (front + tid) % AD_POOL];
+  __syncthreads();
+  for (int r = 0; r < routes; ++r) {
+    const int64_t *p;
+    long stride;
+    if (imp) { p = paths + (size_t)b * Lmax * A + best_s; stride = A; }
+    else { p = pool_routes + ((size_t)b * AD_POOL + (front + r) % AD_POOL) * Lmax; stride = 1; }
+    for (int k = tid; k + 1 < Lmax; k += 256) {
+      const int u = (int)p[(size_t)k * stride], v = (int)p[(size_t)(k + 1) * stride];
+      if (u == 0) { if (i0 == 0) atomicOr(&hubm[r][v >> 5], 1u << (v & 31)); }
+      else if (u >= i0 && u < i0 + Rv) nxt[r][u - i0] = v;
+    }
+  }
+  __syncthreads();
+  const bool clamp = imp && clamp_max != nullptr;
+  const float cmin = clamp ? clamp_min[b] : 0.0f, cmax = clamp ? clamp_max[b] : 0.0f;
+  const float f = imp ? decay : decay * 0.5f;               // (decay * 0.5 rounded once: halving a float32 is exact)
+  float *g = tau + ((size_t)b * n + i0) * n;
+  for (int e = tid; e < Rv * n; e += 256) {
+    const int r_ = e / n, j = e - r_ * n, i = i0 + r_;
+    float x = g[e] * f;
+    if (!imp) x = x + 0.01f;
+    for (int r = 0; r < routes; ++r) {
+      const bool hit = i == 0 ? ((hubm[r][j >> 5] >> (j & 31)) & 1u) != 0 : nxt[r][r_] == j;
+      if (hit) x = x + wts[r];
+    }
+    if (imp) {
+      if (clamp) { x = x < cmin ? cmin : x; x = x > cmax ? cmax : x; }
+      if (floor_val > 0.0f) x = x < floor_val ? floor_val : x;
+    }
+    g[e] = x;
+  }
+  if (imp && i0 == 0) {                                     // self.elite_pool.insert(0, ...); del self.elite_pool[5:] (:98-100)
+    const int nf = (front + AD_POOL - 1) % AD_POOL;
+    int64_t *q = pool_routes + ((size_t)b * AD_POOL + nf) * Lmax;
+    for (int k = tid; k < Lmax; k += 256) q[k] = shortest[(size_t)b * Lmax + k];
+    if (tid == 0) {
+      pool_costs[(size_t)b * AD_POOL + nf] = lowest[b];
+      pool_state[2 * b] = count < AD_POOL ? count + 1 : AD_POOL;
+      pool_state[2 * b + 1] = nf;
+    }
+  }
+}
+
+}  // namespace daco
+
+using namespace daco;
+
+static bool adaptive_sizes_ok(const char *what, int n, int Lmax) {
+  if (n > DACO_MAX_NODES) { set_error("%s: n=%d exceeds DACO_MAX_NODES", what, n); return false; }
+  if (Lmax > 4 * DACO_MAX_NODES) { set_error("%s: Lmax=%d exceeds 4 * DACO_MAX_NODES", what, Lmax); return false; }
+  return true;
+}
+
+extern "C" long daco_cvrp_reinsert(void *stream, int B, int n, int A, int Lmax, int topk, const float *dist, long dist_bstride,
+                                   int64_t *paths, float *costs, int32_t *lens, int32_t *selected) {
+  if (B <= 0 || n < 2 || A <= 0 || Lmax < 2 || !dist || !paths || !costs || !selected || dist_bstride < 0) {
+    set_error("daco_cvrp_reinsert: bad argument (B=%d n=%d A=%d Lmax=%d)", B, n, A, Lmax);
+    return DACO_E_BADARG;
+  }
+  const bool all = topk <= 0 || topk >= A;
+  if (!all && A < AD_TOPK) { set_error("daco_cvrp_reinsert: topk=%d selects the %d cheapest of A=%d ants", topk, AD_TOPK, A); return DACO_E_BADARG; }
+  if (!adaptive_sizes_ok("daco_cvrp_reinsert", n, Lmax)) return DACO_E_TOOLARGE;
+  if (A > 4096) { set_error("daco_cvrp_reinsert: A=%d ants is above 4096", A); return DACO_E_TOOLARGE; }
+  const int K = all ? A : AD_TOPK;
+  const int rt_ld = (Lmax + n + 1 + 7) & ~7;               // u16 entries per wavefront
+  int NW = (int)((64 * 1024) / ((size_t)rt_ld * sizeof(uint16_t)));
+  if (NW > 8) NW = 8;
+  if (NW > K) NW = K;
+  if (NW < 1) NW = 1;
+  const size_t lds = (size_t)NW * rt_ld * sizeof(uint16_t);
+  hipLaunchKernelGGL(cvrp_reinsert_kernel, dim3(B), dim3(64 * NW), lds, (hipStream_t)stream, n, A, Lmax, K, dist, dist_bstride, paths,
+                     costs, lens, selected, rt_ld);
+  return launch_status("cvrp_reinsert_kernel");
+}
+
+extern "C" long daco_cvrp_n1_move(void *stream, int B, int n, int A, int Lmax, const float *dist, long dist_bstride, const float *demand,
+                                  float capacity, const float *noise, uint64_t seed, uint64_t iter, uint32_t inst_gid0, int64_t *paths,
+                                  float *costs, int32_t *lens, float *lowest, int64_t *shortest, int32_t *improved, int track,
+                                  float *mmas_max, float mmas_scale, int32_t *moved) {
+  if (B <= 0 || n < 2 || A <= 0 || Lmax < 2 || !dist || !demand || !paths || !costs || !lowest || !shortest || !improved || dist_bstride < 0) {
+    set_error("daco_cvrp_n1_move: bad argument (B=%d n=%d A=%d Lmax=%d)", B, n, A, Lmax);
+    return DACO_E_BADARG;
+  }
+  if (!adaptive_sizes_ok("daco_cvrp_n1_move", n, Lmax)) return DACO_E_TOOLARGE;
+  const int n_ld = (n + 1) & ~1;
+  const size_t lds = ((size_t)((Lmax + 1) & ~1) + 2 * (size_t)n_ld) * sizeof(uint16_t) + (size_t)n_ld * sizeof(float);
+  hipLaunchKernelGGL(cvrp_n1_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, n, A, Lmax, dist, dist_bstride, demand, capacity, noise,
+                     seed, iter, inst_gid0, paths, costs, lens, lowest, shortest, improved, track, mmas_max, mmas_scale, moved, n_ld);
+  return launch_status("cvrp_n1_kernel");
+}
+
+extern "C" long daco_cvrp_adaptive_update(void *stream, int B, int n, int A, int Lmax, float *tau, const int64_t *paths, const float *costs,
+                                          const int32_t *improved, float decay, const float *clamp_min, const float *clamp_max,
+                                          float floor_val, const int64_t *shortest, const float *lowest, int64_t *pool_routes,
+                                          float *pool_costs, int32_t *pool_state) {
+  if (B <= 0 || n < 2 || A <= 0 || Lmax < 2 || !tau || !paths || !costs || !improved || !shortest || !lowest || !pool_routes || !pool_costs ||
+      !pool_state) {
+    set_error("daco_cvrp_adaptive_update: bad argument (B=%d n=%d A=%d Lmax=%d)", B, n, A, Lmax);
+    return DACO_E_BADARG;
+  }
+  if ((clamp_min == nullptr) != (clamp_max == nullptr)) { set_error("daco_cvrp_adaptive_update: clamp_min/clamp_max must both be given"); return DACO_E_BADARG; }
+  if (!adaptive_sizes_ok("daco_cvrp_adaptive_update", n, Lmax)) return DACO_E_TOOLARGE;
+  // rows per workgroup: as many as keep two workgroups per CU in the launch (daco_costs_update.hip rows_per_block), 64 at the most
+  int R = AD_ROWS;
+  while (R > 1 && (long)B * ((n + R - 1) / R) < 512) R = (R + 1) / 2;
+  const int bpi = (n + R - 1) / R;
+  hipLaunchKernelGGL(cvrp_adaptive_update_kernel, dim3(B * bpi), dim3(256), 0, (hipStream_t)stream, n, A, Lmax, R, tau, paths, costs, improved,
+                     decay, clamp_min, clamp_max, floor_val, shortest, lowest, pool_routes, pool_costs, pool_state);
+  return launch_status("cvrp_adaptive_update_kernel");
+}

@@ -6,7 +6,7 @@ cvrp/aco.py:9-205: `gen_path` returns `paths` of shape (L, n_ants) where L is th
 longest ant's route sequence (shorter ones are padded with the depot), `gen_path_costs` sums
 the open sequence, `update_pheronome` deposits on directed edges and floors at 1e-10.  The
 "adaptive elitist" baseline that shares the reference file (cvrp/aco.py:207-383, declared
-unrelated to DeepACO there) is out of scope: adaptive=True raises.
+unrelated to DeepACO there) is deepaco_amd.cvrp.adaptive.ACO; this constructor keeps refusing adaptive=True and says so.
 Extra keyword-only arguments `sampler`, `seed` as in deepaco_amd/tsp/aco.py.
 """
 import os
@@ -45,7 +45,8 @@ class ACO():
                  seed=None,
                  ):
         if adaptive:
-            raise NotImplementedError("the adaptive elitist baseline (cvrp/aco.py:207-383) is out of scope")
+            raise NotImplementedError("the adaptive elitist baseline (cvrp/aco.py:207-383) is deepaco_amd.cvrp.adaptive.ACO "
+                                      "(engine.BatchedCVRP(adaptive=True) for a batch); this class is the plain colony")
         # device='cpu' + host tensors (cvrp/test.py): staged to the HIP device, see engine.stage_to_hip
         distances = engine.stage_to_hip(distances)
         demand = engine.stage_to_hip(demand, distances)

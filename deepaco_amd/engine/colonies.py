@@ -2,6 +2,7 @@
 import torch
 
 from .common import _f32c, _raise_flags, _require_gpu, _rows
+from .cvrp_adaptive_ops import cvrp_adaptive_update_, cvrp_elite_pool, cvrp_elite_pool_list, cvrp_n1_move_, cvrp_reinsert_
 from .cvrp_ops import cvrp_sample
 from .local_search import HgsTables, TspLocalSearch, heuristic_dist, hgs_local_search_, hgs_polar_angles
 from .tsp_ops import dist_is_symmetric, head_eta_table, head_table, resolve_sampler, sparse_tours16, sparse_workspace, sparsify_heuristic, tsp_sample, tsp_sample_sparse
@@ -362,8 +363,13 @@ class BatchedCVRP:
 
     def __init__(self, distances, demand, n_ants=20, decay=0.9, alpha=1, beta=1, elitist=False, min_max=False,
                  pheromone=None, heuristic=None, min=None, capacity=50, sampler="scan", seed=None, ant_gid0=0,
-                 local_search=None, ls_ants=8, inference=False, positions=None, use_swap_star=False):
-        """local_search="hgs": the colony iteration of cvrp_nls/aco.py:134-171 (swapstar=True) for every instance -- the `ls_ants`
+                 local_search=None, ls_ants=8, inference=False, positions=None, use_swap_star=False, adaptive=False, topk=5):
+        """adaptive=True: the reference's "adaptive elitist AS" (cvrp/aco.py:72-104, 207-383; implies elitist): after the
+        construction, improvement_phase on the `topk` rule's ants (engine.cvrp_reinsert_), the record with the N1 relocation where
+        it improved (engine.cvrp_n1_move_, its draws keyed by (seed, iteration, ant_gid0 // n_ants + b)), and per instance the
+        elitist update with a push to `elite_pool`, or the diversification from that pool (engine.cvrp_adaptive_update_) -- four
+        launches, none of them waited for.  Not with local_search="hgs" (cvrp_nls's colony has no such phases): ValueError.
+        local_search="hgs": the colony iteration of cvrp_nls/aco.py:134-171 (swapstar=True) for every instance -- the `ls_ants`
         cheapest ants of each instance go through neural_swapstar (cvrp_nls/aco.py:143-146, 443-448; daco_hgs_local_search, the
         reference's routes) before best tracking and the deposit.  The local search reads `distances` and the heuristic in the
         dtype they are passed in (float64 instance data as cvrp_nls/utils.py builds it) and the demands as demand / capacity.
@@ -373,8 +379,13 @@ class BatchedCVRP:
             raise ValueError("BatchedCVRP: use_swap_star=True needs positions")
         if use_swap_star and local_search != "hgs":
             raise ValueError('BatchedCVRP: use_swap_star=True belongs to local_search="hgs"')
+        if adaptive and local_search == "hgs":
+            raise ValueError('BatchedCVRP: adaptive=True is the baseline of cvrp/aco.py and does not combine with local_search="hgs"')
         _require_gpu(distances, demand)
         assert local_search in (None, "hgs")
+        self.adaptive, self.topk = bool(adaptive), int(topk)
+        self._pool = None                       # (routes [B, 5, Lmax], costs [B, 5], state [B, 2]) once an adaptive step has run
+        self.last_improved = None               # [B] int32: which instances' records the last adaptive step improved
         self.local_search, self.ls_ants, self.inference = local_search, int(ls_ants), inference
         self.use_swap_star = bool(use_swap_star)
         self._hgs_pos = self._hgs_polar = None
@@ -390,7 +401,7 @@ class BatchedCVRP:
         # load bookkeeping of the construction in double
         self.demand = _rows(demand, self.B, torch.float64 if demand.dtype == torch.float64 else torch.float32)
         self.n_ants, self.decay, self.alpha, self.beta, self.capacity = n_ants, decay, alpha, beta, capacity
-        self.elitist, self.min_max = elitist, min_max
+        self.elitist, self.min_max = elitist or self.adaptive, min_max
         _init_pheromone(self, pheromone, min_max, min)
         self.heuristic = (1 / self.distances) if heuristic is None else heuristic
         self._own_heuristic = self.heuristic if heuristic is None else None        # (derived here from the f32 distances)
@@ -411,6 +422,8 @@ class BatchedCVRP:
 
     def _step(self, Lmax=None, trim=False, events=None):
         """step() without its no_grad context, for run()'s loop under its own (see BatchedTSP._step)."""
+        if self.adaptive:
+            return self._step_adaptive(Lmax, trim, events)
         paths, _, _, lens, flags, costs, table = cvrp_sample(
             self.pheromone, self.heuristic, self.demand, self.capacity, self.n_ants, self.alpha, self.beta,
             mode=self.sampler, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0, Lmax=Lmax, batch=self.B,
@@ -454,6 +467,42 @@ class BatchedCVRP:
         if trim:
             paths = paths[:, :int(lens.max())].contiguous()
         return paths, costs
+
+    def _step_adaptive(self, Lmax=None, trim=False, events=None):
+        """One iteration of the adaptive elitist colony (cvrp/aco.py:74-102) for every instance, without a host read: instances
+        whose record improved and instances whose record did not share each launch."""
+        paths, _, _, lens, flags, costs, _ = cvrp_sample(
+            self.pheromone, self.heuristic, self.demand, self.capacity, self.n_ants, self.alpha, self.beta,
+            mode=self.sampler, seed=self.seed, it=self.iteration, ant_gid0=self.ant_gid0, Lmax=Lmax, batch=self.B,
+            dist=self.distances, events=events, flags=self._flags)
+        it = self.iteration
+        self.iteration += 1
+        self.last_lens, self.last_flags = lens, flags
+        rows = paths.shape[1]
+        if self.shortest_path is None or self.shortest_path.shape[1] != rows:
+            old = self.shortest_path
+            self.shortest_path = torch.zeros((self.B, rows), dtype=torch.int64, device=paths.device)
+            if old is not None:
+                self.shortest_path[:, :min(rows, old.shape[1])] = old[:, :rows]
+        if self._pool is None or self._pool[0].shape[2] != rows:
+            self._pool = cvrp_elite_pool(self.B, rows, paths.device)
+        cvrp_reinsert_(self.distances, paths, costs, lens, self.topk)
+        self.last_improved, new_max, _ = cvrp_n1_move_(
+            self.distances, self.demand, self.capacity, paths, costs, self.lowest_cost, self.shortest_path, lens=lens, seed=self.seed, it=it,
+            inst_gid0=self.ant_gid0 // self.n_ants, mmas_scale=self.n if self.min_max else None)
+        cmin, cmax = _mmas_bounds(self, new_max)
+        cvrp_adaptive_update_(self.pheromone, paths, costs, self.last_improved, self.decay, self.shortest_path, self.lowest_cost, self._pool,
+                              cmin, cmax, floor=1e-10)
+        if trim:
+            paths = paths[:, :int(lens.max())].contiguous()
+        return paths, costs
+
+    @property
+    def elite_pool(self):
+        """The adaptive colony's pools as the reference keeps them: per instance a list of (route, cost), front first (reads the device)."""
+        if self._pool is None:
+            return [[] for _ in range(self.B)]
+        return [cvrp_elite_pool_list(self._pool, b) for b in range(self.B)]
 
     def sample(self):
         """The batched form of cvrp/aco.py:66-69 (`ACO.sample()`): one construction with log-probabilities for all B colonies.

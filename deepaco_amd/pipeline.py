@@ -730,6 +730,8 @@ def infer_cvrp_batch(demands, distances, n_ants, t_aco, net=None, heuristic=None
     """The batched counterpart of cvrp/test.py:14-39 (`infer_instance`): demands [B,n+1], distances [B,n+1,n+1] -> heuristic (the
     network in eval mode through sibling_heuristic_batch; a matrix [B,n+1,n+1]; or None: 1 / distance) -> B colonies -> the
     lowest cost at every checkpoint of t_aco.  Giving both a network and a heuristic is an error.
+    aco_kw: what engine.BatchedCVRP takes -- adaptive=True (and topk) runs the reference's adaptive elitist baseline
+    (cvrp/aco.py:207-383) instead of the plain colony, on the same device and with the same sampler.
     Returns (best costs [len(t_aco), B], colony)."""
     if net is not None:
         if heuristic is not None:

@@ -1131,6 +1131,60 @@ long daco_rcpsp_net_train_backward(void *stream, int B, int n, int feats, const 
                                    const float *params, const void *saved, size_t saved_bytes, const float *grad_heu,
                                    float *grad_params, float *grad_blocks, void *workspace, size_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * daco_cvrp_reinsert / daco_cvrp_n1_move / daco_cvrp_adaptive_update -- the "adaptive elitist AS" of cvrp/aco.py:207-383
+ *   (improvement_phase, the record of run() :81-93 with intensification_phase / N1_neighbourhood, and update_pheronome |
+ *   diversification_phase with the elite pool), one launch each, no host read between them.  Restated in
+ *   tests/cvrp_adaptive_spec.py; lane mapping and arithmetic in csrc/daco_cvrp_adaptive.hip and DESIGN.md section 3.20.
+ *   dist [B][n][n] f32 (dist_bstride elements between instances, 0 = shared; need not be symmetric; d[0][0] as the instance
+ *   has it: it enters the first insertion of every subroute); paths in/out [B][Lmax][A] int64, zero-padded columns
+ *   0 a b 0 c 0 0 ... (cvrp/aco.py:138-165); costs in/out [B][A] f32; lens in/out [B][A] int32 or NULL: rows used by a column,
+ *   its closing depot included, written for the columns that change.
+ *
+ * daco_cvrp_reinsert: topk <= 0 or topk >= A selects every ant, anything else the FIVE cheapest (the reference's literal 5,
+ *   :342; A < 5 is then DACO_E_BADARG), equal costs at the fifth place going to the smaller ant id.  Each selected ant's
+ *   subroutes are rebuilt from [0, 0] by inserting their customers, in their order in the path, at the position of least
+ *   (d[p1][c] + d[c][p2]) - d[p1][p2] (float32, left to right, smallest position among equals); the new cost is the double sum
+ *   of the subroutes' double sums; the column, its cost (rounded to float32) and length are replaced only if
+ *   (float)new < cost.  A column whose last row is a customer keeps that open tail out of the rebuild, as get_subroutes does.
+ *   selected out [B][K] int32, K = A or 5: the ants taken, in ascending order of (cost, id) for K = 5.
+ *   One workgroup per instance, one wavefront per selected ant (up to 8 at a time, fewer where 64 KiB of LDS hold fewer routes).
+ *
+ * daco_cvrp_n1_move: one wavefront per instance.  track != 0: first the record -- the first minimum of costs against lowest
+ *   [B] (strict <), shortest [B][Lmax] int64 and improved [B] int32 written; track == 0: improved is read, shortest and
+ *   lowest are the record as the caller holds it.  Where improved[b] is set, five trials of N1_neighbourhood (:254-286) on the
+ *   record: each takes two uniforms u in [0, 1) -- noise [B][5][2] f32, or, noise == NULL, the counter-based stream keyed
+ *   by (seed, iter, inst_gid0 + b) -- for the subroute and the node in it, a draw over [lo, hi] being
+ *   lo + min(floor(u * (hi - lo + 1)), hi - lo) with the product in float32; route loads are float32 sums in route order,
+ *   `load + demand <= capacity` in float32; the candidate is insertion + gain in float32, the running best replaced on strict <
+ *   from 0.0.  The best move is applied to shortest and to the record's column of paths (the first minimum of costs), a
+ *   subroute left empty disappears, lowest = lowest + delta in float32 is also that column's cost.
+ *   mmas_max out [B] or NULL: (1 / lowest) * mmas_scale after the move, for every instance; moved out [B] int32 or NULL.
+ *   demand [B][n] f32 (demand[.][0] = 0).
+ *
+ * daco_cvrp_adaptive_update: per instance, by improved[b].  Set: tau = tau * decay, the first-minimum ant's directed edges
+ *   + 1 / cost (each index pair once), clamps, floor -- daco_pheromone_update(elitist = 1, symmetric = 0, hub = 0) bit for bit --
+ *   and (shortest[b], lowest[b]) pushed to the front of the instance's pool.  Clear: tau = tau * (decay * 0.5) + 0.01 (the
+ *   factor rounded once to float32, multiply and add rounded separately), then + 1 / cost on the edges of every pool entry from
+ *   the front; no clamp, no floor.  pool_routes [B][5][Lmax] int64, pool_costs [B][5] f32, pool_state [B][2] int32 =
+ *   (entries, slot of the front entry); the entry k places behind the front is slot (front + k) % 5; all three start zeroed.
+ *
+ * Limits: n <= DACO_MAX_NODES, Lmax <= 4 * DACO_MAX_NODES, A <= 4096 for the reinsertion (DACO_E_TOOLARGE above, before any
+ * launch); B, A >= 1, n, Lmax >= 2 and the pointers not marked optional (DACO_E_BADARG).  The statuses are the usual DACO_OK /
+ * DACO_E_* values typed `long`, for the reason given at daco_rcpsp_net_forward; the refusals are in
+ * tests/test_cvrp_adaptive_refusals.py.  Added under DACO_VERSION 130: new entry points only.
+ */
+long daco_cvrp_reinsert(void *stream, int B, int n, int A, int Lmax, int topk, const float *dist, long dist_bstride,
+                        int64_t *paths, float *costs, int32_t *lens, int32_t *selected);
+long daco_cvrp_n1_move(void *stream, int B, int n, int A, int Lmax, const float *dist, long dist_bstride, const float *demand,
+                       float capacity, const float *noise, uint64_t seed, uint64_t iter, uint32_t inst_gid0, int64_t *paths,
+                       float *costs, int32_t *lens, float *lowest, int64_t *shortest, int32_t *improved, int track,
+                       float *mmas_max, float mmas_scale, int32_t *moved);
+long daco_cvrp_adaptive_update(void *stream, int B, int n, int A, int Lmax, float *tau, const int64_t *paths, const float *costs,
+                               const int32_t *improved, float decay, const float *clamp_min, const float *clamp_max,
+                               float floor_val, const int64_t *shortest, const float *lowest, int64_t *pool_routes,
+                               float *pool_costs, int32_t *pool_state);
+
 #ifdef __cplusplus
 }
 #endif
