@@ -68,6 +68,8 @@ SIGNATURES = {
     "daco_cvrp_reinsert": (_l, [_vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _vp]),
     "daco_cvrp_n1_move": (_l, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _f, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f,
                                _vp]),
+    "daco_cvrp_intensify": (_l, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _i, C.c_double, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                 _vp, _f, _vp]),
     "daco_cvrp_adaptive_update": (_l, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "daco_hgs_table_bytes": (_sz, [_i, _i]),
     "daco_hgs_prepare": (_i, [_vp, _i, _i, _vp, _l, _i, _vp]),

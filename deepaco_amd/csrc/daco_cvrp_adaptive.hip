@@ -2,7 +2,10 @@
 //   improvement_phase      -> cvrp_reinsert_kernel   (cheapest-insertion rebuild of the selected ants' subroutes)
 //   intensification_phase  -> cvrp_n1_kernel         (the record of run(), :81-93, and the N1 relocation on a new record)
 //   update_pheronome / diversification_phase / the elite pool -> cvrp_adaptive_update_kernel (per instance, one of the two)
-// Restated in plain Python in tests/cvrp_adaptive_spec.py, which tests/golden/a1_*.npz pin on the reference itself.
+// and the one phase in which cvrp_nls/aco.py's copy of that baseline (:289-441) differs:
+//   intensification_phase with N1 AND N2 (:313-394, 419-434) -> cvrp_intensify_kernel (one workgroup per instance, a wavefront per trial)
+// Restated in plain Python in tests/cvrp_adaptive_spec.py, which tests/golden/a1_*.npz pin on the reference itself, and in
+// tests/cvrp_nls_adaptive_spec.py (tests/golden/a2_*.npz).
 //
 // Arithmetic: an insertion's added length is
 // (d[p1][c] + d[c][p2]) - d[p1][p2] in float32, two roundings, no contraction (the Makefile's -ffp-contract=off); the minimum
@@ -303,6 +306,264 @@ cvrp_n1_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, const fl
   }
 }
 
+// ------------------------------------------------------------------ cvrp_nls's intensification_phase (cvrp_nls/aco.py:313-394, 419-434)
+// The record, then N1 AND N2 on it, both evaluated on the unmodified record.
+constexpr uint32_t STREAM_N2 = 6;            // the N2 draws' stream (4 is N1's, 5 the sparse sampler's retry)
+constexpr int IN_WAVES = 2 * AD_TRIALS;      // wavefront t < 5: N1's trial t; wavefront 5 + t: N2's trial t
+constexpr int IN_RES = 8;                    // ints a trial leaves in LDS: valid | its move
+
+// best_gap on rt[0 .. len-1] with the entry at index `skip` left out (1 <= skip <= len - 2: the route then has len - 1 >= 2
+// entries); the position returned is one of the route without that entry
+__device__ inline KeyIdx best_gap_skip(const float *d, int n, const uint16_t *rt, int len, int skip, int c, int lane) {
+  float bk = 0.0f;
+  int bi = -1;
+  const int L = len - 1;
+  for (int i0 = 0; i0 + 1 < L; i0 += 64) {
+    const int i = i0 + lane;
+    float k = __builtin_inff();
+    int id = 0x7fffffff;
+    if (i + 1 < L) {
+      const int p1 = rt[i + (i >= skip ? 1 : 0)], p2 = rt[i + 1 + (i + 1 >= skip ? 1 : 0)];
+      const float s = d[(size_t)p1 * n + c] + d[(size_t)c * n + p2];
+      k = s - d[(size_t)p1 * n + p2];
+      id = i;
+    }
+    const KeyIdx r = wave_arg<false>(k, id);
+    if (bi < 0 || r.key < bk) { bk = r.key; bi = r.idx == 0x7fffffff ? i0 : r.idx; }
+  }
+  return KeyIdx{bk, bi};
+}
+
+// One workgroup of IN_WAVES wavefronts per instance.  Wavefront 0 takes the record as cvrp_n1_kernel does and lays the record's
+// route, its subroute table and the loads into LDS; after a barrier wavefront w runs its one trial (ten independent chains of
+// gather latencies side by side) and leaves (delta, move) in LDS; after a second barrier wavefront 0 takes the first least
+// delta below 0.0 in the order N1's trials, N2's trials (strict <: the winner rule of cvrp_nls/aco.py:425-429 and of both
+// neighbourhoods' own loops) and applies it.
+// LDS: load[n_ld] DT | rt[Lmax] u16 | sstart[n_ld] u16 | scnt[n_ld] u16 | hdr[2] int (improved, S) | delta[10] f32 |
+// res[10][IN_RES] int.  DT is the demand's dtype: loads and every capacity test run in it.
+template <typename DT>
+__global__ void __launch_bounds__(64 * IN_WAVES)
+cvrp_intensify_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, const DT *demand, double capacity, const float *noise,
+                      uint64_t seed, uint64_t iter, uint32_t inst_gid0, int64_t *paths, float *costs, int32_t *lens, float *lowest,
+                      int64_t *shortest, int32_t *improved, int track, float *mmas_max, float mmas_scale, int32_t *moved, int n_ld) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t ad_lds[];
+  DT *load = (DT *)ad_lds;
+  uint16_t *rt = (uint16_t *)(load + n_ld), *sstart = rt + ((Lmax + 3) & ~3), *scnt = sstart + n_ld;
+  int *hdr = (int *)(scnt + n_ld);
+  float *rdelta = (float *)(hdr + 2);
+  int *res = (int *)(rdelta + IN_WAVES);
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float *d = dist + (size_t)b * dist_bs;
+  const DT *dem = demand + (size_t)b * n;
+  const DT cap = (DT)capacity;
+  float *cb = costs + (size_t)b * A;
+  int64_t *sp = shortest + (size_t)b * Lmax;
+  KeyIdx best = KeyIdx{0.0f, 0};
+  float low = 0.0f;
+  int imp = 0, end = 0;
+  if (wave == 0) {
+    best = first_min(cb, A, lane);
+    low = lowest[b];
+    if (track) {                                            // `if best_cost < self.lowest_cost` (cvrp_nls/aco.py:150-152)
+      imp = best.key < low;
+      if (imp) {
+        low = best.key;
+        for (int k = lane; k < Lmax; k += 64) sp[k] = paths[((size_t)b * Lmax + k) * A + best.idx];
+      }
+      if (lane == 0) improved[b] = imp;
+    } else {
+      imp = improved[b] != 0;
+    }
+    int S = 0;
+    if (imp) {
+      int last = -1;
+      for (int k0 = 0; k0 < Lmax; k0 += 64) {
+        const int k = k0 + lane;
+        const int v = k < Lmax ? (int)(track ? paths[((size_t)b * Lmax + k) * A + best.idx] : sp[k]) : 0;
+        if (k < Lmax) rt[k] = (uint16_t)v;
+        const uint64_t nz = __ballot(v != 0);
+        if (nz) last = k0 + 63 - __builtin_clzll(nz);
+      }
+      __builtin_amdgcn_wave_barrier();
+      __threadfence_block();
+      int start = -1;
+      end = last + 2 <= Lmax ? last + 2 : Lmax;
+      for (int k0 = 0; k0 < end; k0 += 64) {
+        const int k = k0 + lane;
+        uint64_t zero = __ballot(k < end && rt[k] == 0);
+        while (zero) {
+          const int j = k0 + __builtin_ctzll(zero);
+          zero &= zero - 1;
+          if (start >= 0 && j - start > 1 && S < n) {
+            if (lane == 0) { sstart[S] = (uint16_t)start; scnt[S] = (uint16_t)min(j - start - 1, n - 1); }
+            ++S;
+          }
+          start = j;
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      __threadfence_block();
+      for (int s = lane; s < S; s += 64) {                  // self.demand[r].sum() per subroute (:423), sequential in route order
+        DT x = (DT)0;
+        const int s0 = sstart[s], m = scnt[s];
+        for (int t = 1; t <= m; ++t) x = x + dem[rt[s0 + t]];
+        load[s] = x;
+      }
+    }
+    if (lane == 0) { hdr[0] = imp; hdr[1] = S; }
+  }
+  __syncthreads();
+  {
+    const int go = hdr[0], S = hdr[1];
+    float bdelta = 0.0f;
+    int r0 = 0, r1 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0, valid = 0;
+    if (go && wave < AD_TRIALS && S > 0) {                  // N1_neighbourhood's trial `wave`: cvrp_n1_kernel's, one trial
+      const int t = wave;
+      float u0, u1;
+      if (noise) {
+        u0 = noise[(size_t)b * 30 + 2 * t];
+        u1 = noise[(size_t)b * 30 + 2 * t + 1];
+      } else {
+        const u32x4 r = rng_block(seed, iter, STREAM_N1, inst_gid0 + (uint32_t)b, (uint32_t)t);
+        u0 = u01(r.x);
+        u1 = u01(r.y);
+      }
+      const int si = draw_int(u0, 0, S - 1);
+      const int s0 = sstart[si], m = scnt[si];
+      const int ni = draw_int(u1, 1, m);
+      const int pred = rt[s0 + ni - 1], node = rt[s0 + ni], next = rt[s0 + ni + 1];
+      const DT dn = dem[node];
+      const float g0 = d[(size_t)pred * n + next] - d[(size_t)pred * n + node];
+      const float gain = g0 - d[(size_t)node * n + next];
+      for (int i = 0; i < S; ++i) {
+        if (i == si || !(load[i] + dn <= cap)) continue;
+        const KeyIdx g = best_gap(d, n, rt + sstart[i], (int)scnt[i] + 2, node, lane);
+        const float cand = g.key + gain;
+        if (cand < bdelta) { bdelta = cand; valid = 1; r0 = si; r1 = ni; r2 = i; r3 = g.idx + 1; }
+      }
+    } else if (go && wave >= AD_TRIALS && S >= 2) {         // N2_neighbourhood's trial wave - 5 (S < 2: skipped; the reference raises)
+      const int t = wave - AD_TRIALS;
+      float u0, u1, u2, u3;
+      if (noise) {
+        const float *q = noise + (size_t)b * 30 + 10 + 4 * t;
+        u0 = q[0]; u1 = q[1]; u2 = q[2]; u3 = q[3];
+      } else {
+        const u32x4 r = rng_block(seed, iter, STREAM_N2, inst_gid0 + (uint32_t)b, (uint32_t)t);
+        u0 = u01(r.x); u1 = u01(r.y); u2 = u01(r.z); u3 = u01(r.w);
+      }
+      const int sr1 = draw_int(u0, 0, S - 1);
+      int sr2 = draw_int(u1, 0, S - 2);
+      if (sr2 >= sr1) ++sr2;
+      const int a0 = sstart[sr1], m1 = scnt[sr1], c0 = sstart[sr2], m2 = scnt[sr2];
+      const int ni = draw_int(u2, 1, m1);
+      const int p1 = rt[a0 + ni - 1], n1 = rt[a0 + ni], x1 = rt[a0 + ni + 1];
+      const DT d1 = dem[n1];
+      const DT room2 = load[sr2] + d1, room1 = load[sr1] - d1;
+      int cnt = 0;
+      for (int j0 = 1; j0 <= m2; j0 += 64) {
+        const int j = j0 + lane;
+        bool ok = false;
+        if (j <= m2) { const DT c = dem[rt[c0 + j]]; ok = (room2 - c <= cap) && (room1 + c <= cap); }
+        cnt += __popcll(__ballot(ok));
+      }
+      if (cnt > 0) {
+        int k = draw_int(u3, 0, cnt - 1), nj = -1;          // the k-th available position, in increasing order
+        for (int j0 = 1; j0 <= m2 && nj < 0; j0 += 64) {
+          const int j = j0 + lane;
+          bool ok = false;
+          if (j <= m2) { const DT c = dem[rt[c0 + j]]; ok = (room2 - c <= cap) && (room1 + c <= cap); }
+          const uint64_t mask = __ballot(ok);
+          const int pc = __popcll(mask);
+          if (k < pc) {
+            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            nj = j0 + __builtin_ctzll(__ballot(ok && rank == k));
+          } else {
+            k -= pc;
+          }
+        }
+        const int p2 = rt[c0 + nj - 1], n2 = rt[c0 + nj], x2 = rt[c0 + nj + 1];
+        float c = d[(size_t)p1 * n + x1] - d[(size_t)p1 * n + n1];
+        c = c - d[(size_t)n1 * n + x1];
+        float c2 = d[(size_t)p2 * n + x2] - d[(size_t)p2 * n + n2];
+        c2 = c2 - d[(size_t)n2 * n + x2];
+        c = c + c2;
+        const KeyIdx i1 = best_gap_skip(d, n, rt + c0, m2 + 2, nj, n1, lane);    // node1 into sr2 without node2
+        c = c + i1.key;
+        const KeyIdx i2 = best_gap_skip(d, n, rt + a0, m1 + 2, ni, n2, lane);    // node2 into sr1 without node1
+        c = c + i2.key;
+        if (c < bdelta) { bdelta = c; valid = 1; r0 = sr1; r1 = ni; r2 = i2.idx; r3 = sr2; r4 = nj; r5 = i1.idx; }
+      }
+    }
+    if (lane == 0) {
+      rdelta[wave] = bdelta;
+      int *q = res + wave * IN_RES;
+      q[0] = valid; q[1] = r0; q[2] = r1; q[3] = r2; q[4] = r3; q[5] = r4; q[6] = r5;
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  int did = 0;
+  if (imp) {
+    float bdelta = 0.0f;
+    int win = -1;
+    for (int w = 0; w < IN_WAVES; ++w)
+      if (res[w * IN_RES] && rdelta[w] < bdelta) { bdelta = rdelta[w]; win = w; }
+    const int bi = best.idx;
+    if (win >= 0) {
+      const int *q = res + win * IN_RES;
+      low = low + bdelta;                                   // self.lowest_cost = ogcost + best_neighbour[1] (:432)
+      if (win < AD_TRIALS) {                                // N1's move, as cvrp_n1_kernel applies it
+        did = 1;
+        const int bs = q[1], bni = q[2], bt = q[3], bpos = q[4];
+        const int s0 = sstart[bs], vanish = scnt[bs] == 1, prm = s0 + bni, pins = sstart[bt] + bpos;
+        const int node = rt[prm];
+        const int used = end - vanish;
+        for (int k = lane; k < Lmax; k += 64) {
+          if (k >= used) {
+            sp[k] = 0;
+            paths[((size_t)b * Lmax + k) * A + bi] = 0;
+          }
+        }
+        for (int k = lane; k < end; k += 64) {
+          if (k == prm || (vanish && k == s0)) continue;
+          const int to = k - (k > prm ? 1 : 0) - (vanish && k > s0 ? 1 : 0) + (k >= pins ? 1 : 0);
+          sp[to] = rt[k];
+          paths[((size_t)b * Lmax + to) * A + bi] = rt[k];
+        }
+        if (lane == 0) {
+          const int to = pins - (prm < pins ? 1 : 0) - (vanish && s0 < pins ? 1 : 0);
+          sp[to] = node;
+          paths[((size_t)b * Lmax + to) * A + bi] = node;
+          if (lens) lens[(size_t)b * A + bi] = used;
+        }
+      } else {                                              // N2's: both routes keep their rows; each loses one node and takes the other's
+        did = 2;
+        const int node1 = rt[sstart[q[1]] + q[2]], node2 = rt[sstart[q[4]] + q[5]];
+        for (int side = 0; side < 2; ++side) {
+          const int s0 = sstart[side ? q[4] : q[1]], m = scnt[side ? q[4] : q[1]], skip = side ? q[5] : q[2], loc = side ? q[6] : q[3];
+          const int node = side ? node1 : node2;
+          for (int k = lane; k <= m + 1; k += 64) {
+            if (k == skip) continue;
+            const int i = k - (k > skip ? 1 : 0), to = s0 + i + (i > loc ? 1 : 0);
+            sp[to] = rt[s0 + k];
+            paths[((size_t)b * Lmax + to) * A + bi] = rt[s0 + k];
+          }
+          if (lane == 0) {
+            sp[s0 + loc + 1] = node;
+            paths[((size_t)b * Lmax + s0 + loc + 1) * A + bi] = node;
+          }
+        }
+      }
+      if (lane == 0) cb[bi] = low;
+    }
+    if (lane == 0) lowest[b] = low;
+  }
+  if (lane == 0) {
+    if (mmas_max) mmas_max[b] = (1.0f / low) * mmas_scale;
+    if (moved) moved[b] = did;
+  }
+}
+
 // ------------------------------------------------------------------ update_pheronome | diversification_phase, and the pool
 // A workgroup owns R rows of one instance's tau.  It reads the routes whose edges are deposited -- the best ant's column for an
 // improved instance, the pool's entries from the front for the others --, keeps for each route the successor of each of its
@@ -422,6 +683,47 @@ extern "C" long daco_cvrp_n1_move(void *stream, int B, int n, int A, int Lmax, c
   hipLaunchKernelGGL(cvrp_n1_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, n, A, Lmax, dist, dist_bstride, demand, capacity, noise,
                      seed, iter, inst_gid0, paths, costs, lens, lowest, shortest, improved, track, mmas_max, mmas_scale, moved, n_ld);
   return launch_status("cvrp_n1_kernel");
+}
+
+// bytes of LDS cvrp_intensify_kernel takes (its layout comment): 2 Lmax + (4 + sizeof(DT)) n + 368, each rounded to its alignment
+static size_t intensify_lds(int n, int Lmax, bool f64) {
+  const size_t n_ld = (size_t)((n + 1) & ~1);
+  return n_ld * (f64 ? sizeof(double) : sizeof(float)) + ((size_t)((Lmax + 3) & ~3) + 2 * n_ld) * sizeof(uint16_t) + 2 * sizeof(int) +
+         IN_WAVES * sizeof(float) + (size_t)IN_WAVES * IN_RES * sizeof(int);
+}
+
+/* The record and cvrp_nls's intensification_phase, N1 and N2, for B instances in one launch.  Fits (one workgroup's 64 KiB of
+ * LDS): 2 Lmax + 8 n + 368 <= 65536 bytes with float32 demands, 2 Lmax + 12 n + 368 with float64 ones -- with Lmax = 2 n + 1
+ * every n <= DACO_MAX_NODES for float32 and n <= 4072 for float64; a larger (n, Lmax) is DACO_E_TOOLARGE and is not launched. */
+extern "C" long daco_cvrp_intensify(void *stream, int B, int n, int A, int Lmax, const float *dist, long dist_bstride, const void *demand,
+                                    int demand_f64, double capacity, const float *noise, uint64_t seed, uint64_t iter, uint32_t inst_gid0,
+                                    int64_t *paths, float *costs, int32_t *lens, float *lowest, int64_t *shortest, int32_t *improved,
+                                    int track, float *mmas_max, float mmas_scale, int32_t *moved) {
+  if (B <= 0 || n < 2 || A <= 0 || Lmax < 2 || dist_bstride < 0) {
+    set_error("daco_cvrp_intensify: bad argument (B=%d n=%d A=%d Lmax=%d dist_bstride=%ld)", B, n, A, Lmax, dist_bstride);
+    return DACO_E_BADARG;
+  }
+  const void *need[] = {dist, demand, paths, costs, lowest, shortest, improved};
+  const char *names[] = {"dist", "demand", "paths", "costs", "lowest", "shortest", "improved"};
+  for (int i = 0; i < 7; ++i)
+    if (!need[i]) { set_error("daco_cvrp_intensify: bad argument: %s is NULL", names[i]); return DACO_E_BADARG; }
+  if (!adaptive_sizes_ok("daco_cvrp_intensify", n, Lmax)) return DACO_E_TOOLARGE;
+  const size_t lds = intensify_lds(n, Lmax, demand_f64 != 0);
+  if (lds > 64 * 1024) {
+    set_error("daco_cvrp_intensify: n=%d, Lmax=%d with %s demands take %zu bytes of LDS, above 65536", n, Lmax,
+              demand_f64 ? "float64" : "float32", lds);
+    return DACO_E_TOOLARGE;
+  }
+  const int n_ld = (n + 1) & ~1;
+  if (demand_f64)
+    hipLaunchKernelGGL(cvrp_intensify_kernel<double>, dim3(B), dim3(64 * IN_WAVES), lds, (hipStream_t)stream, n, A, Lmax, dist, dist_bstride,
+                       (const double *)demand, capacity, noise, seed, iter, inst_gid0, paths, costs, lens, lowest, shortest, improved, track,
+                       mmas_max, mmas_scale, moved, n_ld);
+  else
+    hipLaunchKernelGGL(cvrp_intensify_kernel<float>, dim3(B), dim3(64 * IN_WAVES), lds, (hipStream_t)stream, n, A, Lmax, dist, dist_bstride,
+                       (const float *)demand, capacity, noise, seed, iter, inst_gid0, paths, costs, lens, lowest, shortest, improved, track,
+                       mmas_max, mmas_scale, moved, n_ld);
+  return launch_status("cvrp_intensify_kernel");
 }
 
 extern "C" long daco_cvrp_adaptive_update(void *stream, int B, int n, int A, int Lmax, float *tau, const int64_t *paths, const float *costs,

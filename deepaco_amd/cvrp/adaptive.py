@@ -5,7 +5,8 @@ list of (route, cost).  The phases are the kernels of csrc/daco_cvrp_adaptive.hi
 cvrp_adaptive_update_); `run` is a one-instance engine.BatchedCVRP(adaptive=True) kept with the object, as cvrp.aco.ACO.run.
 
 The N1 draws (random.randint in the reference) come from the library's counter-based stream, keyed by (seed, iteration).
-N2_neighbourhood is never called by the reference (cvrp/aco.py:366) and is not here.
+N2_neighbourhood is never called by cvrp/aco.py (:366) and is not in this class; cvrp_nls/aco.py:426 does call it: that copy of the
+baseline is deepaco_amd/cvrp_nls/adaptive.py (engine.cvrp_intensify_, engine.BatchedCVRP(adaptive="cvrp_nls")).
 """
 import torch
 

@@ -19,6 +19,9 @@ gen_g11_hgs_ls.py asserts that on every solution).  `use_swap_star=True` (keywor
 search WITH SWAP*, as HGS's sources mean it and as a mended structure would run it (daco_hgs_local_search_ss).  Pinned on the reference's own outputs: fixtures g8 / g11
 (tests/test_gpu_09_cvrp_ls.py, tests/test_gpu_13_hgs_ls.py).  `local_search="best_improvement"` selects round 3's
 deterministic best-improvement kernel instead (daco_cvrp_local_search: moves 1-9 + SWAP*, hard capacity; cost-pinned only).
+
+`adaptive=True` is the reference's "adaptive elitist AS" as this file of it carries it (cvrp_nls/aco.py:135-171, 289-441), with
+`swapstar` False or True: deepaco_amd/cvrp_nls/adaptive.py.
 """
 import os
 import sys
@@ -31,6 +34,7 @@ except ImportError:
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
     from deepaco_amd.cvrp.aco import ACO as _CvrpACO
 from deepaco_amd import engine
+from deepaco_amd.cvrp_nls.adaptive import AdaptivePhases
 
 CAPACITY = 1.0
 
@@ -57,7 +61,7 @@ def merge_subroutes(subroutes, length, device):
     return route
 
 
-class ACO(_CvrpACO):
+class ACO(AdaptivePhases, _CvrpACO):
 
     def __init__(self, distances, demand, n_ants=20, decay=0.9, alpha=1, beta=1, elitist=False, min_max=False,
                  pheromone=None, heuristic=None, min=None, device='cpu', adaptive=False, capacity=CAPACITY,
@@ -71,8 +75,14 @@ class ACO(_CvrpACO):
         # sampler (cvrp_nls/aco.py:254-272 runs it in double; with demands k / capacity the last bit decides exact fits)
         super().__init__(distances.float(), demand, n_ants, decay, alpha, beta, elitist, min_max,
                          None if pheromone is None else pheromone.float(),
-                         None if heuristic is None else heuristic.float(), min, device, adaptive, float(capacity),
+                         None if heuristic is None else heuristic.float(), min, device, False, float(capacity),
                          sampler=sampler, seed=seed)
+        # adaptive=True: the "adaptive elitist AS" this file of the reference carries (cvrp_nls/aco.py:135-171, 289-441), in
+        # the same class as there; its phases and its loop are deepaco_amd/cvrp_nls/adaptive.py
+        self.adaptive = bool(adaptive)
+        if self.adaptive:
+            self.elitist = True                                                     # cvrp_nls/aco.py:66
+            self.elite_pool = []
         self.swapstar, self.positions, self.inference = swapstar, positions, inference
         assert positions is not None if swapstar else True                      # cvrp_nls/aco.py:73
         assert local_search in ('hgs', 'best_improvement')
@@ -180,6 +190,8 @@ class ACO(_CvrpACO):
 
     @torch.no_grad()
     def run(self, n_iterations, inference=False):
+        if self.adaptive:
+            return self._run_adaptive(n_iterations)
         if not self.swapstar:
             return super().run(n_iterations)
         for _ in range(n_iterations):                          # cvrp_nls/aco.py:135-171 (non-adaptive branch)

@@ -9,7 +9,8 @@ from .. import _lib  # noqa: F401
 from .colonies import (BatchedCVRP, BatchedTSP, StreamedTSP, ant_sharded_cvrp, ant_sharded_tsp, run_kept_colony,  # noqa: F401
                        same_state)
 from .common import MODES, RACE_NOISE, RACE_PHILOX, SCAN, SCAN_WAVE, _f32c, _stream, _workspace, stage_to_hip  # noqa: F401
-from .cvrp_adaptive_ops import cvrp_adaptive_update_, cvrp_elite_pool, cvrp_elite_pool_list, cvrp_n1_move_, cvrp_reinsert_  # noqa: F401
+from .cvrp_adaptive_ops import (cvrp_adaptive_update_, cvrp_elite_pool, cvrp_elite_pool_list, cvrp_intensify_, cvrp_n1_move_,  # noqa: F401
+                                cvrp_reinsert_)
 from .cvrp_ops import cvrp_knn_graph, cvrp_sample, sample_backward  # noqa: F401
 from .local_search import (HgsTables, TspLocalSearch, TwoOptTables, cvrp_local_search_, heuristic_dist, hgs_local_search_,  # noqa: F401
                            hgs_polar_angles, nls_, transposed_for_two_opt, two_opt_, two_opt_tables)

@@ -2,7 +2,7 @@
 import torch
 
 from .common import _f32c, _raise_flags, _require_gpu, _rows
-from .cvrp_adaptive_ops import cvrp_adaptive_update_, cvrp_elite_pool, cvrp_elite_pool_list, cvrp_n1_move_, cvrp_reinsert_
+from .cvrp_adaptive_ops import cvrp_adaptive_update_, cvrp_elite_pool, cvrp_elite_pool_list, cvrp_intensify_, cvrp_n1_move_, cvrp_reinsert_
 from .cvrp_ops import cvrp_sample
 from .local_search import HgsTables, TspLocalSearch, heuristic_dist, hgs_local_search_, hgs_polar_angles
 from .tsp_ops import dist_is_symmetric, head_eta_table, head_table, resolve_sampler, sparse_tours16, sparse_workspace, sparsify_heuristic, tsp_sample, tsp_sample_sparse
@@ -368,7 +368,11 @@ class BatchedCVRP:
         construction, improvement_phase on the `topk` rule's ants (engine.cvrp_reinsert_), the record with the N1 relocation where
         it improved (engine.cvrp_n1_move_, its draws keyed by (seed, iteration, ant_gid0 // n_ants + b)), and per instance the
         elitist update with a push to `elite_pool`, or the diversification from that pool (engine.cvrp_adaptive_update_) -- four
-        launches, none of them waited for.  Not with local_search="hgs" (cvrp_nls's colony has no such phases): ValueError.
+        launches, none of them waited for.  Not with local_search="hgs": ValueError.
+        adaptive="cvrp_nls": the same baseline as cvrp_nls/aco.py carries it (:135-171, 289-441): its intensification_phase runs N1
+        AND N2 (engine.cvrp_intensify_, one launch; `last_moved` [B] int32 says which moved), and with local_search="hgs" the
+        order is the reference's -- construction, cvrp_reinsert_, the search on the `ls_ants` cheapest ants, every ant's cost
+        recomputed (engine.tour_costs), cvrp_intensify_, cvrp_adaptive_update_ -- without a host read.
         local_search="hgs": the colony iteration of cvrp_nls/aco.py:134-171 (swapstar=True) for every instance -- the `ls_ants`
         cheapest ants of each instance go through neural_swapstar (cvrp_nls/aco.py:143-146, 443-448; daco_hgs_local_search, the
         reference's routes) before best tracking and the deposit.  The local search reads `distances` and the heuristic in the
@@ -379,13 +383,18 @@ class BatchedCVRP:
             raise ValueError("BatchedCVRP: use_swap_star=True needs positions")
         if use_swap_star and local_search != "hgs":
             raise ValueError('BatchedCVRP: use_swap_star=True belongs to local_search="hgs"')
-        if adaptive and local_search == "hgs":
-            raise ValueError('BatchedCVRP: adaptive=True is the baseline of cvrp/aco.py and does not combine with local_search="hgs"')
+        if adaptive not in (False, True, "cvrp_nls"):
+            raise ValueError(f'BatchedCVRP: adaptive is False, True (cvrp/aco.py\'s loop) or "cvrp_nls" (cvrp_nls/aco.py\'s), got {adaptive!r}')
+        if adaptive is not False and adaptive != "cvrp_nls" and local_search == "hgs":
+            raise ValueError('BatchedCVRP: adaptive=True is the baseline of cvrp/aco.py and does not combine with local_search="hgs" '
+                             '(adaptive="cvrp_nls" is the loop that runs the search)')
         _require_gpu(distances, demand)
         assert local_search in (None, "hgs")
         self.adaptive, self.topk = bool(adaptive), int(topk)
+        self.adaptive_loop = "cvrp_nls" if adaptive == "cvrp_nls" else ("cvrp" if adaptive else None)
         self._pool = None                       # (routes [B, 5, Lmax], costs [B, 5], state [B, 2]) once an adaptive step has run
         self.last_improved = None               # [B] int32: which instances' records the last adaptive step improved
+        self.last_moved = None                  # [B] int32, adaptive="cvrp_nls": which neighbourhood moved them (0 none, 1 N1, 2 N2)
         self.local_search, self.ls_ants, self.inference = local_search, int(ls_ants), inference
         self.use_swap_star = bool(use_swap_star)
         self._hgs_pos = self._hgs_polar = None
@@ -431,31 +440,7 @@ class BatchedCVRP:
         self.iteration += 1
         self.last_lens, self.last_flags = lens, flags
         if self.local_search == "hgs":
-            if self._hgs is None or self._hgs[3] is not self.heuristic:
-                # the heuristic the colony holds NOW (cvrp_nls/aco.py:128-132 reads self.heuristic at first use; an assignment
-                # after construction counts, and a later one rebuilds the perturbation tables -- ADVICE r5).  The colony's own
-                # 1 / distances is taken from the distances in the dtype they were passed in (float64 instance data).
-                d_src, dem_src = self._ls_src
-                heu = (1 / d_src) if self.heuristic is self._own_heuristic else self.heuristic.detach()
-                hd = heuristic_dist(heu)
-                td = self._hgs[0] if self._hgs is not None else HgsTables(d_src)
-                self._hgs = (td, HgsTables(hd), dem_src.double() / float(self.capacity), self.heuristic)
-            td, th, dem_n, _ = self._hgs
-            k = min(self.ls_ants, self.n_ants)
-            idx = costs.topk(k, dim=1, largest=False).indices                               # [B, k]
-            gi = idx.unsqueeze(1).expand(self.B, paths.shape[1], k)
-            work = paths.gather(2, gi).contiguous()
-            limit = 100000 if self.inference else max(self.n, 50)
-            if self.use_swap_star:
-                hgs_local_search_(work, [(td, limit), (th, 10), (td, limit)], dem_n, positions=self._hgs_pos, use_swap_star=True,
-                                  polar=self._hgs_polar)
-            else:
-                hgs_local_search_(work, [(td, limit), (th, 10), (td, limit)], dem_n)
-            paths.scatter_(2, gi, work)
-            costs.scatter_(1, idx, tour_costs(self.distances, work, closed=False))
-            # the rewritten columns' used rows: up to and including the depot after their last client
-            rows = torch.arange(1, work.shape[1] + 1, device=work.device, dtype=lens.dtype).view(1, -1, 1)
-            lens.scatter_(1, idx, ((work != 0) * rows).amax(dim=1) + 1)
+            self._hgs_search(paths, costs, lens)
             table = None                                                                    # (the deposit rebuilds it from the paths)
         if self.shortest_path is None or self.shortest_path.shape[1] != paths.shape[1]:
             self.shortest_path = torch.zeros((self.B, paths.shape[1]), dtype=torch.int64, device=paths.device)
@@ -467,6 +452,35 @@ class BatchedCVRP:
         if trim:
             paths = paths[:, :int(lens.max())].contiguous()
         return paths, costs
+
+    def _hgs_search(self, paths, costs, lens):
+        """cvrp_nls/aco.py:143-146 for every instance, in place: the `ls_ants` cheapest ants through neural_swapstar, their costs
+        and used rows rewritten."""
+        if self._hgs is None or self._hgs[3] is not self.heuristic:
+            # the heuristic the colony holds NOW (cvrp_nls/aco.py:128-132 reads self.heuristic at first use; an assignment
+            # after construction counts, and a later one rebuilds the perturbation tables -- ADVICE r5).  The colony's own
+            # 1 / distances is taken from the distances in the dtype they were passed in (float64 instance data).
+            d_src, dem_src = self._ls_src
+            heu = (1 / d_src) if self.heuristic is self._own_heuristic else self.heuristic.detach()
+            hd = heuristic_dist(heu)
+            td = self._hgs[0] if self._hgs is not None else HgsTables(d_src)
+            self._hgs = (td, HgsTables(hd), dem_src.double() / float(self.capacity), self.heuristic)
+        td, th, dem_n, _ = self._hgs
+        k = min(self.ls_ants, self.n_ants)
+        idx = costs.topk(k, dim=1, largest=False).indices                               # [B, k]
+        gi = idx.unsqueeze(1).expand(self.B, paths.shape[1], k)
+        work = paths.gather(2, gi).contiguous()
+        limit = 100000 if self.inference else max(self.n, 50)
+        if self.use_swap_star:
+            hgs_local_search_(work, [(td, limit), (th, 10), (td, limit)], dem_n, positions=self._hgs_pos, use_swap_star=True,
+                              polar=self._hgs_polar)
+        else:
+            hgs_local_search_(work, [(td, limit), (th, 10), (td, limit)], dem_n)
+        paths.scatter_(2, gi, work)
+        costs.scatter_(1, idx, tour_costs(self.distances, work, closed=False))
+        # the rewritten columns' used rows: up to and including the depot after their last client
+        rows = torch.arange(1, work.shape[1] + 1, device=work.device, dtype=lens.dtype).view(1, -1, 1)
+        lens.scatter_(1, idx, ((work != 0) * rows).amax(dim=1) + 1)
 
     def _step_adaptive(self, Lmax=None, trim=False, events=None):
         """One iteration of the adaptive elitist colony (cvrp/aco.py:74-102) for every instance, without a host read: instances
@@ -487,9 +501,19 @@ class BatchedCVRP:
         if self._pool is None or self._pool[0].shape[2] != rows:
             self._pool = cvrp_elite_pool(self.B, rows, paths.device)
         cvrp_reinsert_(self.distances, paths, costs, lens, self.topk)
-        self.last_improved, new_max, _ = cvrp_n1_move_(
-            self.distances, self.demand, self.capacity, paths, costs, self.lowest_cost, self.shortest_path, lens=lens, seed=self.seed, it=it,
-            inst_gid0=self.ant_gid0 // self.n_ants, mmas_scale=self.n if self.min_max else None)
+        if self.adaptive_loop == "cvrp_nls":
+            if self.local_search == "hgs":
+                # cvrp_nls/aco.py:143-146: the search on the cheapest ants, then EVERY ant's cost recomputed (the reinsertion's
+                # summed costs are replaced by gen_path_costs's)
+                self._hgs_search(paths, costs, lens)
+                costs.copy_(tour_costs(self.distances, paths, closed=False))
+            self.last_improved, new_max, self.last_moved = cvrp_intensify_(
+                self.distances, self.demand, self.capacity, paths, costs, self.lowest_cost, self.shortest_path, lens=lens, seed=self.seed,
+                it=it, inst_gid0=self.ant_gid0 // self.n_ants, mmas_scale=self.n if self.min_max else None, want_moved=True)
+        else:
+            self.last_improved, new_max, _ = cvrp_n1_move_(
+                self.distances, self.demand, self.capacity, paths, costs, self.lowest_cost, self.shortest_path, lens=lens, seed=self.seed,
+                it=it, inst_gid0=self.ant_gid0 // self.n_ants, mmas_scale=self.n if self.min_max else None)
         cmin, cmax = _mmas_bounds(self, new_max)
         cvrp_adaptive_update_(self.pheromone, paths, costs, self.last_improved, self.decay, self.shortest_path, self.lowest_cost, self._pool,
                               cmin, cmax, floor=1e-10)

@@ -75,6 +75,50 @@ def cvrp_n1_move_(dist, demand, capacity, paths, costs, lowest, shortest, improv
     return improved, mx, moved
 
 
+def cvrp_intensify_(dist, demand, capacity, paths, costs, lowest, shortest, improved=None, lens=None, noise=None, seed=0, it=0,
+                    inst_gid0=0, mmas_scale=None, want_moved=False):
+    """The record of ACO.run (cvrp_nls/aco.py:148-152) and that file's intensification_phase (:419-434) for a batch, in place and
+    in one launch: N1_neighbourhood (:313-346) AND N2_neighbourhood (:348-394, two customers of two routes swapped, each
+    re-inserted at its cheapest place) on the unmodified record, N2's move taken only on a strictly smaller delta.  The
+    arguments are cvrp_n1_move_'s, except: demand [n] or [B, n] float32 or float64 is NOT cast -- loads and capacity tests run
+    in its dtype --, and noise [B, 30] float32: entries 2t, 2t+1 N1's trial t, entries 10 + 4t + k draw k of N2's trial t; else
+    the counter-based stream keyed by (seed, it, inst_gid0 + b, trial), N1's draws being cvrp_n1_move_'s for the same key.  An
+    instance with fewer than two routes skips N2 (the reference raises there).  Returns (improved, mmas_max | None, moved | None),
+    moved [B] int32: 0 no move, 1 N1's, 2 N2's.  Sizes whose route tables do not fit 64 KiB of LDS (2 Lmax + 8 n + 368 bytes,
+    12 n for float64 demands) raise DacoTooLarge; nothing is launched."""
+    B, Lmax, A = _check_colony("cvrp_intensify_", paths, costs, lens)
+    if lowest.dtype != torch.float32 or not lowest.is_contiguous() or lowest.numel() != B:
+        raise _lib.DacoError(f"cvrp_intensify_: lowest must be a contiguous float32 [{B}] tensor")
+    if shortest.dtype != torch.int64 or not shortest.is_contiguous() or tuple(shortest.shape) != (B, Lmax):
+        raise _lib.DacoError(f"cvrp_intensify_: shortest must be a contiguous int64 [{B}, {Lmax}] tensor, got {tuple(shortest.shape)}")
+    if noise is not None and (noise.dtype != torch.float32 or not noise.is_contiguous() or tuple(noise.shape) != (B, 30)):
+        raise _lib.DacoError(f"cvrp_intensify_: noise [{B}, 30] float32 expected, got {tuple(noise.shape)} {noise.dtype}")
+    if demand.dtype not in (torch.float32, torch.float64):
+        raise _lib.DacoError(f"cvrp_intensify_: demand must be float32 or float64, got {demand.dtype}")
+    n = dist.shape[-1]
+    if demand.shape[-1] != n or demand.numel() not in (n, B * n):
+        raise _lib.DacoError(f"cvrp_intensify_: demand must be [{n}] or [{B}, {n}], got {tuple(demand.shape)}")
+    track = improved is None
+    if not track and (improved.dtype != torch.int32 or not improved.is_contiguous() or improved.numel() != B):
+        raise _lib.DacoError(f"cvrp_intensify_: improved must be a contiguous int32 [{B}] tensor")
+    _require_gpu(dist, demand, paths, costs, lowest, shortest, improved, lens, noise)      # (the shapes are refused first, device or not)
+    dist, dbs = _bstride(dist, n)
+    demand = _rows(demand, B, demand.dtype)
+    dev = paths.device
+    with _on(dev):
+        if track:
+            improved = torch.empty((B,), dtype=torch.int32, device=dev)
+        mx = torch.empty((B,), dtype=torch.float32, device=dev) if mmas_scale is not None else None
+        moved = torch.empty((B,), dtype=torch.int32, device=dev) if want_moved else None
+        rc = _lib.lib().daco_cvrp_intensify(_stream(dev), B, n, A, Lmax, dist.data_ptr(), dbs, demand.data_ptr(),
+                                            int(demand.dtype == torch.float64), float(capacity), _ptr(noise), int(seed) & (2 ** 64 - 1),
+                                            int(it), int(inst_gid0) & 0xFFFFFFFF, paths.data_ptr(), costs.data_ptr(), _ptr(lens),
+                                            lowest.data_ptr(), shortest.data_ptr(), improved.data_ptr(), int(track), _ptr(mx),
+                                            float(mmas_scale) if mmas_scale is not None else 0.0, _ptr(moved))
+    _lib.check(rc, "daco_cvrp_intensify")
+    return improved, mx, moved
+
+
 def cvrp_elite_pool(B, Lmax, device):
     """An empty elite pool for B instances: (routes [B, 5, Lmax] int64, costs [B, 5] f32, state [B, 2] int32 = entries, front slot)."""
     return (torch.zeros((B, POOL_SIZE, Lmax), dtype=torch.int64, device=device), torch.zeros((B, POOL_SIZE), dtype=torch.float32, device=device),

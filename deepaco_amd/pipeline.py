@@ -265,6 +265,9 @@ def infer_cvrp_nls_batch(locations, demands, n_ants, t_aco, k_sparse, net=None, 
     heuristic (the network in eval mode, + 1e-10; None: 1 / distance) -> B colonies whose `ls_ants` cheapest ants go through the
     reference's local search every iteration (engine.BatchedCVRP(local_search="hgs", inference=True)).
     graph_path: 'torch' (the default) or 'hip' -- see cvrp_nls_graph_batch.
+    aco_kw: what engine.BatchedCVRP takes -- adaptive="cvrp_nls" runs the adaptive elitist baseline of cvrp_nls/aco.py:135-171,
+    289-441 (reinsertion, the search, every cost recomputed, N1 and N2 on a new record, elitist update or diversification) on
+    the same device and sampler as the learned colony; adaptive=True, cvrp/aco.py's loop, does not combine with the search.
     Returns (best costs [len(t_aco), B], colony); colony.shortest_path holds the best route sequences."""
     B, n1, _ = locations.shape
     loc, dist = _cvrp_distances(locations)

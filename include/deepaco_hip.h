@@ -1185,6 +1185,31 @@ long daco_cvrp_adaptive_update(void *stream, int B, int n, int A, int Lmax, floa
                                float floor_val, const int64_t *shortest, const float *lowest, int64_t *pool_routes,
                                float *pool_costs, int32_t *pool_state);
 
+/* ---------------------------------------------------------------------------------------------
+ * daco_cvrp_intensify -- the record and the intensification_phase of cvrp_nls/aco.py:419-434: N1_neighbourhood (:313-346) AND
+ *   N2_neighbourhood (:348-394) on the record, for B instances in one launch.  Restated in tests/cvrp_nls_adaptive_spec.py;
+ *   lane mapping and arithmetic in csrc/daco_cvrp_adaptive.hip and DESIGN.md section 3.21.  The arguments are
+ *   daco_cvrp_n1_move's, except: demand [B][n] float32 (demand_f64 == 0) or float64 (!= 0) -- every load (the sequential sum
+ *   in route order) and every capacity test runs in that type, capacity rounded to it; noise [B][30] f32 or NULL: entries
+ *   2t, 2t+1 are N1's trial t, entries 10 + 4t + k draw k of N2's trial t; without it the counter-based stream keyed by
+ *   (seed, iter, inst_gid0 + b, trial), N1's being daco_cvrp_n1_move's draws for the same key and N2's a stream of its own.
+ *   N1: as daco_cvrp_n1_move.  N2, trial t, S subroutes (S < 2: the trial is skipped -- the reference raises there):
+ *   sr1 = draw(u0, 0, S-1); sr2 = draw(u1, 0, S-2), + 1 if >= sr1; node1 = sr1[draw(u2, 1, len(sr1)-2)]; interior position j
+ *   of sr2 is available iff (load[sr2] + d1) - dem[sr2[j]] <= capacity and (load[sr1] - d1) + dem[sr2[j]] <= capacity; none:
+ *   no move; else node2 is at the draw(u3, 0, count-1)-th available position; the delta is, one float32 rounding per
+ *   operation, ((d[p1,x1] - d[p1,n1]) - d[n1,x1]) + ((d[p2,x2] - d[p2,n2]) - d[n2,x2]), + the least insertion of n1 into sr2
+ *   without n2, + that of n2 into sr1 without n1 (smallest position among equals).  The move applied is the first least
+ *   delta below 0.0 in the order N1's trials, N2's trials (strict <); lowest = lowest + delta in float32.
+ *   moved out [B] int32 or NULL: 0 no move, 1 N1's, 2 N2's.  One workgroup of ten wavefronts per instance, a trial each.
+ * Limits: daco_cvrp_n1_move's, and 2 Lmax + (8 | 12) n + 368 <= 65536 bytes of LDS for float32 | float64 demands
+ * (DACO_E_TOOLARGE above, before any launch).  A NULL pointer not marked optional is DACO_E_BADARG and the message names it;
+ * the refusals are in tests/test_cvrp_nls_adaptive_refusals.py.  Added under DACO_VERSION 130: a new entry point only.
+ */
+long daco_cvrp_intensify(void *stream, int B, int n, int A, int Lmax, const float *dist, long dist_bstride, const void *demand,
+                         int demand_f64, double capacity, const float *noise, uint64_t seed, uint64_t iter, uint32_t inst_gid0,
+                         int64_t *paths, float *costs, int32_t *lens, float *lowest, int64_t *shortest, int32_t *improved,
+                         int track, float *mmas_max, float mmas_scale, int32_t *moved);
+
 #ifdef __cplusplus
 }
 #endif
