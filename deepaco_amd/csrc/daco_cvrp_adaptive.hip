@@ -18,26 +18,40 @@
 // of 64 that is replaced on strict < only, so that a tie between two chunks keeps the earlier one.  A CVRP route under capacity
 // 50 holds about ten customers, so most lanes of a scan idle; the phases are a chain of gather latencies either way, and what a
 // block gains instead is one wavefront per selected ant, all of an instance's ants in flight at once.
+//
+// What the kernels share is written once, as inline device functions: best_gap (the insertion scan, with or without a skipped
+// entry), first_min, load_route (a route column into LDS: all three route-reading kernels), and for the two intensification
+// kernels for_each_subroute (the walk over a route's consecutive depots; the reinsertion keeps that walk as text of its own, for
+// the reason given there), RouteTables (the LDS layout, carved and sized side by side), take_record, lay_record, n1_draws,
+// n1_trial, apply_n1 and record_tail.  cvrp_n1_kernel is those in a row with five
+// trials in one wavefront; cvrp_intensify_kernel runs one n1_trial per wavefront beside N2's, which only it has.
 #include "daco_host.h"
 
 namespace daco {
 
 constexpr uint32_t STREAM_N1 = 4;            // the N1 draws' own stream of the counter-based generator (daco_device.h rng_block)
+constexpr uint32_t STREAM_N2 = 6;            // the N2 draws' stream (5 is the sparse sampler's retry)
 constexpr int AD_POOL = 5;                   // pool_size of cvrp/aco.py:99
 constexpr int AD_TOPK = 5;                   // the literal 5 of cvrp/aco.py:342
-constexpr int AD_TRIALS = 5;                 // count = 5 of N1_neighbourhood
+constexpr int AD_TRIALS = 5;                 // count = 5 of N1_neighbourhood and of N2_neighbourhood
+constexpr int N1_DRAWS = 2, N2_DRAWS = 4;    // uniforms a trial takes: (subroute, node) | (subroute, other subroute, node, position)
+constexpr int N1_ROW = N1_DRAWS * AD_TRIALS;             // an instance's noise row: cvrp_n1_kernel's [5][2], and the head of
+constexpr int IN_ROW = N1_ROW + N2_DRAWS * AD_TRIALS;    // cvrp_intensify_kernel's [30], N2's [5][4] behind it
 
 // least added length of inserting c into rt[0 .. len-1] (len >= 2): the position i of the gap (rt[i], rt[i+1]) and its delta,
-// uniform over the wavefront
-__device__ inline KeyIdx best_gap(const float *d, int n, const uint16_t *rt, int len, int c, int lane) {
+// uniform over the wavefront.  SKIP: the entry at index `skip` is left out (1 <= skip <= len - 2: the route then has len - 1 >= 2
+// entries) and the position returned is one of the route without that entry.
+template <bool SKIP = false>
+__device__ inline KeyIdx best_gap(const float *d, int n, const uint16_t *rt, int len, int c, int lane, int skip = 0) {
   float bk = 0.0f;
   int bi = -1;
+  if (SKIP) --len;
   for (int i0 = 0; i0 + 1 < len; i0 += 64) {
     const int i = i0 + lane;
     float k = __builtin_inff();
     int id = 0x7fffffff;
     if (i + 1 < len) {
-      const int p1 = rt[i], p2 = rt[i + 1];
+      const int p1 = rt[SKIP ? i + (i >= skip ? 1 : 0) : i], p2 = rt[SKIP ? i + 1 + (i + 1 >= skip ? 1 : 0) : i + 1];
       const float s = d[(size_t)p1 * n + c] + d[(size_t)c * n + p2];
       k = s - d[(size_t)p1 * n + p2];
       id = i;
@@ -59,6 +73,43 @@ __device__ inline KeyIdx first_min(const float *costs, int A, int lane) {
   KeyIdx r = wave_arg<false>(bk, bi);
   if (r.idx == 0x7fffffff) r.idx = 0;
   return r;
+}
+
+// the route src[0], src[stride], ... (Lmax rows: a column of paths, or a row of shortest) into rt as u16; the row of its last
+// customer, -1 if it has none.  rt is written for every lane when this returns.
+__device__ inline int load_route(const int64_t *src, long stride, int Lmax, uint16_t *rt, int lane) {
+  int last = -1;
+  for (int k0 = 0; k0 < Lmax; k0 += 64) {
+    const int k = k0 + lane;
+    const int v = k < Lmax ? (int)src[(size_t)k * stride] : 0;
+    if (k < Lmax) rt[k] = (uint16_t)v;
+    const uint64_t nz = __ballot(v != 0);
+    if (nz) last = k0 + 63 - __builtin_clzll(nz);
+  }
+  __builtin_amdgcn_wave_barrier();
+  __threadfence_block();
+  return last;
+}
+
+// rows of a route up to the depot that closes its last subroute (a column whose last row is a customer: that open tail is no
+// subroute, :209-217)
+__device__ inline int route_end(int last, int Lmax) { return last + 2 <= Lmax ? last + 2 : Lmax; }
+
+// get_subroutes(end_with_zero=True): f(start, j) for every two consecutive depots of rt[0 .. end-1] with a customer between
+// them, in route order and uniform over the wavefront.
+template <typename Fn>
+__device__ inline void for_each_subroute(const uint16_t *rt, int end, int lane, Fn f) {
+  int start = -1;
+  for (int k0 = 0; k0 < end; k0 += 64) {
+    const int k = k0 + lane;
+    uint64_t zero = __ballot(k < end && rt[k] == 0);
+    while (zero) {
+      const int j = k0 + __builtin_ctzll(zero);
+      zero &= zero - 1;
+      if (start >= 0 && j - start > 1) f(start, j);
+      start = j;
+    }
+  }
 }
 
 // ------------------------------------------------------------------ improvement_phase (cvrp/aco.py:336-357)
@@ -100,20 +151,12 @@ cvrp_reinsert_kernel(int n, int A, int Lmax, int K, const float *dist, long dist
   for (int r = wave; r < K; r += NW) {
     const int a = sel[r];
     int64_t *p = paths + (size_t)b * Lmax * A + a;
-    int last = -1;                                          // the column's last customer
-    for (int k0 = 0; k0 < Lmax; k0 += 64) {
-      const int k = k0 + lane;
-      const int v = k < Lmax ? (int)p[(size_t)k * A] : 0;
-      if (k < Lmax) out[k] = (uint16_t)v;
-      const uint64_t nz = __ballot(v != 0);
-      if (nz) last = k0 + 63 - __builtin_clzll(nz);
-    }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    // the depots up to the one that closes the last subroute, in order; (start, j): two consecutive ones
+    const int end = route_end(load_route(p, A, Lmax, out, lane), Lmax);
     double total = 0.0;
-    int start = -1, w = 0;                                  // w: entries of the rebuilt column written so far
-    const int end = last + 2 <= Lmax ? last + 2 : Lmax;     // (a column whose last row is a customer: that open tail is no subroute, :209-217)
+    int w = 0;                                              // entries of the rebuilt column written so far
+    // for_each_subroute's walk, written out: with the rebuild as its functor the compiler keeps the ballot word out of VCC and
+    // the insertion scan's selects in it, and the launch measured 1.1 us (1.7 %) slower, outside its windows' spread
+    int start = -1;
     for (int k0 = 0; k0 < end; k0 += 64) {
       const int k = k0 + lane;
       uint64_t zero = __ballot(k < end && out[k] == 0);
@@ -122,7 +165,7 @@ cvrp_reinsert_kernel(int n, int A, int Lmax, int K, const float *dist, long dist
         zero &= zero - 1;
         if (start >= 0 && j - start > 1) {
           // rebuild out[start + 1 .. j - 1] from [0, 0], customers in their order in the path
-          const int m = min(j - start - 1, n - 1);          // (n - 1 customers at the most: rt holds n + 1 entries)
+          const int m = min(j - start - 1, n - 1);              // (n - 1 customers at the most: rt holds n + 1 entries)
           if (lane == 0) { rt[0] = 0; rt[1] = 0; }
           __builtin_amdgcn_wave_barrier();
           __threadfence_block();
@@ -176,276 +219,242 @@ __device__ inline int draw_int(float u, int lo, int hi) {
   return lo + (k < 0 ? 0 : k);
 }
 
-// One wavefront per instance.  LDS: rt[Lmax] u16 the record's route | sstart[n] u16 row of each subroute's opening depot |
-// scnt[n] u16 its customers | load[n] f32 its demand, summed in float32 in route order.
+// The record's route tables in LDS, the layout of both intensification kernels: load[n'] DT each subroute's demand (DT: the
+// demand's dtype; first, so that a double is aligned) | rt[Lmax'] u16 the record's route | sstart[n'] u16 the row of each
+// subroute's opening depot | scnt[n'] u16 its customers | tail: what a kernel keeps behind them, from the next multiple of 8
+// bytes.  n', Lmax': rounded up to even.  end: rows of the route with its closing depot; S: subroutes.  The size, for the host
+// entries, and the carve, for the kernels, stand side by side:
+template <typename DT>
+struct RouteTables {
+  DT *load;
+  uint16_t *rt, *sstart, *scnt;
+  void *tail;
+  int end, S;
+};
+__host__ __device__ inline size_t tables_ld(int x) { return (size_t)((x + 1) & ~1); }
+__host__ __device__ inline size_t route_tables_bytes(int n, int Lmax, size_t dt) {
+  return tables_ld(n) * (dt + 2 * sizeof(uint16_t)) + tables_ld(Lmax) * sizeof(uint16_t);
+}
+__host__ __device__ inline size_t route_tables_tail(int n, int Lmax, size_t dt) { return (route_tables_bytes(n, Lmax, dt) + 7) & ~(size_t)7; }
+template <typename DT>
+__device__ inline RouteTables<DT> carve_route_tables(void *lds, int n, int Lmax) {
+  RouteTables<DT> T;
+  T.load = (DT *)lds;
+  T.rt = (uint16_t *)(T.load + tables_ld(n));
+  T.sstart = T.rt + tables_ld(Lmax);
+  T.scnt = T.sstart + tables_ld(n);
+  T.tail = (char *)lds + route_tables_tail(n, Lmax, sizeof(DT));
+  T.end = T.S = 0;
+  return T;
+}
+
+// The record of run() (cvrp/aco.py:81-85, cvrp_nls/aco.py:148-152) for one instance, by one wavefront: the first minimum of its
+// costs cb[A]; track: `if best_cost < self.lowest_cost`, the ant's column of pb [Lmax][A] copied into sp [Lmax] and *improved
+// written; else *improved read.  low: the record's cost as it stands after that.
+struct Record { KeyIdx best; float low; int imp; };
+__device__ inline Record take_record(const float *cb, int A, int Lmax, const int64_t *pb, int64_t *sp, const float *lowest,
+                                     int32_t *improved, int track, int lane) {
+  Record r;
+  r.best = first_min(cb, A, lane);
+  r.low = *lowest;
+  if (track) {
+    r.imp = r.best.key < r.low;
+    if (r.imp) {
+      r.low = r.best.key;
+      for (int k = lane; k < Lmax; k += 64) sp[k] = pb[(size_t)k * A + r.best.idx];
+    }
+    if (lane == 0) *improved = r.imp;
+  } else {
+    r.imp = *improved != 0;
+  }
+  return r;
+}
+
+// The record's route (load_route's src, stride) laid into T by one wavefront: rt, end, the subroute table and S, the loads.
+template <typename DT>
+__device__ inline void lay_record(RouteTables<DT> &T, const int64_t *src, long stride, int Lmax, int n, const DT *dem, int lane) {
+  T.end = route_end(load_route(src, stride, Lmax, T.rt, lane), Lmax);
+  int S = 0;
+  for_each_subroute(T.rt, T.end, lane, [&](int start, int j) {
+    if (S < n) {                                            // (a route of valid node ids has fewer subroutes than nodes)
+      if (lane == 0) { T.sstart[S] = (uint16_t)start; T.scnt[S] = (uint16_t)min(j - start - 1, n - 1); }
+      ++S;
+    }
+  });
+  T.S = S;
+  __builtin_amdgcn_wave_barrier();
+  __threadfence_block();
+  for (int s = lane; s < S; s += 64) {                      // self.demand[r].sum() per subroute (:363), sequential in route order
+    DT x = (DT)0;
+    const int s0 = T.sstart[s], m = T.scnt[s];
+    for (int t = 1; t <= m; ++t) x = x + dem[T.rt[s0 + t]];
+    T.load[s] = x;
+  }
+  __builtin_amdgcn_wave_barrier();
+  __threadfence_block();
+}
+
+// trial t's two uniforms: entries 2t, 2t + 1 of the instance's noise row, else the counter-based stream keyed by (seed, iter, gid, t)
+__device__ inline void n1_draws(const float *row, int t, uint64_t seed, uint64_t iter, uint32_t gid, float &u0, float &u1) {
+  if (row) {
+    u0 = row[N1_DRAWS * t];
+    u1 = row[N1_DRAWS * t + 1];
+  } else {
+    const u32x4 r = rng_block(seed, iter, STREAM_N1, gid, (uint32_t)t);
+    u0 = u01(r.x);
+    u1 = u01(r.y);
+  }
+}
+
+// source subroute (-1: none), node index in it, target subroute, index in the target the node goes before
+struct N1Move { int src, ni, dst, pos; };
+
+// One trial of N1_neighbourhood (cvrp/aco.py:254-286) against the running best (bdelta, mv), which starts as best_insertion =
+// (None, 0.0) and is replaced on strict < only.  T.S > 0.
+template <typename DT>
+__device__ inline void n1_trial(const RouteTables<DT> &T, const float *d, int n, const DT *dem, DT cap, float u0, float u1, int lane,
+                                float &bdelta, N1Move &mv) {
+  const int S = T.S;
+  const int si = draw_int(u0, 0, S - 1);
+  const int s0 = T.sstart[si], m = T.scnt[si];
+  const int ni = draw_int(u1, 1, m);
+  const int pred = T.rt[s0 + ni - 1], node = T.rt[s0 + ni], next = T.rt[s0 + ni + 1];
+  const DT dn = dem[node];
+  const float g0 = d[(size_t)pred * n + next] - d[(size_t)pred * n + node];
+  const float gain = g0 - d[(size_t)node * n + next];
+  for (int i = 0; i < S; ++i) {
+    if (i == si || !(T.load[i] + dn <= cap)) continue;
+    const KeyIdx g = best_gap(d, n, T.rt + T.sstart[i], (int)T.scnt[i] + 2, node, lane);
+    const float cand = g.key + gain;
+    if (cand < bdelta) { bdelta = cand; mv = N1Move{si, ni, i, g.idx + 1}; }
+  }
+}
+
+// N1's move on the packed route: the node at row prm leaves (with its subroute's opening depot if it was alone) and enters
+// before the element at row pins; every other element keeps its order.  Written to sp [Lmax] and to the column col (stride A);
+// *len, if given, takes the rows of the new route.
+template <typename DT>
+__device__ inline void apply_n1(const RouteTables<DT> &T, N1Move mv, int Lmax, int64_t *sp, int64_t *col, int A, int32_t *len, int lane) {
+  const int s0 = T.sstart[mv.src], vanish = T.scnt[mv.src] == 1, prm = s0 + mv.ni, pins = T.sstart[mv.dst] + mv.pos;
+  const int node = T.rt[prm];
+  const int used = T.end - vanish;                          // rows of the new route, its closing depot included
+  for (int k = lane; k < Lmax; k += 64) {
+    if (k >= used) {
+      sp[k] = 0;
+      col[(size_t)k * A] = 0;
+    }
+  }
+  for (int k = lane; k < T.end; k += 64) {
+    if (k == prm || (vanish && k == s0)) continue;
+    const int to = k - (k > prm ? 1 : 0) - (vanish && k > s0 ? 1 : 0) + (k >= pins ? 1 : 0);
+    sp[to] = T.rt[k];
+    col[(size_t)to * A] = T.rt[k];
+  }
+  if (lane == 0) {
+    const int to = pins - (prm < pins ? 1 : 0) - (vanish && s0 < pins ? 1 : 0);
+    sp[to] = node;
+    col[(size_t)to * A] = node;
+    if (len) *len = used;
+  }
+}
+
+// what both kernels leave of the record: lowest[b] where the instance improved, mmas_max[b] and moved[b] if asked for
+__device__ inline void record_tail(const Record &rec, int did, int b, float *lowest, float *mmas_max, float mmas_scale, int32_t *moved,
+                                   int lane) {
+  if (lane != 0) return;
+  if (rec.imp) lowest[b] = rec.low;
+  if (mmas_max) mmas_max[b] = (1.0f / rec.low) * mmas_scale;    // n / lowest_cost as rtruediv computes it (daco_track_best)
+  if (moved) moved[b] = did;
+}
+
+// cvrp/aco.py's intensification: one wavefront per instance takes the record, lays it, runs N1's five trials against one
+// running best and applies the move.  LDS: RouteTables<float>, no tail.
 __global__ void __launch_bounds__(64)
 cvrp_n1_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, const float *demand, float capacity, const float *noise,
                uint64_t seed, uint64_t iter, uint32_t inst_gid0, int64_t *paths, float *costs, int32_t *lens, float *lowest,
-               int64_t *shortest, int32_t *improved, int track, float *mmas_max, float mmas_scale, int32_t *moved, int n_ld) {
+               int64_t *shortest, int32_t *improved, int track, float *mmas_max, float mmas_scale, int32_t *moved) {
   extern __shared__ __attribute__((aligned(16))) uint16_t ad_lds[];
-  uint16_t *rt = ad_lds, *sstart = rt + ((Lmax + 1) & ~1), *scnt = sstart + n_ld;
-  float *load = (float *)(scnt + n_ld);
+  RouteTables<float> T = carve_route_tables<float>(ad_lds, n, Lmax);
   const int b = blockIdx.x, lane = threadIdx.x;
   const float *d = dist + (size_t)b * dist_bs, *dem = demand + (size_t)b * n;
   float *cb = costs + (size_t)b * A;
-  int64_t *sp = shortest + (size_t)b * Lmax;
-  const KeyIdx best = first_min(cb, A, lane);
-  float low = lowest[b];
-  int imp;
-  if (track) {                                              // `if best_cost < self.lowest_cost` (:83-85)
-    imp = best.key < low;
-    if (imp) {
-      low = best.key;
-      for (int k = lane; k < Lmax; k += 64) sp[k] = paths[((size_t)b * Lmax + k) * A + best.idx];
-    }
-    if (lane == 0) improved[b] = imp;
-  } else {
-    imp = improved[b] != 0;
-  }
+  int64_t *pb = paths + (size_t)b * Lmax * A, *sp = shortest + (size_t)b * Lmax;
+  Record rec = take_record(cb, A, Lmax, pb, sp, lowest + b, improved + b, track, lane);
   int did = 0;
-  if (imp) {
-    int last = -1;
-    for (int k0 = 0; k0 < Lmax; k0 += 64) {
-      const int k = k0 + lane;
-      const int v = k < Lmax ? (int)(track ? paths[((size_t)b * Lmax + k) * A + best.idx] : sp[k]) : 0;
-      if (k < Lmax) rt[k] = (uint16_t)v;
-      const uint64_t nz = __ballot(v != 0);
-      if (nz) last = k0 + 63 - __builtin_clzll(nz);
-    }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    // get_subroutes(end_with_zero=True): (start, j) consecutive depots with a customer between them
-    int S = 0, start = -1;
-    const int end = last + 2 <= Lmax ? last + 2 : Lmax;
-    for (int k0 = 0; k0 < end; k0 += 64) {
-      const int k = k0 + lane;
-      uint64_t zero = __ballot(k < end && rt[k] == 0);
-      while (zero) {
-        const int j = k0 + __builtin_ctzll(zero);
-        zero &= zero - 1;
-        if (start >= 0 && j - start > 1) {
-          if (S < n) {                                      // (a route of valid node ids has fewer subroutes than nodes)
-            if (lane == 0) { sstart[S] = (uint16_t)start; scnt[S] = (uint16_t)min(j - start - 1, n - 1); }
-            ++S;
-          }
-        }
-        start = j;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    for (int s = lane; s < S; s += 64) {                    // self.demand[r].sum() per subroute (:363)
-      float x = 0.0f;
-      const int s0 = sstart[s], m = scnt[s];
-      for (int t = 1; t <= m; ++t) x = x + dem[rt[s0 + t]];
-      load[s] = x;
-    }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    // best_insertion = (None, 0.0): source subroute, node index in it, target subroute, index in the target the node goes before
+  if (rec.imp) {
+    const int bi = rec.best.idx;
+    lay_record(T, track ? pb + bi : sp, track ? A : 1, Lmax, n, dem, lane);
     float bdelta = 0.0f;
-    int bs = -1, bni = 0, bt = 0, bpos = 0;
-    for (int t = 0; t < AD_TRIALS && S > 0; ++t) {
+    N1Move mv{-1, 0, 0, 0};
+    for (int t = 0; t < AD_TRIALS && T.S > 0; ++t) {
       float u0, u1;
-      if (noise) {
-        u0 = noise[((size_t)b * AD_TRIALS + t) * 2];
-        u1 = noise[((size_t)b * AD_TRIALS + t) * 2 + 1];
-      } else {
-        const u32x4 r = rng_block(seed, iter, STREAM_N1, inst_gid0 + (uint32_t)b, (uint32_t)t);
-        u0 = u01(r.x);
-        u1 = u01(r.y);
-      }
-      const int si = draw_int(u0, 0, S - 1);
-      const int s0 = sstart[si], m = scnt[si];
-      const int ni = draw_int(u1, 1, m);
-      const int pred = rt[s0 + ni - 1], node = rt[s0 + ni], next = rt[s0 + ni + 1];
-      const float dn = dem[node];
-      const float g0 = d[(size_t)pred * n + next] - d[(size_t)pred * n + node];
-      const float gain = g0 - d[(size_t)node * n + next];
-      for (int i = 0; i < S; ++i) {
-        if (i == si || !(load[i] + dn <= capacity)) continue;
-        const KeyIdx g = best_gap(d, n, rt + sstart[i], (int)scnt[i] + 2, node, lane);
-        const float cand = g.key + gain;
-        if (cand < bdelta) { bdelta = cand; bs = si; bni = ni; bt = i; bpos = g.idx + 1; }
-      }
+      n1_draws(noise ? noise + (size_t)b * N1_ROW : nullptr, t, seed, iter, inst_gid0 + (uint32_t)b, u0, u1);
+      n1_trial(T, d, n, dem, capacity, u0, u1, lane, bdelta, mv);
     }
-    if (bs >= 0) {
-      // the move on the packed route: the node at row prm leaves (with its subroute's opening depot if it was alone) and
-      // enters before the element at row pins; every other element keeps its order
+    if (mv.src >= 0) {
       did = 1;
-      const int s0 = sstart[bs], vanish = scnt[bs] == 1, prm = s0 + bni, pins = sstart[bt] + bpos;
-      const int node = rt[prm];
-      const int used = end - vanish;                        // rows of the new route, its closing depot included
-      const int bi = best.idx;
-      for (int k = lane; k < Lmax; k += 64) {
-        if (k >= used) {
-          sp[k] = 0;
-          paths[((size_t)b * Lmax + k) * A + bi] = 0;
-        }
-      }
-      for (int k = lane; k < end; k += 64) {
-        if (k == prm || (vanish && k == s0)) continue;
-        const int to = k - (k > prm ? 1 : 0) - (vanish && k > s0 ? 1 : 0) + (k >= pins ? 1 : 0);
-        sp[to] = rt[k];
-        paths[((size_t)b * Lmax + to) * A + bi] = rt[k];
-      }
-      low = low + bdelta;                                   // self.lowest_cost = ogcost + best_neighbour[1] (:374)
-      if (lane == 0) {
-        const int to = pins - (prm < pins ? 1 : 0) - (vanish && s0 < pins ? 1 : 0);
-        sp[to] = node;
-        paths[((size_t)b * Lmax + to) * A + bi] = node;
-        cb[bi] = low;
-        if (lens) lens[(size_t)b * A + bi] = used;
-      }
+      apply_n1(T, mv, Lmax, sp, pb + bi, A, lens ? lens + (size_t)b * A + bi : nullptr, lane);
+      rec.low = rec.low + bdelta;                           // self.lowest_cost = ogcost + best_neighbour[1] (:374)
+      if (lane == 0) cb[bi] = rec.low;
     }
-    if (lane == 0) lowest[b] = low;
   }
-  if (lane == 0) {
-    if (mmas_max) mmas_max[b] = (1.0f / low) * mmas_scale;  // n / lowest_cost as rtruediv computes it (daco_track_best)
-    if (moved) moved[b] = did;
-  }
+  record_tail(rec, did, b, lowest, mmas_max, mmas_scale, moved, lane);
 }
 
 // ------------------------------------------------------------------ cvrp_nls's intensification_phase (cvrp_nls/aco.py:313-394, 419-434)
 // The record, then N1 AND N2 on it, both evaluated on the unmodified record.
-constexpr uint32_t STREAM_N2 = 6;            // the N2 draws' stream (4 is N1's, 5 the sparse sampler's retry)
 constexpr int IN_WAVES = 2 * AD_TRIALS;      // wavefront t < 5: N1's trial t; wavefront 5 + t: N2's trial t
 constexpr int IN_RES = 8;                    // ints a trial leaves in LDS: valid | its move
+constexpr size_t IN_TAIL_BYTES = 2 * sizeof(int) + IN_WAVES * sizeof(float) + (size_t)IN_WAVES * IN_RES * sizeof(int);
 
-// best_gap on rt[0 .. len-1] with the entry at index `skip` left out (1 <= skip <= len - 2: the route then has len - 1 >= 2
-// entries); the position returned is one of the route without that entry
-__device__ inline KeyIdx best_gap_skip(const float *d, int n, const uint16_t *rt, int len, int skip, int c, int lane) {
-  float bk = 0.0f;
-  int bi = -1;
-  const int L = len - 1;
-  for (int i0 = 0; i0 + 1 < L; i0 += 64) {
-    const int i = i0 + lane;
-    float k = __builtin_inff();
-    int id = 0x7fffffff;
-    if (i + 1 < L) {
-      const int p1 = rt[i + (i >= skip ? 1 : 0)], p2 = rt[i + 1 + (i + 1 >= skip ? 1 : 0)];
-      const float s = d[(size_t)p1 * n + c] + d[(size_t)c * n + p2];
-      k = s - d[(size_t)p1 * n + p2];
-      id = i;
-    }
-    const KeyIdx r = wave_arg<false>(k, id);
-    if (bi < 0 || r.key < bk) { bk = r.key; bi = r.idx == 0x7fffffff ? i0 : r.idx; }
-  }
-  return KeyIdx{bk, bi};
-}
-
-// One workgroup of IN_WAVES wavefronts per instance.  Wavefront 0 takes the record as cvrp_n1_kernel does and lays the record's
-// route, its subroute table and the loads into LDS; after a barrier wavefront w runs its one trial (ten independent chains of
-// gather latencies side by side) and leaves (delta, move) in LDS; after a second barrier wavefront 0 takes the first least
-// delta below 0.0 in the order N1's trials, N2's trials (strict <: the winner rule of cvrp_nls/aco.py:425-429 and of both
-// neighbourhoods' own loops) and applies it.
-// LDS: load[n_ld] DT | rt[Lmax] u16 | sstart[n_ld] u16 | scnt[n_ld] u16 | hdr[2] int (improved, S) | delta[10] f32 |
-// res[10][IN_RES] int.  DT is the demand's dtype: loads and every capacity test run in it.
+// One workgroup of IN_WAVES wavefronts per instance.  Wavefront 0 takes the record and lays it as cvrp_n1_kernel does; after a
+// barrier wavefront w runs its one trial (ten independent chains of gather latencies side by side) and leaves (delta, move) in
+// LDS; after a second barrier wavefront 0 takes the first least delta below 0.0 in the order N1's trials, N2's trials (strict <:
+// the winner rule of cvrp_nls/aco.py:425-429 and of both neighbourhoods' own loops) and applies it.
+// LDS: RouteTables<DT> | tail: hdr[2] int (improved, S) | delta[10] f32 | res[10][IN_RES] int (IN_TAIL_BYTES).  DT is the
+// demand's dtype: loads and every capacity test run in it.
 template <typename DT>
 __global__ void __launch_bounds__(64 * IN_WAVES)
 cvrp_intensify_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, const DT *demand, double capacity, const float *noise,
                       uint64_t seed, uint64_t iter, uint32_t inst_gid0, int64_t *paths, float *costs, int32_t *lens, float *lowest,
-                      int64_t *shortest, int32_t *improved, int track, float *mmas_max, float mmas_scale, int32_t *moved, int n_ld) {
+                      int64_t *shortest, int32_t *improved, int track, float *mmas_max, float mmas_scale, int32_t *moved) {
   extern __shared__ __attribute__((aligned(16))) uint16_t ad_lds[];
-  DT *load = (DT *)ad_lds;
-  uint16_t *rt = (uint16_t *)(load + n_ld), *sstart = rt + ((Lmax + 3) & ~3), *scnt = sstart + n_ld;
-  int *hdr = (int *)(scnt + n_ld);
+  RouteTables<DT> T = carve_route_tables<DT>(ad_lds, n, Lmax);
+  int *hdr = (int *)T.tail;
   float *rdelta = (float *)(hdr + 2);
   int *res = (int *)(rdelta + IN_WAVES);
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float *d = dist + (size_t)b * dist_bs;
   const DT *dem = demand + (size_t)b * n;
   const DT cap = (DT)capacity;
+  const float *row = noise ? noise + (size_t)b * IN_ROW : nullptr;
   float *cb = costs + (size_t)b * A;
-  int64_t *sp = shortest + (size_t)b * Lmax;
-  KeyIdx best = KeyIdx{0.0f, 0};
-  float low = 0.0f;
-  int imp = 0, end = 0;
+  int64_t *pb = paths + (size_t)b * Lmax * A, *sp = shortest + (size_t)b * Lmax;
+  Record rec{KeyIdx{0.0f, 0}, 0.0f, 0};
   if (wave == 0) {
-    best = first_min(cb, A, lane);
-    low = lowest[b];
-    if (track) {                                            // `if best_cost < self.lowest_cost` (cvrp_nls/aco.py:150-152)
-      imp = best.key < low;
-      if (imp) {
-        low = best.key;
-        for (int k = lane; k < Lmax; k += 64) sp[k] = paths[((size_t)b * Lmax + k) * A + best.idx];
-      }
-      if (lane == 0) improved[b] = imp;
-    } else {
-      imp = improved[b] != 0;
-    }
-    int S = 0;
-    if (imp) {
-      int last = -1;
-      for (int k0 = 0; k0 < Lmax; k0 += 64) {
-        const int k = k0 + lane;
-        const int v = k < Lmax ? (int)(track ? paths[((size_t)b * Lmax + k) * A + best.idx] : sp[k]) : 0;
-        if (k < Lmax) rt[k] = (uint16_t)v;
-        const uint64_t nz = __ballot(v != 0);
-        if (nz) last = k0 + 63 - __builtin_clzll(nz);
-      }
-      __builtin_amdgcn_wave_barrier();
-      __threadfence_block();
-      int start = -1;
-      end = last + 2 <= Lmax ? last + 2 : Lmax;
-      for (int k0 = 0; k0 < end; k0 += 64) {
-        const int k = k0 + lane;
-        uint64_t zero = __ballot(k < end && rt[k] == 0);
-        while (zero) {
-          const int j = k0 + __builtin_ctzll(zero);
-          zero &= zero - 1;
-          if (start >= 0 && j - start > 1 && S < n) {
-            if (lane == 0) { sstart[S] = (uint16_t)start; scnt[S] = (uint16_t)min(j - start - 1, n - 1); }
-            ++S;
-          }
-          start = j;
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      __threadfence_block();
-      for (int s = lane; s < S; s += 64) {                  // self.demand[r].sum() per subroute (:423), sequential in route order
-        DT x = (DT)0;
-        const int s0 = sstart[s], m = scnt[s];
-        for (int t = 1; t <= m; ++t) x = x + dem[rt[s0 + t]];
-        load[s] = x;
-      }
-    }
-    if (lane == 0) { hdr[0] = imp; hdr[1] = S; }
+    rec = take_record(cb, A, Lmax, pb, sp, lowest + b, improved + b, track, lane);
+    if (rec.imp) lay_record(T, track ? pb + rec.best.idx : sp, track ? A : 1, Lmax, n, dem, lane);
+    if (lane == 0) { hdr[0] = rec.imp; hdr[1] = T.S; }
   }
   __syncthreads();
   {
+    const uint16_t *rt = T.rt, *sstart = T.sstart, *scnt = T.scnt;
+    const DT *load = T.load;
     const int go = hdr[0], S = hdr[1];
     float bdelta = 0.0f;
     int r0 = 0, r1 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0, valid = 0;
-    if (go && wave < AD_TRIALS && S > 0) {                  // N1_neighbourhood's trial `wave`: cvrp_n1_kernel's, one trial
-      const int t = wave;
+    if (go && wave < AD_TRIALS && S > 0) {                  // N1_neighbourhood's trial `wave`
       float u0, u1;
-      if (noise) {
-        u0 = noise[(size_t)b * 30 + 2 * t];
-        u1 = noise[(size_t)b * 30 + 2 * t + 1];
-      } else {
-        const u32x4 r = rng_block(seed, iter, STREAM_N1, inst_gid0 + (uint32_t)b, (uint32_t)t);
-        u0 = u01(r.x);
-        u1 = u01(r.y);
-      }
-      const int si = draw_int(u0, 0, S - 1);
-      const int s0 = sstart[si], m = scnt[si];
-      const int ni = draw_int(u1, 1, m);
-      const int pred = rt[s0 + ni - 1], node = rt[s0 + ni], next = rt[s0 + ni + 1];
-      const DT dn = dem[node];
-      const float g0 = d[(size_t)pred * n + next] - d[(size_t)pred * n + node];
-      const float gain = g0 - d[(size_t)node * n + next];
-      for (int i = 0; i < S; ++i) {
-        if (i == si || !(load[i] + dn <= cap)) continue;
-        const KeyIdx g = best_gap(d, n, rt + sstart[i], (int)scnt[i] + 2, node, lane);
-        const float cand = g.key + gain;
-        if (cand < bdelta) { bdelta = cand; valid = 1; r0 = si; r1 = ni; r2 = i; r3 = g.idx + 1; }
-      }
+      n1_draws(row, wave, seed, iter, inst_gid0 + (uint32_t)b, u0, u1);
+      N1Move mv{-1, 0, 0, 0};
+      T.S = S;
+      n1_trial(T, d, n, dem, cap, u0, u1, lane, bdelta, mv);
+      if (mv.src >= 0) { valid = 1; r0 = mv.src; r1 = mv.ni; r2 = mv.dst; r3 = mv.pos; }
     } else if (go && wave >= AD_TRIALS && S >= 2) {         // N2_neighbourhood's trial wave - 5 (S < 2: skipped; the reference raises)
       const int t = wave - AD_TRIALS;
       float u0, u1, u2, u3;
-      if (noise) {
-        const float *q = noise + (size_t)b * 30 + 10 + 4 * t;
+      if (row) {
+        const float *q = row + N1_ROW + N2_DRAWS * t;
         u0 = q[0]; u1 = q[1]; u2 = q[2]; u3 = q[3];
       } else {
         const u32x4 r = rng_block(seed, iter, STREAM_N2, inst_gid0 + (uint32_t)b, (uint32_t)t);
@@ -487,9 +496,9 @@ cvrp_intensify_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, c
         float c2 = d[(size_t)p2 * n + x2] - d[(size_t)p2 * n + n2];
         c2 = c2 - d[(size_t)n2 * n + x2];
         c = c + c2;
-        const KeyIdx i1 = best_gap_skip(d, n, rt + c0, m2 + 2, nj, n1, lane);    // node1 into sr2 without node2
+        const KeyIdx i1 = best_gap<true>(d, n, rt + c0, m2 + 2, n1, lane, nj);   // node1 into sr2 without node2
         c = c + i1.key;
-        const KeyIdx i2 = best_gap_skip(d, n, rt + a0, m1 + 2, ni, n2, lane);    // node2 into sr1 without node1
+        const KeyIdx i2 = best_gap<true>(d, n, rt + a0, m1 + 2, n2, lane, ni);   // node2 into sr1 without node1
         c = c + i2.key;
         if (c < bdelta) { bdelta = c; valid = 1; r0 = sr1; r1 = ni; r2 = i2.idx; r3 = sr2; r4 = nj; r5 = i1.idx; }
       }
@@ -503,41 +512,21 @@ cvrp_intensify_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, c
   __syncthreads();
   if (wave != 0) return;
   int did = 0;
-  if (imp) {
+  if (rec.imp) {
     float bdelta = 0.0f;
     int win = -1;
     for (int w = 0; w < IN_WAVES; ++w)
       if (res[w * IN_RES] && rdelta[w] < bdelta) { bdelta = rdelta[w]; win = w; }
-    const int bi = best.idx;
+    const int bi = rec.best.idx;
     if (win >= 0) {
       const int *q = res + win * IN_RES;
-      low = low + bdelta;                                   // self.lowest_cost = ogcost + best_neighbour[1] (:432)
-      if (win < AD_TRIALS) {                                // N1's move, as cvrp_n1_kernel applies it
+      rec.low = rec.low + bdelta;                           // self.lowest_cost = ogcost + best_neighbour[1] (:432)
+      if (win < AD_TRIALS) {
         did = 1;
-        const int bs = q[1], bni = q[2], bt = q[3], bpos = q[4];
-        const int s0 = sstart[bs], vanish = scnt[bs] == 1, prm = s0 + bni, pins = sstart[bt] + bpos;
-        const int node = rt[prm];
-        const int used = end - vanish;
-        for (int k = lane; k < Lmax; k += 64) {
-          if (k >= used) {
-            sp[k] = 0;
-            paths[((size_t)b * Lmax + k) * A + bi] = 0;
-          }
-        }
-        for (int k = lane; k < end; k += 64) {
-          if (k == prm || (vanish && k == s0)) continue;
-          const int to = k - (k > prm ? 1 : 0) - (vanish && k > s0 ? 1 : 0) + (k >= pins ? 1 : 0);
-          sp[to] = rt[k];
-          paths[((size_t)b * Lmax + to) * A + bi] = rt[k];
-        }
-        if (lane == 0) {
-          const int to = pins - (prm < pins ? 1 : 0) - (vanish && s0 < pins ? 1 : 0);
-          sp[to] = node;
-          paths[((size_t)b * Lmax + to) * A + bi] = node;
-          if (lens) lens[(size_t)b * A + bi] = used;
-        }
+        apply_n1(T, N1Move{q[1], q[2], q[3], q[4]}, Lmax, sp, pb + bi, A, lens ? lens + (size_t)b * A + bi : nullptr, lane);
       } else {                                              // N2's: both routes keep their rows; each loses one node and takes the other's
         did = 2;
+        const uint16_t *rt = T.rt, *sstart = T.sstart, *scnt = T.scnt;
         const int node1 = rt[sstart[q[1]] + q[2]], node2 = rt[sstart[q[4]] + q[5]];
         for (int side = 0; side < 2; ++side) {
           const int s0 = sstart[side ? q[4] : q[1]], m = scnt[side ? q[4] : q[1]], skip = side ? q[5] : q[2], loc = side ? q[6] : q[3];
@@ -546,22 +535,18 @@ cvrp_intensify_kernel(int n, int A, int Lmax, const float *dist, long dist_bs, c
             if (k == skip) continue;
             const int i = k - (k > skip ? 1 : 0), to = s0 + i + (i > loc ? 1 : 0);
             sp[to] = rt[s0 + k];
-            paths[((size_t)b * Lmax + to) * A + bi] = rt[s0 + k];
+            pb[(size_t)to * A + bi] = rt[s0 + k];
           }
           if (lane == 0) {
             sp[s0 + loc + 1] = node;
-            paths[((size_t)b * Lmax + s0 + loc + 1) * A + bi] = node;
+            pb[((size_t)s0 + loc + 1) * A + bi] = node;
           }
         }
       }
-      if (lane == 0) cb[bi] = low;
+      if (lane == 0) cb[bi] = rec.low;
     }
-    if (lane == 0) lowest[b] = low;
   }
-  if (lane == 0) {
-    if (mmas_max) mmas_max[b] = (1.0f / low) * mmas_scale;
-    if (moved) moved[b] = did;
-  }
+  record_tail(rec, did, b, lowest, mmas_max, mmas_scale, moved, lane);
 }
 
 // ------------------------------------------------------------------ update_pheronome | diversification_phase, and the pool
@@ -669,27 +654,32 @@ extern "C" long daco_cvrp_reinsert(void *stream, int B, int n, int A, int Lmax, 
   return launch_status("cvrp_reinsert_kernel");
 }
 
+// what daco_cvrp_n1_move and daco_cvrp_intensify (`what`) refuse alike: DACO_OK, or the code with the message set
+static long record_args_status(const char *what, int B, int n, int A, int Lmax, long dist_bstride, const void *dist, const void *demand,
+                               const void *paths, const void *costs, const void *lowest, const void *shortest, const void *improved) {
+  if (B <= 0 || n < 2 || A <= 0 || Lmax < 2 || dist_bstride < 0) {
+    set_error("%s: bad argument (B=%d n=%d A=%d Lmax=%d dist_bstride=%ld)", what, B, n, A, Lmax, dist_bstride);
+    return DACO_E_BADARG;
+  }
+  const void *need[] = {dist, demand, paths, costs, lowest, shortest, improved};
+  const char *names[] = {"dist", "demand", "paths", "costs", "lowest", "shortest", "improved"};
+  for (int i = 0; i < 7; ++i)
+    if (!need[i]) { set_error("%s: bad argument: %s is NULL", what, names[i]); return DACO_E_BADARG; }
+  return adaptive_sizes_ok(what, n, Lmax) ? DACO_OK : DACO_E_TOOLARGE;
+}
+
+/* The record and cvrp/aco.py's intensification_phase, N1, for B instances in one launch.  Its route tables take 2 Lmax + 8 n
+ * bytes of LDS, each rounded up to even: 65536 at n = DACO_MAX_NODES, Lmax = 4 DACO_MAX_NODES, so every accepted size fits. */
 extern "C" long daco_cvrp_n1_move(void *stream, int B, int n, int A, int Lmax, const float *dist, long dist_bstride, const float *demand,
                                   float capacity, const float *noise, uint64_t seed, uint64_t iter, uint32_t inst_gid0, int64_t *paths,
                                   float *costs, int32_t *lens, float *lowest, int64_t *shortest, int32_t *improved, int track,
                                   float *mmas_max, float mmas_scale, int32_t *moved) {
-  if (B <= 0 || n < 2 || A <= 0 || Lmax < 2 || !dist || !demand || !paths || !costs || !lowest || !shortest || !improved || dist_bstride < 0) {
-    set_error("daco_cvrp_n1_move: bad argument (B=%d n=%d A=%d Lmax=%d)", B, n, A, Lmax);
-    return DACO_E_BADARG;
-  }
-  if (!adaptive_sizes_ok("daco_cvrp_n1_move", n, Lmax)) return DACO_E_TOOLARGE;
-  const int n_ld = (n + 1) & ~1;
-  const size_t lds = ((size_t)((Lmax + 1) & ~1) + 2 * (size_t)n_ld) * sizeof(uint16_t) + (size_t)n_ld * sizeof(float);
-  hipLaunchKernelGGL(cvrp_n1_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, n, A, Lmax, dist, dist_bstride, demand, capacity, noise,
-                     seed, iter, inst_gid0, paths, costs, lens, lowest, shortest, improved, track, mmas_max, mmas_scale, moved, n_ld);
+  const long rc = record_args_status("daco_cvrp_n1_move", B, n, A, Lmax, dist_bstride, dist, demand, paths, costs, lowest, shortest, improved);
+  if (rc != DACO_OK) return rc;
+  hipLaunchKernelGGL(cvrp_n1_kernel, dim3(B), dim3(64), route_tables_bytes(n, Lmax, sizeof(float)), (hipStream_t)stream, n, A, Lmax, dist,
+                     dist_bstride, demand, capacity, noise, seed, iter, inst_gid0, paths, costs, lens, lowest, shortest, improved, track,
+                     mmas_max, mmas_scale, moved);
   return launch_status("cvrp_n1_kernel");
-}
-
-// bytes of LDS cvrp_intensify_kernel takes (its layout comment): 2 Lmax + (4 + sizeof(DT)) n + 368, each rounded to its alignment
-static size_t intensify_lds(int n, int Lmax, bool f64) {
-  const size_t n_ld = (size_t)((n + 1) & ~1);
-  return n_ld * (f64 ? sizeof(double) : sizeof(float)) + ((size_t)((Lmax + 3) & ~3) + 2 * n_ld) * sizeof(uint16_t) + 2 * sizeof(int) +
-         IN_WAVES * sizeof(float) + (size_t)IN_WAVES * IN_RES * sizeof(int);
 }
 
 /* The record and cvrp_nls's intensification_phase, N1 and N2, for B instances in one launch.  Fits (one workgroup's 64 KiB of
@@ -699,30 +689,22 @@ extern "C" long daco_cvrp_intensify(void *stream, int B, int n, int A, int Lmax,
                                     int demand_f64, double capacity, const float *noise, uint64_t seed, uint64_t iter, uint32_t inst_gid0,
                                     int64_t *paths, float *costs, int32_t *lens, float *lowest, int64_t *shortest, int32_t *improved,
                                     int track, float *mmas_max, float mmas_scale, int32_t *moved) {
-  if (B <= 0 || n < 2 || A <= 0 || Lmax < 2 || dist_bstride < 0) {
-    set_error("daco_cvrp_intensify: bad argument (B=%d n=%d A=%d Lmax=%d dist_bstride=%ld)", B, n, A, Lmax, dist_bstride);
-    return DACO_E_BADARG;
-  }
-  const void *need[] = {dist, demand, paths, costs, lowest, shortest, improved};
-  const char *names[] = {"dist", "demand", "paths", "costs", "lowest", "shortest", "improved"};
-  for (int i = 0; i < 7; ++i)
-    if (!need[i]) { set_error("daco_cvrp_intensify: bad argument: %s is NULL", names[i]); return DACO_E_BADARG; }
-  if (!adaptive_sizes_ok("daco_cvrp_intensify", n, Lmax)) return DACO_E_TOOLARGE;
-  const size_t lds = intensify_lds(n, Lmax, demand_f64 != 0);
+  const long rc = record_args_status("daco_cvrp_intensify", B, n, A, Lmax, dist_bstride, dist, demand, paths, costs, lowest, shortest, improved);
+  if (rc != DACO_OK) return rc;
+  const size_t lds = route_tables_tail(n, Lmax, demand_f64 ? sizeof(double) : sizeof(float)) + IN_TAIL_BYTES;
   if (lds > 64 * 1024) {
     set_error("daco_cvrp_intensify: n=%d, Lmax=%d with %s demands take %zu bytes of LDS, above 65536", n, Lmax,
               demand_f64 ? "float64" : "float32", lds);
     return DACO_E_TOOLARGE;
   }
-  const int n_ld = (n + 1) & ~1;
   if (demand_f64)
     hipLaunchKernelGGL(cvrp_intensify_kernel<double>, dim3(B), dim3(64 * IN_WAVES), lds, (hipStream_t)stream, n, A, Lmax, dist, dist_bstride,
                        (const double *)demand, capacity, noise, seed, iter, inst_gid0, paths, costs, lens, lowest, shortest, improved, track,
-                       mmas_max, mmas_scale, moved, n_ld);
+                       mmas_max, mmas_scale, moved);
   else
     hipLaunchKernelGGL(cvrp_intensify_kernel<float>, dim3(B), dim3(64 * IN_WAVES), lds, (hipStream_t)stream, n, A, Lmax, dist, dist_bstride,
                        (const float *)demand, capacity, noise, seed, iter, inst_gid0, paths, costs, lens, lowest, shortest, improved, track,
-                       mmas_max, mmas_scale, moved, n_ld);
+                       mmas_max, mmas_scale, moved);
   return launch_status("cvrp_intensify_kernel");
 }
 

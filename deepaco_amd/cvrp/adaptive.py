@@ -45,7 +45,11 @@ class ACO(_plain.ACO):
                                      min=self.min if self.min_max else None, capacity=self.capacity, sampler=self.sampler,
                                      seed=self.seed, adaptive=True, topk=5)
             hit = self._adaptive_colony = (key, col)
-        col = hit[1]
+        return self._run_kept(hit[1], n_iterations)
+
+    def _run_kept(self, col, n_iterations):
+        """n_iterations of the kept one-instance colony `col` (this class's, or cvrp_nls's) with the object's state carried in
+        and out: record, pheromone, MMAS bound, iteration counter, elite pool.  One host sync, at the end."""
         dev, rows = self.distances.device, 2 * self.problem_size + 1
         shortest = torch.zeros((1, rows), dtype=torch.int64, device=dev)
         if self.shortest_path is not None:
@@ -72,13 +76,19 @@ class ACO(_plain.ACO):
         pool[2][0, 0] = min(len(self.elite_pool), 5)
         return pool
 
+    def _search_step(self, paths, costs):
+        """What the loop runs between improvement_phase and the record; the costs that hold after it.  Here: nothing
+        (cvrp_nls/aco.py:144-147 has a local search there)."""
+        return costs
+
     @torch.no_grad()
     def _run_phases(self, n_iterations):
-        """cvrp/aco.py:72-104 call by call (gen_path or gen_path_costs were replaced on the object)."""
+        """cvrp/aco.py:72-104 (cvrp_nls/aco.py:135-171) call by call (gen_path or gen_path_costs were replaced on the object)."""
         for _ in range(n_iterations):
             paths = self.gen_path(require_prob=False)
             costs = self.gen_path_costs(paths)
             self.improvement_phase(paths, costs)
+            costs = self._search_step(paths, costs)
             improved = False
             best_cost, best_idx = costs.min(dim=0)
             if best_cost < self.lowest_cost:
@@ -127,9 +137,12 @@ class ACO(_plain.ACO):
         costs.copy_(c[0])
 
     # ------------------------------------------------------------------ cvrp/aco.py:359-376
+    _intensify = "cvrp_n1_move_"         # the engine call of intensification_phase: N1 (cvrp_nls's class: cvrp_intensify_, N1 and N2)
+
     @torch.no_grad()
     def intensification_phase(self, paths, costs, best_idx):
-        """N1 on the record (self.shortest_path, self.lowest_cost), which is the column `best_idx` = costs.argmin() of paths."""
+        """The neighbourhood moves (`_intensify`) on the record (self.shortest_path, self.lowest_cost), which is the column
+        `best_idx` = costs.argmin() of paths."""
         p, c = paths.contiguous().unsqueeze(0), costs.detach().to(torch.float32).contiguous().unsqueeze(0)
         dev = p.device
         shortest = torch.zeros((1, p.shape[1]), dtype=torch.int64, device=dev)
@@ -137,8 +150,8 @@ class ACO(_plain.ACO):
         lowest = torch.as_tensor(self.lowest_cost, dtype=torch.float32, device=dev).reshape(1).clone()
         it = self._calls
         self._calls += 1
-        engine.cvrp_n1_move_(self.distances, self.demand, self.capacity, p, c, lowest, shortest,
-                             improved=torch.ones(1, dtype=torch.int32, device=dev), seed=self.seed, it=it)
+        getattr(engine, self._intensify)(self.distances, self.demand, self.capacity, p, c, lowest, shortest,
+                                         improved=torch.ones(1, dtype=torch.int32, device=dev), seed=self.seed, it=it)
         self.shortest_path, self.lowest_cost = shortest[0], lowest[0]
         paths.copy_(p[0])
         costs.copy_(c[0])

@@ -20,25 +20,20 @@ class AdaptivePhases:
     """Mixed into cvrp_nls.aco.ACO: what that class does when adaptive=True."""
 
     improvement_phase = _CvrpAdaptive.improvement_phase              # cvrp_nls/aco.py:396-417 is cvrp/aco.py:336-357
+    intensification_phase = _CvrpAdaptive.intensification_phase      # :419-434 is :359-376 with N2 beside N1:
+    _intensify = "cvrp_intensify_"
     diversification_phase = _CvrpAdaptive.diversification_phase      # :436-441 is :378-383
     _pool_tensors = _CvrpAdaptive._pool_tensors
+    _run_kept = _CvrpAdaptive._run_kept
+    _run_phases = _CvrpAdaptive._run_phases                          # :135-171 is cvrp/aco.py:72-104 with _search_step
 
-    # ------------------------------------------------------------------ cvrp_nls/aco.py:419-434
-    @torch.no_grad()
-    def intensification_phase(self, paths, costs, best_idx):
-        """N1 and N2 on the record (self.shortest_path, self.lowest_cost), which is the column `best_idx` = costs.argmin() of paths."""
-        p, c = paths.contiguous().unsqueeze(0), costs.detach().to(torch.float32).contiguous().unsqueeze(0)
-        dev = p.device
-        shortest = torch.zeros((1, p.shape[1]), dtype=torch.int64, device=dev)
-        shortest[0, :self.shortest_path.numel()] = self.shortest_path
-        lowest = torch.as_tensor(self.lowest_cost, dtype=torch.float32, device=dev).reshape(1).clone()
-        it = self._calls
-        self._calls += 1
-        engine.cvrp_intensify_(self.distances, self.demand, self.capacity, p, c, lowest, shortest,
-                               improved=torch.ones(1, dtype=torch.int32, device=dev), seed=self.seed, it=it)
-        self.shortest_path, self.lowest_cost = shortest[0], lowest[0]
-        paths.copy_(p[0])
-        costs.copy_(c[0])
+    def _search_step(self, paths, costs):
+        """cvrp_nls/aco.py:144-147: with swapstar the local search on the 8 cheapest ants, every cost recomputed after it."""
+        if not self.swapstar:
+            return costs
+        indexes = costs.topk(min(8, self.n_ants), largest=False).indices
+        self.multiple_swap_star(paths, indexes=indexes)
+        return self.gen_path_costs(paths)
 
     # ------------------------------------------------------------------ cvrp_nls/aco.py:135-171
     @torch.no_grad()
@@ -61,51 +56,4 @@ class AdaptivePhases:
                                      inference=self.inference, use_swap_star=self.use_swap_star,
                                      positions=None if not self.use_swap_star else self.positions.detach().unsqueeze(0))
             hit = self._adaptive_colony = (key, col)
-        col = hit[1]
-        dev, rows = self.distances.device, 2 * self.problem_size + 1
-        shortest = torch.zeros((1, rows), dtype=torch.int64, device=dev)
-        if self.shortest_path is not None:
-            shortest[0, :self.shortest_path.numel()] = self.shortest_path
-        col._pool = self._pool_tensors(rows)
-        engine.run_kept_colony(self, col, n_iterations, shortest)
-        fl = int(col._flags[0])                      # the only host sync of the loop
-        if fl & 1:
-            raise ValueError("ACO.run: a transition row had no feasible candidate")
-        if fl & 2:
-            raise RuntimeError("ACO.run: route buffer too short")
-        route = col.shortest_path[0]
-        last = int(torch.nonzero(route).max()) if bool((route != 0).any()) else 0
-        self.shortest_path = route[:last + 2].clone()
-        self.elite_pool = [(r.clone(), c.clone()) for r, c in col.elite_pool[0]]
-        return self.lowest_cost
-
-    @torch.no_grad()
-    def _run_phases(self, n_iterations):
-        """cvrp_nls/aco.py:135-171 call by call."""
-        for _ in range(n_iterations):
-            paths = self.gen_path(require_prob=False)
-            costs = self.gen_path_costs(paths)
-            self.improvement_phase(paths, costs)
-            if self.swapstar:
-                indexes = costs.topk(min(8, self.n_ants), largest=False).indices
-                self.multiple_swap_star(paths, indexes=indexes)
-                costs = self.gen_path_costs(paths)
-            improved = False
-            best_cost, best_idx = costs.min(dim=0)
-            if best_cost < self.lowest_cost:
-                self.shortest_path = paths[:, best_idx].clone()
-                self.lowest_cost = best_cost
-                self.intensification_phase(paths, costs, best_idx)
-                if self.min_max:
-                    max_ = self.problem_size / self.lowest_cost
-                    if self.max is None:
-                        self.pheromone *= max_ / self.pheromone.max()
-                    self.max = max_
-                improved = True
-            if improved:
-                self.update_pheronome(paths, costs)
-                self.elite_pool.insert(0, (self.shortest_path, self.lowest_cost))
-                del self.elite_pool[5:]
-            else:
-                self.diversification_phase()
-        return self.lowest_cost
+        return self._run_kept(hit[1], n_iterations)

@@ -5,6 +5,7 @@ from .. import _lib
 from .common import _bstride, _on, _ptr, _require_gpu, _rows, _stream
 
 POOL_SIZE = 5          # pool_size of cvrp/aco.py:99
+N1_TRIALS = N2_TRIALS = 5      # count = 5 of N1_neighbourhood and N2_neighbourhood: two and four uniforms per trial
 
 
 def _check_colony(who, paths, costs, lens=None):
@@ -37,6 +38,47 @@ def cvrp_reinsert_(dist, paths, costs, lens=None, topk=5):
     return sel
 
 
+def _record_and_intensify(who, noise_shape, keep_demand_dtype, dist, demand, capacity, paths, costs, lowest, shortest, improved, lens,
+                          noise, seed, it, inst_gid0, mmas_scale, want_moved):
+    """cvrp_n1_move_ and cvrp_intensify_ (`who`): the checks, the allocations and the call.  noise_shape: an instance's noise, (5, 2)
+    or (30,); keep_demand_dtype: the demand goes to daco_cvrp_intensify in its own dtype, else to daco_cvrp_n1_move as float32."""
+    B, Lmax, A = _check_colony(who, paths, costs, lens)
+    if lowest.dtype != torch.float32 or not lowest.is_contiguous() or lowest.numel() != B:
+        raise _lib.DacoError(f"{who}: lowest must be a contiguous float32 [{B}] tensor")
+    if shortest.dtype != torch.int64 or not shortest.is_contiguous() or tuple(shortest.shape) != (B, Lmax):
+        raise _lib.DacoError(f"{who}: shortest must be a contiguous int64 [{B}, {Lmax}] tensor, got {tuple(shortest.shape)}")
+    if noise is not None and (noise.dtype != torch.float32 or not noise.is_contiguous() or tuple(noise.shape) != (B, *noise_shape)):
+        raise _lib.DacoError(f"{who}: noise {[B, *noise_shape]} float32 expected, got {tuple(noise.shape)} {noise.dtype}")
+    n = dist.shape[-1]
+    if keep_demand_dtype:
+        if demand.dtype not in (torch.float32, torch.float64):
+            raise _lib.DacoError(f"{who}: demand must be float32 or float64, got {demand.dtype}")
+        if demand.shape[-1] != n or demand.numel() not in (n, B * n):
+            raise _lib.DacoError(f"{who}: demand must be [{n}] or [{B}, {n}], got {tuple(demand.shape)}")
+    track = improved is None
+    if not track and (improved.dtype != torch.int32 or not improved.is_contiguous() or improved.numel() != B):
+        raise _lib.DacoError(f"{who}: improved must be a contiguous int32 [{B}] tensor")
+    _require_gpu(dist, demand, paths, costs, lowest, shortest, improved, lens, noise)      # (the shapes are refused first, device or not)
+    dist, dbs = _bstride(dist, n)
+    demand = _rows(demand, B, demand.dtype if keep_demand_dtype else torch.float32)
+    dev = paths.device
+    with _on(dev):
+        if track:
+            improved = torch.empty((B,), dtype=torch.int32, device=dev)
+        mx = torch.empty((B,), dtype=torch.float32, device=dev) if mmas_scale is not None else None
+        moved = torch.empty((B,), dtype=torch.int32, device=dev) if want_moved else None
+        head = (_stream(dev), B, n, A, Lmax, dist.data_ptr(), dbs, demand.data_ptr())
+        tail = (float(capacity), _ptr(noise), int(seed) & (2 ** 64 - 1), int(it), int(inst_gid0) & 0xFFFFFFFF, paths.data_ptr(),
+                costs.data_ptr(), _ptr(lens), lowest.data_ptr(), shortest.data_ptr(), improved.data_ptr(), int(track), _ptr(mx),
+                float(mmas_scale) if mmas_scale is not None else 0.0, _ptr(moved))
+        if keep_demand_dtype:
+            entry, rc = "daco_cvrp_intensify", _lib.lib().daco_cvrp_intensify(*head, int(demand.dtype == torch.float64), *tail)
+        else:
+            entry, rc = "daco_cvrp_n1_move", _lib.lib().daco_cvrp_n1_move(*head, *tail)
+    _lib.check(rc, entry)
+    return improved, mx, moved
+
+
 def cvrp_n1_move_(dist, demand, capacity, paths, costs, lowest, shortest, improved=None, lens=None, noise=None, seed=0, it=0,
                   inst_gid0=0, mmas_scale=None, want_moved=False):
     """The record of ACO.run (cvrp/aco.py:81-85) and intensification_phase (:359-376, N1_neighbourhood :254-286) for a batch, in
@@ -47,32 +89,8 @@ def cvrp_n1_move_(dist, demand, capacity, paths, costs, lowest, shortest, improv
     noise [B, 5, 2] float32 uniforms in [0, 1) (the subroute, the node in it, per trial), else the counter-based stream keyed by
     (seed, it, inst_gid0 + b).  Returns (improved, mmas_max | None, moved | None): mmas_max [B] = n / lowest as the reference's
     rtruediv computes it, with mmas_scale = n."""
-    B, Lmax, A = _check_colony("cvrp_n1_move_", paths, costs, lens)
-    if lowest.dtype != torch.float32 or not lowest.is_contiguous() or lowest.numel() != B:
-        raise _lib.DacoError(f"cvrp_n1_move_: lowest must be a contiguous float32 [{B}] tensor")
-    if shortest.dtype != torch.int64 or not shortest.is_contiguous() or tuple(shortest.shape) != (B, Lmax):
-        raise _lib.DacoError(f"cvrp_n1_move_: shortest must be a contiguous int64 [{B}, {Lmax}] tensor, got {tuple(shortest.shape)}")
-    if noise is not None and (noise.dtype != torch.float32 or not noise.is_contiguous() or tuple(noise.shape) != (B, 5, 2)):
-        raise _lib.DacoError(f"cvrp_n1_move_: noise [{B}, 5, 2] float32 expected, got {tuple(noise.shape)} {noise.dtype}")
-    track = improved is None
-    if not track and (improved.dtype != torch.int32 or not improved.is_contiguous() or improved.numel() != B):
-        raise _lib.DacoError(f"cvrp_n1_move_: improved must be a contiguous int32 [{B}] tensor")
-    _require_gpu(dist, demand, paths, costs, lowest, shortest, improved, lens, noise)      # (the shapes are refused first, device or not)
-    n = dist.shape[-1]
-    dist, dbs = _bstride(dist, n)
-    demand = _rows(demand, B)
-    dev = paths.device
-    with _on(dev):
-        if track:
-            improved = torch.empty((B,), dtype=torch.int32, device=dev)
-        mx = torch.empty((B,), dtype=torch.float32, device=dev) if mmas_scale is not None else None
-        moved = torch.empty((B,), dtype=torch.int32, device=dev) if want_moved else None
-        rc = _lib.lib().daco_cvrp_n1_move(_stream(dev), B, n, A, Lmax, dist.data_ptr(), dbs, demand.data_ptr(), float(capacity), _ptr(noise),
-                                          int(seed) & (2 ** 64 - 1), int(it), int(inst_gid0) & 0xFFFFFFFF, paths.data_ptr(), costs.data_ptr(),
-                                          _ptr(lens), lowest.data_ptr(), shortest.data_ptr(), improved.data_ptr(), int(track), _ptr(mx),
-                                          float(mmas_scale) if mmas_scale is not None else 0.0, _ptr(moved))
-    _lib.check(rc, "daco_cvrp_n1_move")
-    return improved, mx, moved
+    return _record_and_intensify("cvrp_n1_move_", (N1_TRIALS, 2), False, dist, demand, capacity, paths, costs, lowest, shortest, improved,
+                                 lens, noise, seed, it, inst_gid0, mmas_scale, want_moved)
 
 
 def cvrp_intensify_(dist, demand, capacity, paths, costs, lowest, shortest, improved=None, lens=None, noise=None, seed=0, it=0,
@@ -86,37 +104,8 @@ def cvrp_intensify_(dist, demand, capacity, paths, costs, lowest, shortest, impr
     instance with fewer than two routes skips N2 (the reference raises there).  Returns (improved, mmas_max | None, moved | None),
     moved [B] int32: 0 no move, 1 N1's, 2 N2's.  Sizes whose route tables do not fit 64 KiB of LDS (2 Lmax + 8 n + 368 bytes,
     12 n for float64 demands) raise DacoTooLarge; nothing is launched."""
-    B, Lmax, A = _check_colony("cvrp_intensify_", paths, costs, lens)
-    if lowest.dtype != torch.float32 or not lowest.is_contiguous() or lowest.numel() != B:
-        raise _lib.DacoError(f"cvrp_intensify_: lowest must be a contiguous float32 [{B}] tensor")
-    if shortest.dtype != torch.int64 or not shortest.is_contiguous() or tuple(shortest.shape) != (B, Lmax):
-        raise _lib.DacoError(f"cvrp_intensify_: shortest must be a contiguous int64 [{B}, {Lmax}] tensor, got {tuple(shortest.shape)}")
-    if noise is not None and (noise.dtype != torch.float32 or not noise.is_contiguous() or tuple(noise.shape) != (B, 30)):
-        raise _lib.DacoError(f"cvrp_intensify_: noise [{B}, 30] float32 expected, got {tuple(noise.shape)} {noise.dtype}")
-    if demand.dtype not in (torch.float32, torch.float64):
-        raise _lib.DacoError(f"cvrp_intensify_: demand must be float32 or float64, got {demand.dtype}")
-    n = dist.shape[-1]
-    if demand.shape[-1] != n or demand.numel() not in (n, B * n):
-        raise _lib.DacoError(f"cvrp_intensify_: demand must be [{n}] or [{B}, {n}], got {tuple(demand.shape)}")
-    track = improved is None
-    if not track and (improved.dtype != torch.int32 or not improved.is_contiguous() or improved.numel() != B):
-        raise _lib.DacoError(f"cvrp_intensify_: improved must be a contiguous int32 [{B}] tensor")
-    _require_gpu(dist, demand, paths, costs, lowest, shortest, improved, lens, noise)      # (the shapes are refused first, device or not)
-    dist, dbs = _bstride(dist, n)
-    demand = _rows(demand, B, demand.dtype)
-    dev = paths.device
-    with _on(dev):
-        if track:
-            improved = torch.empty((B,), dtype=torch.int32, device=dev)
-        mx = torch.empty((B,), dtype=torch.float32, device=dev) if mmas_scale is not None else None
-        moved = torch.empty((B,), dtype=torch.int32, device=dev) if want_moved else None
-        rc = _lib.lib().daco_cvrp_intensify(_stream(dev), B, n, A, Lmax, dist.data_ptr(), dbs, demand.data_ptr(),
-                                            int(demand.dtype == torch.float64), float(capacity), _ptr(noise), int(seed) & (2 ** 64 - 1),
-                                            int(it), int(inst_gid0) & 0xFFFFFFFF, paths.data_ptr(), costs.data_ptr(), _ptr(lens),
-                                            lowest.data_ptr(), shortest.data_ptr(), improved.data_ptr(), int(track), _ptr(mx),
-                                            float(mmas_scale) if mmas_scale is not None else 0.0, _ptr(moved))
-    _lib.check(rc, "daco_cvrp_intensify")
-    return improved, mx, moved
+    return _record_and_intensify("cvrp_intensify_", (N1_TRIALS * 2 + N2_TRIALS * 4,), True, dist, demand, capacity, paths, costs, lowest,
+                                 shortest, improved, lens, noise, seed, it, inst_gid0, mmas_scale, want_moved)
 
 
 def cvrp_elite_pool(B, Lmax, device):

@@ -5,8 +5,9 @@
     smallest position among equals (`min` over (cost, i) tuples);
   * a subroute's cost is the sum of its deltas in double, in insertion order, an ant's the sum of those in double, in subroute
     order; `new_cost < costs[i]` is a float32 comparison and the stored cost the float32 rounding;
-  * N1: two draws per trial, always; removal gain and candidate cost in float32; strict < from 0.0; loads are float32 sums in
-    route order; `lowest = old + delta` in float32;
+  * N1: two draws per trial, always; removal gain and candidate cost in float32; strict < from 0.0, so an earlier trial wins a
+    tie; loads are sums in route order in the demand's dtype, float32 here (cvrp_nls_adaptive_spec.py uses the same functions
+    with float64 too); `lowest = old + delta` in float32;
   * the diversification is tau * f32(decay * 0.5) + f32(0.01), two roundings, then + 1 / cost per pool entry from the front, an
     index pair once per entry; no clamp, no floor.
 
@@ -95,16 +96,26 @@ def route_len(route):
     return int(nz[-1]) + 2 if len(nz) else 1
 
 
-def n1_move(d, demand, capacity, route, cost, u):
-    """intensification_phase on the record (route [L], cost f32) with the uniforms u [5, 2] -> (route, cost, moved)."""
-    L = len(route)
-    subs = [[0] + cust + [0] for _, cust in subroutes(route)]
-    loads = []
+def closed_subroutes(route):
+    return [[0] + cust + [0] for _, cust in subroutes(route)]
+
+
+def loads_of(subs, demand):
+    """Each subroute's demand, summed in route order in the demand's dtype."""
+    T = demand.dtype.type
+    out = []
     for r in subs:
-        x = F(0)
+        x = T(0)
         for c in r[1:-1]:
-            x = F(x + demand[c])
-        loads.append(x)
+            x = T(x + demand[c])
+        out.append(x)
+    return out
+
+
+def n1_best(d, demand, capacity, subs, loads, u):
+    """N1_neighbourhood's five trials, u [5, 2] -> ((source, node index, target, index it goes before) | None, delta f32); the
+    capacity test runs in the demand's dtype."""
+    T = demand.dtype.type
     best, bdelta = None, F(0)
     for t in range(5):
         if not subs:
@@ -115,15 +126,17 @@ def n1_move(d, demand, capacity, route, cost, u):
         pred, node, nxt = r[ni - 1], r[ni], r[ni + 1]
         gain = F(F(d[pred, nxt] - d[pred, node]) - d[node, nxt])
         for i, tr in enumerate(subs):
-            if i == si or not (F(loads[i] + demand[node]) <= F(capacity)):
+            if i == si or not (T(loads[i] + demand[node]) <= T(capacity)):
                 continue
             loc, ins = best_gap(d, tr, node)
             cand = F(ins + gain)
             if cand < bdelta:
                 best, bdelta = (si, ni, i, loc + 1), cand
-    if best is None:
-        return np.array(route, dtype=np.int64), F(cost), False
-    si, ni, ti, tp = best
+    return best, bdelta
+
+
+def n1_apply(subs, move):
+    si, ni, ti, tp = move
     subs = [list(r) for r in subs]
     node = subs[si][ni]
     subs[ti] = subs[ti][:tp] + [node] + subs[ti][tp:]
@@ -131,7 +144,18 @@ def n1_move(d, demand, capacity, route, cost, u):
         del subs[si]
     else:
         subs[si] = subs[si][:ni] + subs[si][ni + 1:]
-    return merge(subs, L), F(F(cost) + bdelta), True
+    return subs
+
+
+def n1_move(d, demand, capacity, route, cost, u):
+    """intensification_phase on the record (route [L], cost f32) with the uniforms u [5, 2] -> (route, cost, moved); the demand
+    as float32, which is what engine.cvrp_n1_move_ makes of it."""
+    demand = np.asarray(demand, F)
+    subs = closed_subroutes(route)
+    best, bdelta = n1_best(d, demand, capacity, subs, loads_of(subs, demand), u)
+    if best is None:
+        return np.array(route, dtype=np.int64), F(cost), False
+    return merge(n1_apply(subs, best), len(route)), F(F(cost) + bdelta), True
 
 
 def edges(route):

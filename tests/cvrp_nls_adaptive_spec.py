@@ -7,7 +7,7 @@ diversification -- is tests/cvrp_adaptive_spec.py's; what differs is here:
   * loads and every capacity test run in the demand's dtype (float32 or float64), a subroute's load being the sequential sum in
     route order (the reference's torch.sum order is not reproduced at the last bit; the fixtures' demands k / 32 sum exactly in
     every order); distances, deltas and `lowest = old + delta` are float32;
-  * N1 is cvrp_adaptive_spec.n1_move's arithmetic: two draws per trial, strict < from 0.0, an earlier trial wins a tie;
+  * N1 is cvrp_adaptive_spec's own (closed_subroutes, loads_of, n1_best, n1_apply), which are written for either dtype;
   * N2, trial t, takes four uniforms u[t][0..3] whether it uses them or not.  S subroutes; S < 2: skipped (the reference
     raises ValueError there: np.random.choice(1, size=2, replace=False)).  sr1 = draw(u0, 0, S-1); sr2 = draw(u1, 0, S-2),
     + 1 if >= sr1 (a uniform ordered pair without replacement); node1_index = draw(u2, 1, len(sr1)-2); interior position j of
@@ -30,54 +30,7 @@ F = S.F
 POOL = S.POOL
 
 
-def closed_subroutes(route):
-    return [[0] + cust + [0] for _, cust in S.subroutes(route)]
-
-
-def loads_of(subs, demand):
-    """Each subroute's demand, summed in route order in the demand's dtype."""
-    T = demand.dtype.type
-    out = []
-    for r in subs:
-        x = T(0)
-        for c in r[1:-1]:
-            x = T(x + demand[c])
-        out.append(x)
-    return out
-
-
-def n1_best(d, demand, capacity, subs, loads, u):
-    """N1_neighbourhood's five trials, u [5, 2] -> ((source, node index, target, index it goes before) | None, delta f32)."""
-    T = demand.dtype.type
-    best, bdelta = None, F(0)
-    for t in range(5):
-        if not subs:
-            break
-        si = S.draw(u[t][0], 0, len(subs) - 1)
-        r = subs[si]
-        ni = S.draw(u[t][1], 1, len(r) - 2)
-        pred, node, nxt = r[ni - 1], r[ni], r[ni + 1]
-        gain = F(F(d[pred, nxt] - d[pred, node]) - d[node, nxt])
-        for i, tr in enumerate(subs):
-            if i == si or not (T(loads[i] + demand[node]) <= T(capacity)):
-                continue
-            loc, ins = S.best_gap(d, tr, node)
-            cand = F(ins + gain)
-            if cand < bdelta:
-                best, bdelta = (si, ni, i, loc + 1), cand
-    return best, bdelta
-
-
-def n1_apply(subs, move):
-    si, ni, ti, tp = move
-    subs = [list(r) for r in subs]
-    node = subs[si][ni]
-    subs[ti] = subs[ti][:tp] + [node] + subs[ti][tp:]
-    if len(subs[si]) == 3:
-        del subs[si]
-    else:
-        subs[si] = subs[si][:ni] + subs[si][ni + 1:]
-    return subs
+closed_subroutes, loads_of, n1_best, n1_apply = S.closed_subroutes, S.loads_of, S.n1_best, S.n1_apply
 
 
 def n2_best(d, demand, capacity, subs, loads, u, trace=None):
